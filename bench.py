@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Headline benchmark on MI355X: proofs/sec for the m=64 matmul circuit (full prove()), plus the 2^20 NTT leg.
+"""Headline benchmark on MI355X: proofs/sec for the m=64 matmul circuit (full prove()), plus (--full) the 2^20 NTT leg.
 
-  python bench.py --gpus N --steps K --warmup W [--config4]
+  python bench.py --gpus N --steps K --warmup W [--config4] [--full] [--dump-outputs DIR]
 
   N = 1:  runs in this process.
   N > 1:  one rank per GPU over RCCL.  Launched by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the environment) the
@@ -21,7 +21,16 @@ inside the timed region.
 
 --config4 (BASELINE configs[3], "scaling": "strong"): a batch of 512 independent proofs (operand seeds 0..511), proof i on rank
 i mod N, through the library's prover pool: operands on the host, witness generation in HBM and prove() per lane inside the
-clock, then the cap gather; value = 512 / t.  At N = 1 the default run reports it as the extra key "config4_batch512".
+clock, then the cap gather; value = 512 / t.  At N = 1 a --full run reports it as the extra key "config4_batch512".
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, config, host); the keys below, host aside, are measured or checked only with --full and are null in a plain run.
+Every test, script or document that relies on them runs `bench.py --full`.
+
+--dump-outputs DIR (after the clock, rank 0): what the timed loop returned in its last step -- the proofs of its --streams (16) lanes, in
+proof order -- as arrays that hold every value exactly: DIR/proof_bytes.npy (proofs x bytes, float32 byte values; past 64 MB a fixed,
+seeded sample of byte positions, the same in every proof, listed in DIR/proof_bytes_index.npy) and DIR/caps.npy (proofs x 3 trees x 16 x 4 words x (hi, lo) 32-bit
+halves, float64).  Inputs are seeded: the same arguments give the same arrays on every run and build.
 
 The same JSON line carries
   roofline:        BASELINE configs[1], the HBM-bound kernel family of the path: forward 2^20-point NTT over 64 polynomials,
@@ -38,8 +47,8 @@ The same JSON line carries
   host:            lanes per GPU (capped by min(affinity mask, cgroup CPU quota) / ranks), GPU_MAX_HW_QUEUES, host CPU seconds;
   cpu_baseline:    the CPU restatement of the reference prover (oracle/, kind "port") on the host cores: all cores (median of 5
                    proofs after a warm-up); `one_thread` quotes the committed measurement of one full 1-thread proof (45 s);
-  vs_baseline:     value / cpu_baseline.value -- the ratio to that CPU PORT (BASELINE.md publishes no number for this metric).
-The last proof of every lane of the timed loop is verified after the clock stops (config.lanes_verified_after_the_clock).
+  vs_baseline:     value / cpu_baseline.value -- the ratio to that CPU PORT (BASELINE.md publishes no number for this metric);
+and the last proof of every lane of the timed loop is verified after the clock stops (config.lanes_verified_after_the_clock).
 """
 import argparse
 import ctypes
@@ -216,7 +225,7 @@ def committed_one_thread(m):
                 d = d.get("cpu_baseline", d)
                 d = d.get("one_thread_measured") or d
                 return {"value": d["value"], "unit": "proofs/s", "seconds": d.get("seconds"), "measured": True,
-                        "source": "profiles/%s (committed profile of `bench.py --cpu-one-thread`, not measured in this run)" % name}
+                        "source": "profiles/%s (committed profile of `bench.py --full --cpu-one-thread`, not measured in this run)" % name}
             except Exception:
                 pass
     return None
@@ -234,6 +243,28 @@ def timed_launches(ctx, fn, reps, run_in=0):
     rep = ctx.timing_report()
     ctx.timing(False)
     return rep
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, proofs):
+    """--dump-outputs: the proofs of the timed loop's last step as float arrays that hold every value exactly (see the module
+    docstring).  Written after the clock stops."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    caps = np.stack([pr.caps() for pr in proofs])                              # (proofs, 3, 16, 4) u64
+    halves = np.stack([caps >> np.uint64(32), caps & np.uint64(0xFFFFFFFF)], axis=-1).astype(np.float64)
+    np.save(os.path.join(dirname, "caps.npy"), halves)
+    raw = np.stack([np.frombuffer(pr.to_bytes(), dtype=np.uint8) for pr in proofs])      # (proofs, bytes)
+    # positions that fit: a float32 per proof and a float64 index each, 1 MB left for the .npy headers
+    room = (DUMP_LIMIT_BYTES - halves.nbytes - (1 << 20)) // (4 * raw.shape[0] + 8)
+    if raw.shape[1] > room:
+        idx = np.sort(np.random.default_rng(0).choice(raw.shape[1], room, replace=False))
+        np.save(os.path.join(dirname, "proof_bytes.npy"), raw[:, idx].astype(np.float32))
+        np.save(os.path.join(dirname, "proof_bytes_index.npy"), idx.astype(np.float64))
+    else:
+        np.save(os.path.join(dirname, "proof_bytes.npy"), raw.astype(np.float32))
 
 
 def ntt_leg(torch, ctx, lib, check, dev, batch, with_rows=True):
@@ -422,7 +453,15 @@ def main():
     ap.add_argument("--spawn", action="store_true", help="run even a 1-GPU job as a spawned rank over RCCL (the N > 1 code path)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the other micro-kernel rows (NTT at batch 1/16/256, LDE, Merkle commit) and the config-4 batch")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run the secondary legs (witness generation, host witness, "
+                    "NTT roofline and micro-kernel rows, per-scope times, config-4 batch, CPU baseline) and verify every lane's last proof; "
+                    "--cpu-*, --e2e-*, --host-witness-steps, --ntt-batch, --no-cpu and --no-extra act on those legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the proofs of the last timed step to DIR/*.npy (see the module docstring)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config4:
+        ap.error("--dump-outputs writes the proofs of the default workload's last step; --config4 has no steps")
 
     if "RANK" not in os.environ and (args.gpus > 1 or args.spawn):
         sys.exit(spawn_ranks(args.gpus))
@@ -668,15 +707,19 @@ def main():
         assert gathered.shape == (world * nproofs, 3, 16, 4)
         assert (gathered[rank::world] == np.stack(caps)).all()
 
-    proof_bytes = len(step(0).to_bytes())
-    lanes_verified = sum(1 for pr in last_proof if pr is not None and cd.verify(pr)[0])      # one proof per lane out of the timed loop
-    lanes_with_proofs = sum(1 for pr in last_proof if pr is not None)
+    # a step is `nstreams` proofs, so lane k's last proof is proof k of the last step
+    proof_bytes = len(last_proof[0].to_bytes())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_proof)
+    if args.full:
+        lanes_verified = sum(1 for pr in last_proof if pr is not None and cd.verify(pr)[0])      # one proof per lane out of the timed loop
+        lanes_with_proofs = sum(1 for pr in last_proof if pr is not None)
     if rank == 0:
         value = world * nproofs / dt
         # secondary figure (not `value`): the same loop with witness generation inside the clock -- operands on the host,
         # arithmetic rows filled by the GPU, the sequential public-input hash sponge by the lane's host thread
         e2e = None
-        if args.e2e_steps > 0 and world == 1:                # single-GPU runs only: the scaling runs measure `value`
+        if args.full and args.e2e_steps > 0 and world == 1:  # single-GPU runs only: the scaling runs measure `value`
             # the host part of witness generation (several ms of sequential Poseidon per proof) hides behind the other lanes' GPU work
             nl = args.e2e_lanes if args.e2e_lanes > 0 else nstreams
             el = lanes + [(lambda c: (c, p.api.CircuitView(cd, c)))(p.Context(device=local_rank)) for _ in range(nl - nstreams)]
@@ -709,7 +752,7 @@ def main():
         # secondary figure (not `value`): the drop-in host path.  gl_prove_columns from full HOST witness matrices (135 pageable
         # vectors per proof, as plonk/prover.rs:145 holds them): 35 MB cross PCIe per proof inside the clock
         hostw = None
-        if args.host_witness_steps > 0 and world == 1:
+        if args.full and args.host_witness_steps > 0 and world == 1:
             hw_dt, hw_cpu, hw_res, _hw = host_witness_run(lanes, args.host_witness_steps, nstreams, 4, 900)
             t_same = torch.from_numpy(np.stack(_hw[0][0].cols).view(np.int64)).to(dev)
             torch.cuda.synchronize()
@@ -720,12 +763,15 @@ def main():
                      "pcie_GBs": 135 * hc.n * 8 * args.host_witness_steps / hw_dt / 1e9, "bytes_equal_to_prove_device": bool(same),
                      "entry_point": "gl_prove_columns: 135 pageable host vectors per proof -> two-deep pinned ring -> HBM, then prove()"}
             del hw_res, _hw
-        # the roofline kernel (forward 2^20 NTT x 64) and the Poseidon ceiling always run; --no-extra skips the other micro-kernel rows
-        roofline, ntt, extra, perm_ceiling = ntt_leg(torch, ctx, lib, check, dev, args.ntt_batch, with_rows=not args.no_extra)
-        ctx.timing(True)
-        step(0)
-        scopes = {k: round(v["ms"], 4) for k, v in ctx.timing_report().items()}
-        ctx.timing(False)
+        # with --full the roofline kernel (forward 2^20 NTT x 64) and the Poseidon ceiling always run; --no-extra skips the other
+        # micro-kernel rows
+        roofline, ntt, extra, perm_ceiling, scopes = None, None, None, None, None
+        if args.full:
+            roofline, ntt, extra, perm_ceiling = ntt_leg(torch, ctx, lib, check, dev, args.ntt_batch, with_rows=not args.no_extra)
+            ctx.timing(True)
+            step(0)
+            scopes = {k: round(v["ms"], 4) for k, v in ctx.timing_report().items()}
+            ctx.timing(False)
         out = dict(common)
         out.update({
             "metric": "proofs/sec for m=64 matmul circuit (full prove(), PoseidonGoldilocksConfig, standard_recursion_config)",
@@ -745,7 +791,8 @@ def main():
             "with_witness_generation": e2e,
             "with_host_witness": hostw,
         })
-        out["config"]["lanes_verified_after_the_clock"] = "%d of %d" % (lanes_verified, lanes_with_proofs)
+        if args.full:
+            out["config"]["lanes_verified_after_the_clock"] = "%d of %d" % (lanes_verified, lanes_with_proofs)
         out["host"]["cpu_seconds_timed_region_rank0"] = round(cpu_timed, 3)
         out["host"]["cpu_seconds_per_proof_rank0"] = cpu_timed / max(1, nproofs)
         if perm_ceiling:
@@ -774,13 +821,13 @@ def main():
                                   "(committed profile, not measured in this run)"}
                 except Exception:
                     pass
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             del lanes[1:]
             c4_dt, _, c4_ok = run_config4(args.batch, args.pool_lanes)
             out["config4_batch512"] = {"value": args.batch / c4_dt, "unit": "proofs/s", "proofs": args.batch, "seconds": round(c4_dt, 3), "n_gpus": 1,
                                        "proofs_in_flight": args.pool_lanes, "first_proof_verifies": bool(c4_ok),
                                        "includes": "operands from host memory, witness generation in HBM, prove(); the multi-GPU form is `bench.py --gpus N --config4`"}
-        out["cpu_baseline"] = cpu_baseline(m, rows=args.cpu_rows, one_thread_full=args.cpu_one_thread) if (world == 1 and not args.no_cpu) else None
+        out["cpu_baseline"] = cpu_baseline(m, rows=args.cpu_rows, one_thread_full=args.cpu_one_thread) if (args.full and world == 1 and not args.no_cpu) else None
         if out["cpu_baseline"]:
             # BASELINE.md publishes no number for this metric: the ratio below is against the CPU PORT timed in this run (kind "port"),
             # a reported baseline and not a kernel-quality figure (the roofline fractions are)

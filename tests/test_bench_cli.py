@@ -63,3 +63,62 @@ def test_one_thread_cpu_figure_is_the_committed_measurement():
     d = b.committed_one_thread(64)
     assert d and d["measured"] is True and 0.015 < d["value"] < 0.04 and "profiles/" in d["source"]
     assert b.committed_one_thread(20) is None
+
+
+class _FakeProof:
+    """Stands in for plonky2_demo_amd.api.Proof: random bytes and caps whose words use all 64 bits."""
+    def __init__(self, seed, nbytes):
+        import numpy as np
+        rng = np.random.default_rng(seed)
+        self._bytes = rng.integers(0, 256, nbytes, dtype=np.uint8).tobytes()
+        self._caps = rng.integers(0, 2**64 - 1, (3, 16, 4), dtype=np.uint64, endpoint=True)
+
+    def to_bytes(self):
+        return self._bytes
+
+    def caps(self):
+        return self._caps
+
+
+def _words(halves):
+    import numpy as np
+    return (halves[..., 0].astype(np.uint64) << np.uint64(32)) | halves[..., 1].astype(np.uint64)
+
+
+def test_dump_outputs_hold_the_last_step_exactly(tmp_path):
+    # the m = 64 step: 16 proofs of 250 756 bytes fit the 64 MB whole, as float32 bytes; the caps' 64-bit words as float64 halves
+    import numpy as np
+    b = _bench_module()
+    proofs = [_FakeProof(k, 250756) for k in range(16)]
+    b.dump_outputs(str(tmp_path), proofs)
+    assert sorted(f.name for f in tmp_path.iterdir()) == ["caps.npy", "proof_bytes.npy"]
+    pb, caps = np.load(tmp_path / "proof_bytes.npy"), np.load(tmp_path / "caps.npy")
+    assert pb.dtype == np.float32 and pb.shape == (16, 250756)
+    assert (pb.astype(np.uint8) == np.stack([np.frombuffer(p.to_bytes(), dtype=np.uint8) for p in proofs])).all()
+    assert caps.dtype == np.float64 and caps.shape == (16, 3, 16, 4, 2)
+    assert (_words(caps) == np.stack([p.caps() for p in proofs])).all()
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= b.DUMP_LIMIT_BYTES
+
+
+def test_dump_outputs_of_large_proofs_are_a_fixed_sample_under_64_mb(tmp_path):
+    # m = 256 proofs (1.77 MB each) would be 113 MB as float32: the same seeded byte positions of every proof, listed
+    import numpy as np
+    b = _bench_module()
+    proofs = [_FakeProof(100 + k, 1770000) for k in range(16)]
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), proofs)
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= b.DUMP_LIMIT_BYTES
+    pb, idx = np.load(tmp_path / "a" / "proof_bytes.npy"), np.load(tmp_path / "a" / "proof_bytes_index.npy")
+    assert pb.dtype == np.float32 and idx.dtype == np.float64 and pb.shape == (16, idx.size) and 800000 < idx.size < 1770000
+    raw = np.stack([np.frombuffer(p.to_bytes(), dtype=np.uint8) for p in proofs])
+    assert (pb.astype(np.uint8) == raw[:, idx.astype(np.int64)]).all()
+    assert (np.load(tmp_path / "b" / "proof_bytes.npy") == pb).all() and (np.load(tmp_path / "b" / "proof_bytes_index.npy") == idx).all()
+    assert (_words(np.load(tmp_path / "a" / "caps.npy")) == np.stack([p.caps() for p in proofs])).all()
+
+
+def test_plain_run_options():
+    # --full (off by default) gates the secondary legs; --steps really is the number of timed steps, so it must be positive
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
