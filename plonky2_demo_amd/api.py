@@ -30,7 +30,37 @@ def _log2_strict(n):
     return lg
 
 
-class DeviceBuffer:
+def _verdict(st):
+    """A verifier's status -> (accepted, reason); a status that is neither accept nor reject raises."""
+    if st == _lib.GL_OK:
+        return True, ""
+    if st == _lib.GL_ERR_VERIFY:
+        return False, (lib.gl_last_error() or b"").decode()
+    check(st)
+
+
+class _Owned:
+    """Base of the classes that own a C handle: close() frees `handle` once with the library function named `_free`, or only forgets it
+    when it is borrowed (`handle_owned` False).  The finaliser calls close() and swallows a failure (at interpreter exit the library may
+    be gone already)."""
+    handle = None
+    handle_owned = True
+    _free = None
+
+    def close(self):
+        if self.handle:
+            if self.handle_owned:
+                getattr(lib, self._free)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceBuffer(_Owned):
     def __init__(self, ctx, nbytes):
         self.ctx = ctx
         self.nbytes = int(nbytes)
@@ -55,16 +85,17 @@ class DeviceBuffer:
             check(lib.gl_dev_free(self.ctx.handle, self.ptr))      # a closed context (handle None) is accepted
             self.ptr = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    close = free
 
 
-class Context:
+class Context(_Owned):
     """One per (device, stream).  `stream` may be a raw hipStream_t (int), e.g.
-    torch.cuda.current_stream().cuda_stream, so that torch events bracket the library's kernels."""
+    torch.cuda.current_stream().cuda_stream, so that torch events bracket the library's kernels.
+
+    close() drops this object's reference to the context (gl_ctx_destroy).  Batches / trees / circuits created on it hold references of
+    their own, so they stay valid and may be freed afterwards in any order; buffers from alloc() must be freed before.  The finaliser is
+    safe in any order too: the library tears the context down when its last handle is freed."""
+    _free = "gl_ctx_destroy"
 
     def __init__(self, device=0, stream=None):
         h = ctypes.c_void_p()
@@ -94,21 +125,6 @@ class Context:
         buf = ctypes.create_string_buffer(1 << 16)
         check(lib.gl_ctx_timing_report(self.handle, buf, len(buf)))
         return json.loads(buf.value.decode())
-
-    def close(self):
-        """Drops this object's reference to the context (gl_ctx_destroy).  Batches / trees / circuits created on it hold
-        references of their own, so they stay valid and may be freed afterwards in any order; buffers from alloc() must be
-        freed before."""
-        if self.handle:
-            lib.gl_ctx_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        # safe in any finalisation order: the library tears the context down when its last handle is freed
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 _default = None
@@ -236,8 +252,9 @@ def hash_or_noop(rows, ctx=None):
     return out[0] if single else out
 
 
-class MerkleTree:
+class MerkleTree(_Owned):
     """plonky2::hash::merkle_tree::MerkleTree (merkle_tree.rs:39-207) with device-resident digests."""
+    _free = "gl_merkle_free"
 
     def __init__(self, leaves, cap_height, ctx=None):
         self.ctx = _ctx(ctx)
@@ -266,17 +283,10 @@ class MerkleTree:
         check(lib.gl_merkle_prove(self.handle, leaf_index, _p(out), ctypes.byref(n)))
         return out[: n.value].copy()
 
-    def __del__(self):
-        try:
-            if self.handle:
-                lib.gl_merkle_free(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
-
-class PolynomialBatch:
+class PolynomialBatch(_Owned):
     """plonky2::fri::oracle::PolynomialBatch (fri/oracle.rs:30-133), device-resident."""
+    _free = "gl_batch_free"
 
     def __init__(self, handle, ctx, rate_bits, cap_height):
         self.handle, self.ctx, self.rate_bits, self.cap_height = handle, ctx, rate_bits, cap_height
@@ -349,8 +359,6 @@ class PolynomialBatch:
         check(lib.gl_batch_prove(self.handle, leaf_index, _p(out), ctypes.byref(n)))
         return out[: n.value].copy()
 
-    handle_owned = True     # False for batches borrowed from a circuit
-
     def open_at(self, z, first_col=0, num_cols=None, ctx=None):
         """eval_commitment of OpeningSet::new (plonk/proof.rs:306-344): [num_cols][2] extension values."""
         num_cols = self.ncols - first_col if num_cols is None else num_cols
@@ -358,22 +366,13 @@ class PolynomialBatch:
         check(lib.gl_open_at((ctx or self.ctx).handle, self.handle, _p(_u64(z)), first_col, num_cols, _p(out)))
         return out
 
-    def free(self):
-        if self.handle:
-            if self.handle_owned:
-                lib.gl_batch_free(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    free = _Owned.close     # a batch borrowed from a circuit (handle_owned False) is only forgotten
 
 
 # ------------------------------------------------------------------------------------- circuit and prove()
-class MatmulCircuit:
+class MatmulCircuit(_Owned):
     """Host side of the demo (plonky2/src/bin/matrix_mul.rs:25-67 + CircuitBuilder::build()): needs no GPU."""
+    _free = "gl_host_circuit_free"
 
     def __init__(self, m):
         h = ctypes.c_void_p()
@@ -410,12 +409,7 @@ class MatmulCircuit:
         cap, dig = _u64(constants_sigmas_cap), _u64(circuit_digest)
         if cap.size != 4 << self.desc.cap_height or dig.size != 4:
             raise ValueError("cap must be [2^cap_height][4], digest [4]")
-        st = lib.gl_host_circuit_verify(self.handle, _p(cap), _p(dig), _p(buf), buf.size)
-        if st == _lib.GL_OK:
-            return True, ""
-        if st == _lib.GL_ERR_VERIFY:
-            return False, (lib.gl_last_error() or b"").decode()
-        check(st)
+        return _verdict(lib.gl_host_circuit_verify(self.handle, _p(cap), _p(dig), _p(buf), buf.size))
 
     def witness_generator(self, ctx=None):
         """Witness generation straight into HBM (GPU arithmetic rows + host hash-sponge rows), one per context."""
@@ -425,17 +419,10 @@ class MatmulCircuit:
         """CircuitBuilder::build(): the device half (constants/sigmas commitment, digest)."""
         return CircuitData(self, _ctx(ctx))
 
-    def __del__(self):
-        try:
-            if self.handle:
-                lib.gl_host_circuit_free(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
-
-class WitnessGenerator:
+class WitnessGenerator(_Owned):
     """generate_partial_witness + full_witness (plonk/prover.rs:118-133) for the matmul family, wire matrix in HBM."""
+    _free = "gl_matmul_witgen_free"
 
     def __init__(self, host, ctx):
         self.host, self.ctx = host, ctx
@@ -453,23 +440,16 @@ class WitnessGenerator:
         check(lib.gl_matmul_witgen_run(self.handle, _p(a), _p(b), filler_seed, d_wires_ptr, _p(pis), _p(self.public_inputs_hash)))
         return pis
 
-    def __del__(self):
-        try:
-            if self.handle:
-                lib.gl_matmul_witgen_free(self.handle)
-                self.handle = None
-        except Exception:
-            pass
+def _circuit_digest(handle):
+    out = np.empty(4, dtype=np.uint64)
+    check(lib.gl_circuit_digest(handle, _p(out)))
+    return out
 
 
-def _prove_device(ctx, circuit_handle, n, d_wires_ptr, public_inputs, public_inputs_hash):
-    pis = _u64(public_inputs)
-    h = ctypes.c_void_p()
-    if public_inputs_hash is None:
-        check(lib.gl_prove_device(ctx.handle, circuit_handle, d_wires_ptr, _p(pis), pis.size, ctypes.byref(h)))
-    else:
-        check(lib.gl_prove_device_hashed(ctx.handle, circuit_handle, d_wires_ptr, _p(pis), pis.size, _p(_u64(public_inputs_hash)), ctypes.byref(h)))
-    return Proof(h.value, n)
+def _constants_sigmas_cap(handle, cap_height):
+    out = np.empty((1 << cap_height, 4), dtype=np.uint64)
+    check(lib.gl_circuit_constants_sigmas_cap(handle, _p(out)))
+    return out
 
 
 class HostColumns:
@@ -483,26 +463,64 @@ class HostColumns:
         self.ptrs = (ctypes.c_void_p * 135)(*[c.ctypes.data for c in self.cols])
 
 
-def _prove_columns(ctx, circuit_handle, n, columns, public_inputs):
-    hc = columns if isinstance(columns, HostColumns) else HostColumns(columns, n)
-    pis = _u64(public_inputs)
-    h = ctypes.c_void_p()
-    check(lib.gl_prove_columns(ctx.handle, circuit_handle, hc.ptrs, _p(pis), pis.size, ctypes.byref(h)))
-    return Proof(h.value, n)
+class _CircuitApi(_Owned):
+    """A device-resident circuit (gl_circuit `handle`) used from the context `ctx`: prove() and verify() of
+    plonky2::plonk::circuit_data::CircuitData, and the phase-level seam (SURVEY 8b) for a caller that owns the Challenger.  `desc` is
+    its gl_circuit_desc (by default the library's completed copy: lookup rows read from the selector columns), `n` its degree.
+    Circuits with the lookup argument pass the 8 delta challenges to the phases."""
+    _free = "gl_circuit_free"
 
+    def __init__(self, handle, ctx, desc=None):
+        self.handle, self.ctx = handle, ctx
+        if desc is None:
+            desc = _lib.CircuitDesc()
+            check(lib.gl_circuit_description(handle, ctypes.byref(desc)))
+        self.desc, self.n = desc, 1 << desc.degree_bits
 
-def _warm_up(ctx, handle):
-    check(lib.gl_circuit_warm_up(ctx.handle, handle))
+    @property
+    def circuit_digest(self):
+        return _circuit_digest(self.handle)
 
+    @property
+    def constants_sigmas_cap(self):
+        return _constants_sigmas_cap(self.handle, self.desc.cap_height)
 
-class _PhaseApi:
-    """The phase-level seam of a device-resident circuit, for a caller that owns the Challenger; `self.desc` is the
-    gl_circuit_desc, `self.handle` the gl_circuit.  Circuits with the lookup argument pass the 8 delta challenges."""
+    def verify(self, proof):
+        """CircuitData::verify (plonk/circuit_data.rs:153-155): (accepted, reason); `proof` is a Proof or its bytes.  Host code."""
+        by = proof.to_bytes() if hasattr(proof, "to_bytes") else proof
+        buf = np.frombuffer(bytes(by), dtype=np.uint8)
+        return _verdict(lib.gl_verify(ctypes.byref(self.desc), _p(self.constants_sigmas_cap), _p(self.circuit_digest), _p(buf), buf.size))
+
+    def _prove(self, entry, wires_ptr, public_inputs, *hash_arg):
+        pis = _u64(public_inputs)
+        keep = pis if pis.size else np.zeros(1, dtype=np.uint64)          # a valid pointer even for zero public inputs
+        h = ctypes.c_void_p()
+        check(entry(self.ctx.handle, self.handle, wires_ptr, _p(keep), pis.size, *hash_arg, ctypes.byref(h)))
+        return Proof(h.value, self.desc)
+
+    def prove(self, wires, public_inputs):
+        """CircuitData::prove (circuit_data.rs:144-151) at the full-witness boundary: the wire matrix [135][n] on the host."""
+        wires = _u64(wires)
+        if wires.shape != (135, self.n):
+            raise ValueError("wire matrix must be [135][n]")
+        return self._prove(lib.gl_prove, _p(wires), public_inputs)
+
+    def prove_columns(self, columns, public_inputs):
+        """prove() from one host array per wire, as the reference keeps MatrixWitness.wire_values (iop/witness.rs:256-258):
+        the drop-in entry INTEGRATION.md patches into plonk/prover.rs:145.  `columns` may be a HostColumns (pointer table built once)."""
+        hc = columns if isinstance(columns, HostColumns) else HostColumns(columns, self.n)
+        return self._prove(lib.gl_prove_columns, hc.ptrs, public_inputs)
+
+    def prove_device(self, d_wires_ptr, public_inputs, public_inputs_hash=None):
+        """prove() with the witness matrix already in HBM (raw device pointer to [135][n] u64)."""
+        if public_inputs_hash is None:
+            return self._prove(lib.gl_prove_device, d_wires_ptr, public_inputs)
+        return self._prove(lib.gl_prove_device_hashed, d_wires_ptr, public_inputs, _p(_u64(public_inputs_hash)))
 
     def warm_up(self, ctx=None):
-        """gl_circuit_warm_up: one throw-away pass of the proving pipeline on `ctx` (default: the circuit's context), so that the first
+        """gl_circuit_warm_up: one throw-away pass of the proving pipeline on `ctx` (default: this object's context), so that the first
         proof does not pay the one-time costs (kernel code objects, twiddle tables, pool growth)."""
-        _warm_up(_ctx(ctx) if ctx is not None else self.ctx, self.handle)
+        check(lib.gl_circuit_warm_up((ctx or self.ctx).handle, self.handle))
         return self
 
     def _batch(self, handle, ctx):
@@ -542,115 +560,37 @@ class _PhaseApi:
         return FriProver(self, batches, zeta, alpha, ctx or self.ctx)
 
 
-class CircuitData(_PhaseApi):
-    """plonky2::plonk::circuit_data::CircuitData for the prover: `prove(wires, public_inputs)` mirrors
-    CircuitData::prove (circuit_data.rs:144-151) at the full-witness boundary."""
+class CircuitData(_CircuitApi):
+    """The matmul demo's CircuitData, built from its host circuit (gl_circuit_from_host)."""
 
     def __init__(self, host, ctx):
-        self.host, self.ctx, self.desc = host, ctx, host.desc
         h = ctypes.c_void_p()
         check(lib.gl_circuit_from_host(ctx.handle, host.handle, ctypes.byref(h)))
-        self.handle = h.value
-
-    @property
-    def circuit_digest(self):
-        out = np.empty(4, dtype=np.uint64)
-        check(lib.gl_circuit_digest(self.handle, _p(out)))
-        return out
-
-    @property
-    def constants_sigmas_cap(self):
-        out = np.empty((1 << self.host.desc.cap_height, 4), dtype=np.uint64)
-        check(lib.gl_circuit_constants_sigmas_cap(self.handle, _p(out)))
-        return out
-
-    def verify(self, proof):
-        """CircuitData::verify (plonk/circuit_data.rs:153-155); `proof` is a Proof or its bytes."""
-        by = proof.to_bytes() if hasattr(proof, "to_bytes") else proof
-        return self.host.verify(by, self.constants_sigmas_cap, self.circuit_digest)
-
-    def prove(self, wires, public_inputs):
-        wires, pis = _u64(wires), _u64(public_inputs)
-        if wires.shape != (135, self.host.n):
-            raise ValueError("wire matrix must be [135][n]")
-        h = ctypes.c_void_p()
-        check(lib.gl_prove(self.ctx.handle, self.handle, _p(wires), _p(pis), pis.size, ctypes.byref(h)))
-        return Proof(h.value, self.host.n)
-
-    def prove_columns(self, columns, public_inputs):
-        """prove() from one host array per wire, as the reference keeps MatrixWitness.wire_values (iop/witness.rs:256-258):
-        the drop-in entry INTEGRATION.md patches into plonk/prover.rs:145.  `columns` may be a HostColumns (pointer table built once)."""
-        return _prove_columns(self.ctx, self.handle, self.host.n, columns, public_inputs)
-
-    def prove_device(self, d_wires_ptr, public_inputs, public_inputs_hash=None):
-        """prove() with the witness matrix already in HBM (raw device pointer to [135][n] u64)."""
-        return _prove_device(self.ctx, self.handle, self.host.n, d_wires_ptr, public_inputs, public_inputs_hash)
-
-    def __del__(self):
-        try:
-            if self.handle:
-                lib.gl_circuit_free(self.handle)
-                self.handle = None
-        except Exception:
-            pass
+        super().__init__(h.value, ctx, host.desc)
+        self.host = host
 
 
-class GenericCircuitData(_PhaseApi):
+class GenericCircuitData(_CircuitApi):
     """Prover + verifier for ANY circuit over the demo's gate set, given what CircuitBuilder::build() produces: the descriptor
     (CommonCircuitData) and the constants || sigmas value columns (gl_circuit_create)."""
 
     def __init__(self, desc, constants_sigmas, ctx=None):
-        self.ctx, self.desc = _ctx(ctx), desc
-        self.n = 1 << desc.degree_bits
+        ctx = _ctx(ctx)
         cs = _u64(constants_sigmas)
-        if cs.shape != (desc.num_constants + 80, self.n):
+        if cs.shape != (desc.num_constants + 80, 1 << desc.degree_bits):
             raise ValueError("constants_sigmas must be [num_constants + 80][n]")
         h = ctypes.c_void_p()
-        check(lib.gl_circuit_create(self.ctx.handle, ctypes.byref(desc), _p(cs), ctypes.byref(h)))
-        self.handle = h.value
-        self.desc = type(desc)()                      # the completed description (lookup rows read from the selector columns)
-        check(lib.gl_circuit_description(self.handle, ctypes.byref(self.desc)))
+        check(lib.gl_circuit_create(ctx.handle, ctypes.byref(desc), _p(cs), ctypes.byref(h)))
+        super().__init__(h.value, ctx)
 
-    @property
-    def circuit_digest(self):
-        out = np.empty(4, dtype=np.uint64)
-        check(lib.gl_circuit_digest(self.handle, _p(out)))
-        return out
 
-    @property
-    def constants_sigmas_cap(self):
-        out = np.empty((1 << self.desc.cap_height, 4), dtype=np.uint64)
-        check(lib.gl_circuit_constants_sigmas_cap(self.handle, _p(out)))
-        return out
+class CircuitView(_CircuitApi):
+    """The same device-resident CircuitData (or GenericCircuitData) used from another context (stream) of the same device."""
+    handle_owned = False
 
-    def prove(self, wires, public_inputs):
-        wires, pis = _u64(wires), _u64(public_inputs)
-        if wires.shape != (135, self.n):
-            raise ValueError("wire matrix must be [135][n]")
-        if pis.size == 0:
-            pis = np.zeros(1, dtype=np.uint64)[:0]
-        h = ctypes.c_void_p()
-        keep = np.zeros(1, dtype=np.uint64) if pis.size == 0 else pis          # a valid pointer even for zero public inputs
-        check(lib.gl_prove(self.ctx.handle, self.handle, _p(wires), _p(keep), pis.size, ctypes.byref(h)))
-        return Proof(h.value, self.n)
-
-    def verify(self, proof):
-        by = proof.to_bytes() if hasattr(proof, "to_bytes") else proof
-        buf = np.frombuffer(bytes(by), dtype=np.uint8)
-        st = lib.gl_verify(ctypes.byref(self.desc), _p(self.constants_sigmas_cap), _p(self.circuit_digest), _p(buf), buf.size)
-        if st == _lib.GL_OK:
-            return True, ""
-        if st == _lib.GL_ERR_VERIFY:
-            return False, (lib.gl_last_error() or b"").decode()
-        check(st)
-
-    def __del__(self):
-        try:
-            if self.handle:
-                lib.gl_circuit_free(self.handle)
-                self.handle = None
-        except Exception:
-            pass
+    def __init__(self, circuit_data, ctx):
+        super().__init__(circuit_data.handle, ctx, circuit_data.desc)
+        self.cd = circuit_data          # the owner of the handle outlives the view
 
 
 # ------------------------------------------------------------------------------- circuit data as bytes (host code)
@@ -700,17 +640,13 @@ def verify_bytes(verifier_data, proof_bytes):
     """VerifierCircuitData::from_bytes(verifier_data).verify(proof): (accepted, reason)."""
     vd = np.frombuffer(bytes(verifier_data), dtype=np.uint8)
     pb = np.frombuffer(bytes(proof_bytes), dtype=np.uint8)
-    st = lib.gl_verify_bytes(_p(vd), vd.size, _p(pb), pb.size)
-    if st == _lib.GL_OK:
-        return True, ""
-    if st == _lib.GL_ERR_VERIFY:
-        return False, (lib.gl_last_error() or b"").decode()
-    check(st)
+    return _verdict(lib.gl_verify_bytes(_p(vd), vd.size, _p(pb), pb.size))
 
 
-class GenericProverPool:
+class GenericProverPool(_Owned):
     """gl_prover_pool_create_generic / _prove_columns: `lanes` warmed-up contexts and host threads inside the library for ANY circuit
     (description + constants || sigmas); a batch of host witnesses (135 column vectors each) becomes one call."""
+    _free = "gl_prover_pool_free"
 
     def __init__(self, desc, constants_sigmas, lanes=4, device=0):
         self.desc, self.n = desc, 1 << desc.degree_bits
@@ -738,24 +674,14 @@ class GenericProverPool:
             pi_ptrs[i] = pv.ctypes.data if pv.size else None
         out = (ctypes.c_void_p * k)()
         st = lib.gl_prover_pool_prove_columns(self.handle, k, col_ptrs, pi_ptrs, out)
-        proofs = [Proof(out[i], self.n) if out[i] else None for i in range(k)]
+        proofs = [Proof(out[i], self.desc) if out[i] else None for i in range(k)]
         check(st)
         return proofs
 
-    def close(self):
-        if self.handle:
-            lib.gl_prover_pool_free(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class ProverPool:
+class ProverPool(_Owned):
     """Many proofs in flight on one GPU from one call (gl_prover_pool_*): one circuit, `lanes` streams and host threads in C++."""
+    _free = "gl_prover_pool_free"
 
     def __init__(self, host, lanes=4, device=0):
         self.host = host
@@ -765,15 +691,11 @@ class ProverPool:
 
     @property
     def circuit_digest(self):
-        out = np.empty(4, dtype=np.uint64)
-        check(lib.gl_circuit_digest(lib.gl_prover_pool_circuit(self.handle), _p(out)))
-        return out
+        return _circuit_digest(lib.gl_prover_pool_circuit(self.handle))
 
     @property
     def constants_sigmas_cap(self):
-        out = np.empty((1 << self.host.desc.cap_height, 4), dtype=np.uint64)
-        check(lib.gl_circuit_constants_sigmas_cap(lib.gl_prover_pool_circuit(self.handle), _p(out)))
-        return out
+        return _constants_sigmas_cap(lib.gl_prover_pool_circuit(self.handle), self.host.desc.cap_height)
 
     def prove_matmul(self, operands, filler_seeds=None):
         """operands: list of (a, b) m x m arrays; returns the list of Proof objects in the same order."""
@@ -788,42 +710,14 @@ class ProverPool:
         seeds = None if filler_seeds is None else np.ascontiguousarray(np.asarray(filler_seeds, dtype=np.uint64))
         out = (ctypes.c_void_p * k)()
         st = lib.gl_prover_pool_prove_matmul(self.handle, k, pa, pb, _p(seeds) if seeds is not None else None, out)
-        proofs = [Proof(out[i], self.host.n) if out[i] else None for i in range(k)]      # owned from here on: freed even when a lane failed
+        proofs = [Proof(out[i], self.host.desc) if out[i] else None for i in range(k)]      # owned from here on: freed even when a lane failed
         check(st)
         return proofs
 
-    def close(self):
-        if self.handle:
-            lib.gl_prover_pool_free(self.handle)
-            self.handle = None
 
-
-class CircuitView:
-    """The same device-resident CircuitData used from another context (stream) of the same device."""
-
-    def __init__(self, circuit_data, ctx):
-        self.cd, self.ctx = circuit_data, ctx
-        self.n = 1 << circuit_data.desc.degree_bits          # CircuitData and GenericCircuitData both carry the description
-
-    def prove_device(self, d_wires_ptr, public_inputs, public_inputs_hash=None):
-        return _prove_device(self.ctx, self.cd.handle, self.n, d_wires_ptr, public_inputs, public_inputs_hash)
-
-    def prove(self, wires, public_inputs):
-        wires, pis = _u64(wires), _u64(public_inputs)
-        if wires.shape != (135, self.n):
-            raise ValueError("wire matrix must be [135][n]")
-        if pis.size == 0:
-            pis = np.zeros(1, dtype=np.uint64)[:0]
-        h = ctypes.c_void_p()
-        check(lib.gl_prove(self.ctx.handle, self.cd.handle, _p(wires), _p(pis), pis.size, ctypes.byref(h)))
-        return Proof(h.value, self.n)
-
-    def prove_columns(self, columns, public_inputs):
-        return _prove_columns(self.ctx, self.cd.handle, self.n, columns, public_inputs)
-
-
-class FriProver:
+class FriProver(_Owned):
     """fri_proof (fri/prover.rs:20-66) split at every transcript dependency."""
+    _free = "gl_fri_free"
 
     def __init__(self, cd, batches, zeta, alpha, ctx):
         self.ctx, self.cd, self.batches = ctx, cd, list(batches)     # the batches must outlive the FRI state
@@ -855,17 +749,10 @@ class FriProver:
         check(lib.gl_fri_query(self.handle, _p(xi), xi.size, _p(blob), blob.size, ctypes.byref(k)))
         return blob.tobytes()
 
-    def __del__(self):
-        try:
-            if self.handle:
-                lib.gl_fri_free(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
-
-class Challenger:
+class Challenger(_Owned):
     """plonky2::iop::challenger::Challenger (iop/challenger.rs:30-153), host code."""
+    _free = "gl_challenger_free"
 
     def __init__(self):
         self.handle = lib.gl_challenger_new()
@@ -885,14 +772,6 @@ class Challenger:
         check(lib.gl_challenger_state(self.handle, _p(st), _p(buf), ctypes.byref(k)))
         return st, buf[: k.value].copy()
 
-    def __del__(self):
-        try:
-            if self.handle:
-                lib.gl_challenger_free(self.handle)
-                self.handle = None
-        except Exception:
-            pass
-
 
 def pow_grind(sponge_state, input_buffer, min_leading_zeros, ctx=None):
     """fri_proof_of_work (fri/prover.rs:115-160): the smallest valid witness."""
@@ -905,9 +784,12 @@ def pow_grind(sponge_state, input_buffer, min_leading_zeros, ctx=None):
     return int(w[0])
 
 
-class Proof:
-    def __init__(self, handle, n):
-        self.handle, self.n = handle, n
+class Proof(_Owned):
+    """A proof of the circuit described by `desc` (gl_circuit_desc), which fixes the shapes of what it holds."""
+    _free = "gl_proof_free"
+
+    def __init__(self, handle, desc):
+        self.handle, self.desc, self.n = handle, desc, 1 << desc.degree_bits
 
     def to_bytes(self):
         """ProofWithPublicInputs::to_bytes (plonk/proof.rs:104-110)."""
@@ -924,13 +806,17 @@ class Proof:
                 "public_inputs_hash": v[11:15], "fri_betas": [v[i:i + 2] for i in range(15, k, 2)]}
 
     def caps(self):
-        out = np.empty((3, 16, 4), dtype=np.uint64)
+        """wires_cap, plonk_zs_partial_products_cap, quotient_polys_cap: [3][2^cap_height][4]."""
+        out = np.empty((3, 1 << self.desc.cap_height, 4), dtype=np.uint64)
         check(lib.gl_proof_caps(self.handle, _p(out)))
         return out
 
-    def zs_partial_products(self, ncols=20):
-        """Z and partial products as value columns; 34 columns for a circuit with lookups (the lookup polynomials follow)."""
-        out = np.empty((ncols, self.n), dtype=np.uint64)
+    def zs_partial_products(self, ncols=None):
+        """Z and partial products as value columns, then the lookup polynomials: [20 + 2 num_lookup_polys][n]."""
+        want = 20 + 2 * self.desc.num_lookup_polys
+        if ncols is not None and ncols != want:
+            raise ValueError("this proof holds %d Z / partial-product / lookup columns, not %d" % (want, ncols))
+        out = np.empty((want, self.n), dtype=np.uint64)
         check(lib.gl_proof_zs_partial_products(self.handle, _p(out)))
         return out
 
@@ -943,11 +829,3 @@ class Proof:
         out = np.zeros(256, dtype=np.uint64)
         k = lib.gl_proof_query_indices(self.handle, _p(out))
         return [int(x) for x in out[:k]]
-
-    def __del__(self):
-        try:
-            if self.handle:
-                lib.gl_proof_free(self.handle)
-                self.handle = None
-        except Exception:
-            pass

@@ -109,6 +109,23 @@ inline void host_hash_no_pad(const gl_t* in, size_t n, gl_t* out4) {     // hash
     for (int i = 0; i < 4; i++) out4[i] = gl_canon(s[i]);
 }
 
+// Challenger (iop/challenger.rs:30-153): the prover's transcript and the verifier's
+struct HostChallenger {
+    gl_t state[12]; gl_t in[8]; int nin = 0; gl_t out[8]; int nout = 0;
+    HostChallenger() { for (auto& s : state) s = 0; }
+    void duplexing() {
+        for (int i = 0; i < nin; i++) state[i] = in[i];
+        nin = 0;
+        psd_permute(state);
+        for (int i = 0; i < 8; i++) out[i] = state[i];
+        nout = 8;
+    }
+    void observe(gl_t x) { nout = 0; in[nin++] = x; if (nin == 8) duplexing(); }
+    void observe_many(const gl_t* v, size_t n) { for (size_t i = 0; i < n; i++) observe(v[i]); }
+    gl_t challenge() { if (nin || !nout) duplexing(); return gl_canon(out[--nout]); }
+    gl2_t challenge_ext() { gl2_t r; r.a = challenge(); r.b = challenge(); return r; }
+};
+
 struct HostCircuit {
     gl_circuit_desc desc;
     size_t m = 0, n = 0;

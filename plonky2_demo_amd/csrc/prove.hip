@@ -8,7 +8,16 @@
 #include <cstring>
 #include <memory>
 
+using glhost::HostChallenger;
 using glhost::HostCircuit;
+
+// The context's 1 MiB device staging area (gl_ctx::dev_small), in words, as this file slices it
+static constexpr size_t DS_BYTES = size_t(1) << 20, DS_WORDS = DS_BYTES / sizeof(gl_t);
+static constexpr size_t DS_APOW = 0, DS_APOW_WORDS = 2 * GLQ_MAX_TERMS;            // quotient: alpha^t per challenge
+static constexpr size_t DS_ZH = DS_APOW + DS_APOW_WORDS, DS_ZH_WORDS = 8;          // build(): Z_H on the coset, for L_0
+static constexpr size_t DS_POW = DS_ZH + DS_ZH_WORDS, DS_POW_WORDS = 1;            // proof-of-work result
+static constexpr size_t DS_OPEN = 4096, DS_OPEN_MAX = 4096, DS_OPEN_WORDS = 2 * DS_OPEN_MAX;   // openings: <= 4096 extension values
+static_assert(DS_POW + DS_POW_WORDS <= DS_OPEN && DS_OPEN + DS_OPEN_WORDS <= DS_WORDS, "dev_small slices overlap or do not fit");
 
 struct gl_circuit {
     gl_ctx* ctx = nullptr;
@@ -27,22 +36,6 @@ struct gl_proof {
     std::vector<gl_t> zs_pp;          // [20][n]
     std::vector<gl_t> quotient;       // [16][n]
     std::vector<uint64_t> query_indices;
-};
-
-// ---- host Challenger (iop/challenger.rs:30-153) -----------------------------------------------------------------
-struct HostChallenger {
-    gl_t state[12]; gl_t in[8]; int nin = 0; gl_t out[8]; int nout = 0;
-    HostChallenger() { for (auto& s : state) s = 0; }
-    void duplexing() {
-        for (int i = 0; i < nin; i++) state[i] = in[i];
-        nin = 0;
-        psd_permute(state);
-        for (int i = 0; i < 8; i++) out[i] = state[i];
-        nout = 8;
-    }
-    void observe(gl_t x) { nout = 0; in[nin++] = x; if (nin == 8) duplexing(); }
-    void observe_many(const gl_t* v, size_t n) { for (size_t i = 0; i < n; i++) observe(v[i]); }
-    gl_t challenge() { if (nin || !nout) duplexing(); return gl_canon(out[--nout]); }
 };
 
 // C handle of the Challenger for callers of the phase API that have no transcript of their own (C / C++ / Python)
@@ -166,6 +159,13 @@ static int lookup_rows_from_selectors(gl_circuit_desc& d, const uint64_t* h_cons
 
 int gl_sigmas_from_classes(gl_ctx* c, const uint64_t* d_classes, uint32_t lgn, uint32_t ncols, const uint64_t* h_k_is, gl_t* d_sigma);      // sigma.hip
 
+// Z_H = X^n - 1 on the LDE coset 7 H_N, which takes the 8 values (7 w_8^i)^n - 1 (ZeroPolyOnCoset, field/src/zero_poly_coset.rs:19-36)
+static void zh_on_coset(const gl_circuit_desc& d, gl_t zh[8]) {
+    gl_t g_pow_n = GL_MULT_GENERATOR; for (uint32_t i = 0; i < d.degree_bits; i++) g_pow_n = gl_sqr(g_pow_n);
+    gl_t w8 = gl_host_root_of_unity(d.rate_bits), x = 1;
+    for (int i = 0; i < 8; i++) { zh[i] = gl_canon(gl_sub(gl_mul(g_pow_n, x), 1)); x = gl_mul(x, w8); }
+}
+
 // the rest of the device half of build() once the constants || sigmas VALUE columns are in HBM (d_cs[num_constants + 80][n])
 static int circuit_finish(gl_ctx* ctx, const gl_circuit_desc* desc, const gl_t* d_cs, gl_circuit** out) {
     std::unique_ptr<gl_circuit, void (*)(gl_circuit*)> c(new gl_circuit(), gl_circuit_free);
@@ -180,13 +180,12 @@ static int circuit_finish(gl_ctx* ctx, const gl_circuit_desc* desc, const gl_t* 
         GL_TRY(ctx->pool_alloc(N * sizeof(gl_t), (void**)&c->d_l0_coset));
         GlPowTable xt;
         GL_TRY(ctx->get_pow_table(gl_host_root_of_unity(lgN), GL_MULT_GENERATOR, (uint32_t)((N + 2047) >> 11), &xt));
-        gl_t zh[8];
-        gl_t g_pow_n = GL_MULT_GENERATOR; for (uint32_t i = 0; i < desc->degree_bits; i++) g_pow_n = gl_sqr(g_pow_n);
-        gl_t w8 = gl_host_root_of_unity(desc->rate_bits), x = 1;
-        for (int i = 0; i < 8; i++) { zh[i] = gl_canon(gl_sub(gl_mul(g_pow_n, x), 1)); x = gl_mul(x, w8); }
-        GL_TRY(ctx->ensure_dev_small(1 << 20));
-        GL_TRY(gl_copy_h2d(ctx, ctx->dev_small, zh, sizeof zh));
-        hipLaunchKernelGGL(k_l0_on_coset, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, xt.lo, xt.hi, (uint32_t)N, (gl_t)n, ctx->dev_small, c->d_l0_coset);
+        gl_t zh[DS_ZH_WORDS];
+        zh_on_coset(*desc, zh);
+        GL_TRY(ctx->ensure_dev_small(DS_BYTES));
+        gl_t* d_zh = ctx->dev_small + DS_ZH;
+        GL_TRY(gl_copy_h2d(ctx, d_zh, zh, sizeof zh));
+        hipLaunchKernelGGL(k_l0_on_coset, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, xt.lo, xt.hi, (uint32_t)N, (gl_t)n, d_zh, c->d_l0_coset);
         GL_CHECK_HIP(hipGetLastError());
         GL_CHECK_HIP(gl_stream_wait(ctx->stream));
     }
@@ -426,15 +425,22 @@ static int check_batch(const gl_circuit* cir, const gl_batch* b, size_t ncols, c
     GL_REQUIRE(b && b->ncols == ncols && b->n == cir->n && b->rate_bits == cir->desc.rate_bits && b->cap_height == cir->desc.cap_height, GL_ERR_ARG, what);
     return GL_OK;
 }
+// Z || partial products (|| lookup polynomials) -> committed batch (prover.rs:189-223), for gl_partial_products[_lookups] and prove().
+// `deltas8` is null exactly for a circuit without lookups; `capture`, if given, receives the value columns.
+static int commit_zs(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, const gl_t* betas, const gl_t* gammas, const gl_t* deltas8,
+                     gl_batch** out, std::vector<gl_t>* capture) {
+    const size_t n = cir->n, nzs = 20 + 2 * (size_t)cir->desc.num_lookup_polys;
+    DevBuf d_zs(ctx); GL_TRY(d_zs.alloc(nzs * n * sizeof(gl_t)));
+    GL_TRY(partial_products_values(ctx, cir, d_wires, betas, gammas, d_zs.as<gl_t>()));
+    if (deltas8) GL_TRY(lookup_polys_values(ctx, cir, d_wires, deltas8, d_zs.as<gl_t>() + 20 * n));
+    if (capture) { capture->resize(nzs * n); GL_TRY(d2h(ctx, capture->data(), d_zs.p, nzs * n * sizeof(gl_t))); }
+    return gl_batch_from_device(ctx, d_zs.as<uint64_t>(), nzs, n, cir->desc.rate_bits, cir->desc.cap_height, 1, out);
+}
 static int partial_products_phase(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* d_wires, const uint64_t* betas, const uint64_t* gammas, const uint64_t* deltas8, gl_batch** out) {
     GL_TRY(check_phase_args(ctx, cir));
     GL_REQUIRE(d_wires && betas && gammas && out, GL_ERR_ARG, "gl_partial_products: null argument");
-    const size_t nlk = 2 * (size_t)cir->desc.num_lookup_polys, nzs = 20 + nlk;
-    GL_REQUIRE((nlk != 0) == (deltas8 != nullptr), GL_ERR_ARG, "circuits with lookups take gl_partial_products_lookups (with the delta challenges), circuits without take gl_partial_products");
-    DevBuf d_zs(ctx); GL_TRY(d_zs.alloc(nzs * cir->n * sizeof(gl_t)));
-    GL_TRY(partial_products_values(ctx, cir, d_wires, betas, gammas, d_zs.as<gl_t>()));
-    if (nlk) GL_TRY(lookup_polys_values(ctx, cir, d_wires, deltas8, d_zs.as<gl_t>() + 20 * cir->n));
-    return gl_batch_from_device(ctx, d_zs.as<uint64_t>(), nzs, cir->n, cir->desc.rate_bits, cir->desc.cap_height, 1, out);
+    GL_REQUIRE((cir->desc.num_lookup_polys != 0) == (deltas8 != nullptr), GL_ERR_ARG, "circuits with lookups take gl_partial_products_lookups (with the delta challenges), circuits without take gl_partial_products");
+    return commit_zs(ctx, cir, d_wires, betas, gammas, deltas8, out, nullptr);
 }
 extern "C" int gl_partial_products(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* d_wires, const uint64_t betas[2], const uint64_t gammas[2], gl_batch** out) {
     return partial_products_phase(ctx, cir, d_wires, betas, gammas, nullptr, out);
@@ -445,33 +451,33 @@ extern "C" int gl_partial_products_lookups(gl_ctx* ctx, const gl_circuit* cir, c
     return partial_products_phase(ctx, cir, d_wires, betas, gammas, deltas, out);
 }
 
-// ---- 9. compute_quotient_polys + split (plonk/prover.rs:229-258,574-744): d_q[2][8n] -> the 16 chunk COEFFICIENT columns ----
-static int quotient_chunks(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* wires, const gl_batch* zs, const gl_t* pi_hash,
-                           const gl_t* betas, const gl_t* gammas, const gl_t* alphas, gl_t* d_q, std::vector<gl_t>& apow, const gl_t* deltas8 = nullptr) {
+// ---- 9/10. compute_quotient_polys + split + commitment (plonk/prover.rs:229-271,574-744), for gl_quotient_polys[_lookups] and prove():
+//      d_q[2][8n] -> the 16 chunk COEFFICIENT columns -> committed batch.  `apow` is the host source of an asynchronous upload: the caller
+//      keeps it alive up to its next sync.  `deltas8` is null exactly for a circuit without lookups; `capture` receives the chunks. ----
+static int commit_quotient(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* wires, const gl_batch* zs, const gl_t* pi_hash, const gl_t* betas,
+                           const gl_t* gammas, const gl_t* alphas, const gl_t* deltas8, std::vector<gl_t>& apow, gl_batch** out, std::vector<gl_t>* capture) {
     const gl_circuit_desc& d = cir->desc;
     const size_t n = cir->n, N = n << d.rate_bits;
-    const uint32_t lgn = d.degree_bits, lgN = lgn + d.rate_bits;
+    const uint32_t lgN = d.degree_bits + d.rate_bits;
     hipStream_t st = ctx->stream;
-    apow.assign(2 * GLQ_MAX_TERMS, 0);
+    DevBuf d_q(ctx); GL_TRY(d_q.alloc(2 * N * sizeof(gl_t)));
+    apow.assign(DS_APOW_WORDS, 0);
     for (int b = 0; b < 2; b++) { gl_t x = 1; const gl_t al = gl_canon(alphas[b]); for (int t = 0; t < GLQ_MAX_TERMS; t++) { apow[b * GLQ_MAX_TERMS + t] = x; x = gl_canon(gl_mul(x, al)); } }
-    GL_TRY(ctx->ensure_dev_small(1 << 20));
-    gl_t* d_apow = ctx->dev_small;
+    GL_TRY(ctx->ensure_dev_small(DS_BYTES));
+    gl_t* d_apow = ctx->dev_small + DS_APOW;
     GL_TRY(h2d_async(ctx, d_apow, apow.data(), apow.size() * sizeof(gl_t)));
     GlPowTable xt;
     GL_TRY(ctx->get_pow_table(gl_host_root_of_unity(lgN), GL_MULT_GENERATOR, (uint32_t)((N + 2047) >> 11), &xt));
     GlQuotParams q;
     ::memset((void*)&q, 0, sizeof q);
     q.cs = cir->cs_batch->lde; q.wires = wires->lde; q.zs = zs->lde; q.xpow_lo = xt.lo; q.xpow_hi = xt.hi;
-    q.alpha_pows = d_apow; q.out = d_q;
+    q.alpha_pows = d_apow; q.out = d_q.as<gl_t>();
     for (int j = 0; j < 80; j++) q.k_is[j] = d.k_is[j];
     q.k_is_powers_of_7 = k_is_are_powers_of_7(d);
     for (int i = 0; i < 2; i++) { q.betas[i] = gl_canon(betas[i]); q.gammas[i] = gl_canon(gammas[i]); }
     for (int i = 0; i < 4; i++) q.pi_hash[i] = gl_canon(pi_hash[i]);
-    {   // ZeroPolyOnCoset (field/src/zero_poly_coset.rs:19-36)
-        gl_t g_pow_n = GL_MULT_GENERATOR; for (uint32_t i = 0; i < lgn; i++) g_pow_n = gl_sqr(g_pow_n);
-        gl_t w8 = gl_host_root_of_unity(d.rate_bits), x = 1;
-        for (int i = 0; i < 8; i++) { q.zh_evals[i] = gl_canon(gl_sub(gl_mul(g_pow_n, x), 1)); q.zh_inv[i] = gl_canon(gl_inv(q.zh_evals[i])); x = gl_mul(x, w8); }
-    }
+    zh_on_coset(d, q.zh_evals);
+    for (int i = 0; i < 8; i++) q.zh_inv[i] = gl_canon(gl_inv(q.zh_evals[i]));
     q.l0_coset = cir->d_l0_coset;
     q.n_field = (gl_t)n; q.lgN = lgN; q.num_constants = d.num_constants; q.num_selectors = d.num_selectors; q.num_gates = d.num_gates;
     q.next_step = 1u << d.rate_bits;
@@ -498,18 +504,9 @@ static int quotient_chunks(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* w
     ctx->timing_end();
     GL_CHECK_HIP(hipGetLastError());
     // coset_ifft(7) of each quotient (prover.rs:739-743); the 8n coefficients ARE the 8 chunks of n (prover.rs:245-258)
-    return gl_ntt_run(ctx, d_q, N, (uint32_t)N, d_q, N, lgN, 2, true, 0, gl_canon(gl_inv(GL_MULT_GENERATOR)), gl_host_inverse_2exp(lgN));
-}
-static int quotient_phase(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* wires, const gl_batch* zs_partial_products, const uint64_t* pi_hash,
-                          const uint64_t* betas, const uint64_t* gammas, const uint64_t* alphas, const uint64_t* deltas8, gl_batch** out);
-extern "C" int gl_quotient_polys(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* wires, const gl_batch* zs_partial_products, const uint64_t pi_hash[4],
-                                 const uint64_t betas[2], const uint64_t gammas[2], const uint64_t alphas[2], gl_batch** out) {
-    return quotient_phase(ctx, cir, wires, zs_partial_products, pi_hash, betas, gammas, alphas, nullptr, out);
-}
-extern "C" int gl_quotient_polys_lookups(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* wires, const gl_batch* zs_partial_products_lookups, const uint64_t pi_hash[4],
-                                         const uint64_t betas[2], const uint64_t gammas[2], const uint64_t alphas[2], const uint64_t deltas[8], gl_batch** out) {
-    GL_REQUIRE(deltas, GL_ERR_ARG, "gl_quotient_polys_lookups: null deltas");
-    return quotient_phase(ctx, cir, wires, zs_partial_products_lookups, pi_hash, betas, gammas, alphas, deltas, out);
+    GL_TRY(gl_ntt_run(ctx, d_q.as<gl_t>(), N, (uint32_t)N, d_q.as<gl_t>(), N, lgN, 2, true, 0, gl_canon(gl_inv(GL_MULT_GENERATOR)), gl_host_inverse_2exp(lgN)));
+    if (capture) { capture->resize(16 * n); GL_TRY(d2h(ctx, capture->data(), d_q.p, 16 * n * sizeof(gl_t))); }
+    return gl_batch_from_device(ctx, d_q.as<uint64_t>(), 16, n, d.rate_bits, d.cap_height, 0, out);
 }
 static int quotient_phase(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* wires, const gl_batch* zs_partial_products, const uint64_t* pi_hash,
                           const uint64_t* betas, const uint64_t* gammas, const uint64_t* alphas, const uint64_t* deltas8, gl_batch** out) {
@@ -519,13 +516,19 @@ static int quotient_phase(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* wi
     GL_REQUIRE((nlk != 0) == (deltas8 != nullptr), GL_ERR_ARG, "circuits with lookups take gl_quotient_polys_lookups (with the delta challenges), circuits without take gl_quotient_polys");
     GL_TRY(check_batch(cir, wires, 135, "gl_quotient_polys: wires batch does not match the circuit"));
     GL_TRY(check_batch(cir, zs_partial_products, 20 + nlk, "gl_quotient_polys: Z / partial-products (/ lookups) batch does not match the circuit"));
-    const size_t N = cir->n << cir->desc.rate_bits;
-    DevBuf d_q(ctx); GL_TRY(d_q.alloc(2 * N * sizeof(gl_t)));
     std::vector<gl_t> apow;
-    GL_TRY(quotient_chunks(ctx, cir, wires, zs_partial_products, pi_hash, betas, gammas, alphas, d_q.as<gl_t>(), apow, deltas8));
-    int rc = gl_batch_from_device(ctx, d_q.as<uint64_t>(), 16, cir->n, cir->desc.rate_bits, cir->desc.cap_height, 0, out);
+    const int rc = commit_quotient(ctx, cir, wires, zs_partial_products, pi_hash, betas, gammas, alphas, deltas8, apow, out, nullptr);
     GL_CHECK_HIP(gl_stream_wait(ctx->stream));      // `apow` was the source of an async upload
     return rc;
+}
+extern "C" int gl_quotient_polys(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* wires, const gl_batch* zs_partial_products, const uint64_t pi_hash[4],
+                                 const uint64_t betas[2], const uint64_t gammas[2], const uint64_t alphas[2], gl_batch** out) {
+    return quotient_phase(ctx, cir, wires, zs_partial_products, pi_hash, betas, gammas, alphas, nullptr, out);
+}
+extern "C" int gl_quotient_polys_lookups(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* wires, const gl_batch* zs_partial_products_lookups, const uint64_t pi_hash[4],
+                                         const uint64_t betas[2], const uint64_t gammas[2], const uint64_t alphas[2], const uint64_t deltas[8], gl_batch** out) {
+    GL_REQUIRE(deltas, GL_ERR_ARG, "gl_quotient_polys_lookups: null deltas");
+    return quotient_phase(ctx, cir, wires, zs_partial_products_lookups, pi_hash, betas, gammas, alphas, deltas, out);
 }
 
 // ---- 12. OpeningSet::new (plonk/proof.rs:306-344): polynomials `first .. first + count` of a batch at an extension point ----
@@ -534,16 +537,41 @@ static void launch_open(gl_ctx* ctx, const gl_batch* b, size_t first, size_t cou
 }
 extern "C" int gl_open_at(gl_ctx* ctx, const gl_batch* b, const uint64_t z[2], size_t first_col, size_t num_cols, uint64_t* h_out) {
     GL_REQUIRE(ctx && b && z && h_out, GL_ERR_ARG, "gl_open_at: null argument");
-    GL_REQUIRE(first_col <= b->ncols && num_cols <= b->ncols - first_col && num_cols <= 4096, GL_ERR_ARG, "gl_open_at: column range out of bounds");
+    GL_REQUIRE(first_col <= b->ncols && num_cols <= b->ncols - first_col && num_cols <= DS_OPEN_MAX, GL_ERR_ARG, "gl_open_at: column range out of bounds");
     if (!num_cols) return GL_OK;
     GL_TRY(ctx->activate());
-    GL_TRY(ctx->ensure_dev_small(1 << 20));
-    gl_t* d_open = ctx->dev_small + 4096;
+    GL_TRY(ctx->ensure_dev_small(DS_BYTES));
+    gl_t* d_open = ctx->dev_small + DS_OPEN;
     ctx->timing_begin("construct the opening set");
     launch_open(ctx, b, first_col, num_cols, gl2_make(gl_canon(z[0]), gl_canon(z[1])), d_open);
     ctx->timing_end();
     GL_CHECK_HIP(hipGetLastError());
     return d2h(ctx, h_out, d_open, 2 * num_cols * sizeof(gl_t));
+}
+
+// fri_all_polys / fri_next_batch_polys (circuit_data.rs:564-597) in FriOpenings order (proof.rs:346-380) over the oracles constants||sigmas,
+// wires, Z||partial products(||lookups), quotient: at zeta the constants, sigmas, wires, zs, partial products, quotient chunks, lookup
+// polynomials; at g zeta the zs and the lookup polynomials.  The lookup polynomials come LAST in both batches.
+struct FriOpenings {
+    std::vector<const gl_t*> cols;          // coefficient columns: the nopen opened at zeta, then the nnext opened at g zeta
+    size_t ncs = 0, nlk = 0, nopen = 0, nnext = 0;
+    size_t wires() const { return ncs; }    // where each group starts in `cols`
+    size_t zs() const { return ncs + 135; }
+    size_t partial_products() const { return zs() + 2; }
+    size_t quotient() const { return zs() + 20; }
+    size_t lookups() const { return quotient() + 16; }
+    size_t zs_next() const { return nopen; }
+    size_t lookups_next() const { return nopen + 2; }
+};
+static FriOpenings fri_openings(const gl_batch* const oracles[4]) {
+    FriOpenings f;
+    f.ncs = oracles[0]->ncols; f.nlk = oracles[2]->ncols - 20;
+    auto add = [&](int o, size_t first, size_t count) { for (size_t c = first; c < first + count; c++) f.cols.push_back(oracles[o]->coeffs + c * oracles[o]->n); };
+    add(0, 0, f.ncs); add(1, 0, 135); add(2, 0, 20); add(3, 0, 16); add(2, 20, f.nlk);
+    f.nopen = f.cols.size();
+    add(2, 0, 2); add(2, 20, f.nlk);
+    f.nnext = f.cols.size() - f.nopen;
+    return f;
 }
 
 // ---- 14. PolynomialBatch::prove_openings (fri/oracle.rs:162-219) + fri_proof (fri/prover.rs:20-216), split at every
@@ -578,10 +606,10 @@ extern "C" int gl_fri_combine(gl_ctx* ctx, const gl_circuit* cir, const gl_batch
     GL_REQUIRE(batches && zeta_in && alpha_in && out, GL_ERR_ARG, "gl_fri_combine: null argument");
     const gl_circuit_desc& d = cir->desc;
     const size_t n = cir->n, N = n << d.rate_bits;
-    const size_t nlk = 2 * (size_t)d.num_lookup_polys;                              // lookup polynomials: behind Z||partial products in oracle 2
-    const size_t ncs = d.num_constants + 80, nopen = ncs + 135 + 20 + 16 + nlk, nnext = 2 + nlk;
-    const size_t want[4] = {ncs, 135, 20 + nlk, 16};
+    const size_t want[4] = {d.num_constants + 80, 135, 20 + 2 * (size_t)d.num_lookup_polys, 16};
     for (int o = 0; o < 4; o++) GL_TRY(check_batch(cir, batches[o], want[o], "gl_fri_combine: oracle order is constants||sigmas, wires, Z||partial products(||lookups), quotient"));
+    FriOpenings op = fri_openings(batches);
+    const size_t nopen = op.nopen, nnext = op.nnext;
     hipStream_t st = ctx->stream;
     std::unique_ptr<gl_fri, void (*)(gl_fri*)> f(new gl_fri(), gl_fri_free);
     f->ctx = ctx; ctx->retain(); f->desc = d; f->n = n; f->lgN = d.degree_bits + d.rate_bits;
@@ -598,11 +626,7 @@ extern "C" int gl_fri_combine(gl_ctx* ctx, const gl_circuit* cir, const gl_batch
         GL_TRY(d_cols.alloc((nopen + nnext) * sizeof(gl_t*)));
         GL_TRY(d_apow.alloc(2 * (nopen + nnext) * sizeof(gl_t)));
         std::vector<const gl_t*>& cols = f->h_cols;
-        // fri_all_polys / fri_next_batch_polys (circuit_data.rs:564-597): the lookup polynomials come LAST in both batches
-        for (int o = 0; o < 4; o++) for (size_t c = 0; c < (o == 2 ? (size_t)20 : batches[o]->ncols); c++) cols.push_back(batches[o]->coeffs + c * n);
-        for (size_t c = 0; c < nlk; c++) cols.push_back(batches[2]->coeffs + (20 + c) * n);
-        cols.push_back(batches[2]->coeffs); cols.push_back(batches[2]->coeffs + n);
-        for (size_t c = 0; c < nlk; c++) cols.push_back(batches[2]->coeffs + (20 + c) * n);
+        cols = std::move(op.cols);
         std::vector<gl_t>& apow = f->h_apow; apow.assign(2 * (nopen + nnext), 0);
         { gl2_t x = gl2_make(1, 0); for (size_t j = 0; j < nopen; j++) { apow[2 * j] = x.a; apow[2 * j + 1] = x.b; x = gl2_canon(gl2_mul(x, fri_alpha)); } }
         gl2_t shift = gl2_make(1, 0);     // alpha^(#polys of batch 1) (reducing.rs:103-106)
@@ -701,8 +725,8 @@ extern "C" int gl_pow_grind(gl_ctx* ctx, const uint64_t sponge_state[12], const 
     GL_REQUIRE(input_len < 8 && min_leading_zeros <= 40, GL_ERR_ARG, "gl_pow_grind: the witness must fit the rate (input_len < 8), at most 40 bits of work");
     GL_TRY(ctx->activate());
     hipStream_t st = ctx->stream;
-    GL_TRY(ctx->ensure_dev_small(1 << 20));
-    unsigned long long* d_res = (unsigned long long*)ctx->dev_small;
+    GL_TRY(ctx->ensure_dev_small(DS_BYTES));
+    unsigned long long* d_res = (unsigned long long*)(ctx->dev_small + DS_POW);
     GlPowParams pw;
     for (int i = 0; i < 12; i++) pw.state[i] = sponge_state[i];
     for (uint32_t i = 0; i < input_len; i++) pw.state[i] = input_buffer[i];
@@ -832,50 +856,9 @@ extern "C" int gl_fri_query(gl_fri* f, const uint32_t* x_index, uint32_t num_que
 // ======================================================================================================================
 // prove(): the driver (plonk/prover.rs:102-329) -- the phases above plus the transcript
 // ======================================================================================================================
-static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* h_wires, bool wires_on_device, const uint64_t* h_pis, size_t npis, const uint64_t* h_pi_hash, gl_proof** out);
-extern "C" int gl_prove(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* h_wires, const uint64_t* h_pis, size_t npis, gl_proof** out) {
-    return prove_impl(ctx, cir, h_wires, false, h_pis, npis, nullptr, out);
-}
-// the witness as the reference holds it: one host vector per wire (MatrixWitness.wire_values: Vec<Vec<F>>, iop/witness.rs:256-258)
-extern "C" int gl_prove_columns(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* const* h_wire_columns, const uint64_t* h_pis, size_t npis, gl_proof** out) {
-    GL_REQUIRE(ctx && cir && h_wire_columns && out, GL_ERR_ARG, "gl_prove_columns: null argument");
-    GL_TRY(ctx->activate());
-    const size_t n = cir->n, nw = cir->desc.num_wires;
-    for (size_t c = 0; c < nw; c++) GL_REQUIRE(h_wire_columns[c], GL_ERR_ARG, "gl_prove_columns: null column");
-    DevBuf d_wit(ctx); GL_TRY(d_wit.alloc(nw * n * sizeof(gl_t)));
-    ctx->timing_begin("H2D witness");
-    GL_TRY(h2d_witness(ctx, d_wit.as<gl_t>(), nw, n, h_wire_columns, nullptr));
-    ctx->timing_end();
-    // the caller's vectors have been read when h2d_witness returns; the proof is finished before d_wit is released
-    return prove_impl(ctx, cir, d_wit.as<uint64_t>(), true, h_pis, npis, nullptr, out);
-}
-extern "C" int gl_prove_device(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* d_wires, const uint64_t* h_pis, size_t npis, gl_proof** out) {
-    return prove_impl(ctx, cir, d_wires, true, h_pis, npis, nullptr, out);
-}
-extern "C" int gl_prove_device_hashed(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* d_wires, const uint64_t* h_pis, size_t npis,
-                                      const uint64_t public_inputs_hash[4], gl_proof** out) {
-    GL_REQUIRE(public_inputs_hash, GL_ERR_ARG, "gl_prove_device_hashed: null hash");
-    return prove_impl(ctx, cir, d_wires, true, h_pis, npis, public_inputs_hash, out);
-}
-// One pass of the proving pipeline over an all-zero witness, result thrown away: afterwards this context holds everything a proof of this
-// circuit needs besides its own data -- the code objects of every kernel on the path loaded, the twiddle / power tables of the circuit's
-// transform sizes built, the context's pool grown to the pipeline's working set.  (The reference precomputes its fft_root_table in build()
-// too, circuit_builder.rs:1016-1019.)  A zero witness does not satisfy the circuit; nothing on the path asserts that it does.
-extern "C" int gl_circuit_warm_up(gl_ctx* ctx, const gl_circuit* cir) {
-    GL_REQUIRE(ctx && cir, GL_ERR_ARG, "gl_circuit_warm_up: null argument");
-    GL_REQUIRE(cir->ctx->device == ctx->device, GL_ERR_ARG, "gl_circuit_warm_up: circuit lives on another device");
-    GL_TRY(ctx->activate());
-    const size_t n = cir->n;
-    DevBuf d_w(ctx); GL_TRY(d_w.alloc(135 * n * sizeof(gl_t)));
-    GL_CHECK_HIP(hipMemsetAsync(d_w.p, 0, 135 * n * sizeof(gl_t), ctx->stream));
-    std::vector<uint64_t> pis(cir->desc.num_public_inputs ? cir->desc.num_public_inputs : 1, 0);
-    gl_proof* pr = nullptr;
-    const int st = prove_impl(ctx, cir, d_w.as<uint64_t>(), true, pis.data(), cir->desc.num_public_inputs, nullptr, &pr);
-    if (pr) gl_proof_free(pr);
-    return st == GL_ERR_ZETA_IN_SUBGROUP ? GL_OK : st;       // (probability 2^-49: still warmed up to the opening point)
-}
-static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* h_wires, bool wires_on_device, const uint64_t* h_pis, size_t npis, const uint64_t* h_pi_hash, gl_proof** out) {
-    GL_REQUIRE(ctx && cir && h_wires && h_pis && out, GL_ERR_ARG, "gl_prove: null argument");
+// `d_wires` is the witness [135][n] in HBM; `wit_owner`, if given, owns it and is released once the last kernel that reads it is queued
+static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, DevBuf* wit_owner, const uint64_t* h_pis, size_t npis, const uint64_t* h_pi_hash, gl_proof** out) {
+    GL_REQUIRE(ctx && cir && d_wires && h_pis && out, GL_ERR_ARG, "gl_prove: null argument");
     // circuit data is read-only while proving: any context (stream) of the same device may prove against it
     GL_REQUIRE(cir->ctx->device == ctx->device, GL_ERR_ARG, "gl_prove: circuit lives on another device");
     const gl_circuit_desc& d = cir->desc;
@@ -887,18 +870,8 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* h_wire
     hipStream_t st = ctx->stream;
     std::unique_ptr<gl_proof> proof(new gl_proof());
     std::vector<gl_t> h_apow_quot;          // sources of async uploads: alive until the function returns (after the last sync)
-    std::vector<const gl_t*> h_open_cols;
 
     // ---- 4. wires commitment (prover.rs:145-156) ----
-    DevBuf d_wit(ctx);
-    const gl_t* d_wires = (const gl_t*)h_wires;
-    if (!wires_on_device) {
-        GL_TRY(d_wit.alloc(135 * n * sizeof(gl_t)));
-        ctx->timing_begin("H2D witness");
-        GL_TRY(h2d_witness(ctx, d_wit.as<gl_t>(), 135, n, nullptr, h_wires));
-        ctx->timing_end();
-        d_wires = d_wit.as<gl_t>();
-    }
     BatchHolder wires; GL_TRY(gl_batch_from_device(ctx, d_wires, 135, n, d.rate_bits, d.cap_height, 1, &wires.b));
     // public_inputs_hash (prover.rs:126-127) on the host while the GPU commits
     gl_t pi_hash[4];
@@ -915,20 +888,14 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* h_wire
     for (int i = 0; i < 2; i++) betas[i] = ch.challenge();
     for (int i = 0; i < 2; i++) gammas[i] = ch.challenge();
     // lookups: four coins per challenge, [betas | gammas | 4 more] (prover.rs:166-184)
-    const size_t nlk = 2 * (size_t)d.num_lookup_polys, nzs = 20 + nlk;
     gl_t deltas[8] = {betas[0], betas[1], gammas[0], gammas[1], 0, 0, 0, 0};
-    if (nlk) for (int i = 4; i < 8; i++) deltas[i] = ch.challenge();
+    const gl_t* lookup_deltas = d.num_lookup_polys ? deltas : nullptr;
+    if (lookup_deltas) for (int i = 4; i < 8; i++) deltas[i] = ch.challenge();
 
     // ---- 6/7. partial products and Z (and the lookup polynomials), commitment (prover.rs:189-223) ----
     BatchHolder zs;
-    {
-        DevBuf d_zs(ctx); GL_TRY(d_zs.alloc(nzs * n * sizeof(gl_t)));
-        GL_TRY(partial_products_values(ctx, cir, d_wires, betas, gammas, d_zs.as<gl_t>()));
-        if (nlk) GL_TRY(lookup_polys_values(ctx, cir, d_wires, deltas, d_zs.as<gl_t>() + 20 * n));
-        if (ctx->capture_intermediates) { proof->zs_pp.resize(nzs * n); GL_TRY(d2h(ctx, proof->zs_pp.data(), d_zs.p, nzs * n * sizeof(gl_t))); }
-        GL_TRY(gl_batch_from_device(ctx, d_zs.as<uint64_t>(), nzs, n, d.rate_bits, d.cap_height, 1, &zs.b));
-    }
-    d_wit.release();                                                            // stream-ordered: the kernels above are already queued
+    GL_TRY(commit_zs(ctx, cir, d_wires, betas, gammas, lookup_deltas, &zs.b, ctx->capture_intermediates ? &proof->zs_pp : nullptr));
+    if (wit_owner) wit_owner->release();                                       // stream-ordered: the kernels above are already queued
     GL_TRY(gl_batch_cap(zs.b, cap.data()));
     proof->caps.insert(proof->caps.end(), cap.begin(), cap.end());
     ch.observe_many(cap.data(), ncap);
@@ -936,18 +903,13 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* h_wire
 
     // ---- 9/10. quotient polynomials (prover.rs:229-271) ----
     BatchHolder quot;
-    {
-        DevBuf d_q(ctx); GL_TRY(d_q.alloc(2 * N * sizeof(gl_t)));
-        GL_TRY(quotient_chunks(ctx, cir, wires.b, zs.b, pi_hash, betas, gammas, alphas, d_q.as<gl_t>(), h_apow_quot, nlk ? deltas : nullptr));
-        if (ctx->capture_intermediates) { proof->quotient.resize(16 * n); GL_TRY(d2h(ctx, proof->quotient.data(), d_q.p, 16 * n * sizeof(gl_t))); }
-        GL_TRY(gl_batch_from_device(ctx, d_q.as<uint64_t>(), 16, n, d.rate_bits, d.cap_height, 0, &quot.b));
-    }
+    GL_TRY(commit_quotient(ctx, cir, wires.b, zs.b, pi_hash, betas, gammas, alphas, lookup_deltas, h_apow_quot, &quot.b, ctx->capture_intermediates ? &proof->quotient : nullptr));
     GL_TRY(gl_batch_cap(quot.b, cap.data()));
     proof->caps.insert(proof->caps.end(), cap.begin(), cap.end());
     ch.observe_many(cap.data(), ncap);
 
     // ---- 11. zeta (prover.rs:273-283) ----
-    gl2_t zeta; zeta.a = ch.challenge(); zeta.b = ch.challenge();
+    const gl2_t zeta = ch.challenge_ext();
     {
         gl2_t zn = zeta;
         for (uint32_t i = 0; i < lgn; i++) zn = gl2_mul(zn, zn);
@@ -956,53 +918,45 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* h_wire
     }
     const gl2_t gzeta = gl2_canon(gl2_scalar(zeta, gl_host_root_of_unity(lgn)));
 
-    // ---- 12. openings (proof.rs:306-344): all five evaluations behind one sync ----
+    // ---- 12. openings (proof.rs:306-344): all of them in one launch behind one sync (gl_open_at is one batch per call) ----
     const gl_batch* oracles[4] = {cir->cs_batch, wires.b, zs.b, quot.b};
-    const size_t ncs = d.num_constants + 80, nopen = ncs + 135 + 20 + 16 + nlk, nnext = 2 + nlk;
-    std::vector<gl_t> open_zeta(2 * nopen), open_next(2 * nnext);
+    const FriOpenings op = fri_openings(oracles);
+    GL_REQUIRE(op.nopen + op.nnext <= DS_OPEN_MAX, GL_ERR_INTERNAL, "too many openings for the staging area");
+    std::vector<gl_t> opened(2 * (op.nopen + op.nnext));                       // extension values, in op.cols order
     {
-        GL_TRY(ctx->ensure_dev_small(1 << 20));
-        gl_t* d_open = ctx->dev_small + 4096;
+        GL_TRY(ctx->ensure_dev_small(DS_BYTES));
+        gl_t* d_open = ctx->dev_small + DS_OPEN;
         ctx->timing_begin("construct the opening set");
         // zeta^i and (g zeta)^i tabulated once per proof, shared by all polynomials
         DevBuf d_zpow(ctx); GL_TRY(d_zpow.alloc(4 * n * sizeof(gl_t)));
         gl_t* zp = d_zpow.as<gl_t>();
         hipLaunchKernelGGL(k_ext_powers2, dim3((unsigned)((n + 255) / 256), 2), dim3(256), 0, st, zeta.a, zeta.b, gzeta.a, gzeta.b, (uint32_t)n, zp);
-        // one launch for all 257 openings: the list of coefficient columns goes up as a small pointer table
-        // FriOpenings order (proof.rs:346-380): constants, sigmas, wires, zs, partial products, quotient, lookups | zs_next, lookups_next
-        for (int o = 0; o < 4; o++) for (size_t c = 0; c < (o == 2 ? (size_t)20 : oracles[o]->ncols); c++) h_open_cols.push_back(oracles[o]->coeffs + c * n);
-        for (size_t c = 0; c < nlk; c++) h_open_cols.push_back(zs.b->coeffs + (20 + c) * n);
-        h_open_cols.push_back(zs.b->coeffs); h_open_cols.push_back(zs.b->coeffs + n);
-        for (size_t c = 0; c < nlk; c++) h_open_cols.push_back(zs.b->coeffs + (20 + c) * n);
-        DevBuf d_open_cols(ctx); GL_TRY(d_open_cols.alloc(h_open_cols.size() * sizeof(gl_t*)));
-        GL_TRY(h2d_async(ctx, d_open_cols.p, h_open_cols.data(), h_open_cols.size() * sizeof(gl_t*)));
-        hipLaunchKernelGGL(k_eval_list_with_powers, dim3((unsigned)h_open_cols.size()), dim3(256), 0, st, d_open_cols.as<const gl_t*>(), (uint32_t)n,
-                           (uint32_t)nopen, zp, zp + n, zp + 2 * n, zp + 3 * n, d_open);
+        // the list of coefficient columns goes up as a small pointer table
+        DevBuf d_open_cols(ctx); GL_TRY(d_open_cols.alloc(op.cols.size() * sizeof(gl_t*)));
+        GL_TRY(h2d_async(ctx, d_open_cols.p, op.cols.data(), op.cols.size() * sizeof(gl_t*)));
+        hipLaunchKernelGGL(k_eval_list_with_powers, dim3((unsigned)op.cols.size()), dim3(256), 0, st, d_open_cols.as<const gl_t*>(), (uint32_t)n,
+                           (uint32_t)op.nopen, zp, zp + n, zp + 2 * n, zp + 3 * n, d_open);
         ctx->timing_end();
         GL_CHECK_HIP(hipGetLastError());
-        std::vector<gl_t> tmp(2 * (nopen + nnext));
-        GL_TRY(d2h(ctx, tmp.data(), d_open, tmp.size() * sizeof(gl_t)));
-        memcpy(open_zeta.data(), tmp.data(), 2 * nopen * sizeof(gl_t));
-        memcpy(open_next.data(), tmp.data() + 2 * nopen, 2 * nnext * sizeof(gl_t));
+        GL_TRY(d2h(ctx, opened.data(), d_open, opened.size() * sizeof(gl_t)));
     }
-    // FriOpenings order = oracle order: constants, sigmas, wires, zs, partial products, quotient; then zs_next
-    ch.observe_many(open_zeta.data(), open_zeta.size());
-    ch.observe_many(open_next.data(), open_next.size());
+    ch.observe_many(opened.data(), opened.size());
 
     // ---- 14. prove_openings (fri/oracle.rs:162-219), fri_proof (fri/prover.rs:20-66) ----
-    gl_t fri_alpha[2], zeta_w[2] = {zeta.a, zeta.b};
-    fri_alpha[0] = ch.challenge(); fri_alpha[1] = ch.challenge();
+    const gl2_t fri_alpha = ch.challenge_ext();
+    const gl_t zeta_w[2] = {zeta.a, zeta.b}, fri_alpha_w[2] = {fri_alpha.a, fri_alpha.b};
     gl_fri* fri_raw = nullptr;
-    GL_TRY(gl_fri_combine(ctx, cir, oracles, zeta_w, fri_alpha, &fri_raw));
+    GL_TRY(gl_fri_combine(ctx, cir, oracles, zeta_w, fri_alpha_w, &fri_raw));
     std::unique_ptr<gl_fri, void (*)(gl_fri*)> fri(fri_raw, gl_fri_free);
     std::vector<gl_t> fri_caps, fri_betas;
     for (unsigned r = 0; r < d.num_fri_rounds; r++) {
         GL_TRY(gl_fri_commit_round(fri.get(), cap.data()));
         fri_caps.insert(fri_caps.end(), cap.begin(), cap.end());
         ch.observe_many(cap.data(), ncap);
-        gl_t beta[2]; beta[0] = ch.challenge(); beta[1] = ch.challenge();
-        fri_betas.push_back(beta[0]); fri_betas.push_back(beta[1]);
-        GL_TRY(gl_fri_fold(fri.get(), beta));
+        const gl2_t beta = ch.challenge_ext();
+        const gl_t beta_w[2] = {beta.a, beta.b};
+        fri_betas.insert(fri_betas.end(), beta_w, beta_w + 2);
+        GL_TRY(gl_fri_fold(fri.get(), beta_w));
     }
     size_t fin_words = 0;
     GL_TRY(gl_fri_final_poly(fri.get(), nullptr, 0, &fin_words));
@@ -1023,21 +977,18 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* h_wire
 
     // ---- 15. assemble ProofWithPublicInputs bytes (util/serialization/mod.rs:1939-1981) ----
     std::vector<uint8_t>& o = proof->bytes;
-    o.reserve(query_blob.size() + 8 * (npis + 2 * nopen + fin_words + 4 * ncap) + 4096);
+    o.reserve(query_blob.size() + 8 * (npis + 2 * op.nopen + fin_words + 4 * ncap) + 4096);
     put_words(o, proof->caps.data(), proof->caps.size());                        // wires_cap, zs_pp_cap, quotient_cap
     // OpeningSet (:1409-1423): constants, sigmas, wires, zs, zs_next, lookup_zs, lookup_zs_next, partial products, quotient
-    {
-        const gl_t* z = open_zeta.data();
-        size_t o_cs = 0, o_w = 2 * ncs, o_z = o_w + 2 * 135, o_pp = o_z + 2 * 2, o_q = o_z + 2 * 20, o_lk = o_q + 2 * 16;
-        put_words(o, z + o_cs, 2 * ncs);
-        put_words(o, z + o_w, 2 * 135);
-        put_words(o, z + o_z, 2 * 2);
-        put_words(o, open_next.data(), 2 * 2);
-        put_words(o, z + o_lk, 2 * nlk);
-        put_words(o, open_next.data() + 2 * 2, 2 * nlk);
-        put_words(o, z + o_pp, 2 * 18);
-        put_words(o, z + o_q, 2 * 16);
-    }
+    const gl_t* z = opened.data();
+    put_words(o, z, 2 * op.ncs);
+    put_words(o, z + 2 * op.wires(), 2 * 135);
+    put_words(o, z + 2 * op.zs(), 2 * 2);
+    put_words(o, z + 2 * op.zs_next(), 2 * 2);
+    put_words(o, z + 2 * op.lookups(), 2 * op.nlk);
+    put_words(o, z + 2 * op.lookups_next(), 2 * op.nlk);
+    put_words(o, z + 2 * op.partial_products(), 2 * 18);
+    put_words(o, z + 2 * op.quotient(), 2 * 16);
     put_words(o, fri_caps.data(), fri_caps.size());
     o.insert(o.end(), query_blob.begin(), query_blob.end());
     put_words(o, fin_il.data(), fin_il.size());
@@ -1049,12 +1000,57 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* h_wire
     for (int i = 0; i < 2; i++) cv.push_back(betas[i]);
     for (int i = 0; i < 2; i++) cv.push_back(gammas[i]);
     for (int i = 0; i < 2; i++) cv.push_back(alphas[i]);
-    cv.push_back(zeta.a); cv.push_back(zeta.b); cv.push_back(fri_alpha[0]); cv.push_back(fri_alpha[1]); cv.push_back(pow_witness);
+    cv.push_back(zeta.a); cv.push_back(zeta.b); cv.push_back(fri_alpha.a); cv.push_back(fri_alpha.b); cv.push_back(pow_witness);
     for (int i = 0; i < 4; i++) cv.push_back(pi_hash[i]);
     cv.insert(cv.end(), fri_betas.begin(), fri_betas.end());
     GL_CHECK_HIP(gl_stream_wait(st));
     *out = proof.release();
     return GL_OK;
+}
+// host witness -> HBM, then prove(): gl_prove (one [135][n] matrix) and gl_prove_columns (135 vectors).  The caller's memory has been
+// read when h2d_witness returns; prove_impl releases the device copy.
+static int prove_host_witness(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* const* cols, const uint64_t* flat, const uint64_t* h_pis, size_t npis, gl_proof** out) {
+    GL_TRY(ctx->activate());
+    DevBuf d_wit(ctx); GL_TRY(d_wit.alloc(135 * cir->n * sizeof(gl_t)));
+    ctx->timing_begin("H2D witness");
+    GL_TRY(h2d_witness(ctx, d_wit.as<gl_t>(), 135, cir->n, cols, flat));
+    ctx->timing_end();
+    return prove_impl(ctx, cir, d_wit.as<gl_t>(), &d_wit, h_pis, npis, nullptr, out);
+}
+extern "C" int gl_prove(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* h_wires, const uint64_t* h_pis, size_t npis, gl_proof** out) {
+    GL_REQUIRE(ctx && cir && h_wires && out, GL_ERR_ARG, "gl_prove: null argument");
+    return prove_host_witness(ctx, cir, nullptr, h_wires, h_pis, npis, out);
+}
+// the witness as the reference holds it: one host vector per wire (MatrixWitness.wire_values: Vec<Vec<F>>, iop/witness.rs:256-258)
+extern "C" int gl_prove_columns(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* const* h_wire_columns, const uint64_t* h_pis, size_t npis, gl_proof** out) {
+    GL_REQUIRE(ctx && cir && h_wire_columns && out, GL_ERR_ARG, "gl_prove_columns: null argument");
+    for (size_t c = 0; c < 135; c++) GL_REQUIRE(h_wire_columns[c], GL_ERR_ARG, "gl_prove_columns: null column");
+    return prove_host_witness(ctx, cir, h_wire_columns, nullptr, h_pis, npis, out);
+}
+extern "C" int gl_prove_device(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* d_wires, const uint64_t* h_pis, size_t npis, gl_proof** out) {
+    return prove_impl(ctx, cir, d_wires, nullptr, h_pis, npis, nullptr, out);
+}
+extern "C" int gl_prove_device_hashed(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* d_wires, const uint64_t* h_pis, size_t npis,
+                                      const uint64_t public_inputs_hash[4], gl_proof** out) {
+    GL_REQUIRE(public_inputs_hash, GL_ERR_ARG, "gl_prove_device_hashed: null hash");
+    return prove_impl(ctx, cir, d_wires, nullptr, h_pis, npis, public_inputs_hash, out);
+}
+// One pass of the proving pipeline over an all-zero witness, result thrown away: afterwards this context holds everything a proof of this
+// circuit needs besides its own data -- the code objects of every kernel on the path loaded, the twiddle / power tables of the circuit's
+// transform sizes built, the context's pool grown to the pipeline's working set.  (The reference precomputes its fft_root_table in build()
+// too, circuit_builder.rs:1016-1019.)  A zero witness does not satisfy the circuit; nothing on the path asserts that it does.
+extern "C" int gl_circuit_warm_up(gl_ctx* ctx, const gl_circuit* cir) {
+    GL_REQUIRE(ctx && cir, GL_ERR_ARG, "gl_circuit_warm_up: null argument");
+    GL_REQUIRE(cir->ctx->device == ctx->device, GL_ERR_ARG, "gl_circuit_warm_up: circuit lives on another device");
+    GL_TRY(ctx->activate());
+    const size_t n = cir->n;
+    DevBuf d_w(ctx); GL_TRY(d_w.alloc(135 * n * sizeof(gl_t)));
+    GL_CHECK_HIP(hipMemsetAsync(d_w.p, 0, 135 * n * sizeof(gl_t), ctx->stream));
+    std::vector<uint64_t> pis(cir->desc.num_public_inputs ? cir->desc.num_public_inputs : 1, 0);
+    gl_proof* pr = nullptr;
+    const int st = prove_impl(ctx, cir, d_w.as<gl_t>(), nullptr, pis.data(), cir->desc.num_public_inputs, nullptr, &pr);
+    if (pr) gl_proof_free(pr);
+    return st == GL_ERR_ZETA_IN_SUBGROUP ? GL_OK : st;       // (probability 2^-49: still warmed up to the opening point)
 }
 
 extern "C" size_t gl_proof_num_bytes(const gl_proof* p) { return p ? p->bytes.size() : 0; }

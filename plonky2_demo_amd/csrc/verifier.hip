@@ -21,24 +21,6 @@ inline bool e_eq(E x, E y) { x = gl2_canon(x); y = gl2_canon(y); return x.a == y
 inline E e_sbox(E x) { E x2 = e_mul(x, x), x4 = e_mul(x2, x2); return e_mul(e_mul(x, x2), x4); }
 inline E e_pow2k(E x, unsigned k) { for (unsigned i = 0; i < k; i++) x = e_mul(x, x); return x; }
 
-// ---- transcript (iop/challenger.rs:30-153) ----
-struct Transcript {
-    gl_t sponge[12], pending[8], ready[8];
-    int npending = 0, nready = 0;
-    Transcript() { for (auto& s : sponge) s = 0; }
-    void squeeze() {
-        for (int i = 0; i < npending; i++) sponge[i] = pending[i];
-        npending = 0;
-        psd_permute(sponge);
-        for (int i = 0; i < 8; i++) ready[i] = sponge[i];
-        nready = 8;
-    }
-    void absorb(gl_t x) { nready = 0; pending[npending++] = x; if (npending == 8) squeeze(); }
-    void absorb(const gl_t* v, size_t n) { for (size_t i = 0; i < n; i++) absorb(v[i]); }
-    gl_t draw() { if (npending || !nready) squeeze(); return gl_canon(ready[--nready]); }
-    E draw_ext() { E r; r.a = draw(); r.b = draw(); return r; }
-};
-
 // ---- Merkle path to a cap (hash/merkle_proofs.rs:54-75; leaf hash plonk/config.rs:55-66) ----
 void hash_leaf(const gl_t* v, size_t n, gl_t out[4]) {
     if (n <= 4) { for (size_t i = 0; i < 4; i++) out[i] = i < n ? gl_canon(v[i]) : 0; return; }
@@ -210,30 +192,30 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
     // ---- challenges (plonk/get_challenges.rs:26-87, fri/challenges.rs:24-64) ----
     gl_t pi_hash[4];
     glhost::host_hash_no_pad(T.data() + o_pis, npis, pi_hash);
-    Transcript tr;
-    tr.absorb(circuit_digest, 4); tr.absorb(pi_hash, 4); tr.absorb(&T[o_caps], 4 * ncap);
+    glhost::HostChallenger tr;
+    tr.observe_many(circuit_digest, 4); tr.observe_many(pi_hash, 4); tr.observe_many(&T[o_caps], 4 * ncap);
     gl_t betas[2], gammas[2], alphas[2];
-    for (auto& b : betas) b = tr.draw();
-    for (auto& g : gammas) g = tr.draw();
+    for (auto& b : betas) b = tr.challenge();
+    for (auto& g : gammas) g = tr.challenge();
     // lookup coins (get_challenges.rs:51-63): [betas | gammas | 4 more], four per challenge
     gl_t deltas[8] = {betas[0], betas[1], gammas[0], gammas[1], 0, 0, 0, 0};
-    if (NLP) for (int i = 4; i < 8; i++) deltas[i] = tr.draw();
-    tr.absorb(&T[o_caps + 4 * ncap], 4 * ncap);
-    for (auto& a : alphas) a = tr.draw();
-    tr.absorb(&T[o_caps + 8 * ncap], 4 * ncap);
-    const E zeta = tr.draw_ext();
+    if (NLP) for (int i = 4; i < 8; i++) deltas[i] = tr.challenge();
+    tr.observe_many(&T[o_caps + 4 * ncap], 4 * ncap);
+    for (auto& a : alphas) a = tr.challenge();
+    tr.observe_many(&T[o_caps + 8 * ncap], 4 * ncap);
+    const E zeta = tr.challenge_ext();
     // FriOpenings (plonk/proof.rs:346-380): constants, sigmas, wires, zs, partial products, quotient at zeta; zs_next at g zeta
-    tr.absorb(&T[o_const], 2 * d.num_constants); tr.absorb(&T[o_sig], 2 * R); tr.absorb(&T[o_wires], 2 * W); tr.absorb(&T[o_zs], 2 * nch);
-    tr.absorb(&T[o_pp], 2 * nch * NPP); tr.absorb(&T[o_quot], 2 * nch * QF); tr.absorb(&T[o_lk], 2 * nch * NLP);
-    tr.absorb(&T[o_zsn], 2 * nch); tr.absorb(&T[o_lkn], 2 * nch * NLP);
-    const E fri_alpha = tr.draw_ext();
+    tr.observe_many(&T[o_const], 2 * d.num_constants); tr.observe_many(&T[o_sig], 2 * R); tr.observe_many(&T[o_wires], 2 * W); tr.observe_many(&T[o_zs], 2 * nch);
+    tr.observe_many(&T[o_pp], 2 * nch * NPP); tr.observe_many(&T[o_quot], 2 * nch * QF); tr.observe_many(&T[o_lk], 2 * nch * NLP);
+    tr.observe_many(&T[o_zsn], 2 * nch); tr.observe_many(&T[o_lkn], 2 * nch * NLP);
+    const E fri_alpha = tr.challenge_ext();
     E fri_betas[8];
-    for (unsigned r = 0; r < d.num_fri_rounds; r++) { tr.absorb(&T[o_fcaps + (size_t)r * 4 * ncap], 4 * ncap); fri_betas[r] = tr.draw_ext(); }
-    tr.absorb(&T[o_final], 2 * final_len);
-    tr.absorb(pow_witness);
-    const gl_t pow_response = tr.draw();
+    for (unsigned r = 0; r < d.num_fri_rounds; r++) { tr.observe_many(&T[o_fcaps + (size_t)r * 4 * ncap], 4 * ncap); fri_betas[r] = tr.challenge_ext(); }
+    tr.observe_many(&T[o_final], 2 * final_len);
+    tr.observe(pow_witness);
+    const gl_t pow_response = tr.challenge();
     std::vector<size_t> x_index(d.num_query_rounds);
-    for (auto& x : x_index) x = (size_t)(tr.draw() % (uint64_t)N);
+    for (auto& x : x_index) x = (size_t)(tr.challenge() % (uint64_t)N);
 
     // ---- vanishing(zeta) == Z_H(zeta) * t(zeta) per challenge (plonk/verifier.rs:64-101, vanishing_poly.rs:54-160) ----
     {

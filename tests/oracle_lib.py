@@ -419,8 +419,12 @@ class OracleProof:
         self.c.o.lib.orc_proof_caps(self.h, _p(out))
         return out
 
-    def zs_partial_products(self, ncols=20):
-        out = np.empty((ncols, self.c.n), dtype=np.uint64)
+    def zs_partial_products(self, ncols=None):
+        """Z and partial products, then the lookup polynomials: [20 + 2 num_lookup_polys][n]."""
+        want = 20 + 2 * self.c.product_desc().num_lookup_polys
+        if ncols is not None and ncols != want:
+            raise ValueError("this proof holds %d Z / partial-product / lookup columns, not %d" % (want, ncols))
+        out = np.empty((want, self.c.n), dtype=np.uint64)
         self.c.o.lib.orc_proof_zs_partial_products(self.h, _p(out))
         return out
 

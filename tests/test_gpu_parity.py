@@ -1112,7 +1112,7 @@ def test_lookup_argument_circuits(gpu, orc, kind, param, inputs):
     expected, nluts = lookup_outputs(kind, param, inputs)
     assert [int(x) for x in w.public_inputs()] == expected and oc.product_desc().num_luts == nluts
     # the lookup polynomials themselves: 14 value columns behind Z and the partial products, equal to the oracle's
-    zs_g, zs_o = gp.zs_partial_products(34), w.prove(threads=8).zs_partial_products(34)
+    zs_g, zs_o = gp.zs_partial_products(), w.prove(threads=8).zs_partial_products()
     assert zs_g.shape[0] == 34 and (zs_g == zs_o).all()
     assert zs_g[20:].any()
 
