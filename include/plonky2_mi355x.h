@@ -155,6 +155,9 @@ int gl_fft_host(gl_ctx* ctx, uint64_t* h_data, uint32_t log_n, uint32_t batch, i
 /* ---- Poseidon / hashing --------------------------------------------------------------------------*/
 /* Poseidon::poseidon (plonky2/src/hash/poseidon.rs:598-609) on `count` 12-word states, in place */
 int gl_poseidon_permute(gl_ctx* ctx, uint64_t* d_states, size_t count);
+/* the same permutation with the MDS layer chosen by `layer` (0: vector ALU, 1: i8 matrix cores), leaving the raw u64
+   representatives (not canonicalised): the two layers return the same words */
+int gl_poseidon_permute_raw(gl_ctx* ctx, uint64_t* d_states, size_t count, int layer);
 /* Hasher::hash_or_noop (plonky2/src/plonk/config.rs:55-66) of `count` rows of `len` elements,
  * row-major d_rows[count][len] -> d_out[count][4] */
 int gl_hash_rows(gl_ctx* ctx, const uint64_t* d_rows, size_t count, size_t len, uint64_t* d_out);

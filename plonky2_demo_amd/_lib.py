@@ -62,6 +62,7 @@ SIGNATURES = {
     "gl_ntt_coset_lde": (c_int, [c_vp, c_vp, c_u32, c_u32, c_u32, c_vp]),
     "gl_fft_host": (c_int, [c_vp, c_vp, c_u32, c_u32, c_int]),
     "gl_poseidon_permute": (c_int, [c_vp, c_vp, c_sz]),
+    "gl_poseidon_permute_raw": (c_int, [c_vp, c_vp, c_sz, c_int]),
     "gl_hash_rows": (c_int, [c_vp, c_vp, c_sz, c_sz, c_vp]),
     "gl_merkle_new": (c_int, [c_vp, c_vp, c_sz, c_sz, c_u32, ctypes.POINTER(c_vp)]),
     "gl_merkle_cap": (c_int, [c_vp, c_vp]),

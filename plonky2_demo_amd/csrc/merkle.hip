@@ -32,12 +32,13 @@ static uint32_t gl_coop_max_nodes() {
 
 __device__ __forceinline__ uint32_t d_bitrev(uint32_t x, uint32_t bits) { return bits ? (__brev(x) >> (32 - bits)) : 0; }
 
-// digest of natural row r -> digests[bitrev(r)].  WPE: waves per SIMD the register allocation must leave room for
+// digest of natural row r -> digests[bitrev(r)].  WPE: waves per SIMD the register allocation must leave room for.
+// The hash kernels keep every lane of a wave active through the permutation (the MFMA layer reads all 64 lanes): lanes past
+// the end hash a copy of the last item and do not store.
 template <int WPE>
 __global__ __launch_bounds__(256, WPE) void k_merkle_leaves(const gl_t* __restrict__ base, const uint64_t* __restrict__ offsets,
                                                        uint32_t leaf_len, uint32_t lg_leaves, gl_t* __restrict__ digests) {
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= (1u << lg_leaves)) return;
+    const uint32_t n = 1u << lg_leaves, gid = blockIdx.x * blockDim.x + threadIdx.x, r = gid < n ? gid : n - 1;
     gl_t s[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = 0;
@@ -49,9 +50,10 @@ __global__ __launch_bounds__(256, WPE) void k_merkle_leaves(const gl_t* __restri
 #pragma unroll
             for (int i = 0; i < 8; i++)
                 if ((uint32_t)i < c) s[i] = base[offsets[e0 + i] + r];
-            psd_permute(s);
+            psd_permute_layer<PSD_LAYER_HASH>(s);
         }
     }
+    if (gid >= n) return;
     const uint32_t j = d_bitrev(r, lg_leaves);
     ulonglong2* out = reinterpret_cast<ulonglong2*>(digests + 4ull * j);
     out[0] = make_ulonglong2(gl_canon(s[0]), gl_canon(s[1]));
@@ -59,13 +61,14 @@ __global__ __launch_bounds__(256, WPE) void k_merkle_leaves(const gl_t* __restri
 }
 
 // parent[i] = two_to_one(child[2i], child[2i+1])   (hashing.rs:98-115)
-__global__ __launch_bounds__(256) void k_merkle_level(const gl_t* __restrict__ child, gl_t* __restrict__ parent, uint32_t count) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
+// (5 waves per SIMD: the register budget the MFMA layer fits without spilling, as the leaf kernel's default below)
+__global__ __launch_bounds__(256, 5) void k_merkle_level(const gl_t* __restrict__ child, gl_t* __restrict__ parent, uint32_t count) {
+    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x, i = gid < count ? gid : count - 1;
     const ulonglong2* in = reinterpret_cast<const ulonglong2*>(child + 8ull * i);
     ulonglong2 a = in[0], b = in[1], c = in[2], d = in[3];
     gl_t s[12] = {a.x, a.y, b.x, b.y, c.x, c.y, d.x, d.y, 0, 0, 0, 0};
-    psd_permute(s);
+    psd_permute_layer<PSD_LAYER_HASH>(s);
+    if (gid >= count) return;
     ulonglong2* out = reinterpret_cast<ulonglong2*>(parent + 4ull * i);
     out[0] = make_ulonglong2(gl_canon(s[0]), gl_canon(s[1]));
     out[1] = make_ulonglong2(gl_canon(s[2]), gl_canon(s[3]));
@@ -120,21 +123,22 @@ __global__ __launch_bounds__(1024) void k_merkle_top_coop(gl_t* __restrict__ dig
     }
 }
 
-__global__ void k_poseidon_states(gl_t* states, size_t count) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
+// LAYER: the MDS layer (PSD_LAYER_*); CANON = false leaves the raw u64 representatives (the layers are compared word for word)
+template <int LAYER, bool CANON>
+__global__ __launch_bounds__(64, 5) void k_poseidon_states(gl_t* states, size_t count) {
+    const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, i = gid < count ? gid : count - 1;
     gl_t s[12];
 #pragma unroll
     for (int k = 0; k < 12; k++) s[k] = states[12 * i + k];
-    psd_permute(s);
+    psd_permute_layer<LAYER>(s);
+    if (gid >= count) return;
 #pragma unroll
-    for (int k = 0; k < 12; k++) states[12 * i + k] = gl_canon(s[k]);
+    for (int k = 0; k < 12; k++) states[12 * i + k] = CANON ? gl_canon(s[k]) : s[k];
 }
 
 // hash_or_noop of row-major rows
-__global__ void k_hash_rows(const gl_t* rows, size_t count, uint32_t len, gl_t* out) {
-    size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= count) return;
+__global__ __launch_bounds__(64, 5) void k_hash_rows(const gl_t* rows, size_t count, uint32_t len, gl_t* out) {
+    const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, r = gid < count ? gid : count - 1;
     gl_t s[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = 0;
@@ -147,9 +151,10 @@ __global__ void k_hash_rows(const gl_t* rows, size_t count, uint32_t len, gl_t* 
 #pragma unroll
             for (int i = 0; i < 8; i++)
                 if ((uint32_t)i < c) s[i] = row[e0 + i];
-            psd_permute(s);
+            psd_permute_layer<PSD_LAYER_HASH>(s);
         }
     }
+    if (gid >= count) return;
     for (int i = 0; i < 4; i++) out[4 * r + i] = gl_canon(s[i]);
 }
 
@@ -211,7 +216,18 @@ extern "C" int gl_poseidon_permute(gl_ctx* c, uint64_t* d_states, size_t count) 
     GL_REQUIRE(c && d_states, GL_ERR_ARG, "null argument");
     if (!count) return GL_OK;
     GL_TRY(c->activate());
-    hipLaunchKernelGGL(k_poseidon_states, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, c->stream, d_states, count);
+    hipLaunchKernelGGL((k_poseidon_states<PSD_LAYER_HASH, true>), dim3((unsigned)((count + 63) / 64)), dim3(64), 0, c->stream, d_states, count);
+    GL_CHECK_HIP(hipGetLastError());
+    return GL_OK;
+}
+extern "C" int gl_poseidon_permute_raw(gl_ctx* c, uint64_t* d_states, size_t count, int layer) {
+    GL_REQUIRE(c && d_states && (layer == PSD_LAYER_VALU || layer == PSD_LAYER_MFMA), GL_ERR_ARG, "bad argument");
+    if (!count) return GL_OK;
+    GL_TRY(c->activate());
+    if (layer == PSD_LAYER_MFMA)
+        hipLaunchKernelGGL((k_poseidon_states<PSD_LAYER_MFMA, false>), dim3((unsigned)((count + 63) / 64)), dim3(64), 0, c->stream, d_states, count);
+    else
+        hipLaunchKernelGGL((k_poseidon_states<PSD_LAYER_VALU, false>), dim3((unsigned)((count + 63) / 64)), dim3(64), 0, c->stream, d_states, count);
     GL_CHECK_HIP(hipGetLastError());
     return GL_OK;
 }

@@ -196,6 +196,87 @@ GL_HD void psd_mds_then_constants(gl_t (&s)[12], const gl_t* __restrict__ rc) {
     }
 #endif
 }
+
+// ---- the same layer on the i8 matrix cores (v_mfma_i32_32x32x32_i8) -------------------------------------------------------
+// Each lane keeps its own state: the B operand of K block Kb is the four 32-bit halves (lo or hi) of words 4 Kb .. 4 Kb + 3,
+// each XOR 0x80808080 (a byte b becomes the signed i8 b - 128; without the bias every byte >= 0x80 would enter as negative).
+// The 32 x 32 result has its column on the lane (lane l and l + 32 share column l & 31) and rows 8 (v / 4) + 4 h + (v & 3)
+// in register v of lane half h; A is non-zero only in the K set the lane half of the row supplies, so register v = 4 o + t of
+// a lane is row (output word o of the row block, byte position t) = sum_j c_oj (byte_t(half_j) - 128) over the lane's OWN
+// state, whatever the K order within a lane half.  3 row blocks x 3 K blocks per half: 18 MFMAs.  The circulant makes A depend
+// only on (K block - row block) mod 3, plus the (0, 0) block holding MDS_MATRIX_DIAG[0]: 4 A operands of 4 VGPRs.
+// Recombined, sum_t 2^(8t) row(o, t) + k = the VALU layer's accumulator exactly (tools/gen_poseidon_constants.py derive_mfma:
+// k = the round constant's half + rowsum 0x80808080), so glx_acc_reduce3 returns the same u64 as psd_mds_then_constants.
+// An MFMA reads A and B from all 64 lanes whatever EXEC holds: the A operands must be valid in every lane, so the layer runs
+// only where the whole wave is active (the hash kernels keep it so: no early exit, stores predicated).
+#ifndef PSD_MDS_MFMA
+#define PSD_MDS_MFMA 1                  // default MDS layer of the hash kernels (-DPSD_MDS_MFMA=0: the VALU layer)
+#endif
+enum { PSD_LAYER_VALU = 0, PSD_LAYER_MFMA = 1, PSD_LAYER_HASH = PSD_MDS_MFMA ? PSD_LAYER_MFMA : PSD_LAYER_VALU };
+#if defined(__HIPCC__)
+typedef int psd_i32x4 __attribute__((ext_vector_type(4)));
+typedef int psd_i32x16 __attribute__((ext_vector_type(16)));
+struct PsdMfmaA { psd_i32x4 blk[4]; };     // blk[d]: d = (K block - row block) mod 3; blk[3]: the (0, 0) block
+#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+// the lane's A operands: row r = lane & 31 is (o = r >> 3, t = r & 3) and lives in lane half (r >> 2) & 1; its K entries are
+// the coefficient of input word q at byte t of register q (the B operand's layout), zero in the other lane half
+__device__ __forceinline__ PsdMfmaA psd_mfma_a() {
+    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), r = lane & 31;
+    const bool mine = ((r >> 2) & 1) == (lane >> 5);
+    const uint32_t o8 = 8 * (r >> 3), t8 = 8 * (r & 3);
+    PsdMfmaA A;
+#pragma unroll
+    for (int d = 0; d < 4; d++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) A.blk[d][q] = mine ? (int)(((d_POSEIDON_MDS_I8A[4 * d + q] >> o8) & 0xFFu) << t8) : 0;
+    return A;
+}
+// M s + the constants of round n (kk = d_POSEIDON_MDS_K + 24 n, n = 30: none) on the matrix cores; bit-identical to
+// psd_mds_then_constants for any u64 representatives
+__device__ __forceinline__ void psd_mds_mfma(gl_t (&s)[12], const gl_t* __restrict__ kk, const PsdMfmaA& A) {
+    psd_i32x4 bl[3], bh[3];
+#pragma unroll
+    for (int kb = 0; kb < 3; kb++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            bl[kb][q] = (int)((uint32_t)s[4 * kb + q] ^ 0x80808080u);
+            bh[kb][q] = (int)((uint32_t)(s[4 * kb + q] >> 32) ^ 0x80808080u);
+        }
+    // opaque multipliers: the recombination stays one v_mad_i64_i32 per byte position (a known power of two becomes a
+    // sign-extension and a 64-bit shift-add); `one` in a VGPR leaves the one scalar operand to the 64-bit constant k
+    int32_t one = 1, m8 = 1 << 8, m16 = 1 << 16, m24 = 1 << 24;
+    asm volatile("" : "+v"(one), "+s"(m8), "+s"(m16), "+s"(m24));
+    gl_t acc[2][12];                       // [half][output word]: the VALU layer's al, ah
+#pragma unroll
+    for (int rb = 0; rb < 3; rb++) {
+#pragma unroll
+        for (int hf = 0; hf < 2; hf++) {
+            // one accumulator chain at a time (16 VGPRs): the scheduler would otherwise start all six at once
+            __builtin_amdgcn_sched_barrier(0);
+            psd_i32x16 d = {};
+#pragma unroll
+            for (int kb = 0; kb < 3; kb++)
+                d = __builtin_amdgcn_mfma_i32_32x32x32_i8((rb == 0 && kb == 0) ? A.blk[3] : A.blk[(kb - rb + 3) % 3], hf ? bh[kb] : bl[kb], d, 0, 0, 0);
+#pragma unroll
+            for (int o = 0; o < 4; o++) {
+                const int i = 4 * rb + o;
+                int64_t x = (int64_t)d[4 * o] * one + (int64_t)kk[2 * i + hf];
+                x += (int64_t)d[4 * o + 1] * m8;
+                x += (int64_t)d[4 * o + 2] * m16;
+                x += (int64_t)d[4 * o + 3] * m24;
+                acc[hf][i] = (gl_t)x;
+            }
+        }
+        // reduce the groups of three this row block completes (outputs 0-2 | 3-5 | 6-8, 9-11)
+#pragma unroll
+        for (int r0 = 3 * rb; r0 < 4 * rb + 2; r0 += 3)
+            glx_acc_reduce3(acc[0][r0], acc[1][r0], acc[0][r0 + 1], acc[1][r0 + 1], acc[0][r0 + 2], acc[1][r0 + 2], s[r0], s[r0 + 1], s[r0 + 2]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+#endif
+
 // M[r][c] of the MDS matrix (circulant + diag(8, 0, ...)), compile-time after unrolling
 GL_HD constexpr uint32_t psd_mds_entry(int r, int c) {
     constexpr uint32_t circ[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
@@ -280,22 +361,38 @@ __device__ __forceinline__ void psd_partial_group(gl_t (&s)[12], int g, const gl
 #endif
 
 #if defined(__HIP_DEVICE_COMPILE__)
-GL_HD void psd_permute(gl_t (&s)[12]) {       // (host + device only so that host code parses in the device pass)
+// the MDS layer of round n - 1 followed by the constants of round n (n = 30: none), on the chosen unit
+template <int LAYER, bool WITH_RC>
+__device__ __forceinline__ void psd_mds_layer(gl_t (&s)[12], int n, const PsdMfmaA& A) {
+    if constexpr (LAYER == PSD_LAYER_MFMA) psd_mds_mfma(s, d_POSEIDON_MDS_K + 24 * (WITH_RC ? n : 8 + POSEIDON_PARTIAL_ROUNDS), A);
+    else psd_mds_then_constants<WITH_RC>(s, WITH_RC ? d_POSEIDON_RC + 12 * n : nullptr);
+}
+// LAYER = PSD_LAYER_MFMA: every lane of the wave must be active (psd_mds_mfma)
+template <int LAYER>
+__device__ __forceinline__ void psd_permute_layer(gl_t (&s)[12]) {
     const gl_t* __restrict__ rc = d_POSEIDON_RC;
+    PsdMfmaA A;
+    if constexpr (LAYER == PSD_LAYER_MFMA) A = psd_mfma_a();
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = gl_add_c(s[i], rc[i]);
 #pragma unroll 1
-    for (int r = 0; r < 4; r++) { psd_sbox_all(s); psd_mds_then_constants<true>(s, rc + 12 * (r + 1)); }
+    for (int r = 0; r < 4; r++) { psd_sbox_all(s); psd_mds_layer<LAYER, true>(s, r + 1, A); }
 #pragma unroll 1
     for (int g = 0; g < POSEIDON_PARTIAL_GROUPS; g++) { gl_t a[3]; psd_partial_group<false>(s, g, nullptr, a); }
 #pragma unroll 1
-    for (int r = 4 + 3 * POSEIDON_PARTIAL_GROUPS; r < 4 + POSEIDON_PARTIAL_ROUNDS; r++) { s[0] = psd_sbox(s[0]); psd_mds_then_constants<true>(s, rc + 12 * (r + 1)); }
+    for (int r = 4 + 3 * POSEIDON_PARTIAL_GROUPS; r < 4 + POSEIDON_PARTIAL_ROUNDS; r++) { s[0] = psd_sbox(s[0]); psd_mds_layer<LAYER, true>(s, r + 1, A); }
 #pragma unroll 1
-    for (int r = 4 + POSEIDON_PARTIAL_ROUNDS; r < 7 + POSEIDON_PARTIAL_ROUNDS; r++) { psd_sbox_all(s); psd_mds_then_constants<true>(s, rc + 12 * (r + 1)); }
+    for (int r = 4 + POSEIDON_PARTIAL_ROUNDS; r < 7 + POSEIDON_PARTIAL_ROUNDS; r++) { psd_sbox_all(s); psd_mds_layer<LAYER, true>(s, r + 1, A); }
     psd_sbox_all(s);
-    psd_mds_then_constants<false>(s, nullptr);
+    psd_mds_layer<LAYER, false>(s, 0, A);
 }
+// any EXEC mask: the VALU layer (the hash kernels call psd_permute_layer<PSD_LAYER_HASH> with the whole wave active)
+GL_HD void psd_permute(gl_t (&s)[12]) { psd_permute_layer<PSD_LAYER_VALU>(s); }
 #else
+#if defined(__HIPCC__)
+template <int LAYER>
+__device__ void psd_permute_layer(gl_t (&s)[12]);       // host pass of a .hip file: kernels that call it must still parse
+#endif
 GL_HD void psd_permute(gl_t (&s)[12]) {         // host formulation (GL_HD only so that kernels parse in the host pass)
     for (int r = 0; r < 4; r++) psd_full_round(s, r);
     psd_partial_rounds(s);

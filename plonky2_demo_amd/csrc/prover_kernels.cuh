@@ -812,19 +812,18 @@ __global__ __launch_bounds__(256) void k_fri_fold(const gl_t* ia, const gl_t* ib
 
 // ---- proof of work: smallest w >= base with clz(permute(state with w at pos)[7]) >= bits ----------------------------------
 struct GlPowParams { gl_t state[12]; uint32_t pos, min_leading_zeros; uint64_t base, count; unsigned long long* result; };
-__global__ __launch_bounds__(256) void k_pow_grind(GlPowParams p) {
+__global__ __launch_bounds__(256, 5) void k_pow_grind(GlPowParams p) {
     const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= p.count) return;
     const uint64_t cand = p.base + idx;
     gl_t s[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = p.state[i];
 #pragma unroll
     for (int i = 0; i < 8; i++) if ((uint32_t)i == p.pos) s[i] = cand;
-    psd_permute(s);
+    psd_permute_layer<PSD_LAYER_HASH>(s);            // the whole wave active (MFMA layer); candidates past count are not reported
     const gl_t r = gl_canon(s[7]);
     const uint32_t lz = r ? (uint32_t)__clzll((long long)r) : 64u;
-    if (lz >= p.min_leading_zeros) atomicMin(p.result, (unsigned long long)cand);
+    if (idx < p.count && lz >= p.min_leading_zeros) atomicMin(p.result, (unsigned long long)cand);
 }
 
 // ---- gathers for the query phase -----------------------------------------------------------------------------------------

@@ -175,6 +175,68 @@ def derive_groups(rc, M):
     return G
 
 
+MFMA_BIAS = 0x80808080                     # each 32-bit half XOR 0x80808080: bytes b -> signed b - 128 (i8 operands)
+
+
+def derive_mfma(rc):
+    """GPU MDS layer on v_mfma_i32_32x32x32_i8 (poseidon.cuh psd_mds_mfma).
+
+    Every lane multiplies its own state: the B operand of K block q0 is the four 32-bit halves of words 4 q0 .. 4 q0 + 3,
+    each XOR 0x80808080, and the 16 result rows of a lane are (output word o of a row block, byte position t): row (o, t)
+    = sum_j c_oj (byte_t(half_j) - 128).  The matrix is circulant, so the A operand of (row block R, K block Kb) depends
+    only on d = (Kb - R) mod 3, except (0, 0), which also holds MDS_MATRIX_DIAG[0].  A[d][q] packs the coefficients of input
+    word q of the K block for the output words o = 0..3 of the row block (byte o); blocks 0..2 by d, block 3 = (0, 0).
+
+    Recombined, sum_t 2^(8t) row(o, t) = sum_j c_oj half_j - rowsum_o 0x80808080, so the constant of the first multiply-add,
+    K[n][i] = ((rc_n[i] mod 2^32) + rowsum_i 0x80808080, (rc_n[i] >> 32) + rowsum_i 0x80808080), makes the two 64-bit
+    accumulators of output word i exactly those of the VALU layer (psd_mds_then_constants).  Row n = 30: no round constants
+    (the last layer)."""
+    Mi = [[MDS_CIRC[(c - r) % W] + (MDS_DIAG[r] if r == c else 0) for c in range(W)] for r in range(W)]
+    A = []
+    for d in range(4):
+        for q in range(4):
+            w = 0
+            for o in range(4):
+                c = Mi[o][q] if d == 3 else MDS_CIRC[(4 * d + q - o) % W]
+                assert 0 <= c < 128
+                w |= c << (8 * o)
+            A.append(w)
+    rowsum = [sum(r) for r in Mi]
+    K = []
+    for n in range(N_ROUNDS + 1):
+        row = rc[n] if n < N_ROUNDS else [0] * W
+        for i in range(W):
+            K += [(row[i] & 0xFFFFFFFF) + rowsum[i] * MFMA_BIAS, (row[i] >> 32) + rowsum[i] * MFMA_BIAS]
+    return dict(A=A, K=K)
+
+
+def mds_mfma(s, A, K, n):
+    """The MFMA layer's arithmetic in Python, operand by operand: the MDS layer followed by round n's constants (n = 30:
+    none), on u64 representatives; returns the (al, ah) pairs, which equal the VALU layer's, and the reduced words."""
+    sbyte = lambda x, t: ((x >> (8 * t)) & 0xFF) ^ 0x80
+    signed = lambda b: b - 256 if b >= 128 else b
+    coef = lambda blk, o, q: (A[4 * blk + q] >> (8 * o)) & 0xFF
+    acc = []
+    for R in range(3):
+        for o in range(4):
+            i = 4 * R + o
+            pair = []
+            for h in range(2):
+                tot = K[24 * n + 2 * i + h]
+                for t in range(4):
+                    row = 0
+                    for Kb in range(3):
+                        blk = 3 if (R == 0 and Kb == 0) else (Kb - R) % 3
+                        for q in range(4):
+                            half = (s[4 * Kb + q] >> (32 * h)) & 0xFFFFFFFF
+                            row += coef(blk, o, q) * signed(sbyte(half, t))
+                    assert -2**31 <= row < 2**31
+                    tot += row << (8 * t)
+                pair.append(tot % 2**64)
+            acc.append(tuple(pair))
+    return acc, [(al + (ah << 32)) % P for al, ah in acc]
+
+
 def perm_grouped(state, rc, M, G):
     s = [x % P for x in state]
     r = 0
@@ -221,7 +283,7 @@ KATS = [
 ]
 
 
-def emit(path, rc, T, G):
+def emit(path, rc, T, G, F):
     """Writes <path> (host wrapper, guarded) and <path minus .h>.inc (raw tables behind POSEIDON_TABLE)."""
     def arr(name, vals, per_line=4):
         out = ["POSEIDON_TABLE(%s, %d) = {" % (name, len(vals))]
@@ -264,6 +326,11 @@ def emit(path, rc, T, G):
         arr32("POSEIDON_G3_V1", G["V1"]),
         arr32("POSEIDON_G3_V2", G["V2"]),
         arr("POSEIDON_G3_K", flat(G["K"])),
+        "// GPU MDS layer on the i8 matrix cores (derive_mfma): A operand coefficients, word 4 d + q = input word q of a K block",
+        "// for the output words o = 0..3 of a row block (byte o), d = (K block - row block) mod 3, d = 3: block (0, 0) with the",
+        "// diagonal; and per round n (n = 30: no constants) the bias-corrected (k_lo, k_hi) of output word i at 24 n + 2 i",
+        arr32("POSEIDON_MDS_I8A", F["A"], 16),
+        arr("POSEIDON_MDS_K", F["K"]),
         "",
     ]
     inc_path = path[:-2] + ".inc" if path.endswith(".h") else path + ".inc"
@@ -301,10 +368,20 @@ def main():
         assert perm_naive(t, rc, T["M"]) == perm_grouped(t, rc, T["M"], G), "grouped != naive"
     for inp, out in KATS:
         assert perm_fast(inp, rc, T) == out, "KAT mismatch"
+    F = derive_mfma(rc)
+    M = T["M"]
+    for t in tests + [[0] * W, [2**64 - 1] * W, [P] * W, [0x7F7F7F7F80808080] * W, [0xFFFFFFFF7F7F7F7F] * W]:
+        for n in (1, 17, N_ROUNDS):
+            acc, out = mds_mfma(t, F["A"], F["K"], n)
+            cst = rc[n] if n < N_ROUNDS else [0] * W
+            lo = [x & 0xFFFFFFFF for x in t]; hi = [x >> 32 for x in t]
+            assert acc == [(cst[i] % 2**32 + sum(M[i][j] * lo[j] for j in range(W)), (cst[i] >> 32) + sum(M[i][j] * hi[j] for j in range(W)))
+                           for i in range(W)], "MFMA accumulators != VALU accumulators"
+            assert out == [(a + c) % P for a, c in zip(mat_vec(M, t), cst)], "MFMA layer != M s + rc"
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(
         HERE, "..", "plonky2_demo_amd", "csrc", "poseidon_constants.h")
-    emit(out, rc, T, G)
-    print("ok: naive==fast==grouped on %d inputs, 4 KATs pass; wrote %s" % (len(tests), os.path.normpath(out)))
+    emit(out, rc, T, G, F)
+    print("ok: naive==fast==grouped on %d inputs, 4 KATs pass, MFMA layer == VALU layer; wrote %s" % (len(tests), os.path.normpath(out)))
     return T
 
 
