@@ -1,14 +1,17 @@
 // The reference's demo program (plonky2/src/bin/matrix_mul.rs, examples/matrix_multiplication.rs) on the MI355X
 // backend: "I know A * B = C" for random m x m matrices of u32 entries -- build, prove, print, verify.
 //
-//   matrix_mul [m = 20] [seed] [batch]  (seed 0 / absent: operands from std::random_device, as the reference draws them
+//   matrix_mul [m = 20] [seed] [batch] [--zk]
+//                                       (seed 0 / absent: operands from std::random_device, as the reference draws them
 //                                        from ChaChaRng::from_entropy(), matrix_mul.rs:72-80; batch > 1: that many
-//                                        independent proofs through gl_prover_pool, four in flight, each verified)
+//                                        independent proofs through gl_prover_pool, four in flight, each verified;
+//                                        --zk: the zero-knowledge circuit, standard_recursion_zk_config, witnesses blinded)
 //
 // Plain C++ over the C ABI of include/plonky2_mi355x.h; the only GPU-specific line is gl_ctx_create.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <vector>
 #include "../include/plonky2_mi355x.h"
@@ -24,6 +27,9 @@ static double ms_since(std::chrono::steady_clock::time_point t0) {
 }
 
 int main(int argc, char** argv) {
+    bool zk = false;
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--zk")) { zk = true; for (int j = i; j + 1 < argc; j++) argv[j] = argv[j + 1]; argc--; i--; }
     const size_t m = argc > 1 ? (size_t)atoi(argv[1]) : 20;                      // matrix_mul.rs:30
     const uint64_t seed_arg = argc > 2 ? (uint64_t)strtoull(argv[2], nullptr, 10) : 0;
     std::mt19937_64 rng(seed_arg ? seed_arg : ((uint64_t)std::random_device{}() << 32) ^ std::random_device{}());
@@ -35,7 +41,7 @@ int main(int argc, char** argv) {
     // ---- build (matrix_mul.rs:25-67): circuit description on the host, constants/sigmas commitment on the GPU ----
     auto t0 = std::chrono::steady_clock::now();
     gl_host_circuit* hc = nullptr;
-    CHECK(gl_matmul_circuit_build(m, &hc));
+    CHECK(zk ? gl_matmul_circuit_build_zk(m, &hc) : gl_matmul_circuit_build(m, &hc));
     gl_circuit_desc desc;
     CHECK(gl_host_circuit_desc(hc, &desc));
     gl_ctx* ctx = nullptr;
@@ -48,7 +54,7 @@ int main(int argc, char** argv) {
     std::vector<uint64_t> cap(4 * ncap), digest(4);
     CHECK(gl_circuit_constants_sigmas_cap(circuit, cap.data()));
     CHECK(gl_circuit_digest(circuit, digest.data()));
-    fprintf(stderr, "build: m = %zu, %zu rows (2^%u), %.1f ms\n", m, n, desc.degree_bits, ms_since(t0));
+    fprintf(stderr, "build: m = %zu, %zu rows (2^%u)%s, %.1f ms\n", m, n, desc.degree_bits, zk ? ", zero knowledge" : "", ms_since(t0));
 
     // ---- witness (matrix_mul.rs:70-83): u32 operands, gen_range(u32::MIN..u32::MAX) ----
     std::vector<uint64_t> a(m * m), b(m * m), pis(3 * m * m), pi_hash(4);
@@ -61,6 +67,7 @@ int main(int argc, char** argv) {
     void* d_wires = nullptr;
     CHECK(gl_dev_alloc(ctx, 135 * n * sizeof(uint64_t), &d_wires));
     CHECK(gl_matmul_witgen_run(gen, a.data(), b.data(), rng(), (uint64_t*)d_wires, pis.data(), pi_hash.data()));
+    if (zk) CHECK(gl_witness_blind(ctx, circuit, (uint64_t*)d_wires, nullptr));      // blinding rows from OS entropy
     fprintf(stderr, "witness: %.1f ms\n", ms_since(t0));
 
     // ---- prove (matrix_mul.rs:86) ----

@@ -48,7 +48,7 @@ extern "C" {
 #define GL_OK 0
 #define GL_ERR_ARG 1          /* bad shape / null pointer / unsupported size          */
 #define GL_ERR_HIP 2          /* HIP runtime error (no device, OOM, launch failure)   */
-#define GL_ERR_UNSUPPORTED 3  /* e.g. blinding != 0 (zero-knowledge salts)            */
+#define GL_ERR_UNSUPPORTED 3  /* e.g. gl_batch_from_values with blinding != 0 (use the _blinded entries), zk with lookups */
 #define GL_ERR_ZETA_IN_SUBGROUP 4 /* prover.rs:280-283: opening point lies in H       */
 #define GL_ERR_INTERNAL 5
 #define GL_ERR_VERIFY 6       /* gl_verify: the proof is rejected (gl_last_error says which check failed) */
@@ -100,6 +100,12 @@ typedef struct gl_circuit_desc {
     uint32_t last_lu_row[4], last_lut_row[4], first_lut_row[4];
     uint32_t lut_len[4];               /* entries per table; their sum <= GL_MAX_LUT_ENTRIES                                   */
     uint16_t lut[2 * 1024];            /* (input, output) pairs (gates/lookup_table.rs:22), the tables one after the other     */
+    /* ---- zero knowledge (CircuitConfig::standard_recursion_zk_config, circuit_data.rs:104-110): the wires, Z / partial-products and
+     * quotient commitments are salted (config.zero_knowledge = fri_params.hiding), and blind_and_pad appended blinding rows
+     * (circuit_builder.rs:713-818).  Not together with lookups (GL_ERR_UNSUPPORTED). ---- */
+    uint32_t zero_knowledge;           /* 0 / 1                                                                                 */
+    uint32_t num_gate_rows;            /* rows before blind_and_pad, or 0 when unknown (a description read from bytes); when set,
+                                          degree_bits must be what blinding_counts + padding give, and gl_witness_blind needs it */
 } gl_circuit_desc;
 #define GL_MAX_GATES 16
 #define GL_MAX_LUTS 4
@@ -176,19 +182,26 @@ void gl_merkle_free(gl_merkle* t);
 /* ---- PolynomialBatch -----------------------------------------------------------------------------*/
 /* PolynomialBatch::from_values(values, rate_bits, blinding, cap_height, timing, fft_root_table)
  * (plonky2/src/fri/oracle.rs:43-66).  h_cols[c] points at the n = 2^k values of polynomial c.
- * blinding must be 0 (GL_ERR_UNSUPPORTED otherwise).  Keeps coefficients, LDE values and all Merkle
- * digests device-resident. */
+ * blinding must be 0 (GL_ERR_UNSUPPORTED otherwise): blinding = true is gl_batch_from_values_blinded below.  Keeps
+ * coefficients, LDE values and all Merkle digests device-resident. */
 int gl_batch_from_values(gl_ctx* ctx, const uint64_t* const* h_cols, size_t ncols, size_t n,
                          uint32_t rate_bits, uint32_t blinding, uint32_t cap_height, gl_batch** out);
 /* PolynomialBatch::from_coeffs (plonky2/src/fri/oracle.rs:68-98) */
 int gl_batch_from_coeffs(gl_ctx* ctx, const uint64_t* const* h_cols, size_t ncols, size_t n,
                          uint32_t rate_bits, uint32_t blinding, uint32_t cap_height, gl_batch** out);
+/* from_values / from_coeffs with blinding = true: every leaf salted with SALT_SIZE = 4 random elements (fri/oracle.rs:100-125); salt
+ * column j is stream 0x200 + j of the keystream below, keyed by `seed` (NULL = a fresh OS seed).  The salt enters the Merkle leaves
+ * only (get_leaf / prove: ncols + 4 elements), never the polynomials (get_lde_values, the coefficients, the LDE). */
+int gl_batch_from_values_blinded(gl_ctx* ctx, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
+                                 uint32_t cap_height, const uint8_t seed[32], gl_batch** out);
+int gl_batch_from_coeffs_blinded(gl_ctx* ctx, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
+                                 uint32_t cap_height, const uint8_t seed[32], gl_batch** out);
 /* same, from a device-resident column-major matrix d_cols[ncols][n]; is_values selects from_values */
 int gl_batch_from_device(gl_ctx* ctx, const uint64_t* d_cols, size_t ncols, size_t n, uint32_t rate_bits,
                          uint32_t cap_height, int is_values, gl_batch** out);
 /* field `merkle_tree.cap` (used at prover.rs:164,225,273,319-321): h_out[2^cap_height][4] */
 int gl_batch_cap(const gl_batch* b, uint64_t* h_out);
-/* merkle_tree.get(i) (merkle_tree.rs:167-169): the leaf at Merkle index i, h_out[ncols] */
+/* merkle_tree.get(i) (merkle_tree.rs:167-169): the leaf at Merkle index i, h_out[ncols] (h_out[ncols + 4] with blinding: the salt last) */
 int gl_batch_get_leaf(const gl_batch* b, size_t leaf_index, uint64_t* h_out);
 /* PolynomialBatch::get_lde_values(index, step) (oracle.rs:128-133), h_out[ncols] */
 int gl_batch_get_lde_values(const gl_batch* b, size_t index, size_t step, uint64_t* h_out);
@@ -204,11 +217,29 @@ const uint64_t* gl_batch_dev_coeffs(const gl_batch* b);   /* d [ncols][n]  */
 const uint64_t* gl_batch_dev_lde(const gl_batch* b);      /* d [ncols][N]  */
 void gl_batch_free(gl_batch* b);
 
+/* ---- randomness of zero-knowledge proving ------------------------------------------------------------
+ * A keyed counter-based generator: ChaCha20's block function (RFC 8439 section 2.3) with key = the 32-byte seed, nonce =
+ * (stream as u32 LE, 0, 0) and block counter = block index; element i of a stream is (w_{2i} + 2^64 w_{2i+1}) mod p over the
+ * keystream's little-endian u64 words (canonical, within 2^-64 of uniform).  Streams: 0x100 + w = blinding values of wire column w
+ * (element index = row), 0x200 + 4 o + j = salt column j of PlonkOracle o (1 wires, 2 zs_partial_products, 3 quotient; element
+ * index = natural LDE row).  Everywhere a seed is taken, NULL means 32 fresh bytes from getrandom(2), one per proof.
+ * A seed must never be reused for two different witnesses of a circuit: the two proofs' blinding and salts cancel, and hiding is
+ * lost.  Fixed seeds are for tests and reproducible runs. */
+/* d_out[i] = element first + i of `stream`, i < count (first + count <= 2^34) */
+int gl_random_elements(gl_ctx* ctx, const uint8_t seed[32], uint32_t stream, uint64_t first, uint64_t count, uint64_t* d_out);
+/* the same on the host (no GPU needed) */
+int gl_random_elements_host(const uint8_t seed[32], uint32_t stream, uint64_t first, uint64_t count, uint64_t* h_out);
+
 /* ---- circuit data ----------------------------------------------------------------------------------*/
 /* Host side of the demo (no GPU needed): the matmul circuit of plonky2/src/bin/matrix_mul.rs:25-67 after
  * CircuitBuilder::build() (plonk/circuit_builder.rs:913-1146): descriptor, gate type per row, and the
  * constants || sigmas VALUE columns, h_out[(num_constants + 80)][n]. */
 int gl_matmul_circuit_build(size_t m, gl_host_circuit** out);
+/* The same circuit built with standard_recursion_zk_config: the same gate rows (gates, constants, copy classes), then blind_and_pad's
+ * blinding rows and padding -- NoopGate rows with singleton copy classes -- and degree_bits / FRI arities of the longer trace.
+ * desc.zero_knowledge = 1, desc.num_gate_rows = the rows before blinding.  gl_matmul_witness and the witness generator leave the
+ * rows from num_gate_rows on zero; gl_witness_blind fills them in before proving. */
+int gl_matmul_circuit_build_zk(size_t m, gl_host_circuit** out);
 int gl_host_circuit_desc(const gl_host_circuit* hc, gl_circuit_desc* out);
 int gl_host_circuit_row_gates(const gl_host_circuit* hc, uint8_t* h_out /* n */);
 int gl_host_circuit_constants_sigmas(const gl_host_circuit* hc, uint64_t* h_out);
@@ -248,12 +279,18 @@ int gl_circuit_description(const gl_circuit* c, gl_circuit_desc* out);
  * so that the first gl_prove on this context does not pay for loading the kernels' code objects, building the twiddle tables of the
  * circuit's transform sizes and growing the context's pool (m = 64: 15 ms for the first proof without it, 7 ms with). */
 int gl_circuit_warm_up(gl_ctx* ctx, const gl_circuit* c);
+/* The RandomValueGenerators and CopyGenerators of blind() (circuit_builder.rs:777-818) on the device, for a zero-knowledge circuit with
+ * num_gate_rows set: from row num_gate_rows on, `regular` rows of 135 random wires, then `pairs` row pairs whose first row's 80 routed
+ * wires are random and copied to the second, every other wire of those rows and the padding rows 0 (full_witness, iop/witness.rs:340-352).
+ * seed NULL = OS entropy.  A Rust-built zk circuit's witness arrives blinded by Rust's own generators and goes straight to gl_prove*. */
+int gl_witness_blind(gl_ctx* ctx, const gl_circuit* c, uint64_t* d_wires, const uint8_t seed[32]);
 int gl_circuit_digest(const gl_circuit* c, uint64_t h_out[4]);                 /* verifier_only.circuit_digest */
 int gl_circuit_constants_sigmas_cap(const gl_circuit* c, uint64_t* h_out);     /* [2^cap_height][4]            */
 const gl_batch* gl_circuit_constants_sigmas_batch(const gl_circuit* c);
 void gl_circuit_free(gl_circuit* c);
 
 /* ---- prover phases ---------------------------------------------------------------------------------*/
+/* Not for zero-knowledge circuits (GL_ERR_UNSUPPORTED): they are proved by gl_prove* only. */
 /* The seam for a caller that keeps the Fiat-Shamir transcript (iop/challenger.rs) on its own side: each entry
  * point replaces one call of plonk::prover::prove and returns exactly what the transcript absorbs next.
  * gl_prove() below is these calls in the order of prover.rs:102-329 with the Challenger in C++.
@@ -333,6 +370,10 @@ int gl_prove_device(gl_ctx* ctx, const gl_circuit* c, const uint64_t* d_wires, c
  * generator's sponge produces it as a by-product, and hashing 3 m^2 inputs is a sequential host job */
 int gl_prove_device_hashed(gl_ctx* ctx, const gl_circuit* c, const uint64_t* d_wires, const uint64_t* h_public_inputs,
                            size_t num_public_inputs, const uint64_t public_inputs_hash[4], gl_proof** out);
+/* gl_prove_device with the salt of the three salted commitments of a zero-knowledge circuit drawn from `seed` (NULL = OS entropy, which is
+ * what every other gl_prove* entry and both pools use).  Ignored without zero knowledge. */
+int gl_prove_device_seeded(gl_ctx* ctx, const gl_circuit* c, const uint64_t* d_wires, const uint64_t* h_public_inputs,
+                           size_t num_public_inputs, const uint8_t seed[32], gl_proof** out);
 /* Many independent proofs in flight on one GPU from one call -- what the reference gets from its Rayon pool when a batch of
  * witnesses is proved.  The pool owns one device-resident circuit and `lanes` contexts (HIP stream, allocator, witness
  * generator each); item i is proved on lane i % lanes by `lanes` host threads inside the call.  `hc` is borrowed. */
@@ -384,8 +425,8 @@ int gl_host_circuit_verify(const gl_host_circuit* hc, const uint64_t* constants_
  * 1736-1790 CommonCircuitData, :909-930,1889-1906 VerifierOnlyCircuitData, :1908-1919 VerifierCircuitData = verifier_only ||
  * common; gates tagged as by DefaultGateSerializer, util/serialization/gate_serialization.rs:87-108), so that a Rust-built
  * circuit's CommonCircuitData / VerifierCircuitData bytes can be handed over instead of a hand-filled gl_circuit_desc.  Host code.
- * Representable: the demo's five gates, standard_recursion_config's shape (no lookups, no zero-knowledge); anything else
- * is GL_ERR_UNSUPPORTED when reading.  h_out may be null to query *num_bytes.  The value columns (constants, sigmas) and the
+ * Representable: the demo's gates, standard_recursion_config's shape, and its zero-knowledge form (zero_knowledge = hiding = 1;
+ * num_gate_rows reads as 0); anything else, mixed zero_knowledge / hiding flags among it, is GL_ERR_UNSUPPORTED when reading.  h_out may be null to query *num_bytes.  The value columns (constants, sigmas) and the
  * generators of ProverOnlyCircuitData are not part of these forms: gl_circuit_create still takes the columns. */
 int gl_common_data_to_bytes(const gl_circuit_desc* desc, uint8_t* h_out, size_t cap, size_t* num_bytes);
 int gl_common_data_from_bytes(const uint8_t* h_bytes, size_t num_bytes, gl_circuit_desc* out, size_t* consumed /* may be null */);

@@ -83,6 +83,12 @@ SIGNATURES = {
     "gl_batch_dev_lde": (c_vp, [c_vp]),
     "gl_batch_free": (None, [c_vp]),
     "gl_matmul_circuit_build": (c_int, [c_sz, ctypes.POINTER(c_vp)]),
+    "gl_matmul_circuit_build_zk": (c_int, [c_sz, ctypes.POINTER(c_vp)]),
+    "gl_batch_from_values_blinded": (c_int, [c_vp, ctypes.POINTER(c_vp), c_sz, c_sz, c_u32, c_u32, c_vp, ctypes.POINTER(c_vp)]),
+    "gl_batch_from_coeffs_blinded": (c_int, [c_vp, ctypes.POINTER(c_vp), c_sz, c_sz, c_u32, c_u32, c_vp, ctypes.POINTER(c_vp)]),
+    "gl_random_elements": (c_int, [c_vp, c_vp, c_u32, c_u64, c_u64, c_vp]),
+    "gl_random_elements_host": (c_int, [c_vp, c_u32, c_u64, c_u64, c_vp]),
+    "gl_witness_blind": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "gl_host_circuit_desc": (c_int, [c_vp, c_vp]),
     "gl_host_circuit_row_gates": (c_int, [c_vp, c_vp]),
     "gl_host_circuit_constants_sigmas": (c_int, [c_vp, c_vp]),
@@ -123,6 +129,7 @@ SIGNATURES = {
     "gl_prove_columns": (c_int, [c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, c_sz, ctypes.POINTER(c_vp)]),
     "gl_prove_device": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(c_vp)]),
     "gl_prove_device_hashed": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, ctypes.POINTER(c_vp)]),
+    "gl_prove_device_seeded": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, ctypes.POINTER(c_vp)]),
     "gl_prover_pool_create": (c_int, [c_int, c_vp, c_u32, ctypes.POINTER(c_vp)]),
     "gl_prover_pool_lanes": (c_u32, [c_vp]),
     "gl_prover_pool_circuit": (c_vp, [c_vp]),
@@ -160,6 +167,7 @@ class CircuitDesc(ctypes.Structure):
         ("num_lookup_polys", c_u32), ("num_lookup_selectors", c_u32), ("num_luts", c_u32),
         ("last_lu_row", c_u32 * 4), ("last_lut_row", c_u32 * 4), ("first_lut_row", c_u32 * 4), ("lut_len", c_u32 * 4),
         ("lut", ctypes.c_uint16 * 2048),
+        ("zero_knowledge", c_u32), ("num_gate_rows", c_u32),
     ]
 
     def lookup_table(self, t):

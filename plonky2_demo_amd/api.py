@@ -288,6 +288,8 @@ class PolynomialBatch(_Owned):
     """plonky2::fri::oracle::PolynomialBatch (fri/oracle.rs:30-133), device-resident."""
     _free = "gl_batch_free"
 
+    salt = 0        # SALT_SIZE random elements behind every leaf of a blinded batch (oracle.rs:100-125)
+
     def __init__(self, handle, ctx, rate_bits, cap_height):
         self.handle, self.ctx, self.rate_bits, self.cap_height = handle, ctx, rate_bits, cap_height
         self.ncols = lib.gl_batch_ncols(handle)
@@ -295,7 +297,8 @@ class PolynomialBatch(_Owned):
         self.degree_log = _log2_strict(self.degree)
 
     @classmethod
-    def _from_host(cls, fn, cols, rate_bits, blinding, cap_height, ctx):
+    def _from_host(cls, fn, cols, rate_bits, cap_height, ctx, *args, salt=0):
+        """fn(ctx, column pointers, ncols, n, rate_bits, *args, out)"""
         ctx = _ctx(ctx)
         cols = [_u64(c) for c in cols]
         if not cols:
@@ -305,18 +308,32 @@ class PolynomialBatch(_Owned):
             raise ValueError("Polynomial degrees inconsistent")   # oracle.rs:114
         ptrs = (ctypes.c_void_p * len(cols))(*[c.ctypes.data for c in cols])
         h = ctypes.c_void_p()
-        check(fn(ctx.handle, ptrs, len(cols), n, rate_bits, 1 if blinding else 0, cap_height, ctypes.byref(h)))
-        return cls(h.value, ctx, rate_bits, cap_height)
+        check(fn(ctx.handle, ptrs, len(cols), n, rate_bits, *args, ctypes.byref(h)))
+        b = cls(h.value, ctx, rate_bits, cap_height)
+        b.salt = salt
+        return b
 
     @classmethod
     def from_values(cls, values, rate_bits, blinding, cap_height, ctx=None):
-        """PolynomialBatch::from_values (fri/oracle.rs:43-66)."""
-        return cls._from_host(lib.gl_batch_from_values, values, rate_bits, blinding, cap_height, ctx)
+        """PolynomialBatch::from_values (fri/oracle.rs:43-66); blinding = True is from_values_blinded."""
+        return cls._from_host(lib.gl_batch_from_values, values, rate_bits, cap_height, ctx, 1 if blinding else 0, cap_height)
 
     @classmethod
     def from_coeffs(cls, polynomials, rate_bits, blinding, cap_height, ctx=None):
-        """PolynomialBatch::from_coeffs (fri/oracle.rs:68-98)."""
-        return cls._from_host(lib.gl_batch_from_coeffs, polynomials, rate_bits, blinding, cap_height, ctx)
+        """PolynomialBatch::from_coeffs (fri/oracle.rs:68-98); blinding = True is from_coeffs_blinded."""
+        return cls._from_host(lib.gl_batch_from_coeffs, polynomials, rate_bits, cap_height, ctx, 1 if blinding else 0, cap_height)
+
+    @classmethod
+    def from_values_blinded(cls, values, rate_bits, cap_height, seed=None, ctx=None):
+        """from_values with blinding = true: every leaf salted with SALT_SIZE elements keyed by `seed` (32 bytes; None = OS entropy)."""
+        return cls._from_host(lib.gl_batch_from_values_blinded, values, rate_bits, cap_height, ctx, cap_height,
+                              _seed(seed) if seed is not None else None, salt=SALT_SIZE)
+
+    @classmethod
+    def from_coeffs_blinded(cls, polynomials, rate_bits, cap_height, seed=None, ctx=None):
+        """from_coeffs with blinding = true (see from_values_blinded)."""
+        return cls._from_host(lib.gl_batch_from_coeffs_blinded, polynomials, rate_bits, cap_height, ctx, cap_height,
+                              _seed(seed) if seed is not None else None, salt=SALT_SIZE)
 
     @classmethod
     def from_device(cls, d_ptr, ncols, n, rate_bits, cap_height, is_values, ctx=None):
@@ -343,7 +360,8 @@ class PolynomialBatch(_Owned):
         return out
 
     def get_leaf(self, i):
-        out = np.empty(self.ncols, dtype=np.uint64)
+        """merkle_tree.get(i): the LDE row with its salt (ncols + salt elements)."""
+        out = np.empty(self.ncols + self.salt, dtype=np.uint64)
         check(lib.gl_batch_get_leaf(self.handle, i, _p(out)))
         return out
 
@@ -371,13 +389,15 @@ class PolynomialBatch(_Owned):
 
 # ------------------------------------------------------------------------------------- circuit and prove()
 class MatmulCircuit(_Owned):
-    """Host side of the demo (plonky2/src/bin/matrix_mul.rs:25-67 + CircuitBuilder::build()): needs no GPU."""
+    """Host side of the demo (plonky2/src/bin/matrix_mul.rs:25-67 + CircuitBuilder::build()): needs no GPU.  zero_knowledge=True
+    builds it with standard_recursion_zk_config: blinding rows after the gate rows, salted commitments (blind the witness with
+    CircuitData.blind_witness before proving)."""
     _free = "gl_host_circuit_free"
 
-    def __init__(self, m):
+    def __init__(self, m, zero_knowledge=False):
         h = ctypes.c_void_p()
-        check(lib.gl_matmul_circuit_build(int(m), ctypes.byref(h)))
-        self.handle, self.m = h.value, int(m)
+        check((lib.gl_matmul_circuit_build_zk if zero_knowledge else lib.gl_matmul_circuit_build)(int(m), ctypes.byref(h)))
+        self.handle, self.m, self.zero_knowledge = h.value, int(m), bool(zero_knowledge)
         self.desc = _lib.CircuitDesc()
         check(lib.gl_host_circuit_desc(self.handle, ctypes.byref(self.desc)))
         self.degree_bits = self.desc.degree_bits
@@ -439,6 +459,33 @@ class WitnessGenerator(_Owned):
         self.public_inputs_hash = np.empty(4, dtype=np.uint64)      # by-product of the sponge rows
         check(lib.gl_matmul_witgen_run(self.handle, _p(a), _p(b), filler_seed, d_wires_ptr, _p(pis), _p(self.public_inputs_hash)))
         return pis
+
+SALT_SIZE = 4     # fri/oracle.rs:26
+
+
+def _seed(seed):
+    """A 32-byte seed as a ctypes buffer (kept alive by the caller's expression)."""
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("a seed is 32 bytes")
+    return ctypes.create_string_buffer(seed, 32)
+
+
+def random_elements(seed, stream, first, count, ctx=None):
+    """Elements first .. first + count of a stream of the zero-knowledge generator (ChaCha20 keystream, include/plonky2_mi355x.h),
+    computed on the device.  `ctx=False` computes them on the host instead (gl_random_elements_host)."""
+    out = np.empty(int(count), dtype=np.uint64)
+    if ctx is False:
+        check(lib.gl_random_elements_host(_seed(seed), stream, first, count, _p(out)))
+        return out
+    ctx = _ctx(ctx)
+    buf = ctx.alloc(max(1, out.size) * 8)
+    try:
+        check(lib.gl_random_elements(ctx.handle, _seed(seed), stream, first, count, buf.ptr))
+        return buf.download(out.size)
+    finally:
+        buf.free()
+
 
 def _circuit_digest(handle):
     out = np.empty(4, dtype=np.uint64)
@@ -511,11 +558,21 @@ class _CircuitApi(_Owned):
         hc = columns if isinstance(columns, HostColumns) else HostColumns(columns, self.n)
         return self._prove(lib.gl_prove_columns, hc.ptrs, public_inputs)
 
-    def prove_device(self, d_wires_ptr, public_inputs, public_inputs_hash=None):
-        """prove() with the witness matrix already in HBM (raw device pointer to [135][n] u64)."""
+    def prove_device(self, d_wires_ptr, public_inputs, public_inputs_hash=None, seed=None):
+        """prove() with the witness matrix already in HBM (raw device pointer to [135][n] u64).  `seed` (32 bytes) keys the salts of a
+        zero-knowledge circuit (gl_prove_device_seeded); without it they come from the OS."""
+        if seed is not None:
+            if public_inputs_hash is not None:
+                raise ValueError("prove_device takes a seed or a public-inputs hash, not both")
+            return self._prove(lib.gl_prove_device_seeded, d_wires_ptr, public_inputs, _seed(seed))
         if public_inputs_hash is None:
             return self._prove(lib.gl_prove_device, d_wires_ptr, public_inputs)
         return self._prove(lib.gl_prove_device_hashed, d_wires_ptr, public_inputs, _p(_u64(public_inputs_hash)))
+
+    def blind_witness(self, d_wires_ptr, seed=None, ctx=None):
+        """gl_witness_blind: the blinding rows of a zero-knowledge circuit's device witness [135][n] (RandomValueGenerator +
+        CopyGenerator of blind(), circuit_builder.rs:777-818); seed None = OS entropy."""
+        check(lib.gl_witness_blind((ctx or self.ctx).handle, self.handle, d_wires_ptr, _seed(seed) if seed is not None else None))
 
     def warm_up(self, ctx=None):
         """gl_circuit_warm_up: one throw-away pass of the proving pipeline on `ctx` (default: this object's context), so that the first

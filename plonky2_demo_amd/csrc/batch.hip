@@ -3,16 +3,18 @@
 // HBM layout (all u64, canonical):
 //   coeffs  [ncols][n]        coefficient form            (oracle.rs:32 `polynomials`)
 //   lde     [ncols][N]        values on 7*H_N, NATURAL order (index i <-> 7*w_N^i), N = n << rate_bits
+//           (+ [4][N] salt)   blinding: SALT_SIZE random columns, element = natural LDE row (oracle.rs:100-125, rng.cuh streams)
 //   digests level-ordered Merkle digests; leaf j of the tree is LDE row bitrev(j)  (oracle.rs:83-84)
 // The reference materialises row-major, bit-reversed `merkle_tree.leaves` (N x ncols); here rows are
 // gathered on demand (get_leaf / get_lde_values) and later kernels read the natural-order columns.
 #include "context.hpp"
+#include "rng.cuh"
 #include <cstring>
 
 
 // `values`: column-major VALUES to interpolate into b->coeffs (may be b->coeffs itself), or null when b->coeffs already
-// holds coefficients
-static int batch_commit(gl_ctx* c, gl_batch* b, const gl_t* values) {
+// holds coefficients; `seed`: the salt columns' key when b->salt != 0 (salt column j of PlonkOracle `oracle` = stream 0x200 + 4 oracle + j)
+static int batch_commit(gl_ctx* c, gl_batch* b, const gl_t* values, const uint8_t* seed = nullptr, uint32_t oracle = 0) {
     // values -> coefficients (oracle.rs:51-55)
     if (values) {
         c->timing_begin("IFFT");
@@ -27,14 +29,15 @@ static int batch_commit(gl_ctx* c, gl_batch* b, const gl_t* values) {
                             false, GL_MULT_GENERATOR, 0, 1);
     c->timing_end();
     GL_TRY(st_lde);
-    std::vector<uint64_t> offs(b->ncols);
-    for (size_t e = 0; e < b->ncols; e++) offs[e] = e * b->N();
-    GL_TRY(gl_merkle_build(c, b->lde, offs.data(), (uint32_t)b->ncols, b->degree_log + b->rate_bits, b->cap_height, &b->tree));
+    if (b->salt) GL_TRY(gl_fill_random(c, seed, GL_STREAM_SALT + 4 * oracle, b->salt, 0, b->N(), b->lde + b->ncols * b->N(), b->N()));
+    std::vector<uint64_t> offs(b->leaf_len());
+    for (size_t e = 0; e < b->leaf_len(); e++) offs[e] = e * b->N();
+    GL_TRY(gl_merkle_build(c, b->lde, offs.data(), (uint32_t)b->leaf_len(), b->degree_log + b->rate_bits, b->cap_height, &b->tree));
     return GL_OK;
 }
 
 extern "C" void gl_batch_free(gl_batch* b);
-static int batch_alloc(gl_ctx* c, size_t ncols, size_t n, uint32_t rate_bits, uint32_t cap_height, gl_batch** out) {
+static int batch_alloc(gl_ctx* c, size_t ncols, size_t n, uint32_t rate_bits, uint32_t cap_height, uint32_t salt, gl_batch** out) {
     GL_REQUIRE(c && out && ncols >= 1 && n >= 1, GL_ERR_ARG, "PolynomialBatch: bad argument");
     uint32_t lg = 0;
     while ((size_t(1) << lg) < n) lg++;
@@ -44,52 +47,71 @@ static int batch_alloc(gl_ctx* c, size_t ncols, size_t n, uint32_t rate_bits, ui
     GL_TRY(c->activate());
     gl_batch* b = new gl_batch();
     b->ctx = c; c->retain(); b->ncols = ncols; b->n = n; b->degree_log = lg; b->rate_bits = rate_bits; b->cap_height = cap_height;
+    b->salt = salt;
     int st = c->pool_alloc(ncols * n * sizeof(gl_t), (void**)&b->coeffs);
-    if (st == GL_OK) st = c->pool_alloc(ncols * b->N() * sizeof(gl_t), (void**)&b->lde);
+    if (st == GL_OK) st = c->pool_alloc(b->leaf_len() * b->N() * sizeof(gl_t), (void**)&b->lde);
     if (st != GL_OK) { gl_batch_free(b); return st; }      // nothing leaks when the device is out of memory
     *out = b;
     return GL_OK;
 }
 
-static int batch_from_host(gl_ctx* c, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits, uint32_t blinding,
-                           uint32_t cap_height, bool is_values, gl_batch** out) {
+// blinding: salt columns keyed by `seed_in` (null = a fresh OS seed)
+static int batch_from_host(gl_ctx* c, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits, bool blinding,
+                           const uint8_t* seed_in, uint32_t cap_height, bool is_values, gl_batch** out) {
     GL_REQUIRE(h_cols, GL_ERR_ARG, "PolynomialBatch: null columns");
-    GL_REQUIRE(blinding == 0, GL_ERR_UNSUPPORTED, "blinding (zero-knowledge salts) is not supported");
+    uint8_t seed[32];
+    if (blinding && seed_in) memcpy(seed, seed_in, 32);
+    else if (blinding) GL_TRY(gl_os_seed(seed));
     gl_batch* b = nullptr;
-    GL_TRY(batch_alloc(c, ncols, n, rate_bits, cap_height, &b));
+    GL_TRY(batch_alloc(c, ncols, n, rate_bits, cap_height, blinding ? GL_SALT_SIZE : 0, &b));
     for (size_t col = 0; col < ncols; col++) {
         if (!h_cols[col]) { gl_batch_free(b); return gl_fail(GL_ERR_ARG, "null column", __FILE__, __LINE__); }
         hipError_t e = hipMemcpyAsync(b->coeffs + col * n, h_cols[col], n * sizeof(gl_t), hipMemcpyHostToDevice, c->stream);
         if (e != hipSuccess) { gl_batch_free(b); return gl_fail(GL_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__); }
     }
     GL_CHECK_HIP(gl_stream_wait(c->stream));   // caller-owned pageable columns
-    int st = batch_commit(c, b, is_values ? b->coeffs : nullptr);
+    int st = batch_commit(c, b, is_values ? b->coeffs : nullptr, seed);
     if (st != GL_OK) { gl_batch_free(b); return st; }
     *out = b;
     return GL_OK;
 }
 
+#define GL_BLINDED_ENTRY "blinding: use gl_batch_from_values_blinded / gl_batch_from_coeffs_blinded (salted leaves)"
 extern "C" int gl_batch_from_values(gl_ctx* c, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
                                     uint32_t blinding, uint32_t cap_height, gl_batch** out) {
-    return batch_from_host(c, h_cols, ncols, n, rate_bits, blinding, cap_height, true, out);
+    GL_REQUIRE(blinding == 0, GL_ERR_UNSUPPORTED, GL_BLINDED_ENTRY);
+    return batch_from_host(c, h_cols, ncols, n, rate_bits, false, nullptr, cap_height, true, out);
 }
 extern "C" int gl_batch_from_coeffs(gl_ctx* c, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
                                     uint32_t blinding, uint32_t cap_height, gl_batch** out) {
-    return batch_from_host(c, h_cols, ncols, n, rate_bits, blinding, cap_height, false, out);
+    GL_REQUIRE(blinding == 0, GL_ERR_UNSUPPORTED, GL_BLINDED_ENTRY);
+    return batch_from_host(c, h_cols, ncols, n, rate_bits, false, nullptr, cap_height, false, out);
 }
-extern "C" int gl_batch_from_device(gl_ctx* c, const uint64_t* d_cols, size_t ncols, size_t n, uint32_t rate_bits,
-                                    uint32_t cap_height, int is_values, gl_batch** out) {
+extern "C" int gl_batch_from_values_blinded(gl_ctx* c, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
+                                            uint32_t cap_height, const uint8_t seed[32], gl_batch** out) {
+    return batch_from_host(c, h_cols, ncols, n, rate_bits, true, seed, cap_height, true, out);
+}
+extern "C" int gl_batch_from_coeffs_blinded(gl_ctx* c, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
+                                            uint32_t cap_height, const uint8_t seed[32], gl_batch** out) {
+    return batch_from_host(c, h_cols, ncols, n, rate_bits, true, seed, cap_height, false, out);
+}
+int gl_batch_from_device_salted(gl_ctx* c, const uint64_t* d_cols, size_t ncols, size_t n, uint32_t rate_bits, uint32_t cap_height,
+                                int is_values, const uint8_t* seed, uint32_t oracle, gl_batch** out) {
     GL_REQUIRE(d_cols, GL_ERR_ARG, "PolynomialBatch: null device columns");
     gl_batch* b = nullptr;
-    GL_TRY(batch_alloc(c, ncols, n, rate_bits, cap_height, &b));
+    GL_TRY(batch_alloc(c, ncols, n, rate_bits, cap_height, seed ? GL_SALT_SIZE : 0, &b));
     if (!is_values) {      // coefficients are kept: copy; values are interpolated straight out of the caller's matrix (left untouched)
         hipError_t e = hipMemcpyAsync(b->coeffs, d_cols, ncols * n * sizeof(gl_t), hipMemcpyDeviceToDevice, c->stream);
         if (e != hipSuccess) { gl_batch_free(b); return gl_fail(GL_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__); }
     }
-    int st = batch_commit(c, b, is_values ? (const gl_t*)d_cols : nullptr);
+    int st = batch_commit(c, b, is_values ? (const gl_t*)d_cols : nullptr, seed, oracle);
     if (st != GL_OK) { gl_batch_free(b); return st; }
     *out = b;
     return GL_OK;
+}
+extern "C" int gl_batch_from_device(gl_ctx* c, const uint64_t* d_cols, size_t ncols, size_t n, uint32_t rate_bits,
+                                    uint32_t cap_height, int is_values, gl_batch** out) {
+    return gl_batch_from_device_salted(c, d_cols, ncols, n, rate_bits, cap_height, is_values, nullptr, 0, out);
 }
 
 extern "C" int gl_batch_cap(const gl_batch* b, uint64_t* h_out) {
@@ -108,23 +130,24 @@ static size_t host_bitrev(size_t x, uint32_t bits) {
     for (uint32_t i = 0; i < bits; i++) r = (r << 1) | ((x >> i) & 1);
     return r;
 }
-static int batch_row(const gl_batch* b, size_t natural_row, uint64_t* h_out) {
+// the first `ncols` LDE columns of a row: the polynomials' values, or with the salt the whole leaf
+static int batch_row(const gl_batch* b, size_t natural_row, size_t ncols, uint64_t* h_out) {
     gl_ctx* c = b->ctx;
     GL_TRY(c->activate());
-    GL_TRY(c->ensure_dev_small(b->ncols * sizeof(gl_t)));
-    hipLaunchKernelGGL(k_gather_row, dim3((unsigned)((b->ncols + 127) / 128)), dim3(128), 0, c->stream, b->lde, (uint64_t)b->N(),
-                       (uint32_t)b->ncols, (uint64_t)natural_row, c->dev_small);
+    GL_TRY(c->ensure_dev_small(ncols * sizeof(gl_t)));
+    hipLaunchKernelGGL(k_gather_row, dim3((unsigned)((ncols + 127) / 128)), dim3(128), 0, c->stream, b->lde, (uint64_t)b->N(),
+                       (uint32_t)ncols, (uint64_t)natural_row, c->dev_small);
     GL_CHECK_HIP(hipGetLastError());
-    return gl_copy_d2h(c, h_out, c->dev_small, b->ncols * sizeof(gl_t));
+    return gl_copy_d2h(c, h_out, c->dev_small, ncols * sizeof(gl_t));
 }
 extern "C" int gl_batch_get_leaf(const gl_batch* b, size_t leaf_index, uint64_t* h_out) {
     GL_REQUIRE(b && h_out && leaf_index < b->N(), GL_ERR_ARG, "bad leaf index");
-    return batch_row(b, host_bitrev(leaf_index, b->degree_log + b->rate_bits), h_out);
+    return batch_row(b, host_bitrev(leaf_index, b->degree_log + b->rate_bits), b->leaf_len(), h_out);
 }
 extern "C" int gl_batch_get_lde_values(const gl_batch* b, size_t index, size_t step, uint64_t* h_out) {
     GL_REQUIRE(b && h_out && index * step < b->N(), GL_ERR_ARG, "bad LDE index");
-    // oracle.rs:128-133 reads leaves[reverse_bits(index*step)]; leaf j is LDE row bitrev(j), so this is row index*step
-    return batch_row(b, index * step, h_out);
+    // oracle.rs:128-133 reads leaves[reverse_bits(index*step)] without its salt; leaf j is LDE row bitrev(j), so this is row index*step
+    return batch_row(b, index * step, b->ncols, h_out);
 }
 extern "C" int gl_batch_prove(const gl_batch* b, size_t leaf_index, uint64_t* h_out, uint32_t* n_siblings) {
     GL_REQUIRE(b && h_out, GL_ERR_ARG, "null argument");

@@ -183,11 +183,26 @@ struct gl_batch {
     gl_ctx* ctx = nullptr;
     size_t ncols = 0, n = 0;
     uint32_t degree_log = 0, rate_bits = 0, cap_height = 0;
+    uint32_t salt = 0;           // 0, or GL_SALT_SIZE random columns behind the LDE (blinding, fri/oracle.rs:100-125)
     gl_t* coeffs = nullptr;      // [ncols][n]
-    gl_t* lde = nullptr;         // [ncols][N], natural order (index i <-> 7 * w_N^i)
+    gl_t* lde = nullptr;         // [ncols + salt][N], natural order (index i <-> 7 * w_N^i); the salt columns only enter the leaves
     GlMerkle tree;
     size_t N() const { return n << rate_bits; }
+    size_t leaf_len() const { return ncols + salt; }
 };
+// from_values / from_coeffs of a device matrix with the salt columns of PlonkOracle `oracle` drawn from `seed` (rng.cuh); a null seed
+// commits without salt, as gl_batch_from_device
+int gl_batch_from_device_salted(gl_ctx* c, const uint64_t* d_cols, size_t ncols, size_t n, uint32_t rate_bits, uint32_t cap_height,
+                                int is_values, const uint8_t* seed, uint32_t oracle, gl_batch** out);
+
+// ---- randomness (rng.hip) -------------------------------------------------------------------------------
+// 32 bytes from getrandom(2)
+int gl_os_seed(uint8_t seed[32]);
+// d_out[s * out_stride + i] = element first + i of stream stream0 + s (rng.cuh), s < nstreams, i < count
+int gl_fill_random(gl_ctx* c, const uint8_t seed[32], uint32_t stream0, uint32_t nstreams, uint64_t first, uint64_t count, gl_t* d_out,
+                   uint64_t out_stride);
+// the blinding rows of a zero-knowledge witness d_wires[135][n] from row g on (circuit_builder.rs:777-818 + full_witness)
+int gl_launch_witness_blind(gl_ctx* c, const uint8_t seed[32], gl_t* d_wires, uint32_t n, uint32_t g, uint32_t regular, uint32_t pairs);
 
 // RAII block from a context's stream-ordered pool
 struct DevBuf {

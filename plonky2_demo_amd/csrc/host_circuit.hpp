@@ -126,6 +126,41 @@ struct HostChallenger {
     gl2_t challenge_ext() { gl2_t r; r.a = challenge(); r.b = challenge(); return r; }
 };
 
+// ConstantArityBits(4, 5) (fri/reduction_strategies.rs:39-49) at degree_bits lg: arity bits into out[], returns their number
+inline unsigned fri_arity_bits(unsigned lg, unsigned rate_bits, unsigned cap_height, uint32_t out[8]) {
+    unsigned db = lg, k = 0;
+    while (db > 5 && db + rate_bits - 4 >= cap_height && k < 8) { out[k++] = 4; db -= 4; }
+    return k;
+}
+// blinding_counts (circuit_builder.rs:718-766): the blinding rows a zero-knowledge build appends after its num_gate_rows gate rows --
+// `regular` rows of 135 random wires and `pairs` row pairs for Z -- with num_blinding_gates (D = 2) at a degree estimate that doubles
+// until they fit.  degree_bits: log2 of the length blind_and_pad pads to (circuit_builder.rs:767-774); without zero knowledge only the
+// padding, regular = pairs = 0.
+struct BlindingCounts { uint32_t regular = 0, pairs = 0, degree_bits = 0; };
+inline BlindingCounts blinding_counts(uint64_t num_gate_rows, bool zero_knowledge, unsigned rate_bits, unsigned cap_height, unsigned num_query_rounds) {
+    BlindingCounts b;
+    uint64_t total = num_gate_rows;
+    if (zero_knowledge) {
+        unsigned lg = 0;
+        while ((uint64_t(1) << lg) < num_gate_rows) lg++;
+        for (;; lg++) {
+            uint32_t ab[8];
+            const unsigned k = fri_arity_bits(lg, rate_bits, cap_height, ab);
+            uint64_t points = 0, prod_bits = 0;
+            for (unsigned r = 0; r < k; r++) { points += (uint64_t(1) << ab[r]) - 1; prod_bits += ab[r]; }
+            const uint64_t final_coeffs = (uint64_t(1) << lg) >> prod_bits;
+            const uint64_t fri_openings = (uint64_t)num_query_rounds * (1 + 2 * points + 2 * final_coeffs);
+            const uint64_t regular = 2 + fri_openings, z = 4 + fri_openings;
+            if (num_gate_rows + regular + 2 * z <= (uint64_t(1) << lg)) { b.regular = (uint32_t)regular; b.pairs = (uint32_t)z; break; }
+        }
+        total += b.regular + 2 * (uint64_t)b.pairs;
+    }
+    while ((uint64_t(1) << b.degree_bits) < total) b.degree_bits++;
+    return b;
+}
+// the standard_recursion_config FRI parameters every description here carries (circuit_data.rs:72-90)
+enum { STD_RATE_BITS = 3, STD_CAP_HEIGHT = 4, STD_NUM_QUERY_ROUNDS = 28 };
+
 struct HostCircuit {
     gl_circuit_desc desc;
     size_t m = 0, n = 0;
@@ -142,7 +177,9 @@ struct HostCircuit {
 // position (row, slot) of the t-th operation of a kind
 struct OpPos { uint32_t row, slot; };
 
-inline int build_matmul(size_t m, HostCircuit* hc) {
+// zero_knowledge: CircuitConfig::standard_recursion_zk_config (circuit_data.rs:104-110) -- the same gate rows, then blind_and_pad's
+// blinding rows (NoopGates, singleton copy classes: generate_copy adds no copy constraint, circuit_builder.rs:418-420) and padding
+inline int build_matmul(size_t m, HostCircuit* hc, bool zero_knowledge = false) {
     if (m < 1 || m > 256) return GL_ERR_ARG;
     hc->m = m;
     const size_t n_mul = m * m * m, n_add = m * m * (m - 1);
@@ -166,7 +203,7 @@ inline int build_matmul(size_t m, HostCircuit* hc) {
     hc->pi_row = hc->first_poseidon_row + hc->num_poseidon_rows;
     hc->constant_row = hc->pi_row + 1;
     const size_t rows_used = hc->constant_row + 1;
-    unsigned lg = 0; while ((size_t(1) << lg) < rows_used) lg++;
+    const unsigned lg = blinding_counts(rows_used, zero_knowledge, STD_RATE_BITS, STD_CAP_HEIGHT, STD_NUM_QUERY_ROUNDS).degree_bits;
     const size_t n = size_t(1) << lg;
     hc->n = n;
     hc->row_gate.assign(n, G_NOOP);
@@ -180,12 +217,11 @@ inline int build_matmul(size_t m, HostCircuit* hc) {
     gl_circuit_desc& d = hc->desc;
     ::memset((void*)&d, 0, sizeof d);
     d.degree_bits = lg; d.num_wires = 135; d.num_routed_wires = 80; d.num_challenges = 2; d.quotient_degree_factor = 8;
-    d.rate_bits = 3; d.cap_height = 4; d.proof_of_work_bits = 16; d.num_query_rounds = 28;
+    d.rate_bits = STD_RATE_BITS; d.cap_height = STD_CAP_HEIGHT; d.proof_of_work_bits = 16; d.num_query_rounds = STD_NUM_QUERY_ROUNDS;
     d.num_public_inputs = (uint32_t)n_pi;
-    {   // ConstantArityBits(4, 5) (fri/reduction_strategies.rs:39-49)
-        unsigned db = lg; d.num_fri_rounds = 0;
-        while (db > 5 && db + d.rate_bits - 4 >= d.cap_height) { d.fri_arity_bits[d.num_fri_rounds++] = 4; db -= 4; }
-    }
+    d.num_fri_rounds = fri_arity_bits(lg, d.rate_bits, d.cap_height, d.fri_arity_bits);
+    d.zero_knowledge = zero_knowledge ? 1 : 0;
+    d.num_gate_rows = zero_knowledge ? (uint32_t)rows_used : 0;
     // gates present, sorted by (degree, id): Noop(0) < Constant(1) < PublicInput(1) < Arithmetic(3) < Poseidon(7)
     bool present[5] = {false, false, false, false, false};
     for (auto g : hc->row_gate) present[g] = true;

@@ -62,14 +62,16 @@ extern "C" int gl_challenger_state(const gl_challenger* c, uint64_t h_sponge_sta
 }
 
 // ---- host circuit API ------------------------------------------------------------------------------------------------
-extern "C" int gl_matmul_circuit_build(size_t m, gl_host_circuit** out) {
+static int matmul_circuit_build(size_t m, bool zero_knowledge, gl_host_circuit** out) {
     GL_REQUIRE(out, GL_ERR_ARG, "null out");
     std::unique_ptr<gl_host_circuit> h(new gl_host_circuit());
-    int st = glhost::build_matmul(m, &h->hc);
+    int st = glhost::build_matmul(m, &h->hc, zero_knowledge);
     if (st != GL_OK) return gl_fail(st, "matmul dimension out of range (1..256)", __FILE__, __LINE__);
     *out = h.release();
     return GL_OK;
 }
+extern "C" int gl_matmul_circuit_build(size_t m, gl_host_circuit** out) { return matmul_circuit_build(m, false, out); }
+extern "C" int gl_matmul_circuit_build_zk(size_t m, gl_host_circuit** out) { return matmul_circuit_build(m, true, out); }
 extern "C" int gl_host_circuit_desc(const gl_host_circuit* hc, gl_circuit_desc* out) {
     GL_REQUIRE(hc && out, GL_ERR_ARG, "null argument");
     *out = hc->hc.desc;
@@ -113,6 +115,12 @@ static int validate_desc(const gl_circuit_desc& d) {
     for (unsigned g = 0; g < d.num_gates; g++) {
         GL_REQUIRE(d.gate_types[g] <= glhost::G_LAST, GL_ERR_UNSUPPORTED, "gate type not in {Noop, Constant, PublicInput, Arithmetic, Poseidon, BaseSum<2>, Lookup, LookupTable, Exponentiation, RandomAccess}");
         GL_REQUIRE(d.gate_selector_index[g] < d.num_selectors && d.gate_group_start[g] <= g && g < d.gate_group_end[g] && d.gate_group_end[g] <= d.num_gates, GL_ERR_ARG, "bad selector group");
+    }
+    GL_REQUIRE(d.zero_knowledge <= 1, GL_ERR_ARG, "zero_knowledge is 0 or 1");
+    GL_REQUIRE(!d.zero_knowledge || !d.num_luts, GL_ERR_UNSUPPORTED, "zero knowledge together with lookups is not supported");
+    if (d.num_gate_rows) {
+        const glhost::BlindingCounts b = glhost::blinding_counts(d.num_gate_rows, d.zero_knowledge, d.rate_bits, d.cap_height, d.num_query_rounds);
+        GL_REQUIRE(b.degree_bits == d.degree_bits, GL_ERR_ARG, "degree_bits is not the length blind_and_pad gives num_gate_rows");
     }
     return GL_OK;
 }
@@ -421,23 +429,29 @@ static int check_phase_args(gl_ctx* ctx, const gl_circuit* cir) {
     GL_REQUIRE(cir->ctx->device == ctx->device, GL_ERR_ARG, "circuit lives on another device");
     return ctx->activate();
 }
+// the phase API commits without salt: a zero-knowledge circuit is proved by gl_prove* only
+static int check_phase_api(gl_ctx* ctx, const gl_circuit* cir) {
+    GL_TRY(check_phase_args(ctx, cir));
+    GL_REQUIRE(!cir->desc.zero_knowledge, GL_ERR_UNSUPPORTED, "the phase API does not prove zero-knowledge circuits (use gl_prove*)");
+    return GL_OK;
+}
 static int check_batch(const gl_circuit* cir, const gl_batch* b, size_t ncols, const char* what) {
     GL_REQUIRE(b && b->ncols == ncols && b->n == cir->n && b->rate_bits == cir->desc.rate_bits && b->cap_height == cir->desc.cap_height, GL_ERR_ARG, what);
     return GL_OK;
 }
 // Z || partial products (|| lookup polynomials) -> committed batch (prover.rs:189-223), for gl_partial_products[_lookups] and prove().
-// `deltas8` is null exactly for a circuit without lookups; `capture`, if given, receives the value columns.
+// `deltas8` is null exactly for a circuit without lookups; `capture`, if given, receives the value columns; `seed`: salt key (zero knowledge) or null.
 static int commit_zs(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, const gl_t* betas, const gl_t* gammas, const gl_t* deltas8,
-                     gl_batch** out, std::vector<gl_t>* capture) {
+                     gl_batch** out, std::vector<gl_t>* capture, const uint8_t* seed = nullptr) {
     const size_t n = cir->n, nzs = 20 + 2 * (size_t)cir->desc.num_lookup_polys;
     DevBuf d_zs(ctx); GL_TRY(d_zs.alloc(nzs * n * sizeof(gl_t)));
     GL_TRY(partial_products_values(ctx, cir, d_wires, betas, gammas, d_zs.as<gl_t>()));
     if (deltas8) GL_TRY(lookup_polys_values(ctx, cir, d_wires, deltas8, d_zs.as<gl_t>() + 20 * n));
     if (capture) { capture->resize(nzs * n); GL_TRY(d2h(ctx, capture->data(), d_zs.p, nzs * n * sizeof(gl_t))); }
-    return gl_batch_from_device(ctx, d_zs.as<uint64_t>(), nzs, n, cir->desc.rate_bits, cir->desc.cap_height, 1, out);
+    return gl_batch_from_device_salted(ctx, d_zs.as<uint64_t>(), nzs, n, cir->desc.rate_bits, cir->desc.cap_height, 1, seed, 2, out);
 }
 static int partial_products_phase(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* d_wires, const uint64_t* betas, const uint64_t* gammas, const uint64_t* deltas8, gl_batch** out) {
-    GL_TRY(check_phase_args(ctx, cir));
+    GL_TRY(check_phase_api(ctx, cir));
     GL_REQUIRE(d_wires && betas && gammas && out, GL_ERR_ARG, "gl_partial_products: null argument");
     GL_REQUIRE((cir->desc.num_lookup_polys != 0) == (deltas8 != nullptr), GL_ERR_ARG, "circuits with lookups take gl_partial_products_lookups (with the delta challenges), circuits without take gl_partial_products");
     return commit_zs(ctx, cir, d_wires, betas, gammas, deltas8, out, nullptr);
@@ -455,7 +469,8 @@ extern "C" int gl_partial_products_lookups(gl_ctx* ctx, const gl_circuit* cir, c
 //      d_q[2][8n] -> the 16 chunk COEFFICIENT columns -> committed batch.  `apow` is the host source of an asynchronous upload: the caller
 //      keeps it alive up to its next sync.  `deltas8` is null exactly for a circuit without lookups; `capture` receives the chunks. ----
 static int commit_quotient(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* wires, const gl_batch* zs, const gl_t* pi_hash, const gl_t* betas,
-                           const gl_t* gammas, const gl_t* alphas, const gl_t* deltas8, std::vector<gl_t>& apow, gl_batch** out, std::vector<gl_t>* capture) {
+                           const gl_t* gammas, const gl_t* alphas, const gl_t* deltas8, std::vector<gl_t>& apow, gl_batch** out, std::vector<gl_t>* capture,
+                           const uint8_t* seed = nullptr) {
     const gl_circuit_desc& d = cir->desc;
     const size_t n = cir->n, N = n << d.rate_bits;
     const uint32_t lgN = d.degree_bits + d.rate_bits;
@@ -506,11 +521,11 @@ static int commit_quotient(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* w
     // coset_ifft(7) of each quotient (prover.rs:739-743); the 8n coefficients ARE the 8 chunks of n (prover.rs:245-258)
     GL_TRY(gl_ntt_run(ctx, d_q.as<gl_t>(), N, (uint32_t)N, d_q.as<gl_t>(), N, lgN, 2, true, 0, gl_canon(gl_inv(GL_MULT_GENERATOR)), gl_host_inverse_2exp(lgN)));
     if (capture) { capture->resize(16 * n); GL_TRY(d2h(ctx, capture->data(), d_q.p, 16 * n * sizeof(gl_t))); }
-    return gl_batch_from_device(ctx, d_q.as<uint64_t>(), 16, n, d.rate_bits, d.cap_height, 0, out);
+    return gl_batch_from_device_salted(ctx, d_q.as<uint64_t>(), 16, n, d.rate_bits, d.cap_height, 0, seed, 3, out);
 }
 static int quotient_phase(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* wires, const gl_batch* zs_partial_products, const uint64_t* pi_hash,
                           const uint64_t* betas, const uint64_t* gammas, const uint64_t* alphas, const uint64_t* deltas8, gl_batch** out) {
-    GL_TRY(check_phase_args(ctx, cir));
+    GL_TRY(check_phase_api(ctx, cir));
     GL_REQUIRE(pi_hash && betas && gammas && alphas && out, GL_ERR_ARG, "gl_quotient_polys: null argument");
     const size_t nlk = 2 * (size_t)cir->desc.num_lookup_polys;
     GL_REQUIRE((nlk != 0) == (deltas8 != nullptr), GL_ERR_ARG, "circuits with lookups take gl_quotient_polys_lookups (with the delta challenges), circuits without take gl_quotient_polys");
@@ -601,7 +616,7 @@ extern "C" void gl_fri_free(gl_fri* f) {
     delete f;                                  // its trees and buffers go back to the context's pool first
     gl_ctx_release(ctx);
 }
-extern "C" int gl_fri_combine(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* const batches[4], const uint64_t zeta_in[2], const uint64_t alpha_in[2], gl_fri** out) {
+static int fri_combine(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* const batches[4], const uint64_t zeta_in[2], const uint64_t alpha_in[2], gl_fri** out) {
     GL_TRY(check_phase_args(ctx, cir));
     GL_REQUIRE(batches && zeta_in && alpha_in && out, GL_ERR_ARG, "gl_fri_combine: null argument");
     const gl_circuit_desc& d = cir->desc;
@@ -656,6 +671,10 @@ extern "C" int gl_fri_combine(gl_ctx* ctx, const gl_circuit* cir, const gl_batch
     f->cur_n = n; f->cur_lgN = f->lgN;
     *out = f.release();
     return GL_OK;
+}
+extern "C" int gl_fri_combine(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* const batches[4], const uint64_t zeta_in[2], const uint64_t alpha_in[2], gl_fri** out) {
+    GL_TRY(check_phase_api(ctx, cir));
+    return fri_combine(ctx, cir, batches, zeta_in, alpha_in, out);
 }
 // fri_committed_trees, first half of one loop iteration (fri/prover.rs:76-92): Merkle tree of the current codeword
 extern "C" int gl_fri_commit_round(gl_fri* f, uint64_t* h_cap_out) {
@@ -777,7 +796,7 @@ static int fri_query_blob(gl_fri* f, const uint32_t* x_index, uint32_t nq, std::
     size_t total = 0;
     const uint32_t init_levels = lgN - d.cap_height;
     for (int o2 = 0; o2 < 4; o2++) {
-        row_piece[o2] = {total, nq * f->oracles[o2]->ncols}; total += row_piece[o2].words;
+        row_piece[o2] = {total, nq * f->oracles[o2]->leaf_len()}; total += row_piece[o2].words;
         path_piece[o2] = {total, (size_t)nq * init_levels * 4}; total += path_piece[o2].words;
     }
     for (unsigned r = 0; r < d.num_fri_rounds; r++) {
@@ -803,8 +822,8 @@ static int fri_query_blob(gl_fri* f, const uint32_t* x_index, uint32_t nq, std::
         const gl_batch* b = f->oracles[o2];
         const uint64_t* d_lo = nullptr;
         GL_TRY(ctx->get_offsets_table(b->tree.level_off.data(), b->tree.level_off.size(), &d_lo));
-        unsigned cnt = nq * (unsigned)b->ncols;
-        hipLaunchKernelGGL(k_gather_rows, dim3((cnt + 255) / 256), dim3(256), 0, st, b->lde, (uint64_t)N, (uint32_t)b->ncols, d_rows, nq, stage + row_piece[o2].off);
+        unsigned cnt = nq * (unsigned)b->leaf_len();      // the whole leaf: with blinding the salt follows the values (query rounds open salted leaves)
+        hipLaunchKernelGGL(k_gather_rows, dim3((cnt + 255) / 256), dim3(256), 0, st, b->lde, (uint64_t)N, (uint32_t)b->leaf_len(), d_rows, nq, stage + row_piece[o2].off);
         cnt = nq * init_levels * 4;
         if (cnt) hipLaunchKernelGGL(k_gather_paths, dim3((cnt + 255) / 256), dim3(256), 0, st, b->tree.digests, d_lo, init_levels, d_leaf, nq, stage + path_piece[o2].off);
     }
@@ -826,7 +845,7 @@ static int fri_query_blob(gl_fri* f, const uint32_t* x_index, uint32_t nq, std::
     GL_TRY(d2h(ctx, host_stage.data(), stage, total * sizeof(gl_t)));      // also orders the idx_host upload before it dies
     for (uint32_t q = 0; q < nq; q++) {
         for (int oi = 0; oi < 4; oi++) {
-            const size_t nc = f->oracles[oi]->ncols;
+            const size_t nc = f->oracles[oi]->leaf_len();
             put_words(o, host_stage.data() + row_piece[oi].off + (size_t)q * nc, nc);
             o.push_back((uint8_t)init_levels);
             put_words(o, host_stage.data() + path_piece[oi].off + (size_t)q * init_levels * 4, (size_t)init_levels * 4);
@@ -857,7 +876,9 @@ extern "C" int gl_fri_query(gl_fri* f, const uint32_t* x_index, uint32_t num_que
 // prove(): the driver (plonk/prover.rs:102-329) -- the phases above plus the transcript
 // ======================================================================================================================
 // `d_wires` is the witness [135][n] in HBM; `wit_owner`, if given, owns it and is released once the last kernel that reads it is queued
-static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, DevBuf* wit_owner, const uint64_t* h_pis, size_t npis, const uint64_t* h_pi_hash, gl_proof** out) {
+// `seed`: the salt key of a zero-knowledge circuit (null = OS entropy); unused without zero knowledge
+static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, DevBuf* wit_owner, const uint64_t* h_pis, size_t npis, const uint64_t* h_pi_hash, gl_proof** out,
+                      const uint8_t* seed = nullptr) {
     GL_REQUIRE(ctx && cir && d_wires && h_pis && out, GL_ERR_ARG, "gl_prove: null argument");
     // circuit data is read-only while proving: any context (stream) of the same device may prove against it
     GL_REQUIRE(cir->ctx->device == ctx->device, GL_ERR_ARG, "gl_prove: circuit lives on another device");
@@ -871,8 +892,17 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, D
     std::unique_ptr<gl_proof> proof(new gl_proof());
     std::vector<gl_t> h_apow_quot;          // sources of async uploads: alive until the function returns (after the last sync)
 
+    // zero knowledge: wires, Z || partial products and quotient are committed with blinding = true (prover.rs:151,218,266)
+    uint8_t salt_seed[32];
+    const uint8_t* salt = nullptr;
+    if (d.zero_knowledge) {
+        if (seed) memcpy(salt_seed, seed, 32);
+        else GL_TRY(gl_os_seed(salt_seed));
+        salt = salt_seed;
+    }
+
     // ---- 4. wires commitment (prover.rs:145-156) ----
-    BatchHolder wires; GL_TRY(gl_batch_from_device(ctx, d_wires, 135, n, d.rate_bits, d.cap_height, 1, &wires.b));
+    BatchHolder wires; GL_TRY(gl_batch_from_device_salted(ctx, d_wires, 135, n, d.rate_bits, d.cap_height, 1, salt, 1, &wires.b));
     // public_inputs_hash (prover.rs:126-127) on the host while the GPU commits
     gl_t pi_hash[4];
     if (h_pi_hash) for (int i = 0; i < 4; i++) pi_hash[i] = gl_canon(h_pi_hash[i]);      // the witness generator's sponge already produced it
@@ -894,7 +924,7 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, D
 
     // ---- 6/7. partial products and Z (and the lookup polynomials), commitment (prover.rs:189-223) ----
     BatchHolder zs;
-    GL_TRY(commit_zs(ctx, cir, d_wires, betas, gammas, lookup_deltas, &zs.b, ctx->capture_intermediates ? &proof->zs_pp : nullptr));
+    GL_TRY(commit_zs(ctx, cir, d_wires, betas, gammas, lookup_deltas, &zs.b, ctx->capture_intermediates ? &proof->zs_pp : nullptr, salt));
     if (wit_owner) wit_owner->release();                                       // stream-ordered: the kernels above are already queued
     GL_TRY(gl_batch_cap(zs.b, cap.data()));
     proof->caps.insert(proof->caps.end(), cap.begin(), cap.end());
@@ -903,7 +933,8 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, D
 
     // ---- 9/10. quotient polynomials (prover.rs:229-271) ----
     BatchHolder quot;
-    GL_TRY(commit_quotient(ctx, cir, wires.b, zs.b, pi_hash, betas, gammas, alphas, lookup_deltas, h_apow_quot, &quot.b, ctx->capture_intermediates ? &proof->quotient : nullptr));
+    GL_TRY(commit_quotient(ctx, cir, wires.b, zs.b, pi_hash, betas, gammas, alphas, lookup_deltas, h_apow_quot, &quot.b, ctx->capture_intermediates ? &proof->quotient : nullptr,
+                           salt));
     GL_TRY(gl_batch_cap(quot.b, cap.data()));
     proof->caps.insert(proof->caps.end(), cap.begin(), cap.end());
     ch.observe_many(cap.data(), ncap);
@@ -946,7 +977,7 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, D
     const gl2_t fri_alpha = ch.challenge_ext();
     const gl_t zeta_w[2] = {zeta.a, zeta.b}, fri_alpha_w[2] = {fri_alpha.a, fri_alpha.b};
     gl_fri* fri_raw = nullptr;
-    GL_TRY(gl_fri_combine(ctx, cir, oracles, zeta_w, fri_alpha_w, &fri_raw));
+    GL_TRY(fri_combine(ctx, cir, oracles, zeta_w, fri_alpha_w, &fri_raw));
     std::unique_ptr<gl_fri, void (*)(gl_fri*)> fri(fri_raw, gl_fri_free);
     std::vector<gl_t> fri_caps, fri_betas;
     for (unsigned r = 0; r < d.num_fri_rounds; r++) {
@@ -1029,6 +1060,21 @@ extern "C" int gl_prove_columns(gl_ctx* ctx, const gl_circuit* cir, const uint64
 }
 extern "C" int gl_prove_device(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* d_wires, const uint64_t* h_pis, size_t npis, gl_proof** out) {
     return prove_impl(ctx, cir, d_wires, nullptr, h_pis, npis, nullptr, out);
+}
+extern "C" int gl_prove_device_seeded(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* d_wires, const uint64_t* h_pis, size_t npis, const uint8_t seed[32],
+                                      gl_proof** out) {
+    return prove_impl(ctx, cir, d_wires, nullptr, h_pis, npis, nullptr, out, seed);
+}
+extern "C" int gl_witness_blind(gl_ctx* ctx, const gl_circuit* cir, uint64_t* d_wires, const uint8_t seed[32]) {
+    GL_REQUIRE(ctx && cir && d_wires, GL_ERR_ARG, "gl_witness_blind: null argument");
+    GL_REQUIRE(cir->ctx->device == ctx->device, GL_ERR_ARG, "gl_witness_blind: circuit lives on another device");
+    const gl_circuit_desc& d = cir->desc;
+    GL_REQUIRE(d.zero_knowledge && d.num_gate_rows, GL_ERR_ARG, "gl_witness_blind: needs a zero-knowledge circuit with num_gate_rows set");
+    GL_TRY(ctx->activate());
+    const glhost::BlindingCounts b = glhost::blinding_counts(d.num_gate_rows, true, d.rate_bits, d.cap_height, d.num_query_rounds);
+    uint8_t os[32];
+    if (!seed) { GL_TRY(gl_os_seed(os)); seed = os; }
+    return gl_launch_witness_blind(ctx, seed, d_wires, (uint32_t)cir->n, d.num_gate_rows, b.regular, b.pairs);
 }
 extern "C" int gl_prove_device_hashed(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* d_wires, const uint64_t* h_pis, size_t npis,
                                       const uint64_t public_inputs_hash[4], gl_proof** out) {

@@ -89,12 +89,12 @@ extern "C" int gl_common_data_to_bytes(const gl_circuit_desc* desc, uint8_t* h_o
     Writer w;
     // CircuitConfig (mod.rs:1662-1686)
     w.u64(d.num_wires); w.u64(d.num_routed_wires); w.u64(STD_CONFIG_NUM_CONSTANTS); w.u64(STD_SECURITY_BITS); w.u64(d.num_challenges);
-    w.u64(d.quotient_degree_factor); w.u8(1 /* use_base_arithmetic_gate */); w.u8(0 /* zero_knowledge */);
+    w.u64(d.quotient_degree_factor); w.u8(1 /* use_base_arithmetic_gate */); w.u8(d.zero_knowledge ? 1 : 0);
     write_fri_config(w, d);
     // FriParams (mod.rs:1646-1660)
     write_fri_config(w, d);
     w.u64(d.num_fri_rounds); for (uint32_t i = 0; i < d.num_fri_rounds; i++) w.u64(d.fri_arity_bits[i]);
-    w.u64(d.degree_bits); w.u8(0 /* hiding */);
+    w.u64(d.degree_bits); w.u8(d.zero_knowledge ? 1 : 0 /* hiding = zero_knowledge (circuit_builder.rs fri_params) */);
     // gates (mod.rs:1759-1762)
     w.u64(d.num_gates);
     uint64_t max_constraints = 0;
@@ -153,7 +153,8 @@ extern "C" int gl_common_data_from_bytes(const uint8_t* h_bytes, size_t num_byte
     const uint8_t hiding = r.u8();
     GL_REQUIRE(!r.wide, GL_ERR_UNSUPPORTED, "a size field of CommonCircuitData exceeds 32 bits");
     GL_REQUIRE(r.ok, GL_ERR_ARG, "truncated CommonCircuitData");
-    GL_REQUIRE(!zk && !hiding, GL_ERR_UNSUPPORTED, "zero-knowledge circuits are not supported");
+    GL_REQUIRE(zk <= 1 && zk == hiding, GL_ERR_UNSUPPORTED, "config.zero_knowledge and fri_params.hiding differ");
+    d.zero_knowledge = zk;                              // num_gate_rows is not part of the bytes: it stays 0
     // fields gl_circuit_desc does not carry are written back as standard_recursion_config's: anything else is refused, not dropped
     GL_REQUIRE(security_bits == STD_SECURITY_BITS && base_arith == 1, GL_ERR_UNSUPPORTED, "security_bits / use_base_arithmetic_gate differ from standard_recursion_config");
     GL_REQUIRE(fp.rate_bits == d.rate_bits && fp.cap_height == d.cap_height && fp.num_query_rounds == d.num_query_rounds && fp.proof_of_work_bits == d.proof_of_work_bits,
@@ -227,6 +228,7 @@ extern "C" int gl_common_data_from_bytes(const uint8_t* h_bytes, size_t num_byte
     GL_REQUIRE(nluts <= GL_MAX_LUTS && ((nluts == 0 && nlp == 0 && nls == 0) || (nluts >= 1 && nlp == 7 && nls == glhost::LU_SEL_START_END + nluts)), GL_ERR_UNSUPPORTED,
                "lookup argument: at most 4 tables, 7 lookup polynomials and 4 + #tables lookup selectors per challenge");
     d.num_luts = (uint32_t)nluts; d.num_lookup_polys = (uint32_t)nlp; d.num_lookup_selectors = (uint32_t)nls;
+    GL_REQUIRE(!d.zero_knowledge || !nluts, GL_ERR_UNSUPPORTED, "zero knowledge together with lookups is not supported");
     uint32_t total = 0;
     for (uint64_t t = 0; t < nluts; t++) {
         const uint64_t len = r.u64();

@@ -128,6 +128,7 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
                GL_ERR_UNSUPPORTED, "gl_verify: only standard_recursion_config circuits are supported");
     GL_REQUIRE(d.num_gates >= 1 && d.num_gates <= GL_MAX_GATES, GL_ERR_ARG, "gl_verify: bad gate count");
     { const char* why = glhost::lookup_shape_error(d); GL_REQUIRE(!why, GL_ERR_UNSUPPORTED, why); }
+    GL_REQUIRE(d.zero_knowledge <= 1 && (!d.zero_knowledge || !d.num_luts), GL_ERR_UNSUPPORTED, "gl_verify: zero knowledge is 0 / 1 and not together with lookups");
     GL_REQUIRE(d.num_selectors >= 1 && d.num_constants == d.num_selectors + d.num_lookup_selectors + 2 && d.num_fri_rounds <= 8 &&
                d.degree_bits >= 1 && d.degree_bits + d.rate_bits <= 32 && d.cap_height <= d.degree_bits + d.rate_bits && d.num_query_rounds >= 1,
                GL_ERR_ARG, "gl_verify: bad circuit description");
@@ -149,6 +150,8 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
     const size_t NLP = d.num_lookup_polys;                              // lookup polynomials per challenge, behind Z and the partial products
     const size_t nzp = nch * (1 + NPP);
     const size_t widths[4] = {ncs, W, nzp + nch * NLP, nch * QF};
+    // hiding: the leaves of the wires, Z / partial-products and quotient trees end in SALT_SIZE = 4 salt elements (mod.rs:431-456)
+    const size_t salt = d.zero_knowledge ? 4 : 0, leaf_lens[4] = {ncs, W + salt, widths[2] + salt, widths[3] + salt};
 
     // ---- decode (util/serialization/mod.rs:1939-1981 read side, plonk/validate_shape.rs, fri/validate_shape.rs) ----
     // like the reference's read_field (from_canonical_u64 without a range check in release builds) a word >= p is taken mod p
@@ -166,7 +169,7 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
     for (unsigned q = 0; q < d.num_query_rounds && in.ok; q++) {
         for (int o = 0; o < 4; o++) {
             PathRef& pr = init_paths[q * 4 + o];
-            pr.leaf = words(widths[o]); pr.leaf_len = widths[o];
+            pr.leaf = words(leaf_lens[o]); pr.leaf_len = leaf_lens[o];
             pr.nsib = in.u8(); pr.sib = words(4 * pr.nsib);
         }
         unsigned lg_cur = lgN;
@@ -383,9 +386,10 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
         size_t rev = 0;
         for (unsigned i = 0; i < lgN; i++) rev |= ((x >> i) & 1) << (lgN - 1 - i);
         gl_t subgroup_x = gl_canon(gl_mul(GL_MULT_GENERATOR, gl_exp(wN, rev)));
-        // fri_combine_initial (fri/verifier.rs:124-165): batch 0 = every polynomial at zeta, batch 1 = the Z polynomials at g zeta
+        // fri_combine_initial (fri/verifier.rs:124-165): batch 0 = every polynomial at zeta, batch 1 = the Z polynomials at g zeta; the
+        // unsalted prefix of each leaf only (unsalted_eval)
         ev0.clear(); ev1.clear();
-        for (int o = 0; o < 4; o++) { const PathRef& pr = init_paths[q * 4 + o]; for (size_t i = 0; i < (o == 2 ? nzp : pr.leaf_len); i++) ev0.push_back(e_of(T[pr.leaf + i])); }
+        for (int o = 0; o < 4; o++) { const PathRef& pr = init_paths[q * 4 + o]; for (size_t i = 0; i < (o == 2 ? nzp : widths[o]); i++) ev0.push_back(e_of(T[pr.leaf + i])); }
         for (size_t i = nzp; i < widths[2]; i++) ev0.push_back(e_of(T[init_paths[q * 4 + 2].leaf + i]));
         for (size_t i = 0; i < nch; i++) ev1.push_back(e_of(T[init_paths[q * 4 + 2].leaf + i]));
         for (size_t i = nzp; i < widths[2]; i++) ev1.push_back(e_of(T[init_paths[q * 4 + 2].leaf + i]));

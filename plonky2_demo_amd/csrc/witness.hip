@@ -261,6 +261,7 @@ extern "C" int gl_prover_pool_prove_matmul(gl_prover_pool* p, size_t count, cons
     GL_REQUIRE(p->hc, GL_ERR_ARG, "gl_prover_pool_prove_matmul: this pool was created for a generic circuit (gl_prover_pool_prove_columns)");
     for (size_t i = 0; i < count; i++) out_proofs[i] = nullptr;
     const size_t lanes = p->ctxs.size(), npis = 3 * p->hc->hc.m * p->hc->hc.m;
+    const bool zero_knowledge = p->hc->hc.desc.zero_knowledge != 0;      // the salts: OS entropy inside gl_prove_device_hashed
     std::atomic<int> first_error{GL_OK};
     std::vector<std::string> messages(lanes);
     auto work = [&](size_t lane) {
@@ -269,6 +270,7 @@ extern "C" int gl_prover_pool_prove_matmul(gl_prover_pool* p, size_t count, cons
         for (size_t i = lane; i < count && first_error.load() == GL_OK; i += lanes) {
             int st = (a[i] && b[i]) ? GL_OK : GL_ERR_ARG;
             if (st == GL_OK) st = gl_matmul_witgen_run(p->gens[lane], a[i], b[i], filler_seeds ? filler_seeds[i] : (uint64_t)i, p->d_wires[lane], pis.data(), pi_hash);
+            if (st == GL_OK && zero_knowledge) st = gl_witness_blind(p->ctxs[lane], p->circuit, p->d_wires[lane], nullptr);     // a fresh OS seed per item
             if (st == GL_OK) st = gl_prove_device_hashed(p->ctxs[lane], p->circuit, p->d_wires[lane], pis.data(), npis, pi_hash, &out_proofs[i]);
             if (st != GL_OK) { int expected = GL_OK; messages[lane] = gl_last_error(); first_error.compare_exchange_strong(expected, st); }
         }
