@@ -1,11 +1,13 @@
 // The reference's demo program (plonky2/src/bin/matrix_mul.rs, examples/matrix_multiplication.rs) on the MI355X
 // backend: "I know A * B = C" for random m x m matrices of u32 entries -- build, prove, print, verify.
 //
-//   matrix_mul [m = 20] [seed] [batch] [--zk]
+//   matrix_mul [m = 20] [seed] [batch] [--zk] [--keccak]
 //                                       (seed 0 / absent: operands from std::random_device, as the reference draws them
 //                                        from ChaChaRng::from_entropy(), matrix_mul.rs:72-80; batch > 1: that many
 //                                        independent proofs through gl_prover_pool, four in flight, each verified;
-//                                        --zk: the zero-knowledge circuit, standard_recursion_zk_config, witnesses blinded)
+//                                        --zk: the zero-knowledge circuit, standard_recursion_zk_config, witnesses blinded;
+//                                        --keccak: `type C = KeccakGoldilocksConfig` (matrix_mul.rs:21-23) -- Keccak-256 Merkle trees,
+//                                        transcript and proof of work; the default is PoseidonGoldilocksConfig)
 //
 // Plain C++ over the C ABI of include/plonky2_mi355x.h; the only GPU-specific line is gl_ctx_create.
 #include <chrono>
@@ -27,9 +29,13 @@ static double ms_since(std::chrono::steady_clock::time_point t0) {
 }
 
 int main(int argc, char** argv) {
-    bool zk = false;
+    bool zk = false, keccak = false;
     for (int i = 1; i < argc; i++)
-        if (!strcmp(argv[i], "--zk")) { zk = true; for (int j = i; j + 1 < argc; j++) argv[j] = argv[j + 1]; argc--; i--; }
+        if (!strcmp(argv[i], "--zk") || !strcmp(argv[i], "--keccak")) {
+            if (argv[i][2] == 'z') zk = true; else keccak = true;
+            for (int j = i; j + 1 < argc; j++) argv[j] = argv[j + 1];
+            argc--; i--;
+        }
     const size_t m = argc > 1 ? (size_t)atoi(argv[1]) : 20;                      // matrix_mul.rs:30
     const uint64_t seed_arg = argc > 2 ? (uint64_t)strtoull(argv[2], nullptr, 10) : 0;
     std::mt19937_64 rng(seed_arg ? seed_arg : ((uint64_t)std::random_device{}() << 32) ^ std::random_device{}());
@@ -41,7 +47,7 @@ int main(int argc, char** argv) {
     // ---- build (matrix_mul.rs:25-67): circuit description on the host, constants/sigmas commitment on the GPU ----
     auto t0 = std::chrono::steady_clock::now();
     gl_host_circuit* hc = nullptr;
-    CHECK(zk ? gl_matmul_circuit_build_zk(m, &hc) : gl_matmul_circuit_build(m, &hc));
+    CHECK(gl_matmul_circuit_build_h(m, zk ? 1 : 0, keccak ? GL_HASHER_KECCAK : GL_HASHER_POSEIDON, &hc));
     gl_circuit_desc desc;
     CHECK(gl_host_circuit_desc(hc, &desc));
     gl_ctx* ctx = nullptr;
@@ -54,6 +60,7 @@ int main(int argc, char** argv) {
     std::vector<uint64_t> cap(4 * ncap), digest(4);
     CHECK(gl_circuit_constants_sigmas_cap(circuit, cap.data()));
     CHECK(gl_circuit_digest(circuit, digest.data()));
+    fprintf(stderr, "configuration: %s\n", keccak ? "KeccakGoldilocksConfig" : "PoseidonGoldilocksConfig");
     fprintf(stderr, "build: m = %zu, %zu rows (2^%u)%s, %.1f ms\n", m, n, desc.degree_bits, zk ? ", zero knowledge" : "", ms_since(t0));
 
     // ---- witness (matrix_mul.rs:70-83): u32 operands, gen_range(u32::MIN..u32::MAX) ----

@@ -14,6 +14,13 @@
  *  - An extension element (F_p[X]/(X^2-7)) is two consecutive uint64_t: (a0, a1)
  *    (field/src/extension/quadratic.rs:14).  A digest (HashOut) is four uint64_t
  *    (plonky2/src/hash/hash_types.rs:20-24).
+ *  - `hasher` selects the reference's `C::Hasher` (plonk/config.rs:95-118): GL_HASHER_POSEIDON = PoseidonGoldilocksConfig, the default
+ *    of every entry point without the argument, or GL_HASHER_KECCAK = KeccakGoldilocksConfig (Hasher = KeccakHash<25>, hash/keccak.rs;
+ *    InnerHasher stays Poseidon).  A BytesHash<25> (hash_types.rs:156-192) travels in the same four-uint64_t slot as a HashOut: its 25
+ *    bytes little-endian in words 0..3, the top 7 bytes of word 3 zero; an input slot whose padding bytes are not zero is GL_ERR_ARG
+ *    (verifier: "malformed").  On the wire such a hash is 25 bytes (util/serialization/mod.rs:248-256), so caps, Merkle-proof siblings
+ *    and VerifierOnlyCircuitData are 7 bytes per hash shorter than under Poseidon.  Entry points that take a hasher of their own carry
+ *    the suffix _h; handles (gl_merkle, gl_batch, gl_circuit, gl_fri, gl_challenger) remember theirs, and mixing them is GL_ERR_ARG.
  *  - `h_` pointers are host memory owned by the caller; `d_` pointers are device (HIP) memory on the
  *    context's device.  Opaque handles own device memory and are released with their *_free.
  *  - All functions return GL_OK (0) or a GL_ERR_* code and never unwind; gl_last_error() gives the
@@ -52,6 +59,9 @@ extern "C" {
 #define GL_ERR_ZETA_IN_SUBGROUP 4 /* prover.rs:280-283: opening point lies in H       */
 #define GL_ERR_INTERNAL 5
 #define GL_ERR_VERIFY 6       /* gl_verify: the proof is rejected (gl_last_error says which check failed) */
+
+#define GL_HASHER_POSEIDON 0u /* PoseidonGoldilocksConfig (plonk/config.rs:95-105)  */
+#define GL_HASHER_KECCAK 1u   /* KeccakGoldilocksConfig (plonk/config.rs:107-118)   */
 
 typedef struct gl_ctx gl_ctx;
 typedef struct gl_batch gl_batch;      /* device-resident PolynomialBatch (fri/oracle.rs:30-37)  */
@@ -106,6 +116,8 @@ typedef struct gl_circuit_desc {
     uint32_t zero_knowledge;           /* 0 / 1                                                                                 */
     uint32_t num_gate_rows;            /* rows before blind_and_pad, or 0 when unknown (a description read from bytes); when set,
                                           degree_bits must be what blinding_counts + padding give, and gl_witness_blind needs it */
+    /* ---- C::Hasher (a type parameter in Rust, not part of CommonCircuitData's bytes): Merkle trees, transcript, proof of work ---- */
+    uint32_t hasher;                   /* GL_HASHER_POSEIDON (0) / GL_HASHER_KECCAK (1)                                         */
 } gl_circuit_desc;
 #define GL_MAX_GATES 16
 #define GL_MAX_LUTS 4
@@ -167,12 +179,22 @@ int gl_poseidon_permute_raw(gl_ctx* ctx, uint64_t* d_states, size_t count, int l
 /* Hasher::hash_or_noop (plonky2/src/plonk/config.rs:55-66) of `count` rows of `len` elements,
  * row-major d_rows[count][len] -> d_out[count][4] */
 int gl_hash_rows(gl_ctx* ctx, const uint64_t* d_rows, size_t count, size_t len, uint64_t* d_out);
+/* the same under `hasher`; KeccakHash<25> (hash/keccak.rs:105-117): a row of <= 3 elements is copied into the 25 bytes, a longer one is
+ * Keccak-256 (original padding: domain byte 0x01) over its canonical little-endian words, truncated to 25 bytes */
+int gl_hash_rows_h(gl_ctx* ctx, uint32_t hasher, const uint64_t* d_rows, size_t count, size_t len, uint64_t* d_out);
+/* Hasher::hash_or_noop (plonk/config.rs:55-66) and Hasher::two_to_one (hash/hashing.rs:98-115 PoseidonHash, hash/keccak.rs:119-126
+ * KeccakHash<25>) on the host, no GPU needed: h_rows[count][len] -> h_out[count][4]; h_left[count][4], h_right[count][4] -> h_out[count][4] */
+int gl_hash_or_noop_host(uint32_t hasher, const uint64_t* h_rows, size_t count, size_t len, uint64_t* h_out);
+int gl_two_to_one_host(uint32_t hasher, const uint64_t* h_left, const uint64_t* h_right, size_t count, uint64_t* h_out);
 
 /* ---- Merkle tree ---------------------------------------------------------------------------------*/
 /* MerkleTree::new(leaves, cap_height) (plonky2/src/hash/merkle_tree.rs:135-165) for row-major host
  * leaves h_leaves[num_leaves][leaf_len]; the tree keeps a device copy of the leaves. */
 int gl_merkle_new(gl_ctx* ctx, const uint64_t* h_leaves, size_t num_leaves, size_t leaf_len,
                   uint32_t cap_height, gl_merkle** out);
+/* MerkleTree::<F, H>::new for H = `hasher` (merkle_tree.rs:69-165: hash_or_noop on the leaves, two_to_one inside) */
+int gl_merkle_new_h(gl_ctx* ctx, uint32_t hasher, const uint64_t* h_leaves, size_t num_leaves, size_t leaf_len,
+                    uint32_t cap_height, gl_merkle** out);
 /* field `cap` (merkle_tree.rs:54): h_out[2^cap_height][4] */
 int gl_merkle_cap(const gl_merkle* t, uint64_t* h_out);
 /* MerkleTree::prove (merkle_tree.rs:171-207): siblings bottom-up, h_out[log2(n) - cap_height][4] */
@@ -199,6 +221,19 @@ int gl_batch_from_coeffs_blinded(gl_ctx* ctx, const uint64_t* const* h_cols, siz
 /* same, from a device-resident column-major matrix d_cols[ncols][n]; is_values selects from_values */
 int gl_batch_from_device(gl_ctx* ctx, const uint64_t* d_cols, size_t ncols, size_t n, uint32_t rate_bits,
                          uint32_t cap_height, int is_values, gl_batch** out);
+/* The five constructors above for PolynomialBatch<F, C, D> with C::Hasher = `hasher` (fri/oracle.rs:43-125): the same polynomials and
+ * LDE values, the Merkle tree under that hasher.  seed as above; gl_batch_from_device_h commits without salt. */
+int gl_batch_from_values_h(gl_ctx* ctx, uint32_t hasher, const uint64_t* const* h_cols, size_t ncols, size_t n,
+                           uint32_t rate_bits, uint32_t blinding, uint32_t cap_height, gl_batch** out);
+int gl_batch_from_coeffs_h(gl_ctx* ctx, uint32_t hasher, const uint64_t* const* h_cols, size_t ncols, size_t n,
+                           uint32_t rate_bits, uint32_t blinding, uint32_t cap_height, gl_batch** out);
+int gl_batch_from_values_blinded_h(gl_ctx* ctx, uint32_t hasher, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
+                                   uint32_t cap_height, const uint8_t seed[32], gl_batch** out);
+int gl_batch_from_coeffs_blinded_h(gl_ctx* ctx, uint32_t hasher, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
+                                   uint32_t cap_height, const uint8_t seed[32], gl_batch** out);
+int gl_batch_from_device_h(gl_ctx* ctx, uint32_t hasher, const uint64_t* d_cols, size_t ncols, size_t n, uint32_t rate_bits,
+                           uint32_t cap_height, int is_values, gl_batch** out);
+uint32_t gl_batch_hasher(const gl_batch* b);
 /* field `merkle_tree.cap` (used at prover.rs:164,225,273,319-321): h_out[2^cap_height][4] */
 int gl_batch_cap(const gl_batch* b, uint64_t* h_out);
 /* merkle_tree.get(i) (merkle_tree.rs:167-169): the leaf at Merkle index i, h_out[ncols] (h_out[ncols + 4] with blinding: the salt last) */
@@ -240,6 +275,9 @@ int gl_matmul_circuit_build(size_t m, gl_host_circuit** out);
  * desc.zero_knowledge = 1, desc.num_gate_rows = the rows before blinding.  gl_matmul_witness and the witness generator leave the
  * rows from num_gate_rows on zero; gl_witness_blind fills them in before proving. */
 int gl_matmul_circuit_build_zk(size_t m, gl_host_circuit** out);
+/* either of the two with the configuration's hasher chosen: the circuit the demo builds under `C = KeccakGoldilocksConfig`
+ * (plonky2/src/bin/matrix_mul.rs:21-23 names the type parameter).  Gates, constants, sigmas and witness are the same; desc.hasher differs. */
+int gl_matmul_circuit_build_h(size_t m, uint32_t zero_knowledge, uint32_t hasher, gl_host_circuit** out);
 int gl_host_circuit_desc(const gl_host_circuit* hc, gl_circuit_desc* out);
 int gl_host_circuit_row_gates(const gl_host_circuit* hc, uint8_t* h_out /* n */);
 int gl_host_circuit_constants_sigmas(const gl_host_circuit* hc, uint64_t* h_out);
@@ -335,6 +373,11 @@ int gl_fri_final_poly(gl_fri* f, uint64_t* h_out, size_t cap_words, size_t* num_
  * leading_zeros(permute(sponge_state overlaid with input_buffer[0..input_len) and w at input_len)[7]) >= min_leading_zeros */
 int gl_pow_grind(gl_ctx* ctx, const uint64_t sponge_state[12], const uint64_t* input_buffer, uint32_t input_len,
                  uint32_t min_leading_zeros, uint64_t* witness);
+/* the same over `hasher`'s permutation.  KeccakPermutation (hash/keccak.rs:64-95): the candidate goes into its state word, H1 =
+ * Keccak-256 of the 96 state bytes, H2 = Keccak-256(H1), ...; the response is element 7 of the stream of their words < p (normally
+ * word 3 of H2; a rejected word moves it, possibly into H3, and the kernel follows). */
+int gl_pow_grind_h(gl_ctx* ctx, uint32_t hasher, const uint64_t sponge_state[12], const uint64_t* input_buffer, uint32_t input_len,
+                   uint32_t min_leading_zeros, uint64_t* witness);
 /* fri_prover_query_rounds (fri/prover.rs:162-216) for the given x_index values (challenge mod lde_size), as the
  * serialised Vec<FriQueryRound> body (util/serialization/mod.rs:1477-1546).  h_blob may be null to query the size. */
 int gl_fri_query(gl_fri* f, const uint32_t* x_index, uint32_t num_queries, uint8_t* h_blob, size_t cap_bytes,
@@ -346,6 +389,11 @@ void gl_fri_free(gl_fri* f);
  * the way fri_proof_of_work reads them (fri/prover.rs:127-140), for gl_pow_grind. */
 typedef struct gl_challenger gl_challenger;
 gl_challenger* gl_challenger_new(void);
+/* Challenger<F, H> for H = `hasher` (NULL for another value); under Keccak the permutation is KeccakPermutation (hash/keccak.rs:64-95) */
+gl_challenger* gl_challenger_new_h(uint32_t hasher);
+/* observe_hash::<OH> / observe_cap::<OH> (challenger.rs:72-80) of `count` digests h_hashes[count][4] of hasher `oh`: a HashOut is its
+ * four elements, a BytesHash<25> the four elements of its bytes in chunks of 7, 7, 7, 4 (hash_types.rs:181-191) */
+int gl_challenger_observe_hashes(gl_challenger* c, uint32_t oh, const uint64_t* h_hashes, size_t count);
 int gl_challenger_observe(gl_challenger* c, const uint64_t* h_elements, size_t count);
 int gl_challenger_get_challenges(gl_challenger* c, uint64_t* h_out, size_t count);
 int gl_challenger_state(const gl_challenger* c, uint64_t h_sponge_state[12], uint64_t h_input_buffer[8], uint32_t* input_len);
@@ -436,6 +484,13 @@ int gl_verifier_only_from_bytes(const uint8_t* h_bytes, size_t num_bytes, uint32
                                 size_t cap_words, uint64_t circuit_digest[4], size_t* consumed /* may be null */);
 /* VerifierCircuitData::from_bytes(data).verify(proof): GL_OK = accepted, GL_ERR_VERIFY = rejected (as gl_verify) */
 int gl_verify_bytes(const uint8_t* h_verifier_data, size_t num_data_bytes, const uint8_t* proof_bytes, size_t num_proof_bytes);
+/* The hasher is a type parameter of these forms in Rust and not in their bytes (gl_common_data_from_bytes returns hasher = 0): the three
+ * entries above for `C::Hasher = hasher`.  Under Keccak a hash is 25 bytes (util/serialization/mod.rs:248-256,1332-1338). */
+int gl_verifier_only_to_bytes_h(uint32_t hasher, uint32_t cap_height, const uint64_t* constants_sigmas_cap, const uint64_t circuit_digest[4],
+                                uint8_t* h_out, size_t cap, size_t* num_bytes);
+int gl_verifier_only_from_bytes_h(uint32_t hasher, const uint8_t* h_bytes, size_t num_bytes, uint32_t* cap_height, uint64_t* h_cap, size_t cap_words,
+                                  uint64_t circuit_digest[4], size_t* consumed);
+int gl_verify_bytes_h(uint32_t hasher, const uint8_t* h_verifier_data, size_t num_data_bytes, const uint8_t* proof_bytes, size_t num_proof_bytes);
 
 #ifdef __cplusplus
 }

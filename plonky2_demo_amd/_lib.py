@@ -152,7 +152,37 @@ SIGNATURES = {
     "gl_verifier_only_to_bytes": (c_int, [c_u32, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "gl_verifier_only_from_bytes": (c_int, [c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_vp]),
     "gl_verify_bytes": (c_int, [c_vp, c_sz, c_vp, c_sz]),
+    # the hasher-carrying entry points (hasher: 0 Poseidon, 1 Keccak)
+    "gl_hash_rows_h": (c_int, [c_vp, c_u32, c_vp, c_sz, c_sz, c_vp]),
+    "gl_hash_or_noop_host": (c_int, [c_u32, c_vp, c_sz, c_sz, c_vp]),
+    "gl_two_to_one_host": (c_int, [c_u32, c_vp, c_vp, c_sz, c_vp]),
+    "gl_merkle_new_h": (c_int, [c_vp, c_u32, c_vp, c_sz, c_sz, c_u32, ctypes.POINTER(c_vp)]),
+    "gl_batch_from_values_h": (c_int, [c_vp, c_u32, ctypes.POINTER(c_vp), c_sz, c_sz, c_u32, c_u32, c_u32, ctypes.POINTER(c_vp)]),
+    "gl_batch_from_coeffs_h": (c_int, [c_vp, c_u32, ctypes.POINTER(c_vp), c_sz, c_sz, c_u32, c_u32, c_u32, ctypes.POINTER(c_vp)]),
+    "gl_batch_from_values_blinded_h": (c_int, [c_vp, c_u32, ctypes.POINTER(c_vp), c_sz, c_sz, c_u32, c_u32, c_vp, ctypes.POINTER(c_vp)]),
+    "gl_batch_from_coeffs_blinded_h": (c_int, [c_vp, c_u32, ctypes.POINTER(c_vp), c_sz, c_sz, c_u32, c_u32, c_vp, ctypes.POINTER(c_vp)]),
+    "gl_batch_from_device_h": (c_int, [c_vp, c_u32, c_vp, c_sz, c_sz, c_u32, c_u32, c_int, ctypes.POINTER(c_vp)]),
+    "gl_batch_hasher": (c_u32, [c_vp]),
+    "gl_matmul_circuit_build_h": (c_int, [c_sz, c_u32, c_u32, ctypes.POINTER(c_vp)]),
+    "gl_pow_grind_h": (c_int, [c_vp, c_u32, c_vp, c_vp, c_u32, c_u32, c_vp]),
+    "gl_challenger_new_h": (c_vp, [c_u32]),
+    "gl_challenger_observe_hashes": (c_int, [c_vp, c_u32, c_vp, c_sz]),
+    "gl_verifier_only_to_bytes_h": (c_int, [c_u32, c_u32, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "gl_verifier_only_from_bytes_h": (c_int, [c_u32, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "gl_verify_bytes_h": (c_int, [c_u32, c_vp, c_sz, c_vp, c_sz]),
 }
+
+HASHERS = {"poseidon": 0, "keccak": 1}
+
+
+def hasher_id(hasher):
+    """"poseidon" | "keccak" (or 0 | 1) -> the C ABI's number; anything else is a ValueError."""
+    if hasher in HASHERS:
+        return HASHERS[hasher]
+    if hasher in (0, 1) and not isinstance(hasher, bool):
+        return int(hasher)
+    raise ValueError("hasher must be 'poseidon' or 'keccak', not %r" % (hasher,))
+
 
 
 class CircuitDesc(ctypes.Structure):
@@ -168,6 +198,7 @@ class CircuitDesc(ctypes.Structure):
         ("last_lu_row", c_u32 * 4), ("last_lut_row", c_u32 * 4), ("first_lut_row", c_u32 * 4), ("lut_len", c_u32 * 4),
         ("lut", ctypes.c_uint16 * 2048),
         ("zero_knowledge", c_u32), ("num_gate_rows", c_u32),
+        ("hasher", c_u32),
     ]
 
     def lookup_table(self, t):

@@ -8,7 +8,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import check, hasher_id, lib
 
 GOLDILOCKS_ORDER = 0xFFFFFFFF00000001   # field/src/goldilocks_field.rs:152
 COSET_SHIFT = 7                          # field/src/types.rs:437-439, goldilocks_field.rs:80
@@ -235,9 +235,62 @@ def poseidon(states, ctx=None):
     return d.download(s.shape)
 
 
-def hash_or_noop(rows, ctx=None):
+def hash_to_bytes(digests, hasher="keccak"):
+    """[k][4] digest words -> k byte strings as they go on the wire: 32 bytes of a HashOut, the 25 bytes of a BytesHash<25>."""
+    d = _u64(digests).reshape(-1, 4)
+    size = 25 if hasher_id(hasher) else 32
+    return [d[i].tobytes()[:size] for i in range(d.shape[0])]
+
+
+def hash_from_bytes(strings, hasher="keccak"):
+    """The inverse of hash_to_bytes: byte strings -> [k][4] digest words (a 25-byte hash zero-padded into its slot)."""
+    size = 25 if hasher_id(hasher) else 32
+    out = np.zeros((len(strings), 4), dtype=np.uint64)
+    for i, b in enumerate(strings):
+        if len(b) != size:
+            raise ValueError("a %s hash is %d bytes" % ("keccak" if size == 25 else "poseidon", size))
+        out[i] = np.frombuffer(bytes(b).ljust(32, b"\0"), dtype="<u8")
+    return out
+
+
+def hash_to_elements(digests, hasher="keccak"):
+    """GenericHashOut::to_vec per digest, [k][4] -> [k][4] field elements: what a Challenger observes of a hash.  A BytesHash<25> is
+    its bytes in chunks of 7, 7, 7, 4 (hash/hash_types.rs:181-191); a HashOut is its own elements."""
+    d = _u64(digests).reshape(-1, 4)
+    if not hasher_id(hasher):
+        return d.copy()
+    raw = np.ascontiguousarray(d).view(np.uint8).reshape(-1, 32)
+    out = np.zeros((d.shape[0], 4, 8), dtype=np.uint8)
+    for j, (lo, hi) in enumerate(((0, 7), (7, 14), (14, 21), (21, 25))):
+        out[:, j, : hi - lo] = raw[:, lo:hi]
+    return out.view("<u8").reshape(-1, 4)
+
+
+def hash_or_noop_host(rows, hasher="poseidon"):
+    """hash_or_noop per row on the host (no GPU): [count][len] -> [count][4]."""
+    r = _u64(rows)
+    single = r.ndim == 1
+    if single:
+        r = r.reshape(1, -1)
+    out = np.zeros((r.shape[0], 4), dtype=np.uint64)
+    check(lib.gl_hash_or_noop_host(hasher_id(hasher), _p(r) if r.size else None, r.shape[0], r.shape[1], _p(out)))
+    return out[0] if single else out
+
+
+def two_to_one_host(left, right, hasher="poseidon"):
+    """Hasher::two_to_one on the host (no GPU): [k][4], [k][4] -> [k][4] (or [4], [4] -> [4])."""
+    l, r = _u64(left), _u64(right)
+    single = l.ndim == 1
+    l, r = l.reshape(-1, 4), r.reshape(-1, 4)
+    out = np.zeros_like(l)
+    check(lib.gl_two_to_one_host(hasher_id(hasher), _p(l), _p(r), l.shape[0], _p(out)))
+    return out[0] if single else out
+
+
+def hash_or_noop(rows, ctx=None, hasher="poseidon"):
     """Hasher::hash_or_noop (plonky2/src/plonk/config.rs:55-66) per row of [count][len] -> [count][4]."""
     ctx = _ctx(ctx)
+    hid = hasher_id(hasher)
     r = _u64(rows)
     single = r.ndim == 1
     if single:
@@ -247,7 +300,7 @@ def hash_or_noop(rows, ctx=None):
         return np.zeros((4,) if single else (count, 4), dtype=np.uint64)
     d = ctx.alloc(max(8, r.nbytes)).upload(r)
     o = ctx.alloc(max(32, count * 32))
-    check(lib.gl_hash_rows(ctx.handle, d.ptr, count, ln, o.ptr))
+    check(lib.gl_hash_rows_h(ctx.handle, hid, d.ptr, count, ln, o.ptr))
     out = o.download((count, 4))
     return out[0] if single else out
 
@@ -256,8 +309,9 @@ class MerkleTree(_Owned):
     """plonky2::hash::merkle_tree::MerkleTree (merkle_tree.rs:39-207) with device-resident digests."""
     _free = "gl_merkle_free"
 
-    def __init__(self, leaves, cap_height, ctx=None):
+    def __init__(self, leaves, cap_height, ctx=None, hasher="poseidon"):
         self.ctx = _ctx(ctx)
+        self.hasher = hasher_id(hasher)
         l2 = _u64(leaves)
         if l2.ndim != 2:
             raise ValueError("leaves must be [num_leaves][leaf_len]")
@@ -265,7 +319,7 @@ class MerkleTree(_Owned):
         self.cap_height = cap_height
         self.leaves = l2
         h = ctypes.c_void_p()
-        check(lib.gl_merkle_new(self.ctx.handle, _p(l2), self.num_leaves, self.leaf_len, cap_height, ctypes.byref(h)))
+        check(lib.gl_merkle_new_h(self.ctx.handle, self.hasher, _p(l2), self.num_leaves, self.leaf_len, cap_height, ctypes.byref(h)))
         self.handle = h.value
 
     @property
@@ -295,10 +349,11 @@ class PolynomialBatch(_Owned):
         self.ncols = lib.gl_batch_ncols(handle)
         self.degree = lib.gl_batch_degree(handle)
         self.degree_log = _log2_strict(self.degree)
+        self.hasher = lib.gl_batch_hasher(handle)
 
     @classmethod
-    def _from_host(cls, fn, cols, rate_bits, cap_height, ctx, *args, salt=0):
-        """fn(ctx, column pointers, ncols, n, rate_bits, *args, out)"""
+    def _from_host(cls, fn, cols, rate_bits, cap_height, ctx, *args, salt=0, hasher="poseidon"):
+        """fn(ctx, hasher, column pointers, ncols, n, rate_bits, *args, out)"""
         ctx = _ctx(ctx)
         cols = [_u64(c) for c in cols]
         if not cols:
@@ -308,38 +363,38 @@ class PolynomialBatch(_Owned):
             raise ValueError("Polynomial degrees inconsistent")   # oracle.rs:114
         ptrs = (ctypes.c_void_p * len(cols))(*[c.ctypes.data for c in cols])
         h = ctypes.c_void_p()
-        check(fn(ctx.handle, ptrs, len(cols), n, rate_bits, *args, ctypes.byref(h)))
+        check(fn(ctx.handle, hasher_id(hasher), ptrs, len(cols), n, rate_bits, *args, ctypes.byref(h)))
         b = cls(h.value, ctx, rate_bits, cap_height)
         b.salt = salt
         return b
 
     @classmethod
-    def from_values(cls, values, rate_bits, blinding, cap_height, ctx=None):
+    def from_values(cls, values, rate_bits, blinding, cap_height, ctx=None, hasher="poseidon"):
         """PolynomialBatch::from_values (fri/oracle.rs:43-66); blinding = True is from_values_blinded."""
-        return cls._from_host(lib.gl_batch_from_values, values, rate_bits, cap_height, ctx, 1 if blinding else 0, cap_height)
+        return cls._from_host(lib.gl_batch_from_values_h, values, rate_bits, cap_height, ctx, 1 if blinding else 0, cap_height, hasher=hasher)
 
     @classmethod
-    def from_coeffs(cls, polynomials, rate_bits, blinding, cap_height, ctx=None):
+    def from_coeffs(cls, polynomials, rate_bits, blinding, cap_height, ctx=None, hasher="poseidon"):
         """PolynomialBatch::from_coeffs (fri/oracle.rs:68-98); blinding = True is from_coeffs_blinded."""
-        return cls._from_host(lib.gl_batch_from_coeffs, polynomials, rate_bits, cap_height, ctx, 1 if blinding else 0, cap_height)
+        return cls._from_host(lib.gl_batch_from_coeffs_h, polynomials, rate_bits, cap_height, ctx, 1 if blinding else 0, cap_height, hasher=hasher)
 
     @classmethod
-    def from_values_blinded(cls, values, rate_bits, cap_height, seed=None, ctx=None):
+    def from_values_blinded(cls, values, rate_bits, cap_height, seed=None, ctx=None, hasher="poseidon"):
         """from_values with blinding = true: every leaf salted with SALT_SIZE elements keyed by `seed` (32 bytes; None = OS entropy)."""
-        return cls._from_host(lib.gl_batch_from_values_blinded, values, rate_bits, cap_height, ctx, cap_height,
-                              _seed(seed) if seed is not None else None, salt=SALT_SIZE)
+        return cls._from_host(lib.gl_batch_from_values_blinded_h, values, rate_bits, cap_height, ctx, cap_height,
+                              _seed(seed) if seed is not None else None, salt=SALT_SIZE, hasher=hasher)
 
     @classmethod
-    def from_coeffs_blinded(cls, polynomials, rate_bits, cap_height, seed=None, ctx=None):
+    def from_coeffs_blinded(cls, polynomials, rate_bits, cap_height, seed=None, ctx=None, hasher="poseidon"):
         """from_coeffs with blinding = true (see from_values_blinded)."""
-        return cls._from_host(lib.gl_batch_from_coeffs_blinded, polynomials, rate_bits, cap_height, ctx, cap_height,
-                              _seed(seed) if seed is not None else None, salt=SALT_SIZE)
+        return cls._from_host(lib.gl_batch_from_coeffs_blinded_h, polynomials, rate_bits, cap_height, ctx, cap_height,
+                              _seed(seed) if seed is not None else None, salt=SALT_SIZE, hasher=hasher)
 
     @classmethod
-    def from_device(cls, d_ptr, ncols, n, rate_bits, cap_height, is_values, ctx=None):
+    def from_device(cls, d_ptr, ncols, n, rate_bits, cap_height, is_values, ctx=None, hasher="poseidon"):
         ctx = _ctx(ctx)
         h = ctypes.c_void_p()
-        check(lib.gl_batch_from_device(ctx.handle, d_ptr, ncols, n, rate_bits, cap_height, 1 if is_values else 0, ctypes.byref(h)))
+        check(lib.gl_batch_from_device_h(ctx.handle, hasher_id(hasher), d_ptr, ncols, n, rate_bits, cap_height, 1 if is_values else 0, ctypes.byref(h)))
         return cls(h.value, ctx, rate_bits, cap_height)
 
     @property
@@ -391,12 +446,13 @@ class PolynomialBatch(_Owned):
 class MatmulCircuit(_Owned):
     """Host side of the demo (plonky2/src/bin/matrix_mul.rs:25-67 + CircuitBuilder::build()): needs no GPU.  zero_knowledge=True
     builds it with standard_recursion_zk_config: blinding rows after the gate rows, salted commitments (blind the witness with
-    CircuitData.blind_witness before proving)."""
+    CircuitData.blind_witness before proving).  hasher="keccak" builds it under KeccakGoldilocksConfig: the same gates, constants,
+    sigmas and witness; Merkle trees, transcript and proof of work under Keccak-256."""
     _free = "gl_host_circuit_free"
 
-    def __init__(self, m, zero_knowledge=False):
+    def __init__(self, m, zero_knowledge=False, hasher="poseidon"):
         h = ctypes.c_void_p()
-        check((lib.gl_matmul_circuit_build_zk if zero_knowledge else lib.gl_matmul_circuit_build)(int(m), ctypes.byref(h)))
+        check(lib.gl_matmul_circuit_build_h(int(m), 1 if zero_knowledge else 0, hasher_id(hasher), ctypes.byref(h)))
         self.handle, self.m, self.zero_knowledge = h.value, int(m), bool(zero_knowledge)
         self.desc = _lib.CircuitDesc()
         check(lib.gl_host_circuit_desc(self.handle, ctypes.byref(self.desc)))
@@ -668,36 +724,37 @@ def common_data_from_bytes(data):
     return d, used.value
 
 
-def verifier_only_to_bytes(constants_sigmas_cap, circuit_digest):
+def verifier_only_to_bytes(constants_sigmas_cap, circuit_digest, hasher="poseidon"):
+    """VerifierOnlyCircuitData::to_bytes; the hasher is a type parameter on the Rust side and not in the bytes (a Keccak hash is 25 bytes)."""
     cap, dig = _u64(constants_sigmas_cap).reshape(-1, 4), _u64(circuit_digest)
     h = _log2_strict(cap.shape[0])
     n = ctypes.c_size_t()
     buf = np.empty(8 + 32 * cap.shape[0] + 32, dtype=np.uint8)
-    check(lib.gl_verifier_only_to_bytes(h, _p(cap), _p(dig), _p(buf), buf.size, ctypes.byref(n)))
+    check(lib.gl_verifier_only_to_bytes_h(hasher_id(hasher), h, _p(cap), _p(dig), _p(buf), buf.size, ctypes.byref(n)))
     return buf[: n.value].tobytes()
 
 
-def verifier_only_from_bytes(data):
+def verifier_only_from_bytes(data, hasher="poseidon"):
     """-> (cap[2^h][4], digest[4], bytes consumed)"""
     buf = np.frombuffer(bytes(data), dtype=np.uint8)
-    h, used = ctypes.c_uint32(), ctypes.c_size_t()
+    h, used, hid = ctypes.c_uint32(), ctypes.c_size_t(), hasher_id(hasher)
     dig = np.empty(4, dtype=np.uint64)
-    check(lib.gl_verifier_only_from_bytes(_p(buf), buf.size, ctypes.byref(h), None, 0, _p(dig), ctypes.byref(used)))
+    check(lib.gl_verifier_only_from_bytes_h(hid, _p(buf), buf.size, ctypes.byref(h), None, 0, _p(dig), ctypes.byref(used)))
     cap = np.empty((1 << h.value, 4), dtype=np.uint64)
-    check(lib.gl_verifier_only_from_bytes(_p(buf), buf.size, ctypes.byref(h), _p(cap), cap.size, _p(dig), ctypes.byref(used)))
+    check(lib.gl_verifier_only_from_bytes_h(hid, _p(buf), buf.size, ctypes.byref(h), _p(cap), cap.size, _p(dig), ctypes.byref(used)))
     return cap, dig, used.value
 
 
 def verifier_data_to_bytes(desc, constants_sigmas_cap, circuit_digest):
-    """VerifierCircuitData::to_bytes = verifier_only || common (util/serialization/mod.rs:1908-1919)."""
-    return verifier_only_to_bytes(constants_sigmas_cap, circuit_digest) + common_data_to_bytes(desc)
+    """VerifierCircuitData::to_bytes = verifier_only || common (util/serialization/mod.rs:1908-1919), under desc.hasher."""
+    return verifier_only_to_bytes(constants_sigmas_cap, circuit_digest, hasher=desc.hasher) + common_data_to_bytes(desc)
 
 
-def verify_bytes(verifier_data, proof_bytes):
+def verify_bytes(verifier_data, proof_bytes, hasher="poseidon"):
     """VerifierCircuitData::from_bytes(verifier_data).verify(proof): (accepted, reason)."""
     vd = np.frombuffer(bytes(verifier_data), dtype=np.uint8)
     pb = np.frombuffer(bytes(proof_bytes), dtype=np.uint8)
-    return _verdict(lib.gl_verify_bytes(_p(vd), vd.size, _p(pb), pb.size))
+    return _verdict(lib.gl_verify_bytes_h(hasher_id(hasher), _p(vd), vd.size, _p(pb), pb.size))
 
 
 class GenericProverPool(_Owned):
@@ -811,8 +868,14 @@ class Challenger(_Owned):
     """plonky2::iop::challenger::Challenger (iop/challenger.rs:30-153), host code."""
     _free = "gl_challenger_free"
 
-    def __init__(self):
-        self.handle = lib.gl_challenger_new()
+    def __init__(self, hasher="poseidon"):
+        self.hasher = hasher_id(hasher)
+        self.handle = lib.gl_challenger_new_h(self.hasher)
+
+    def observe_hashes(self, digests, hasher=None):
+        """observe_hash / observe_cap (challenger.rs:72-80) of [k][4] digests of `hasher` (default: the Challenger's own)."""
+        d = _u64(digests).reshape(-1, 4)
+        check(lib.gl_challenger_observe_hashes(self.handle, self.hasher if hasher is None else hasher_id(hasher), _p(d), d.shape[0]))
 
     def observe_elements(self, xs):
         a = _u64(np.asarray(xs, dtype=np.uint64).reshape(-1))
@@ -830,14 +893,14 @@ class Challenger(_Owned):
         return st, buf[: k.value].copy()
 
 
-def pow_grind(sponge_state, input_buffer, min_leading_zeros, ctx=None):
+def pow_grind(sponge_state, input_buffer, min_leading_zeros, ctx=None, hasher="poseidon"):
     """fri_proof_of_work (fri/prover.rs:115-160): the smallest valid witness."""
     ctx = _ctx(ctx)
     st, buf = _u64(sponge_state), _u64(input_buffer)
     if st.size != 12:
         raise ValueError("sponge state has 12 words")
     w = np.zeros(1, dtype=np.uint64)
-    check(lib.gl_pow_grind(ctx.handle, _p(st), _p(buf) if buf.size else None, buf.size, min_leading_zeros, _p(w)))
+    check(lib.gl_pow_grind_h(ctx.handle, hasher_id(hasher), _p(st), _p(buf) if buf.size else None, buf.size, min_leading_zeros, _p(w)))
     return int(w[0])
 
 

@@ -32,13 +32,14 @@ static int batch_commit(gl_ctx* c, gl_batch* b, const gl_t* values, const uint8_
     if (b->salt) GL_TRY(gl_fill_random(c, seed, GL_STREAM_SALT + 4 * oracle, b->salt, 0, b->N(), b->lde + b->ncols * b->N(), b->N()));
     std::vector<uint64_t> offs(b->leaf_len());
     for (size_t e = 0; e < b->leaf_len(); e++) offs[e] = e * b->N();
-    GL_TRY(gl_merkle_build(c, b->lde, offs.data(), (uint32_t)b->leaf_len(), b->degree_log + b->rate_bits, b->cap_height, &b->tree));
+    GL_TRY(gl_merkle_build(c, b->lde, offs.data(), (uint32_t)b->leaf_len(), b->degree_log + b->rate_bits, b->cap_height, &b->tree, b->hasher));
     return GL_OK;
 }
 
 extern "C" void gl_batch_free(gl_batch* b);
-static int batch_alloc(gl_ctx* c, size_t ncols, size_t n, uint32_t rate_bits, uint32_t cap_height, uint32_t salt, gl_batch** out) {
+static int batch_alloc(gl_ctx* c, size_t ncols, size_t n, uint32_t rate_bits, uint32_t cap_height, uint32_t salt, uint32_t hasher, gl_batch** out) {
     GL_REQUIRE(c && out && ncols >= 1 && n >= 1, GL_ERR_ARG, "PolynomialBatch: bad argument");
+    GL_REQUIRE(hasher <= 1, GL_ERR_ARG, "PolynomialBatch: hasher is 0 (Poseidon) or 1 (Keccak)");
     uint32_t lg = 0;
     while ((size_t(1) << lg) < n) lg++;
     GL_REQUIRE((size_t(1) << lg) == n, GL_ERR_ARG, "polynomial length must be a power of two");
@@ -47,7 +48,7 @@ static int batch_alloc(gl_ctx* c, size_t ncols, size_t n, uint32_t rate_bits, ui
     GL_TRY(c->activate());
     gl_batch* b = new gl_batch();
     b->ctx = c; c->retain(); b->ncols = ncols; b->n = n; b->degree_log = lg; b->rate_bits = rate_bits; b->cap_height = cap_height;
-    b->salt = salt;
+    b->salt = salt; b->hasher = hasher;
     int st = c->pool_alloc(ncols * n * sizeof(gl_t), (void**)&b->coeffs);
     if (st == GL_OK) st = c->pool_alloc(b->leaf_len() * b->N() * sizeof(gl_t), (void**)&b->lde);
     if (st != GL_OK) { gl_batch_free(b); return st; }      // nothing leaks when the device is out of memory
@@ -57,13 +58,13 @@ static int batch_alloc(gl_ctx* c, size_t ncols, size_t n, uint32_t rate_bits, ui
 
 // blinding: salt columns keyed by `seed_in` (null = a fresh OS seed)
 static int batch_from_host(gl_ctx* c, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits, bool blinding,
-                           const uint8_t* seed_in, uint32_t cap_height, bool is_values, gl_batch** out) {
+                           const uint8_t* seed_in, uint32_t cap_height, bool is_values, gl_batch** out, uint32_t hasher = 0) {
     GL_REQUIRE(h_cols, GL_ERR_ARG, "PolynomialBatch: null columns");
     uint8_t seed[32];
     if (blinding && seed_in) memcpy(seed, seed_in, 32);
     else if (blinding) GL_TRY(gl_os_seed(seed));
     gl_batch* b = nullptr;
-    GL_TRY(batch_alloc(c, ncols, n, rate_bits, cap_height, blinding ? GL_SALT_SIZE : 0, &b));
+    GL_TRY(batch_alloc(c, ncols, n, rate_bits, cap_height, blinding ? GL_SALT_SIZE : 0, hasher, &b));
     for (size_t col = 0; col < ncols; col++) {
         if (!h_cols[col]) { gl_batch_free(b); return gl_fail(GL_ERR_ARG, "null column", __FILE__, __LINE__); }
         hipError_t e = hipMemcpyAsync(b->coeffs + col * n, h_cols[col], n * sizeof(gl_t), hipMemcpyHostToDevice, c->stream);
@@ -96,10 +97,10 @@ extern "C" int gl_batch_from_coeffs_blinded(gl_ctx* c, const uint64_t* const* h_
     return batch_from_host(c, h_cols, ncols, n, rate_bits, true, seed, cap_height, false, out);
 }
 int gl_batch_from_device_salted(gl_ctx* c, const uint64_t* d_cols, size_t ncols, size_t n, uint32_t rate_bits, uint32_t cap_height,
-                                int is_values, const uint8_t* seed, uint32_t oracle, gl_batch** out) {
+                                int is_values, const uint8_t* seed, uint32_t oracle, gl_batch** out, uint32_t hasher) {
     GL_REQUIRE(d_cols, GL_ERR_ARG, "PolynomialBatch: null device columns");
     gl_batch* b = nullptr;
-    GL_TRY(batch_alloc(c, ncols, n, rate_bits, cap_height, seed ? GL_SALT_SIZE : 0, &b));
+    GL_TRY(batch_alloc(c, ncols, n, rate_bits, cap_height, seed ? GL_SALT_SIZE : 0, hasher, &b));
     if (!is_values) {      // coefficients are kept: copy; values are interpolated straight out of the caller's matrix (left untouched)
         hipError_t e = hipMemcpyAsync(b->coeffs, d_cols, ncols * n * sizeof(gl_t), hipMemcpyDeviceToDevice, c->stream);
         if (e != hipSuccess) { gl_batch_free(b); return gl_fail(GL_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__); }
@@ -113,6 +114,30 @@ extern "C" int gl_batch_from_device(gl_ctx* c, const uint64_t* d_cols, size_t nc
                                     uint32_t cap_height, int is_values, gl_batch** out) {
     return gl_batch_from_device_salted(c, d_cols, ncols, n, rate_bits, cap_height, is_values, nullptr, 0, out);
 }
+// the constructors for PolynomialBatch<F, C, D> with C::Hasher = `hasher` (fri/oracle.rs:43-125)
+extern "C" int gl_batch_from_values_h(gl_ctx* c, uint32_t hasher, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
+                                      uint32_t blinding, uint32_t cap_height, gl_batch** out) {
+    GL_REQUIRE(blinding == 0, GL_ERR_UNSUPPORTED, GL_BLINDED_ENTRY);
+    return batch_from_host(c, h_cols, ncols, n, rate_bits, false, nullptr, cap_height, true, out, hasher);
+}
+extern "C" int gl_batch_from_coeffs_h(gl_ctx* c, uint32_t hasher, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
+                                      uint32_t blinding, uint32_t cap_height, gl_batch** out) {
+    GL_REQUIRE(blinding == 0, GL_ERR_UNSUPPORTED, GL_BLINDED_ENTRY);
+    return batch_from_host(c, h_cols, ncols, n, rate_bits, false, nullptr, cap_height, false, out, hasher);
+}
+extern "C" int gl_batch_from_values_blinded_h(gl_ctx* c, uint32_t hasher, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
+                                              uint32_t cap_height, const uint8_t seed[32], gl_batch** out) {
+    return batch_from_host(c, h_cols, ncols, n, rate_bits, true, seed, cap_height, true, out, hasher);
+}
+extern "C" int gl_batch_from_coeffs_blinded_h(gl_ctx* c, uint32_t hasher, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
+                                              uint32_t cap_height, const uint8_t seed[32], gl_batch** out) {
+    return batch_from_host(c, h_cols, ncols, n, rate_bits, true, seed, cap_height, false, out, hasher);
+}
+extern "C" int gl_batch_from_device_h(gl_ctx* c, uint32_t hasher, const uint64_t* d_cols, size_t ncols, size_t n, uint32_t rate_bits,
+                                      uint32_t cap_height, int is_values, gl_batch** out) {
+    return gl_batch_from_device_salted(c, d_cols, ncols, n, rate_bits, cap_height, is_values, nullptr, 0, out, hasher);
+}
+extern "C" uint32_t gl_batch_hasher(const gl_batch* b) { return b ? b->hasher : 0; }
 
 extern "C" int gl_batch_cap(const gl_batch* b, uint64_t* h_out) {
     GL_REQUIRE(b && h_out, GL_ERR_ARG, "null argument");

@@ -166,6 +166,7 @@ int gl_ntt_run(gl_ctx* ctx, const gl_t* src, uint64_t src_stride, uint32_t n_in,
 // ---- Merkle (merkle.hip) ------------------------------------------------------------------------------
 struct GlMerkle {
     uint32_t lg_leaves = 0, cap_height = 0, leaf_len = 0;
+    uint32_t hasher = 0;                     // 0 Poseidon (HashOut digests), 1 Keccak (BytesHash<25> in the same four-word slots)
     gl_t* digests = nullptr;                 // levels concatenated, level l at level_off[l] (in digests)
     std::vector<uint64_t> level_off;         // in units of digests (4 x u64)
     uint64_t total_digests = 0;
@@ -174,7 +175,7 @@ struct GlMerkle {
 };
 // leaf r (natural order) has elements base[offsets[e] + r], e < leaf_len; it is leaf bitrev(r) of the tree
 int gl_merkle_build(gl_ctx* ctx, const gl_t* base, const uint64_t* host_offsets, uint32_t leaf_len,
-                    uint32_t lg_leaves, uint32_t cap_height, GlMerkle* out);
+                    uint32_t lg_leaves, uint32_t cap_height, GlMerkle* out, uint32_t hasher = 0);
 void gl_merkle_release(gl_ctx* ctx, GlMerkle* m);
 int gl_merkle_prove_impl(gl_ctx* c, const GlMerkle& m, size_t leaf_index, uint64_t* h_out, uint32_t* n_siblings);
 
@@ -183,6 +184,7 @@ struct gl_batch {
     gl_ctx* ctx = nullptr;
     size_t ncols = 0, n = 0;
     uint32_t degree_log = 0, rate_bits = 0, cap_height = 0;
+    uint32_t hasher = 0;         // C::Hasher of the Merkle tree: 0 Poseidon, 1 Keccak
     uint32_t salt = 0;           // 0, or GL_SALT_SIZE random columns behind the LDE (blinding, fri/oracle.rs:100-125)
     gl_t* coeffs = nullptr;      // [ncols][n]
     gl_t* lde = nullptr;         // [ncols + salt][N], natural order (index i <-> 7 * w_N^i); the salt columns only enter the leaves
@@ -193,7 +195,7 @@ struct gl_batch {
 // from_values / from_coeffs of a device matrix with the salt columns of PlonkOracle `oracle` drawn from `seed` (rng.cuh); a null seed
 // commits without salt, as gl_batch_from_device
 int gl_batch_from_device_salted(gl_ctx* c, const uint64_t* d_cols, size_t ncols, size_t n, uint32_t rate_bits, uint32_t cap_height,
-                                int is_values, const uint8_t* seed, uint32_t oracle, gl_batch** out);
+                                int is_values, const uint8_t* seed, uint32_t oracle, gl_batch** out, uint32_t hasher = 0);
 
 // ---- randomness (rng.hip) -------------------------------------------------------------------------------
 // 32 bytes from getrandom(2)

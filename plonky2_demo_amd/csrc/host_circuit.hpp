@@ -17,6 +17,7 @@
 #include <vector>
 #include "gl64.cuh"
 #include "poseidon.cuh"
+#include "keccak.cuh"
 #include "../../include/plonky2_mi355x.h"
 
 namespace glhost {
@@ -109,19 +110,60 @@ inline void host_hash_no_pad(const gl_t* in, size_t n, gl_t* out4) {     // hash
     for (int i = 0; i < 4; i++) out4[i] = gl_canon(s[i]);
 }
 
-// Challenger (iop/challenger.rs:30-153): the prover's transcript and the verifier's
+// ---- C::Hasher by number: 0 = PoseidonHash (HashOut), 1 = KeccakHash<25> (BytesHash<25> in the four-word slot, keccak.cuh) ----
+inline void hash_no_pad(uint32_t hasher, const gl_t* in, size_t n, gl_t* out4) {
+    if (hasher == GL_HASHER_KECCAK) kck_hash_no_pad_host(in, n, out4); else host_hash_no_pad(in, n, out4);
+}
+inline void hash_or_noop(uint32_t hasher, const gl_t* in, size_t n, gl_t* out4) {          // plonk/config.rs:55-66
+    if (hasher == GL_HASHER_KECCAK) { kck_hash_or_noop_host(in, n, out4); return; }
+    if (n <= 4) { for (size_t i = 0; i < 4; i++) out4[i] = i < n ? gl_canon(in[i]) : 0; return; }
+    host_hash_no_pad(in, n, out4);
+}
+inline void two_to_one(uint32_t hasher, const gl_t* l, const gl_t* r, gl_t* out4) {       // hashing.rs:98-115, keccak.rs:119-126
+    if (hasher == GL_HASHER_KECCAK) kck_two_to_one(l, r, out4); else psd_two_to_one(l, r, out4);
+}
+// GenericHashOut::to_vec: what a transcript or a digest absorbs of one hash -- the four elements of a HashOut, or a BytesHash<25> in
+// chunks of 7, 7, 7, 4 bytes (hash_types.rs:181-191)
+inline void hash_to_elements(uint32_t hasher, const gl_t* h, gl_t* out4) {
+    if (hasher == GL_HASHER_KECCAK) kck_hash_to_elements(h, out4); else for (int i = 0; i < 4; i++) out4[i] = h[i];
+}
+// are `count` digest slots well formed for the hasher (a BytesHash<25> has zero padding bytes)?
+inline bool hashes_well_formed(uint32_t hasher, const gl_t* h, size_t count) {
+    if (hasher == GL_HASHER_KECCAK) for (size_t i = 0; i < count; i++) if (!kck_hash_is_padded(h + 4 * i)) return false;
+    return true;
+}
+// circuit_digest = hash_no_pad(cap.flatten() || hash_pad([]).to_vec() || [degree_bits])   (circuit_builder.rs:1086-1098; hash_pad of the
+// empty domain separator, plonk/config.rs:41-51, is hash_no_pad of [1, 0 x 10, 1])
+inline void circuit_digest(uint32_t hasher, const gl_t* cap, size_t cap_len, uint32_t degree_bits, gl_t* out4) {
+    std::vector<gl_t> parts(4 * cap_len + 5);
+    for (size_t i = 0; i < cap_len; i++) hash_to_elements(hasher, cap + 4 * i, &parts[4 * i]);
+    const gl_t padded[12] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};
+    gl_t ds[4];
+    hash_no_pad(hasher, padded, 12, ds);
+    hash_to_elements(hasher, ds, &parts[4 * cap_len]);
+    parts[4 * cap_len + 4] = degree_bits;
+    hash_no_pad(hasher, parts.data(), parts.size(), out4);
+}
+
+// Challenger<F, C::Hasher> (iop/challenger.rs:30-153): the prover's transcript and the verifier's.  The permutation is Poseidon's or
+// KeccakPermutation (hash/keccak.rs:64-95: RATE 8, WIDTH 12, squeeze = the first 8).
 struct HostChallenger {
     gl_t state[12]; gl_t in[8]; int nin = 0; gl_t out[8]; int nout = 0;
-    HostChallenger() { for (auto& s : state) s = 0; }
+    uint32_t hasher = GL_HASHER_POSEIDON;
+    explicit HostChallenger(uint32_t h = GL_HASHER_POSEIDON) : hasher(h) { for (auto& s : state) s = 0; }
     void duplexing() {
         for (int i = 0; i < nin; i++) state[i] = in[i];
         nin = 0;
-        psd_permute(state);
+        if (hasher == GL_HASHER_KECCAK) kck_permute_host(state); else psd_permute(state);
         for (int i = 0; i < 8; i++) out[i] = state[i];
         nout = 8;
     }
     void observe(gl_t x) { nout = 0; in[nin++] = x; if (nin == 8) duplexing(); }
     void observe_many(const gl_t* v, size_t n) { for (size_t i = 0; i < n; i++) observe(v[i]); }
+    // observe_hash::<OH> / observe_cap::<OH> (challenger.rs:72-80) of `count` digests of hasher `oh`
+    void observe_hashes(uint32_t oh, const gl_t* h, size_t count) {
+        for (size_t i = 0; i < count; i++) { gl_t e[4]; hash_to_elements(oh, h + 4 * i, e); observe_many(e, 4); }
+    }
     gl_t challenge() { if (nin || !nout) duplexing(); return gl_canon(out[--nout]); }
     gl2_t challenge_ext() { gl2_t r; r.a = challenge(); r.b = challenge(); return r; }
 };
@@ -179,8 +221,8 @@ struct OpPos { uint32_t row, slot; };
 
 // zero_knowledge: CircuitConfig::standard_recursion_zk_config (circuit_data.rs:104-110) -- the same gate rows, then blind_and_pad's
 // blinding rows (NoopGates, singleton copy classes: generate_copy adds no copy constraint, circuit_builder.rs:418-420) and padding
-inline int build_matmul(size_t m, HostCircuit* hc, bool zero_knowledge = false) {
-    if (m < 1 || m > 256) return GL_ERR_ARG;
+inline int build_matmul(size_t m, HostCircuit* hc, bool zero_knowledge = false, uint32_t hasher = GL_HASHER_POSEIDON) {
+    if (m < 1 || m > 256 || hasher > GL_HASHER_KECCAK) return GL_ERR_ARG;
     hc->m = m;
     const size_t n_mul = m * m * m, n_add = m * m * (m - 1);
     // --- row allocation: replay the demo's op order; a row is opened when a kind has no free slot ---
@@ -222,6 +264,7 @@ inline int build_matmul(size_t m, HostCircuit* hc, bool zero_knowledge = false) 
     d.num_fri_rounds = fri_arity_bits(lg, d.rate_bits, d.cap_height, d.fri_arity_bits);
     d.zero_knowledge = zero_knowledge ? 1 : 0;
     d.num_gate_rows = zero_knowledge ? (uint32_t)rows_used : 0;
+    d.hasher = hasher;
     // gates present, sorted by (degree, id): Noop(0) < Constant(1) < PublicInput(1) < Arithmetic(3) < Poseidon(7)
     bool present[5] = {false, false, false, false, false};
     for (auto g : hc->row_gate) present[g] = true;

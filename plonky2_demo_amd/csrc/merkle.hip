@@ -8,6 +8,8 @@
 // Hashing is integer-ALU bound (one permutation ~ 1e3 modular multiplies per 64 B of input).
 #include "context.hpp"
 #include "poseidon.cuh"
+#include "keccak.cuh"
+#include "host_circuit.hpp"
 #include <cstring>
 #include <memory>
 
@@ -17,6 +19,7 @@ struct gl_merkle {
     gl_t* leaves = nullptr;      // device copy, row-major [num_leaves][leaf_len] in Merkle order
     size_t num_leaves = 0, leaf_len = 0;
 };
+#define GL_REQUIRE_HASHER(h, who) GL_REQUIRE((h) == GL_HASHER_POSEIDON || (h) == GL_HASHER_KECCAK, GL_ERR_ARG, who ": hasher is 0 (Poseidon) or 1 (Keccak)")
 
 #define GL_COOP_MAX_NODES_DEFAULT 8192u      // 8192 hashes x 16 lanes = 2048 waves = 2 per SIMD
 #define GL_COOP_MAX_NODES_THROUGHPUT 1024u   // with more than two proofs in flight
@@ -158,13 +161,122 @@ __global__ __launch_bounds__(64, 5) void k_hash_rows(const gl_t* rows, size_t co
     for (int i = 0; i < 4; i++) out[4 * r + i] = gl_canon(s[i]);
 }
 
+// ---------------------------------------------------------------------------- Keccak-256 trees (KeccakGoldilocksConfig, keccak.cuh)
+// One state per lane everywhere: a Keccak permutation is a third of a Poseidon one and absorbs twice the words, and the state's 50
+// registers leave no room for a cooperative form; launches too small to fill the chip are latency bound.
+// Absorbs the leaf whose element e is load(e) (absorbed as its canonical little-endian u64): whole 17-word blocks with compile-time
+// state indices, then the tail block with the padding; `len` > 3.
+template <class Load>
+__device__ __forceinline__ void kck_absorb_leaf(kck_state& s, uint32_t len, Load load) {
+    kck_clear(s);
+    uint32_t e0 = 0;
+    for (; len - e0 >= KCK_RATE_WORDS; e0 += KCK_RATE_WORDS) {
+#pragma unroll
+        for (int i = 0; i < KCK_RATE_WORDS; i++) kck_xor_word(s, i, gl_canon(load(e0 + i)));
+        kck_f1600(s);
+    }
+    const uint32_t rem = len - e0;                       // 0..16 words in the closing block
+#pragma unroll
+    for (int i = 0; i < KCK_RATE_WORDS - 1; i++)
+        if ((uint32_t)i < rem) kck_xor_word(s, i, gl_canon(load(e0 + i)));
+    kck_pad_words(s, rem);
+    kck_f1600(s);
+}
+// hash_or_noop (plonk/config.rs:55-66, HASH_SIZE 25): digest of natural row r -> digests[bitrev(r)], as k_merkle_leaves.
+// (No waves-per-SIMD bound: left alone the allocator takes 84 VGPRs = 5 waves per SIMD without scratch, and bounds of 3, 4 and 5 compile
+// to the same code; a bound of 6 spills 32 bytes per lane.  DESIGN.md section 13.)
+__global__ __launch_bounds__(256) void k_kck_leaves(const gl_t* __restrict__ base, const uint64_t* __restrict__ offsets, uint32_t leaf_len,
+                                                    uint32_t lg_leaves, gl_t* __restrict__ digests) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= (1u << lg_leaves)) return;
+    uint64_t out[4] = {0, 0, 0, 0};
+    if (leaf_len * 8 <= KCK_HASH_BYTES) {
+        for (uint32_t e = 0; e < leaf_len; e++) out[e] = gl_canon(base[offsets[e] + r]);
+    } else {
+        kck_state s;
+        kck_absorb_leaf(s, leaf_len, [&](uint32_t e) { return base[offsets[e] + r]; });
+        kck_digest25(s, out);
+    }
+    ulonglong2* o = reinterpret_cast<ulonglong2*>(digests + 4ull * d_bitrev(r, lg_leaves));
+    o[0] = make_ulonglong2(out[0], out[1]);
+    o[1] = make_ulonglong2(out[2], out[3]);
+}
+// parent[i] = two_to_one(child[2i], child[2i+1])   (hash/keccak.rs:119-126)
+__device__ __forceinline__ void kck_node(const gl_t* __restrict__ child, gl_t* __restrict__ parent, uint32_t i) {
+    const ulonglong2* in = reinterpret_cast<const ulonglong2*>(child + 8ull * i);
+    const ulonglong2 a = in[0], b = in[1], c = in[2], d = in[3];
+    const uint64_t l[4] = {a.x, a.y, b.x, b.y}, r[4] = {c.x, c.y, d.x, d.y};
+    uint64_t out[4];
+    kck_two_to_one(l, r, out);
+    ulonglong2* o = reinterpret_cast<ulonglong2*>(parent + 4ull * i);
+    o[0] = make_ulonglong2(out[0], out[1]);
+    o[1] = make_ulonglong2(out[2], out[3]);
+}
+__global__ __launch_bounds__(256) void k_kck_level(const gl_t* __restrict__ child, gl_t* __restrict__ parent, uint32_t count) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) kck_node(child, parent, i);
+}
+// the top of the tree in one launch, as k_merkle_top_coop: workgroup b walks cap subtree b from the level with `nodes_first` (<= GL_KCK_TOP_NODES)
+// nodes up to its root, one lane per hash, a workgroup barrier between levels
+#define GL_KCK_TOP_NODES 64u
+__global__ __launch_bounds__(64) void k_kck_top(gl_t* __restrict__ digests, const uint64_t* __restrict__ lev_off, uint32_t first_level, uint32_t num_levels,
+                                                uint32_t nodes_first) {
+    const uint32_t sub = blockIdx.x, g = threadIdx.x;
+    uint32_t nodes = nodes_first;
+    for (uint32_t lev = first_level; lev < num_levels; lev++, nodes >>= 1) {
+        if (g < nodes) kck_node(digests + 4 * lev_off[lev - 1] + 8ull * sub * nodes, digests + 4 * lev_off[lev] + 4ull * sub * nodes, g);
+        __syncthreads();
+    }
+}
+// hash_or_noop of row-major rows
+__global__ __launch_bounds__(64) void k_kck_hash_rows(const gl_t* rows, size_t count, uint32_t len, gl_t* out) {
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= count) return;
+    const gl_t* row = rows + r * len;
+    uint64_t h[4] = {0, 0, 0, 0};
+    if (len * 8 <= KCK_HASH_BYTES) {
+        for (uint32_t e = 0; e < len; e++) h[e] = gl_canon(row[e]);
+    } else {
+        kck_state s;
+        kck_absorb_leaf(s, len, [&](uint32_t e) { return row[e]; });
+        kck_digest25(s, h);
+    }
+    for (int i = 0; i < 4; i++) out[4 * r + i] = h[i];
+}
+
+// MerkleTree::new under KeccakHash<25>: leaves, levels and the fused top, all one lane per hash
+static int kck_merkle_levels(gl_ctx* c, const gl_t* base, const uint64_t* d_off, uint32_t leaf_len, uint32_t lg_leaves, uint32_t cap_height, GlMerkle* out) {
+    const uint32_t levels = lg_leaves - cap_height + 1, n = 1u << lg_leaves;
+    c->timing_begin("merkle_leaf_hash");
+    hipLaunchKernelGGL(k_kck_leaves, dim3((n + 255) / 256), dim3(256), 0, c->stream, base, d_off, leaf_len, lg_leaves, out->level_ptr(0));
+    c->timing_end();
+    GL_CHECK_HIP(hipGetLastError());
+    c->timing_begin("merkle_levels");
+    uint32_t top_first = levels;
+    for (uint32_t l = 1; l < levels; l++)
+        if (((1u << (lg_leaves - l)) >> cap_height) <= GL_KCK_TOP_NODES) { top_first = l; break; }
+    const uint64_t* d_lev_off = nullptr;
+    if (top_first < levels && levels - top_first >= 2) GL_TRY(c->get_offsets_table(out->level_off.data(), out->level_off.size(), &d_lev_off));
+    else top_first = levels;
+    for (uint32_t l = 1; l < top_first; l++) {
+        const uint32_t cnt = 1u << (lg_leaves - l);
+        hipLaunchKernelGGL(k_kck_level, dim3((cnt + 255) / 256), dim3(256), 0, c->stream, out->level_ptr(l - 1), out->level_ptr(l), cnt);
+    }
+    if (top_first < levels)
+        hipLaunchKernelGGL(k_kck_top, dim3(1u << cap_height), dim3(64), 0, c->stream, out->digests, d_lev_off, top_first, levels, (1u << (lg_leaves - top_first)) >> cap_height);
+    c->timing_end();
+    GL_CHECK_HIP(hipGetLastError());
+    return GL_OK;
+}
+
 int gl_merkle_build(gl_ctx* c, const gl_t* base, const uint64_t* host_offsets, uint32_t leaf_len, uint32_t lg_leaves,
-                    uint32_t cap_height, GlMerkle* out) {
+                    uint32_t cap_height, GlMerkle* out, uint32_t hasher) {
     GL_REQUIRE(c && base && host_offsets && out, GL_ERR_ARG, "gl_merkle_build: null argument");
+    GL_REQUIRE_HASHER(hasher, "gl_merkle_build");
     GL_REQUIRE(cap_height <= lg_leaves, GL_ERR_ARG, "cap_height should be at most log2(leaves.len())");   // merkle_tree.rs:137-143
     GL_REQUIRE(lg_leaves <= 30 && leaf_len >= 1 && leaf_len <= 4096, GL_ERR_ARG, "gl_merkle_build: unsupported shape");
     GL_TRY(c->activate());
-    out->lg_leaves = lg_leaves; out->cap_height = cap_height; out->leaf_len = leaf_len;
+    out->lg_leaves = lg_leaves; out->cap_height = cap_height; out->leaf_len = leaf_len; out->hasher = hasher;
     const uint32_t levels = lg_leaves - cap_height + 1;
     out->level_off.resize(levels);
     uint64_t off = 0;
@@ -174,6 +286,7 @@ int gl_merkle_build(gl_ctx* c, const gl_t* base, const uint64_t* host_offsets, u
     // offsets -> device: tiny table, cached per content in the context (no sync in steady state)
     const uint64_t* d_off = nullptr;
     GL_TRY(c->get_offsets_table(host_offsets, leaf_len, &d_off));
+    if (hasher == GL_HASHER_KECCAK) return kck_merkle_levels(c, base, d_off, leaf_len, lg_leaves, cap_height, out);
     const uint32_t n = 1u << lg_leaves;
     const uint32_t coop = gl_coop_max_nodes();                 // one decision per tree
     c->timing_begin("merkle_leaf_hash");
@@ -231,6 +344,35 @@ extern "C" int gl_poseidon_permute_raw(gl_ctx* c, uint64_t* d_states, size_t cou
     GL_CHECK_HIP(hipGetLastError());
     return GL_OK;
 }
+// KeccakHash<25> / PoseidonHash ::hash_or_noop (plonk/config.rs:55-66) of rows, by hasher
+extern "C" int gl_hash_rows_h(gl_ctx* c, uint32_t hasher, const uint64_t* d_rows, size_t count, size_t len, uint64_t* d_out) {
+    GL_REQUIRE_HASHER(hasher, "gl_hash_rows_h");
+    if (hasher == GL_HASHER_POSEIDON) return gl_hash_rows(c, d_rows, count, len, d_out);
+    GL_REQUIRE(c && d_rows && d_out && len >= 1 && len <= 0xFFFFFFFFu, GL_ERR_ARG, "bad argument");
+    if (!count) return GL_OK;
+    GL_TRY(c->activate());
+    hipLaunchKernelGGL(k_kck_hash_rows, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, c->stream, d_rows, count, (uint32_t)len, d_out);
+    GL_CHECK_HIP(hipGetLastError());
+    return GL_OK;
+}
+// the same two functions on the host (no GPU needed), `count` rows / pairs: hash_or_noop (plonk/config.rs:55-66) and two_to_one
+// (hash/hashing.rs:98-115, hash/keccak.rs:119-126)
+extern "C" int gl_hash_or_noop_host(uint32_t hasher, const uint64_t* h_rows, size_t count, size_t len, uint64_t* h_out) {
+    GL_REQUIRE_HASHER(hasher, "gl_hash_or_noop_host");
+    GL_REQUIRE((h_rows || !count || !len) && (h_out || !count), GL_ERR_ARG, "gl_hash_or_noop_host: null argument");
+    for (size_t r = 0; r < count; r++) glhost::hash_or_noop(hasher, h_rows + r * len, len, h_out + 4 * r);
+    return GL_OK;
+}
+extern "C" int gl_two_to_one_host(uint32_t hasher, const uint64_t* h_left, const uint64_t* h_right, size_t count, uint64_t* h_out) {
+    GL_REQUIRE_HASHER(hasher, "gl_two_to_one_host");
+    GL_REQUIRE((h_left && h_right && h_out) || !count, GL_ERR_ARG, "gl_two_to_one_host: null argument");
+    for (size_t i = 0; i < count; i++) {
+        if (hasher == GL_HASHER_KECCAK)
+            GL_REQUIRE(kck_hash_is_padded(h_left + 4 * i) && kck_hash_is_padded(h_right + 4 * i), GL_ERR_ARG, "a BytesHash<25> slot with non-zero padding bytes");
+        glhost::two_to_one(hasher, h_left + 4 * i, h_right + 4 * i, h_out + 4 * i);
+    }
+    return GL_OK;
+}
 extern "C" int gl_hash_rows(gl_ctx* c, const uint64_t* d_rows, size_t count, size_t len, uint64_t* d_out) {
     GL_REQUIRE(c && d_rows && d_out && len >= 1, GL_ERR_ARG, "bad argument");
     if (!count) return GL_OK;
@@ -250,7 +392,12 @@ __global__ void k_rows_to_natural_cols(const gl_t* rows, uint32_t lg_rows, uint3
 }
 
 extern "C" int gl_merkle_new(gl_ctx* c, const uint64_t* h_leaves, size_t num_leaves, size_t leaf_len, uint32_t cap_height, gl_merkle** out) {
+    return gl_merkle_new_h(c, GL_HASHER_POSEIDON, h_leaves, num_leaves, leaf_len, cap_height, out);
+}
+// MerkleTree::<F, C::Hasher>::new (hash/merkle_tree.rs:135-165) for either hasher
+extern "C" int gl_merkle_new_h(gl_ctx* c, uint32_t hasher, const uint64_t* h_leaves, size_t num_leaves, size_t leaf_len, uint32_t cap_height, gl_merkle** out) {
     GL_REQUIRE(c && h_leaves && out && num_leaves >= 1 && leaf_len >= 1, GL_ERR_ARG, "gl_merkle_new: bad argument");
+    GL_REQUIRE_HASHER(hasher, "gl_merkle_new_h");
     uint32_t lg = 0;
     while ((size_t(1) << lg) < num_leaves) lg++;
     GL_REQUIRE((size_t(1) << lg) == num_leaves, GL_ERR_ARG, "number of leaves must be a power of two");
@@ -268,7 +415,7 @@ extern "C" int gl_merkle_new(gl_ctx* c, const uint64_t* h_leaves, size_t num_lea
     GL_CHECK_HIP(hipGetLastError());
     std::vector<uint64_t> offs(leaf_len);
     for (size_t e = 0; e < leaf_len; e++) offs[e] = e * num_leaves;
-    GL_TRY(gl_merkle_build(c, cols.p, offs.data(), (uint32_t)leaf_len, lg, cap_height, &t->tree));
+    GL_TRY(gl_merkle_build(c, cols.p, offs.data(), (uint32_t)leaf_len, lg, cap_height, &t->tree, hasher));
     *out = t.release();
     return GL_OK;
 }

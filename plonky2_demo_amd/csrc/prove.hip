@@ -41,6 +41,20 @@ struct gl_proof {
 // C handle of the Challenger for callers of the phase API that have no transcript of their own (C / C++ / Python)
 struct gl_challenger { HostChallenger ch; };
 extern "C" gl_challenger* gl_challenger_new(void) { return new gl_challenger(); }
+// Challenger::<F, H>::new (iop/challenger.rs:31-37) for H = Poseidon (0) or Keccak (1, KeccakPermutation: hash/keccak.rs:64-95)
+extern "C" gl_challenger* gl_challenger_new_h(uint32_t hasher) {
+    if (hasher > GL_HASHER_KECCAK) { (void)gl_fail(GL_ERR_ARG, "gl_challenger_new_h: hasher is 0 (Poseidon) or 1 (Keccak)", __FILE__, __LINE__); return nullptr; }
+    gl_challenger* c = new gl_challenger();
+    c->ch.hasher = hasher;
+    return c;
+}
+// observe_hash::<OH> / observe_cap::<OH> (iop/challenger.rs:72-80; BytesHash::to_vec hash_types.rs:181-191)
+extern "C" int gl_challenger_observe_hashes(gl_challenger* c, uint32_t oh, const uint64_t* h_hashes, size_t count) {
+    GL_REQUIRE(c && (h_hashes || !count) && oh <= GL_HASHER_KECCAK, GL_ERR_ARG, "gl_challenger_observe_hashes: bad argument");
+    GL_REQUIRE(glhost::hashes_well_formed(oh, h_hashes, count), GL_ERR_ARG, "a BytesHash<25> slot with non-zero padding bytes");
+    c->ch.observe_hashes(oh, h_hashes, count);
+    return GL_OK;
+}
 extern "C" void gl_challenger_free(gl_challenger* c) { delete c; }
 extern "C" int gl_challenger_observe(gl_challenger* c, const uint64_t* h_elements, size_t count) {
     GL_REQUIRE(c && (h_elements || !count), GL_ERR_ARG, "gl_challenger_observe: null argument");
@@ -62,16 +76,22 @@ extern "C" int gl_challenger_state(const gl_challenger* c, uint64_t h_sponge_sta
 }
 
 // ---- host circuit API ------------------------------------------------------------------------------------------------
-static int matmul_circuit_build(size_t m, bool zero_knowledge, gl_host_circuit** out) {
+static int matmul_circuit_build(size_t m, bool zero_knowledge, gl_host_circuit** out, uint32_t hasher = GL_HASHER_POSEIDON) {
     GL_REQUIRE(out, GL_ERR_ARG, "null out");
+    GL_REQUIRE(hasher <= GL_HASHER_KECCAK, GL_ERR_ARG, "hasher is 0 (Poseidon) or 1 (Keccak)");
     std::unique_ptr<gl_host_circuit> h(new gl_host_circuit());
-    int st = glhost::build_matmul(m, &h->hc, zero_knowledge);
+    int st = glhost::build_matmul(m, &h->hc, zero_knowledge, hasher);
     if (st != GL_OK) return gl_fail(st, "matmul dimension out of range (1..256)", __FILE__, __LINE__);
     *out = h.release();
     return GL_OK;
 }
 extern "C" int gl_matmul_circuit_build(size_t m, gl_host_circuit** out) { return matmul_circuit_build(m, false, out); }
 extern "C" int gl_matmul_circuit_build_zk(size_t m, gl_host_circuit** out) { return matmul_circuit_build(m, true, out); }
+// the demo's circuit under `type C = KeccakGoldilocksConfig` (plonky2/src/bin/matrix_mul.rs:21-23) or the Poseidon one, zk or not
+extern "C" int gl_matmul_circuit_build_h(size_t m, uint32_t zero_knowledge, uint32_t hasher, gl_host_circuit** out) {
+    GL_REQUIRE(zero_knowledge <= 1, GL_ERR_ARG, "zero_knowledge is 0 or 1");
+    return matmul_circuit_build(m, zero_knowledge != 0, out, hasher);
+}
 extern "C" int gl_host_circuit_desc(const gl_host_circuit* hc, gl_circuit_desc* out) {
     GL_REQUIRE(hc && out, GL_ERR_ARG, "null argument");
     *out = hc->hc.desc;
@@ -117,6 +137,7 @@ static int validate_desc(const gl_circuit_desc& d) {
         GL_REQUIRE(d.gate_selector_index[g] < d.num_selectors && d.gate_group_start[g] <= g && g < d.gate_group_end[g] && d.gate_group_end[g] <= d.num_gates, GL_ERR_ARG, "bad selector group");
     }
     GL_REQUIRE(d.zero_knowledge <= 1, GL_ERR_ARG, "zero_knowledge is 0 or 1");
+    GL_REQUIRE(d.hasher <= GL_HASHER_KECCAK, GL_ERR_ARG, "hasher is 0 (Poseidon) or 1 (Keccak)");
     GL_REQUIRE(!d.zero_knowledge || !d.num_luts, GL_ERR_UNSUPPORTED, "zero knowledge together with lookups is not supported");
     if (d.num_gate_rows) {
         const glhost::BlindingCounts b = glhost::blinding_counts(d.num_gate_rows, d.zero_knowledge, d.rate_bits, d.cap_height, d.num_query_rounds);
@@ -179,7 +200,7 @@ static int circuit_finish(gl_ctx* ctx, const gl_circuit_desc* desc, const gl_t* 
     std::unique_ptr<gl_circuit, void (*)(gl_circuit*)> c(new gl_circuit(), gl_circuit_free);
     c->ctx = ctx; ctx->retain(); c->desc = *desc; c->n = size_t(1) << desc->degree_bits;
     const size_t n = c->n, ncs = desc->num_constants + 80;
-    GL_TRY(gl_batch_from_device(ctx, d_cs, ncs, n, desc->rate_bits, desc->cap_height, 1, &c->cs_batch));      // circuit_builder.rs:1020-1028
+    GL_TRY(gl_batch_from_device_h(ctx, desc->hasher, d_cs, ncs, n, desc->rate_bits, desc->cap_height, 1, &c->cs_batch));      // circuit_builder.rs:1020-1028
     GL_TRY(ctx->pool_alloc(80 * n * sizeof(gl_t), (void**)&c->d_sigmas));
     GL_CHECK_HIP(hipMemcpyAsync(c->d_sigmas, d_cs + (size_t)desc->num_constants * n, 80 * n * sizeof(gl_t), hipMemcpyDeviceToDevice, ctx->stream));
     {   // L_0 on the coset 7 H_N, N = n << rate_bits
@@ -197,14 +218,10 @@ static int circuit_finish(gl_ctx* ctx, const gl_circuit_desc* desc, const gl_t* 
         GL_CHECK_HIP(hipGetLastError());
         GL_CHECK_HIP(gl_stream_wait(ctx->stream));
     }
-    // circuit_digest = hash_no_pad(cap || hash_pad([]) || [degree_bits])   (circuit_builder.rs:1089-1100)
-    std::vector<gl_t> parts((size_t(4) << desc->cap_height));
-    GL_TRY(gl_batch_cap(c->cs_batch, parts.data()));
-    gl_t padded[12] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1}, ds[4];                   // plonk/config.rs:41-51
-    glhost::host_hash_no_pad(padded, 12, ds);
-    for (int k = 0; k < 4; k++) parts.push_back(ds[k]);
-    parts.push_back(desc->degree_bits);
-    glhost::host_hash_no_pad(parts.data(), parts.size(), c->circuit_digest);
+    // circuit_digest = hash_no_pad(cap || hash_pad([]) || [degree_bits]) under C::Hasher   (circuit_builder.rs:1086-1098)
+    std::vector<gl_t> cap((size_t(4) << desc->cap_height));
+    GL_TRY(gl_batch_cap(c->cs_batch, cap.data()));
+    glhost::circuit_digest(desc->hasher, cap.data(), size_t(1) << desc->cap_height, desc->degree_bits, c->circuit_digest);
     *out = c.release();
     return GL_OK;
 }
@@ -271,6 +288,14 @@ extern "C" const gl_batch* gl_circuit_constants_sigmas_batch(const gl_circuit* c
 static inline gl2_t h_ext(gl_t a, gl_t b) { return gl2_make(a, b); }
 static void put_u64(std::vector<uint8_t>& o, uint64_t v) { for (int i = 0; i < 8; i++) o.push_back((uint8_t)(v >> (8 * i))); }
 static void put_words(std::vector<uint8_t>& o, const gl_t* v, size_t n) { for (size_t i = 0; i < n; i++) put_u64(o, gl_canon(v[i])); }
+// write_hash (util/serialization/mod.rs:248-256): a HashOut is four field elements, a BytesHash<25> its 25 bytes
+static void put_hashes(std::vector<uint8_t>& o, uint32_t hasher, const gl_t* h, size_t count) {
+    if (hasher != GL_HASHER_KECCAK) { put_words(o, h, 4 * count); return; }
+    for (size_t i = 0; i < count; i++) {
+        for (int k = 0; k < 3; k++) put_u64(o, h[4 * i + k]);
+        o.push_back((uint8_t)h[4 * i + 3]);
+    }
+}
 static uint32_t host_bitrev32(uint32_t x, uint32_t bits) { uint32_t r = 0; for (uint32_t i = 0; i < bits; i++) r = (r << 1) | ((x >> i) & 1); return r; }
 
 struct BatchHolder { gl_batch* b = nullptr; ~BatchHolder() { if (b) gl_batch_free(b); } };
@@ -437,6 +462,7 @@ static int check_phase_api(gl_ctx* ctx, const gl_circuit* cir) {
 }
 static int check_batch(const gl_circuit* cir, const gl_batch* b, size_t ncols, const char* what) {
     GL_REQUIRE(b && b->ncols == ncols && b->n == cir->n && b->rate_bits == cir->desc.rate_bits && b->cap_height == cir->desc.cap_height, GL_ERR_ARG, what);
+    GL_REQUIRE(b->hasher == cir->desc.hasher, GL_ERR_ARG, "a batch committed under another hasher than the circuit's");
     return GL_OK;
 }
 // Z || partial products (|| lookup polynomials) -> committed batch (prover.rs:189-223), for gl_partial_products[_lookups] and prove().
@@ -448,7 +474,7 @@ static int commit_zs(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, co
     GL_TRY(partial_products_values(ctx, cir, d_wires, betas, gammas, d_zs.as<gl_t>()));
     if (deltas8) GL_TRY(lookup_polys_values(ctx, cir, d_wires, deltas8, d_zs.as<gl_t>() + 20 * n));
     if (capture) { capture->resize(nzs * n); GL_TRY(d2h(ctx, capture->data(), d_zs.p, nzs * n * sizeof(gl_t))); }
-    return gl_batch_from_device_salted(ctx, d_zs.as<uint64_t>(), nzs, n, cir->desc.rate_bits, cir->desc.cap_height, 1, seed, 2, out);
+    return gl_batch_from_device_salted(ctx, d_zs.as<uint64_t>(), nzs, n, cir->desc.rate_bits, cir->desc.cap_height, 1, seed, 2, out, cir->desc.hasher);
 }
 static int partial_products_phase(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* d_wires, const uint64_t* betas, const uint64_t* gammas, const uint64_t* deltas8, gl_batch** out) {
     GL_TRY(check_phase_api(ctx, cir));
@@ -521,7 +547,7 @@ static int commit_quotient(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* w
     // coset_ifft(7) of each quotient (prover.rs:739-743); the 8n coefficients ARE the 8 chunks of n (prover.rs:245-258)
     GL_TRY(gl_ntt_run(ctx, d_q.as<gl_t>(), N, (uint32_t)N, d_q.as<gl_t>(), N, lgN, 2, true, 0, gl_canon(gl_inv(GL_MULT_GENERATOR)), gl_host_inverse_2exp(lgN)));
     if (capture) { capture->resize(16 * n); GL_TRY(d2h(ctx, capture->data(), d_q.p, 16 * n * sizeof(gl_t))); }
-    return gl_batch_from_device_salted(ctx, d_q.as<uint64_t>(), 16, n, d.rate_bits, d.cap_height, 0, seed, 3, out);
+    return gl_batch_from_device_salted(ctx, d_q.as<uint64_t>(), 16, n, d.rate_bits, d.cap_height, 0, seed, 3, out, d.hasher);
 }
 static int quotient_phase(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* wires, const gl_batch* zs_partial_products, const uint64_t* pi_hash,
                           const uint64_t* betas, const uint64_t* gammas, const uint64_t* alphas, const uint64_t* deltas8, gl_batch** out) {
@@ -689,7 +715,7 @@ extern "C" int gl_fri_commit_round(gl_fri* f, uint64_t* h_cap_out) {
     for (uint32_t k = 0; k < arity; k++)
         for (uint32_t cpt = 0; cpt < 2; cpt++) offs[2 * k + cpt] = (uint64_t)cpt * curN + (uint64_t)host_bitrev32(k, ab) * (curN >> ab);
     std::unique_ptr<MerkleHolder> tree(new MerkleHolder(ctx));
-    GL_TRY(gl_merkle_build(ctx, f->cur_vals->as<gl_t>(), offs.data(), 2 * arity, f->cur_lgN - ab, f->desc.cap_height, &tree->m));
+    GL_TRY(gl_merkle_build(ctx, f->cur_vals->as<gl_t>(), offs.data(), 2 * arity, f->cur_lgN - ab, f->desc.cap_height, &tree->m, f->desc.hasher));
     GL_TRY(d2h(ctx, h_cap_out, tree->m.level_ptr(tree->m.num_levels() - 1), (size_t(4) << f->desc.cap_height) * sizeof(gl_t)));
     f->trees.push_back(std::move(tree));
     f->committed = true;
@@ -740,6 +766,12 @@ extern "C" int gl_fri_final_poly(gl_fri* f, uint64_t* h_out, size_t cap_words, s
 // ---- fri_proof_of_work (fri/prover.rs:115-160): smallest w such that permute(state with the pending inputs and w)[7] has
 //      enough leading zeros.  `sponge_state` is the Challenger's sponge, `input_buffer[0..input_len)` its pending inputs. ----
 extern "C" int gl_pow_grind(gl_ctx* ctx, const uint64_t sponge_state[12], const uint64_t* input_buffer, uint32_t input_len, uint32_t min_leading_zeros, uint64_t* witness) {
+    return gl_pow_grind_h(ctx, GL_HASHER_POSEIDON, sponge_state, input_buffer, input_len, min_leading_zeros, witness);
+}
+// fri_proof_of_work over Challenger<F, H>'s permutation, H = `hasher` (fri/prover.rs:115-160; KeccakPermutation hash/keccak.rs:64-95)
+extern "C" int gl_pow_grind_h(gl_ctx* ctx, uint32_t hasher, const uint64_t sponge_state[12], const uint64_t* input_buffer, uint32_t input_len, uint32_t min_leading_zeros,
+                              uint64_t* witness) {
+    GL_REQUIRE(hasher <= GL_HASHER_KECCAK, GL_ERR_ARG, "gl_pow_grind: hasher is 0 (Poseidon) or 1 (Keccak)");
     GL_REQUIRE(ctx && sponge_state && witness && (input_buffer || !input_len), GL_ERR_ARG, "gl_pow_grind: null argument");
     GL_REQUIRE(input_len < 8 && min_leading_zeros <= 40, GL_ERR_ARG, "gl_pow_grind: the witness must fit the rate (input_len < 8), at most 40 bits of work");
     GL_TRY(ctx->activate());
@@ -747,8 +779,9 @@ extern "C" int gl_pow_grind(gl_ctx* ctx, const uint64_t sponge_state[12], const 
     GL_TRY(ctx->ensure_dev_small(DS_BYTES));
     unsigned long long* d_res = (unsigned long long*)(ctx->dev_small + DS_POW);
     GlPowParams pw;
-    for (int i = 0; i < 12; i++) pw.state[i] = sponge_state[i];
-    for (uint32_t i = 0; i < input_len; i++) pw.state[i] = input_buffer[i];
+    // (KeccakPermutation hashes the canonical bytes of the state: canonical here, once)
+    for (int i = 0; i < 12; i++) pw.state[i] = hasher == GL_HASHER_KECCAK ? gl_canon(sponge_state[i]) : sponge_state[i];
+    for (uint32_t i = 0; i < input_len; i++) pw.state[i] = hasher == GL_HASHER_KECCAK ? gl_canon(input_buffer[i]) : input_buffer[i];
     pw.pos = input_len; pw.min_leading_zeros = min_leading_zeros; pw.result = d_res;
     // (measured, 16 proofs in flight: windows of 2^pow_bits, and a small grid that walks a longer window in ascending sweeps and
     // stops at the first witness -- 40 % fewer permutations -- gave the same 287 proofs/s within noise, resp. 8 % less for
@@ -768,7 +801,8 @@ extern "C" int gl_pow_grind(gl_ctx* ctx, const uint64_t sponge_state[12], const 
     for (uint64_t base = 0; base < GL_P; base += batch) {
         GL_CHECK_HIP(hipMemsetAsync(d_res, 0xFF, sizeof(unsigned long long), st));
         pw.base = base; pw.count = (GL_P - base < batch) ? GL_P - base : batch;
-        hipLaunchKernelGGL(k_pow_grind, dim3((unsigned)((pw.count + 255) / 256)), dim3(256), 0, st, pw);
+        if (hasher == GL_HASHER_KECCAK) hipLaunchKernelGGL(k_kck_pow_grind, dim3((unsigned)((pw.count + 255) / 256)), dim3(256), 0, st, pw);
+        else hipLaunchKernelGGL(k_pow_grind, dim3((unsigned)((pw.count + 255) / 256)), dim3(256), 0, st, pw);
         GL_CHECK_HIP(hipGetLastError());
         GL_TRY(d2h(ctx, &res, d_res, sizeof res));
         if (res != ~0ull) break;
@@ -848,13 +882,13 @@ static int fri_query_blob(gl_fri* f, const uint32_t* x_index, uint32_t nq, std::
             const size_t nc = f->oracles[oi]->leaf_len();
             put_words(o, host_stage.data() + row_piece[oi].off + (size_t)q * nc, nc);
             o.push_back((uint8_t)init_levels);
-            put_words(o, host_stage.data() + path_piece[oi].off + (size_t)q * init_levels * 4, (size_t)init_levels * 4);
+            put_hashes(o, d.hasher, host_stage.data() + path_piece[oi].off + (size_t)q * init_levels * 4, init_levels);
         }
         for (unsigned r = 0; r < d.num_fri_rounds; r++) {
             const uint32_t ab = d.fri_arity_bits[r], lv = f->lg[r] - ab - d.cap_height;
             put_words(o, host_stage.data() + fleaf_piece[r].off + (size_t)q * (2u << ab), 2u << ab);
             o.push_back((uint8_t)lv);
-            put_words(o, host_stage.data() + fpath_piece[r].off + (size_t)q * lv * 4, (size_t)lv * 4);
+            put_hashes(o, d.hasher, host_stage.data() + fpath_piece[r].off + (size_t)q * lv * 4, lv);
         }
     }
     return GL_OK;
@@ -902,18 +936,19 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, D
     }
 
     // ---- 4. wires commitment (prover.rs:145-156) ----
-    BatchHolder wires; GL_TRY(gl_batch_from_device_salted(ctx, d_wires, 135, n, d.rate_bits, d.cap_height, 1, salt, 1, &wires.b));
+    BatchHolder wires; GL_TRY(gl_batch_from_device_salted(ctx, d_wires, 135, n, d.rate_bits, d.cap_height, 1, salt, 1, &wires.b, d.hasher));
     // public_inputs_hash (prover.rs:126-127) on the host while the GPU commits
     gl_t pi_hash[4];
     if (h_pi_hash) for (int i = 0; i < 4; i++) pi_hash[i] = gl_canon(h_pi_hash[i]);      // the witness generator's sponge already produced it
     else glhost::host_hash_no_pad(h_pis, npis, pi_hash);
-    HostChallenger ch;
-    ch.observe_many(cir->circuit_digest, 4);
+    // Challenger<F, C::Hasher>: circuit_digest is a C::Hasher hash, public_inputs_hash a C::InnerHasher (Poseidon) one (prover.rs:158-161)
+    HostChallenger ch(d.hasher);
+    ch.observe_hashes(d.hasher, cir->circuit_digest, 1);
     ch.observe_many(pi_hash, 4);
     std::vector<gl_t> cap(ncap);
     GL_TRY(gl_batch_cap(wires.b, cap.data()));
     proof->caps.insert(proof->caps.end(), cap.begin(), cap.end());
-    ch.observe_many(cap.data(), ncap);
+    ch.observe_hashes(d.hasher, cap.data(), ncap / 4);
     gl_t betas[2], gammas[2], alphas[2];
     for (int i = 0; i < 2; i++) betas[i] = ch.challenge();
     for (int i = 0; i < 2; i++) gammas[i] = ch.challenge();
@@ -928,7 +963,7 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, D
     if (wit_owner) wit_owner->release();                                       // stream-ordered: the kernels above are already queued
     GL_TRY(gl_batch_cap(zs.b, cap.data()));
     proof->caps.insert(proof->caps.end(), cap.begin(), cap.end());
-    ch.observe_many(cap.data(), ncap);
+    ch.observe_hashes(d.hasher, cap.data(), ncap / 4);
     for (int i = 0; i < 2; i++) alphas[i] = ch.challenge();
 
     // ---- 9/10. quotient polynomials (prover.rs:229-271) ----
@@ -937,7 +972,7 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, D
                            salt));
     GL_TRY(gl_batch_cap(quot.b, cap.data()));
     proof->caps.insert(proof->caps.end(), cap.begin(), cap.end());
-    ch.observe_many(cap.data(), ncap);
+    ch.observe_hashes(d.hasher, cap.data(), ncap / 4);
 
     // ---- 11. zeta (prover.rs:273-283) ----
     const gl2_t zeta = ch.challenge_ext();
@@ -983,7 +1018,7 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, D
     for (unsigned r = 0; r < d.num_fri_rounds; r++) {
         GL_TRY(gl_fri_commit_round(fri.get(), cap.data()));
         fri_caps.insert(fri_caps.end(), cap.begin(), cap.end());
-        ch.observe_many(cap.data(), ncap);
+        ch.observe_hashes(d.hasher, cap.data(), ncap / 4);
         const gl2_t beta = ch.challenge_ext();
         const gl_t beta_w[2] = {beta.a, beta.b};
         fri_betas.insert(fri_betas.end(), beta_w, beta_w + 2);
@@ -995,7 +1030,7 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, D
     GL_TRY(gl_fri_final_poly(fri.get(), fin_il.data(), fin_il.size(), &fin_words));
     ch.observe_many(fin_il.data(), fin_il.size());
     gl_t pow_witness = 0;
-    GL_TRY(gl_pow_grind(ctx, ch.state, ch.in, (uint32_t)ch.nin, d.proof_of_work_bits, &pow_witness));
+    GL_TRY(gl_pow_grind_h(ctx, d.hasher, ch.state, ch.in, (uint32_t)ch.nin, d.proof_of_work_bits, &pow_witness));
     ch.observe(pow_witness);
     const gl_t pow_response = ch.challenge();
     GL_REQUIRE(pow_response == 0 || (uint32_t)__builtin_clzll(pow_response) >= d.proof_of_work_bits, GL_ERR_INTERNAL, "PoW response mismatch");
@@ -1009,7 +1044,7 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, D
     // ---- 15. assemble ProofWithPublicInputs bytes (util/serialization/mod.rs:1939-1981) ----
     std::vector<uint8_t>& o = proof->bytes;
     o.reserve(query_blob.size() + 8 * (npis + 2 * op.nopen + fin_words + 4 * ncap) + 4096);
-    put_words(o, proof->caps.data(), proof->caps.size());                        // wires_cap, zs_pp_cap, quotient_cap
+    put_hashes(o, d.hasher, proof->caps.data(), proof->caps.size() / 4);           // wires_cap, zs_pp_cap, quotient_cap
     // OpeningSet (:1409-1423): constants, sigmas, wires, zs, zs_next, lookup_zs, lookup_zs_next, partial products, quotient
     const gl_t* z = opened.data();
     put_words(o, z, 2 * op.ncs);
@@ -1020,7 +1055,7 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, D
     put_words(o, z + 2 * op.lookups_next(), 2 * op.nlk);
     put_words(o, z + 2 * op.partial_products(), 2 * 18);
     put_words(o, z + 2 * op.quotient(), 2 * 16);
-    put_words(o, fri_caps.data(), fri_caps.size());
+    put_hashes(o, d.hasher, fri_caps.data(), fri_caps.size() / 4);
     o.insert(o.end(), query_blob.begin(), query_blob.end());
     put_words(o, fin_il.data(), fin_il.size());
     put_u64(o, pow_witness);

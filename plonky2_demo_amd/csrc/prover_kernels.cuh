@@ -15,6 +15,7 @@
 #pragma once
 #include "gl64.cuh"
 #include "poseidon.cuh"
+#include "keccak.cuh"
 #include "../../include/plonky2_mi355x.h"
 
 #define GLP_MAX_ROUTED 80
@@ -824,6 +825,22 @@ __global__ __launch_bounds__(256, 5) void k_pow_grind(GlPowParams p) {
     const gl_t r = gl_canon(s[7]);
     const uint32_t lz = r ? (uint32_t)__clzll((long long)r) : 64u;
     if (idx < p.count && lz >= p.min_leading_zeros) atomicMin(p.result, (unsigned long long)cand);
+}
+// The same search over KeccakPermutation (hash/keccak.rs:64-95): the response is element 7 of the onion's words < p -- word 3 of the
+// second hash unless a word was rejected, which kck_onion follows.  p.state is canonical.
+__global__ __launch_bounds__(256) void k_kck_pow_grind(GlPowParams p) {
+    const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= p.count) return;
+    const uint64_t cand = p.base + idx;
+    gl_t s[12], e[8];
+#pragma unroll
+    for (int i = 0; i < 12; i++) s[i] = p.state[i];
+#pragma unroll
+    for (int i = 0; i < 8; i++) if ((uint32_t)i == p.pos) s[i] = cand;
+    kck_onion<8>(s, e);
+    const gl_t r = e[7];
+    const uint32_t lz = r ? (uint32_t)__clzll((long long)r) : 64u;
+    if (lz >= p.min_leading_zeros) atomicMin(p.result, (unsigned long long)cand);
 }
 
 // ---- gathers for the query phase -----------------------------------------------------------------------------------------

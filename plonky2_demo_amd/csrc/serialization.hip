@@ -275,11 +275,22 @@ extern "C" int gl_common_data_from_bytes(const uint8_t* h_bytes, size_t num_byte
 // VerifierOnlyCircuitData (mod.rs:1889-1906): usize cap height, the cap's 2^height digests, the circuit digest
 extern "C" int gl_verifier_only_to_bytes(uint32_t cap_height, const uint64_t* constants_sigmas_cap, const uint64_t circuit_digest[4], uint8_t* h_out, size_t cap,
                                          size_t* num_bytes) {
-    GL_REQUIRE(constants_sigmas_cap && circuit_digest && num_bytes && cap_height <= 16, GL_ERR_ARG, "gl_verifier_only_to_bytes: bad argument");
+    return gl_verifier_only_to_bytes_h(GL_HASHER_POSEIDON, cap_height, constants_sigmas_cap, circuit_digest, h_out, cap, num_bytes);
+}
+// write_verifier_only_circuit_data for C::Hasher = `hasher` (mod.rs:1889-1906; write_hash :248-256: a BytesHash<25> is its 25 bytes)
+extern "C" int gl_verifier_only_to_bytes_h(uint32_t hasher, uint32_t cap_height, const uint64_t* constants_sigmas_cap, const uint64_t circuit_digest[4], uint8_t* h_out,
+                                           size_t cap, size_t* num_bytes) {
+    GL_REQUIRE(constants_sigmas_cap && circuit_digest && num_bytes && cap_height <= 16 && hasher <= GL_HASHER_KECCAK, GL_ERR_ARG, "gl_verifier_only_to_bytes: bad argument");
+    GL_REQUIRE(glhost::hashes_well_formed(hasher, constants_sigmas_cap, size_t(1) << cap_height) && glhost::hashes_well_formed(hasher, circuit_digest, 1), GL_ERR_ARG,
+               "a BytesHash<25> slot with non-zero padding bytes");
     Writer w;
     w.u64(cap_height);
-    for (size_t i = 0; i < (size_t(4) << cap_height); i++) w.field(constants_sigmas_cap[i]);
-    for (int i = 0; i < 4; i++) w.field(circuit_digest[i]);
+    auto hash = [&](const uint64_t* h) {
+        if (hasher == GL_HASHER_KECCAK) { for (int i = 0; i < 3; i++) w.u64(h[i]); w.b.push_back((uint8_t)h[3]); }
+        else for (int i = 0; i < 4; i++) w.field(h[i]);
+    };
+    for (size_t i = 0; i < (size_t(1) << cap_height); i++) hash(constants_sigmas_cap + 4 * i);
+    hash(circuit_digest);
     *num_bytes = w.b.size();
     if (!h_out) return GL_OK;
     GL_REQUIRE(cap >= w.b.size(), GL_ERR_ARG, "gl_verifier_only_to_bytes: output too small");
@@ -288,15 +299,22 @@ extern "C" int gl_verifier_only_to_bytes(uint32_t cap_height, const uint64_t* co
 }
 extern "C" int gl_verifier_only_from_bytes(const uint8_t* h_bytes, size_t num_bytes, uint32_t* cap_height, uint64_t* h_cap, size_t cap_words, uint64_t circuit_digest[4],
                                            size_t* consumed) {
-    GL_REQUIRE(h_bytes && cap_height && circuit_digest, GL_ERR_ARG, "gl_verifier_only_from_bytes: null argument");
+    return gl_verifier_only_from_bytes_h(GL_HASHER_POSEIDON, h_bytes, num_bytes, cap_height, h_cap, cap_words, circuit_digest, consumed);
+}
+// read_verifier_only_circuit_data for C::Hasher = `hasher` (mod.rs:909-930; read_hash :1332-1338)
+extern "C" int gl_verifier_only_from_bytes_h(uint32_t hasher, const uint8_t* h_bytes, size_t num_bytes, uint32_t* cap_height, uint64_t* h_cap, size_t cap_words,
+                                             uint64_t circuit_digest[4], size_t* consumed) {
+    GL_REQUIRE(h_bytes && cap_height && circuit_digest && hasher <= GL_HASHER_KECCAK, GL_ERR_ARG, "gl_verifier_only_from_bytes: bad argument");
     Reader r(h_bytes, num_bytes);
     const uint64_t h = r.u64();
     GL_REQUIRE(r.ok && h <= 16, GL_ERR_ARG, "bad cap height");
     *cap_height = (uint32_t)h;
     const size_t words = size_t(4) << h;
     GL_REQUIRE(!h_cap || cap_words >= words, GL_ERR_ARG, "gl_verifier_only_from_bytes: cap buffer too small");
-    for (size_t i = 0; i < words; i++) { const uint64_t v = r.u64(); if (h_cap) h_cap[i] = v; }
-    for (int i = 0; i < 4; i++) circuit_digest[i] = r.u64();
+    // a 25-byte hash fills three words and the low byte of the fourth
+    auto word = [&](size_t i) -> uint64_t { return hasher == GL_HASHER_KECCAK && i % 4 == 3 ? (uint64_t)r.u8() : r.u64(); };
+    for (size_t i = 0; i < words; i++) { const uint64_t v = word(i); if (h_cap) h_cap[i] = v; }
+    for (int i = 0; i < 4; i++) circuit_digest[i] = word(i);
     GL_REQUIRE(r.ok, GL_ERR_ARG, "truncated VerifierOnlyCircuitData");
     if (consumed) *consumed = r.pos;
     return GL_OK;
@@ -305,13 +323,18 @@ extern "C" int gl_verifier_only_from_bytes(const uint8_t* h_bytes, size_t num_by
 // VerifierCircuitData::from_bytes(..).verify(proof) (circuit_data.rs:208-238; the bytes are verifier_only || common,
 // mod.rs:1908-1919)
 extern "C" int gl_verify_bytes(const uint8_t* h_verifier_data, size_t num_data_bytes, const uint8_t* proof_bytes, size_t num_proof_bytes) {
-    GL_REQUIRE(h_verifier_data && proof_bytes, GL_ERR_ARG, "gl_verify_bytes: null argument");
+    return gl_verify_bytes_h(GL_HASHER_POSEIDON, h_verifier_data, num_data_bytes, proof_bytes, num_proof_bytes);
+}
+// VerifierCircuitData::<F, C, D>::from_bytes(..).verify(proof) with C::Hasher = `hasher` (circuit_data.rs:208-238)
+extern "C" int gl_verify_bytes_h(uint32_t hasher, const uint8_t* h_verifier_data, size_t num_data_bytes, const uint8_t* proof_bytes, size_t num_proof_bytes) {
+    GL_REQUIRE(h_verifier_data && proof_bytes && hasher <= GL_HASHER_KECCAK, GL_ERR_ARG, "gl_verify_bytes: bad argument");
     uint32_t cap_height = 0; uint64_t digest[4]; size_t used = 0, used2 = 0;
     std::vector<uint64_t> cap(size_t(4) << 16);
-    GL_TRY(gl_verifier_only_from_bytes(h_verifier_data, num_data_bytes, &cap_height, cap.data(), cap.size(), digest, &used));
+    GL_TRY(gl_verifier_only_from_bytes_h(hasher, h_verifier_data, num_data_bytes, &cap_height, cap.data(), cap.size(), digest, &used));
     gl_circuit_desc d;
     GL_TRY(gl_common_data_from_bytes(h_verifier_data + used, num_data_bytes - used, &d, &used2));
     GL_REQUIRE(used + used2 == num_data_bytes, GL_ERR_ARG, "trailing bytes after VerifierCircuitData");
     GL_REQUIRE(cap_height == d.cap_height, GL_ERR_ARG, "cap height of the verifier data differs from the FRI configuration");
+    d.hasher = hasher;
     return gl_verify(&d, cap.data(), digest, proof_bytes, num_proof_bytes);
 }

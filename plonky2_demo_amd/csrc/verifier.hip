@@ -22,22 +22,19 @@ inline E e_sbox(E x) { E x2 = e_mul(x, x), x4 = e_mul(x2, x2); return e_mul(e_mu
 inline E e_pow2k(E x, unsigned k) { for (unsigned i = 0; i < k; i++) x = e_mul(x, x); return x; }
 
 // ---- Merkle path to a cap (hash/merkle_proofs.rs:54-75; leaf hash plonk/config.rs:55-66) ----
-void hash_leaf(const gl_t* v, size_t n, gl_t out[4]) {
-    if (n <= 4) { for (size_t i = 0; i < 4; i++) out[i] = i < n ? gl_canon(v[i]) : 0; return; }
-    glhost::host_hash_no_pad(v, n, out);
-}
-bool path_opens_to_cap(const gl_t* leaf, size_t leaf_len, size_t index, const gl_t* siblings, size_t nsib, const gl_t* cap, size_t cap_len) {
+// `hasher`: C::Hasher.  A HashOut's words compare as field elements; a BytesHash<25>'s as the bytes they are.
+bool path_opens_to_cap(uint32_t hasher, const gl_t* leaf, size_t leaf_len, size_t index, const gl_t* siblings, size_t nsib, const gl_t* cap, size_t cap_len) {
     gl_t cur[4];
-    hash_leaf(leaf, leaf_len, cur);
+    glhost::hash_or_noop(hasher, leaf, leaf_len, cur);
     for (size_t l = 0; l < nsib; l++) {
         const gl_t* sib = siblings + 4 * l;
         gl_t out[4];
-        if (index & 1) psd_two_to_one(sib, cur, out); else psd_two_to_one(cur, sib, out);
+        if (index & 1) glhost::two_to_one(hasher, sib, cur, out); else glhost::two_to_one(hasher, cur, sib, out);
         for (int k = 0; k < 4; k++) cur[k] = out[k];
         index >>= 1;
     }
     if (index >= cap_len) return false;
-    for (int k = 0; k < 4; k++) if (cur[k] != gl_canon(cap[4 * index + k])) return false;
+    for (int k = 0; k < 4; k++) if (cur[k] != (hasher == GL_HASHER_KECCAK ? cap[4 * index + k] : gl_canon(cap[4 * index + k]))) return false;
     return true;
 }
 
@@ -129,6 +126,7 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
     GL_REQUIRE(d.num_gates >= 1 && d.num_gates <= GL_MAX_GATES, GL_ERR_ARG, "gl_verify: bad gate count");
     { const char* why = glhost::lookup_shape_error(d); GL_REQUIRE(!why, GL_ERR_UNSUPPORTED, why); }
     GL_REQUIRE(d.zero_knowledge <= 1 && (!d.zero_knowledge || !d.num_luts), GL_ERR_UNSUPPORTED, "gl_verify: zero knowledge is 0 / 1 and not together with lookups");
+    GL_REQUIRE(d.hasher <= GL_HASHER_KECCAK, GL_ERR_ARG, "gl_verify: hasher is 0 (Poseidon) or 1 (Keccak)");
     GL_REQUIRE(d.num_selectors >= 1 && d.num_constants == d.num_selectors + d.num_lookup_selectors + 2 && d.num_fri_rounds <= 8 &&
                d.degree_bits >= 1 && d.degree_bits + d.rate_bits <= 32 && d.cap_height <= d.degree_bits + d.rate_bits && d.num_query_rounds >= 1,
                GL_ERR_ARG, "gl_verify: bad circuit description");
@@ -159,24 +157,36 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
     std::vector<gl_t> T;                               // all words of the proof in wire order, canonical
     T.reserve(num_bytes / 8 + 8);
     auto words = [&](size_t k) { size_t at = T.size(); for (size_t i = 0; i < k && in.ok; i++) T.push_back(gl_canon(in.u64())); return at; };
+    // read_hash (util/serialization/mod.rs:1332-1338): k hashes into four-word slots -- a HashOut's four elements, or the 25 bytes of a
+    // BytesHash<25> (raw words, zero padding)
+    const uint32_t hasher = d.hasher;
+    auto hashes = [&](size_t k) {
+        if (hasher != GL_HASHER_KECCAK) return words(4 * k);
+        size_t at = T.size();
+        for (size_t i = 0; i < k && in.ok; i++) { for (int w = 0; w < 3; w++) T.push_back(in.u64()); T.push_back(in.u8()); }
+        return at;
+    };
+    // the verifier data's own hashes arrive in four-word slots
+    if (!glhost::hashes_well_formed(hasher, constants_sigmas_cap, ncap) || !glhost::hashes_well_formed(hasher, circuit_digest, 1))
+        return reject("malformed verifier data: a 25-byte hash with non-zero padding bytes");
     struct PathRef { size_t leaf, leaf_len, sib, nsib; };
-    const size_t o_caps = words(3 * 4 * ncap);
+    const size_t o_caps = hashes(3 * ncap);
     // OpeningSet in wire order (mod.rs:1409-1423): the lookup vectors sit between zs_next and the partial products
     const size_t o_const = words(2 * d.num_constants), o_sig = words(2 * R), o_wires = words(2 * W), o_zs = words(2 * nch), o_zsn = words(2 * nch),
                  o_lk = words(2 * nch * NLP), o_lkn = words(2 * nch * NLP), o_pp = words(2 * nch * NPP), o_quot = words(2 * nch * QF);
-    const size_t o_fcaps = words((size_t)d.num_fri_rounds * 4 * ncap);
+    const size_t o_fcaps = hashes((size_t)d.num_fri_rounds * ncap);
     std::vector<PathRef> init_paths((size_t)d.num_query_rounds * 4), step_paths((size_t)d.num_query_rounds * d.num_fri_rounds);
     for (unsigned q = 0; q < d.num_query_rounds && in.ok; q++) {
         for (int o = 0; o < 4; o++) {
             PathRef& pr = init_paths[q * 4 + o];
             pr.leaf = words(leaf_lens[o]); pr.leaf_len = leaf_lens[o];
-            pr.nsib = in.u8(); pr.sib = words(4 * pr.nsib);
+            pr.nsib = in.u8(); pr.sib = hashes(pr.nsib);
         }
         unsigned lg_cur = lgN;
         for (unsigned r = 0; r < d.num_fri_rounds; r++) {
             PathRef& pr = step_paths[q * d.num_fri_rounds + r];
             pr.leaf_len = size_t(2) << d.fri_arity_bits[r]; pr.leaf = words(pr.leaf_len);
-            pr.nsib = in.u8(); pr.sib = words(4 * pr.nsib);
+            pr.nsib = in.u8(); pr.sib = hashes(pr.nsib);
             lg_cur -= d.fri_arity_bits[r];
             if (in.ok && pr.nsib + d.cap_height != lg_cur) return reject("malformed proof: FRI step Merkle path has the wrong length");
         }
@@ -195,17 +205,17 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
     // ---- challenges (plonk/get_challenges.rs:26-87, fri/challenges.rs:24-64) ----
     gl_t pi_hash[4];
     glhost::host_hash_no_pad(T.data() + o_pis, npis, pi_hash);
-    glhost::HostChallenger tr;
-    tr.observe_many(circuit_digest, 4); tr.observe_many(pi_hash, 4); tr.observe_many(&T[o_caps], 4 * ncap);
+    glhost::HostChallenger tr(hasher);
+    tr.observe_hashes(hasher, circuit_digest, 1); tr.observe_many(pi_hash, 4); tr.observe_hashes(hasher, &T[o_caps], ncap);
     gl_t betas[2], gammas[2], alphas[2];
     for (auto& b : betas) b = tr.challenge();
     for (auto& g : gammas) g = tr.challenge();
     // lookup coins (get_challenges.rs:51-63): [betas | gammas | 4 more], four per challenge
     gl_t deltas[8] = {betas[0], betas[1], gammas[0], gammas[1], 0, 0, 0, 0};
     if (NLP) for (int i = 4; i < 8; i++) deltas[i] = tr.challenge();
-    tr.observe_many(&T[o_caps + 4 * ncap], 4 * ncap);
+    tr.observe_hashes(hasher, &T[o_caps + 4 * ncap], ncap);
     for (auto& a : alphas) a = tr.challenge();
-    tr.observe_many(&T[o_caps + 8 * ncap], 4 * ncap);
+    tr.observe_hashes(hasher, &T[o_caps + 8 * ncap], ncap);
     const E zeta = tr.challenge_ext();
     // FriOpenings (plonk/proof.rs:346-380): constants, sigmas, wires, zs, partial products, quotient at zeta; zs_next at g zeta
     tr.observe_many(&T[o_const], 2 * d.num_constants); tr.observe_many(&T[o_sig], 2 * R); tr.observe_many(&T[o_wires], 2 * W); tr.observe_many(&T[o_zs], 2 * nch);
@@ -213,7 +223,7 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
     tr.observe_many(&T[o_zsn], 2 * nch); tr.observe_many(&T[o_lkn], 2 * nch * NLP);
     const E fri_alpha = tr.challenge_ext();
     E fri_betas[8];
-    for (unsigned r = 0; r < d.num_fri_rounds; r++) { tr.observe_many(&T[o_fcaps + (size_t)r * 4 * ncap], 4 * ncap); fri_betas[r] = tr.challenge_ext(); }
+    for (unsigned r = 0; r < d.num_fri_rounds; r++) { tr.observe_hashes(hasher, &T[o_fcaps + (size_t)r * 4 * ncap], ncap); fri_betas[r] = tr.challenge_ext(); }
     tr.observe_many(&T[o_final], 2 * final_len);
     tr.observe(pow_witness);
     const gl_t pow_response = tr.challenge();
@@ -380,7 +390,7 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
         size_t x = x_index[q];
         for (int o = 0; o < 4; o++) {
             const PathRef& pr = init_paths[q * 4 + o];
-            if (!path_opens_to_cap(&T[pr.leaf], pr.leaf_len, x, &T[pr.sib], pr.nsib, caps[o], ncap)) return reject("initial Merkle proof fails");
+            if (!path_opens_to_cap(hasher, &T[pr.leaf], pr.leaf_len, x, &T[pr.sib], pr.nsib, caps[o], ncap)) return reject("initial Merkle proof fails");
         }
         // subgroup_x = g * w_N^{reverse_bits(x_index)} (fri/verifier.rs:183-186)
         size_t rev = 0;
@@ -417,7 +427,7 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
                 acc = e_add(acc, e_mul(ext_at(pr.leaf, arev), e_scale(numer, gl_inv(denom))));
             }
             eval = acc;
-            if (!path_opens_to_cap(&T[pr.leaf], pr.leaf_len, coset, &T[pr.sib], pr.nsib, &T[o_fcaps + (size_t)r * 4 * ncap], ncap)) return reject("FRI step Merkle proof fails");
+            if (!path_opens_to_cap(hasher, &T[pr.leaf], pr.leaf_len, coset, &T[pr.sib], pr.nsib, &T[o_fcaps + (size_t)r * 4 * ncap], ncap)) return reject("FRI step Merkle proof fails");
             for (unsigned i = 0; i < ab; i++) subgroup_x = gl_sqr(subgroup_x);
             x = coset;
         }
