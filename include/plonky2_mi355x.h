@@ -76,7 +76,20 @@ typedef struct gl_proof gl_proof;      /* ProofWithPublicInputs + the prover's i
  * of BaseSumGate::new_from_config (gates/base_sum.rs:31-35; range_check / split_le), 6 LookupGate and 7 LookupTableGate
  * (the lookup argument, several tables: fields at the end of this struct; phase API: the *_lookups variants), 8 ExponentiationGate
  * with the 66 power bits of new_from_config (gates/exponentiation.rs:43-53; CircuitBuilder::exp), 9 RandomAccessGate::new_from_config
- * (gates/random_access.rs:55-72; CircuitBuilder::random_access, Merkle caps) with its index bits (1..6) in `gate_params`; `gate_types` is the list
+ * (gates/random_access.rs:55-72; CircuitBuilder::random_access, Merkle caps) with its index bits (1..6) in `gate_params`, and the four
+ * extension-field arithmetic gates (two adjacent wires = one element of F_p[X]/(X^2 - 7)), each in its new_from_config layout under
+ * standard_recursion_config only, `gate_params` 0, parity unpinned against a Rust proof like every gate above the demo's five:
+ *   10 ArithmeticExtensionGate (gates/arithmetic_extension.rs:35-51,150-164): num_ops = 80 / 8 = 10; op i owns wires 8i .. 8i+8 = m0, m1,
+ *      addend, output; 20 constraints, the components of output - (c0 m0 m1 + c1 addend); 2 constants; degree 3
+ *   11 MulExtensionGate (gates/multiplication_extension.rs:35-48,137-151): num_ops = 80 / 6 = 13; op i owns wires 6i .. 6i+6 = m0, m1,
+ *      output; 26 constraints output - c0 m0 m1; 1 constant; degree 3
+ *   12 ReducingGate (gates/reducing.rs:29-55,163-177): num_coeffs = min(80 - 6, (135 - 4) / 3) = 43; wires 0-1 output, 2-3 alpha, 4-5
+ *      old_acc, 6..48 base-field coefficients, accumulator i at 49 + 2i for i < 42, the last accumulator IS the output; 86 constraints
+ *      acc_(i-1) alpha + coeff_i - acc_i with acc_(-1) = old_acc; no constants; degree 2
+ *   13 ReducingExtensionGate (gates/reducing_extension.rs:29-58,163-177): num_coeffs = min((80 - 6) / 2, (135 - 4) / 4) = 32; coefficient
+ *      i at 6 + 2i (extension elements), accumulator i at 70 + 2i for i < 31, the last accumulator is the output; 64 constraints; degree 2
+ * (CircuitBuilder::arithmetic_extension / mul_extension, ReducingFactorTarget::reduce*).  gl_common_data_to_bytes / _from_bytes refuse
+ * (GL_ERR_UNSUPPORTED) a gate list that is not in build()'s order (degree, then id: circuit_builder.rs:987).  `gate_types` is the list
  * `common_data.gates` (sorted by degree, id) and the group arrays are `selectors_info`
  * (plonky2/src/gates/selectors.rs:17-26). */
 typedef struct gl_circuit_desc {

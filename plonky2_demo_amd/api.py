@@ -9,6 +9,10 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, hasher_id, lib
+from ._lib import (  # noqa: F401  (gl_circuit_desc.gate_types codes)
+    G_NOOP, G_CONSTANT, G_PUBLIC_INPUT, G_ARITHMETIC, G_POSEIDON, G_BASE_SUM, G_LOOKUP, G_LOOKUP_TABLE, G_EXPONENTIATION, G_RANDOM_ACCESS,
+    G_ARITHMETIC_EXT, G_MUL_EXT, G_REDUCING, G_REDUCING_EXT,
+)
 
 GOLDILOCKS_ORDER = 0xFFFFFFFF00000001   # field/src/goldilocks_field.rs:152
 COSET_SHIFT = 7                          # field/src/types.rs:437-439, goldilocks_field.rs:80
@@ -695,6 +699,21 @@ class GenericCircuitData(_CircuitApi):
         h = ctypes.c_void_p()
         check(lib.gl_circuit_create(ctx.handle, ctypes.byref(desc), _p(cs), ctypes.byref(h)))
         super().__init__(h.value, ctx)
+
+    @classmethod
+    def from_classes(cls, desc, constants, wire_classes, ctx=None):
+        """The same from the constant columns [num_constants][n] and the copy-constraint class id of every routed wire [80][n] (equal id
+        = constrained equal): the sigma polynomials are computed on the device (gl_circuit_create_from_classes)."""
+        ctx = _ctx(ctx)
+        n = 1 << desc.degree_bits
+        consts, classes = _u64(constants), _u64(wire_classes)
+        if consts.shape != (desc.num_constants, n) or classes.shape != (80, n):
+            raise ValueError("constants must be [num_constants][n] and wire_classes [80][n]")
+        h = ctypes.c_void_p()
+        check(lib.gl_circuit_create_from_classes(ctx.handle, ctypes.byref(desc), _p(consts), _p(classes), ctypes.byref(h)))
+        self = cls.__new__(cls)
+        _CircuitApi.__init__(self, h.value, ctx)
+        return self
 
 
 class CircuitView(_CircuitApi):

@@ -28,7 +28,13 @@ inline gl_t root_of_unity(unsigned lg) { gl_t r = POW2_GEN; for (unsigned i = lg
 
 // gate type codes shared with the device kernels (order = the reference's sort by (degree, id))
 enum { G_NOOP = 0, G_CONSTANT = 1, G_PUBLIC_INPUT = 2, G_ARITHMETIC = 3, G_POSEIDON = 4, G_BASE_SUM = 5, G_LOOKUP = 6, G_LOOKUP_TABLE = 7, G_EXPONENTIATION = 8,
-       G_RANDOM_ACCESS = 9, G_LAST = G_RANDOM_ACCESS };
+       G_RANDOM_ACCESS = 9, G_ARITHMETIC_EXT = 10, G_MUL_EXT = 11, G_REDUCING = 12, G_REDUCING_EXT = 13, G_LAST = G_REDUCING_EXT };
+// the new_from_config parameters of the extension-field gates under standard_recursion_config (D = 2, 80 routed wires, 135 wires):
+// ArithmeticExtensionGate num_ops = 80 / 8 (gates/arithmetic_extension.rs:35-38), MulExtensionGate num_ops = 80 / 6
+// (gates/multiplication_extension.rs:35-38), ReducingGate num_coeffs = min(80 - 6, (135 - 4) / 3) (gates/reducing.rs:29-31),
+// ReducingExtensionGate num_coeffs = min((80 - 6) / 2, (135 - 4) / 4) (gates/reducing_extension.rs:29-33)
+enum { ARITH_EXT_OPS = 10, MUL_EXT_OPS = 13, REDUCING_COEFFS = 43, REDUCING_EXT_COEFFS = 32 };
+#define GL_GATE_LIST "{Noop, Constant, PublicInput, Arithmetic, Poseidon, BaseSum<2>, Lookup, LookupTable, Exponentiation, RandomAccess, ArithmeticExtension, MulExtension, Reducing, ReducingExtension}"
 // RandomAccessGate::new_from_config(standard_recursion_config, bits) (gates/random_access.rs:55-110), bits = gate_params[g] in 1..6: copy c
 // owns wires (2 + 2^bits) c ..: access index, claimed element, the list; then the extra constants; then (unrouted) every copy's index bits
 struct RandomAccessLayout {
@@ -54,6 +60,34 @@ enum { LU_CH_A = 0, LU_CH_B = 1, LU_CH_ALPHA = 2, LU_CH_DELTA = 3 };            
 enum { LU_SEL_TRANS_SRE = 0, LU_SEL_TRANS_LDC = 1, LU_SEL_INIT_SRE = 2, LU_SEL_LAST_LDC = 3, LU_SEL_START_END = 4 };      // gates/selectors.rs:34-40
 enum { BASE_SUM_LIMBS = 63 };      // BaseSumGate::<2>::new_from_config (gates/base_sum.rs:31-35): wire 0 = sum, wires 1..=63 = limbs
 static const uint64_t UNUSED_SELECTOR = 0xFFFFFFFFull;        // gates/selectors.rs:14
+
+// common_data.gates is sorted by (degree, id) (circuit_builder.rs:987; selector_polynomials takes the LAST gate's degree for the largest,
+// gates/selectors.rs:118): degree() and the leading type name of id() (the Debug string) per gate type.  Two gates of one type (lookup gates
+// of several tables, RandomAccessGates of equal bits cannot occur) compare by fields this table does not see and pass.  nullptr = in order
+inline unsigned gate_degree(uint8_t type, uint8_t param) {
+    switch (type) {
+        case G_CONSTANT: case G_PUBLIC_INPUT: return 1;
+        case G_BASE_SUM: case G_REDUCING: case G_REDUCING_EXT: return 2;
+        case G_ARITHMETIC: case G_ARITHMETIC_EXT: case G_MUL_EXT: return 3;
+        case G_EXPONENTIATION: return 4;
+        case G_POSEIDON: return 7;
+        case G_RANDOM_ACCESS: return param + 1u;       // gates/random_access.rs:278-280
+        default: return 0;                             // Noop, Lookup, LookupTable
+    }
+}
+inline const char* gate_id_name(uint8_t type) {
+    static const char* const names[G_LAST + 1] = {"NoopGate", "ConstantGate", "PublicInputGate", "ArithmeticGate", "PoseidonGate", "BaseSumGate", "LookupGate", "LookupTableGate",
+                                                  "ExponentiationGate", "RandomAccessGate", "ArithmeticExtensionGate", "MulExtensionGate", "ReducingGate", "ReducingExtensionGate"};
+    return type <= G_LAST ? names[type] : "";
+}
+inline const char* gate_order_error(const gl_circuit_desc& d) {
+    for (unsigned g = 1; g < d.num_gates && g < GL_MAX_GATES; g++) {
+        const unsigned da = gate_degree(d.gate_types[g - 1], d.gate_params[g - 1]), db = gate_degree(d.gate_types[g], d.gate_params[g]);
+        if (da > db || (da == db && strcmp(gate_id_name(d.gate_types[g - 1]), gate_id_name(d.gate_types[g])) > 0))
+            return "the gate list is not in CircuitBuilder::build()'s order (degree, then id): not a CommonCircuitData the reference produces";
+    }
+    return nullptr;
+}
 
 // ---- lookup tables of a description: `lut` holds the tables one after the other ----
 inline uint32_t lut_offset(const gl_circuit_desc& d, unsigned t) { uint32_t o = 0; for (unsigned i = 0; i < t && i < GL_MAX_LUTS; i++) o += d.lut_len[i]; return o; }

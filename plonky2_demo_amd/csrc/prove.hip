@@ -133,7 +133,7 @@ static int validate_desc(const gl_circuit_desc& d) {
     for (unsigned r = 0; r < d.num_fri_rounds; r++) { GL_REQUIRE(d.fri_arity_bits[r] == 4, GL_ERR_UNSUPPORTED, "FRI arity must be 16"); tot += 4; }
     GL_REQUIRE(tot <= d.degree_bits && d.degree_bits + d.rate_bits >= tot + d.cap_height, GL_ERR_ARG, "FRI total reduction arity is too large");   // circuit_builder.rs:977-980
     for (unsigned g = 0; g < d.num_gates; g++) {
-        GL_REQUIRE(d.gate_types[g] <= glhost::G_LAST, GL_ERR_UNSUPPORTED, "gate type not in {Noop, Constant, PublicInput, Arithmetic, Poseidon, BaseSum<2>, Lookup, LookupTable, Exponentiation, RandomAccess}");
+        GL_REQUIRE(d.gate_types[g] <= glhost::G_LAST, GL_ERR_UNSUPPORTED, "gate type not in " GL_GATE_LIST);
         GL_REQUIRE(d.gate_selector_index[g] < d.num_selectors && d.gate_group_start[g] <= g && g < d.gate_group_end[g] && d.gate_group_end[g] <= d.num_gates, GL_ERR_ARG, "bad selector group");
     }
     GL_REQUIRE(d.zero_knowledge <= 1, GL_ERR_ARG, "zero_knowledge is 0 or 1");
@@ -541,6 +541,9 @@ static int commit_quotient(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* w
     bool has_random_access_gate = false;
     for (unsigned g = 0; g < d.num_gates; g++) has_random_access_gate |= d.gate_types[g] == glhost::G_RANDOM_ACCESS;
     if (has_random_access_gate) hipLaunchKernelGGL(k_quotient_random_access, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, q);
+    bool has_ext_arith_gate = false;
+    for (unsigned g = 0; g < d.num_gates; g++) has_ext_arith_gate |= d.gate_types[g] >= glhost::G_ARITHMETIC_EXT && d.gate_types[g] <= glhost::G_REDUCING_EXT;
+    if (has_ext_arith_gate) hipLaunchKernelGGL(k_quotient_ext_arith, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, q);
     if (d.num_lookup_polys) hipLaunchKernelGGL(k_quotient_lookup, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, q);
     ctx->timing_end();
     GL_CHECK_HIP(hipGetLastError());

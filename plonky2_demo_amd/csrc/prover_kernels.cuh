@@ -180,6 +180,9 @@ struct GlQuotParams {
 #define GLQ_MAX_TERMS 192
 // per challenge: last LDC, initial Sum, initial RE, final RE (one per table), RE transition, 6 x (Sum, LDC) transitions
 #define GLQ_LOOKUP_TERMS(num_luts) (16u + (num_luts))
+// the alpha-power table holds the terms of every supported circuit: Z and partial-product checks, the lookup terms of GL_MAX_LUTS tables,
+// then the widest gate (PoseidonGate 123; ReducingGate 86, ExponentiationGate 67, ReducingExtensionGate 64, ...)
+static_assert(2 + 2 * GLP_CHUNKS + 2 * GLQ_LOOKUP_TERMS(GL_MAX_LUTS) + 123 <= GLQ_MAX_TERMS, "alpha-power table too small");
 
 // running alpha-weighted sums for the two alphas: unreduced (GlxWideAcc2: 16 instructions per term for both), one reduction
 // when the sum is used
@@ -542,6 +545,132 @@ __global__ __launch_bounds__(256) void k_quotient_random_access(GlQuotParams p) 
             case 4: glq_random_access_gate<4>(w, gc, N, acc, p.gate_term0); break;
             case 5: glq_random_access_gate<5>(w, gc, N, acc, p.gate_term0); break;
             default: glq_random_access_gate<6>(w, gc, N, acc, p.gate_term0); break;
+        }
+        gl_t fs0, fs1, unused;
+        glx_mul3<true>(filter, acc.sum(0), filter, acc.sum(1), 0, 0, fs0, fs1, unused);
+        tot0 = glx_add_cc(tot0, fs0); tot1 = glx_add_cc(tot1, fs1);
+    }
+    const gl_t zi = p.zh_inv[i & 7];
+    gl_t o0, o1, unused;
+    glx_mul3<true>(tot0, zi, tot1, zi, 0, 0, o0, o1, unused);
+    p.out[i] = glx_add_cc(p.out[i], o0);
+    p.out[N + i] = glx_add_cc(p.out[N + i], o1);
+}
+
+// ---- the extension-field arithmetic gates: ArithmeticExtensionGate, MulExtensionGate, ReducingGate, ReducingExtensionGate ------------
+// On the base-field LDE points two adjacent wire columns are ONE element of F_p[X]/(X^2 - 7) (eval_unfiltered_base_one and the
+// get_local_ext views, plonk/vars.rs); a constraint's two components are two consecutive terms.  A launch of its own, made only for
+// circuits that hold one of the four (like the RandomAccessGate and lookup launches), adding into what k_quotient<false> wrote.
+// Every operand is canonical in and canonical out.  7 y = 8 y - y.
+__device__ __forceinline__ gl_t glq_times7(gl_t y) { return glx_sub_cc(glx_shl_c<3>(y), y); }
+// two extension products (a0, a1)(b0, b1) and (c0, c1)(d0, d1) = (x0 y0 + 7 x1 y1, x0 y1 + x1 y0) and one spare base product e f: nine
+// base products in three groups of three independent carry chains
+__device__ __forceinline__ void glq_ext_mul2(gl_t a0, gl_t a1, gl_t b0, gl_t b1, gl_t c0, gl_t c1, gl_t d0, gl_t d1, gl_t e, gl_t f,
+                                             gl_t& r0, gl_t& r1, gl_t& s0, gl_t& s1, gl_t& ef) {
+    gl_t a00, a11, a01, a10, c00, c11, c01, c10;
+    glx_mul3<true>(a0, b0, a1, b1, a0, b1, a00, a11, a01);
+    glx_mul3<true>(a1, b0, c0, d0, c1, d1, a10, c00, c11);
+    glx_mul3<true>(c0, d1, c1, d0, e, f, c01, c10, ef);
+    r0 = glx_add_cc(a00, glq_times7(a11)); r1 = glx_add_cc(a01, a10);
+    s0 = glx_add_cc(c00, glq_times7(c11)); s1 = glx_add_cc(c01, c10);
+}
+// ArithmeticExtensionGate, 10 operations (gates/arithmetic_extension.rs:87-105): op k owns wires 8k..8k+8 = m0, m1, addend, output;
+// output - (c0 m0 m1 + c1 addend), two operations at a time
+__device__ __forceinline__ void glq_arithmetic_ext_gate(const gl_t* w, const gl_t* gc, size_t N, GlAlphaAcc& acc, uint32_t T0) {
+    const gl_t c0 = gc[0], c1 = gc[N];
+#pragma unroll 1
+    for (int k = 0; k < 10; k += 2) {
+        const gl_t* wa = w + (size_t)(8 * k) * N;
+        const gl_t* wb = wa + 8 * N;
+        const gl_t ada0 = wa[4 * N], ada1 = wa[5 * N], adb0 = wb[4 * N], adb1 = wb[5 * N];
+        gl_t pa0, pa1, pb0, pb1, qa0, qa1, qb0, qb1;
+        glq_ext_mul2(wa[0], wa[N], wa[2 * N], wa[3 * N], wb[0], wb[N], wb[2 * N], wb[3 * N], ada0, c1, pa0, pa1, pb0, pb1, qa0);
+        glx_mul3<true>(pa0, c0, pa1, c0, ada1, c1, pa0, pa1, qa1);
+        glx_mul3<true>(pb0, c0, pb1, c0, adb0, c1, pb0, pb1, qb0);
+        qb1 = glx_mul<true>(adb1, c1);
+        acc.add(T0 + 2 * k, glx_sub_cc(wa[6 * N], glx_add_cc(pa0, qa0)));
+        acc.add(T0 + 2 * k + 1, glx_sub_cc(wa[7 * N], glx_add_cc(pa1, qa1)));
+        acc.add(T0 + 2 * k + 2, glx_sub_cc(wb[6 * N], glx_add_cc(pb0, qb0)));
+        acc.add(T0 + 2 * k + 3, glx_sub_cc(wb[7 * N], glx_add_cc(pb1, qb1)));
+    }
+}
+// MulExtensionGate, 13 operations (gates/multiplication_extension.rs:81-96): op k owns wires 6k..6k+6 = m0, m1, output;
+// output - c0 m0 m1 = output - (c0 m0) m1.  Two operations at a time, twelve products in four groups; the fourteenth operation does not
+// exist: its operands are those of the thirteenth and its terms are dropped.
+__device__ __forceinline__ void glq_mul_ext_gate(const gl_t* w, const gl_t* gc, size_t N, GlAlphaAcc& acc, uint32_t T0) {
+    const gl_t c0 = gc[0];
+#pragma unroll 1
+    for (int k = 0; k < 13; k += 2) {
+        const bool pair = k + 1 < 13;
+        const gl_t* wa = w + (size_t)(6 * k) * N;
+        const gl_t* wb = pair ? wa + 6 * N : wa;
+        const gl_t bA0 = wa[2 * N], bA1 = wa[3 * N], bB0 = wb[2 * N], bB1 = wb[3 * N];
+        gl_t aA0, aA1, aB0, aB1, A00, A11, A01, A10, B00, B11, B01, B10;
+        glx_mul3<true>(c0, wa[0], c0, wa[N], c0, wb[0], aA0, aA1, aB0);
+        glx_mul3<true>(c0, wb[N], aA0, bA0, aA1, bA1, aB1, A00, A11);
+        glx_mul3<true>(aA0, bA1, aA1, bA0, aB0, bB0, A01, A10, B00);
+        glx_mul3<true>(aB1, bB1, aB0, bB1, aB1, bB0, B11, B01, B10);
+        acc.add(T0 + 2 * k, glx_sub_cc(wa[4 * N], glx_add_cc(A00, glq_times7(A11))));
+        acc.add(T0 + 2 * k + 1, glx_sub_cc(wa[5 * N], glx_add_cc(A01, A10)));
+        if (pair) {
+            acc.add(T0 + 2 * k + 2, glx_sub_cc(wb[4 * N], glx_add_cc(B00, glq_times7(B11))));
+            acc.add(T0 + 2 * k + 3, glx_sub_cc(wb[5 * N], glx_add_cc(B01, B10)));
+        }
+    }
+}
+// ReducingGate, 43 base-field coefficients (gates/reducing.rs:100-120) and ReducingExtensionGate, 32 extension coefficients
+// (gates/reducing_extension.rs:102-121): wires 0-1 output, 2-3 alpha, 4-5 old_acc, then the coefficients, then the accumulators
+// (two wires each); the LAST accumulator is the output.  Step i: acc_(i-1) alpha + coeff_i - acc_i with acc_(-1) = old_acc.  The
+// accumulators are read from the wires, so the steps are independent: two at a time.  An odd count's last pair repeats its first step
+// and drops the repeated terms.
+template <bool EXT>
+__device__ __forceinline__ void glq_reducing_gate(const gl_t* w, size_t N, GlAlphaAcc& acc, uint32_t T0) {
+    constexpr int NC = EXT ? 32 : 43, COEFF0 = 6, ACC0 = COEFF0 + (EXT ? 2 : 1) * NC;
+    const gl_t al0 = w[2 * N], al1 = w[3 * N];
+    gl_t prev0 = w[4 * N], prev1 = w[5 * N];
+#pragma unroll 1
+    for (int i = 0; i < NC; i += 2) {
+        const bool pair = i + 1 < NC;
+        const int ia = i, ib = pair ? i + 1 : i;
+        const gl_t* acc_a = w + (size_t)(ia == NC - 1 ? 0 : ACC0 + 2 * ia) * N;
+        const gl_t* acc_b = w + (size_t)(ib == NC - 1 ? 0 : ACC0 + 2 * ib) * N;
+        const gl_t* co_a = w + (size_t)(COEFF0 + (EXT ? 2 : 1) * ia) * N;
+        const gl_t* co_b = w + (size_t)(COEFF0 + (EXT ? 2 : 1) * ib) * N;
+        const gl_t a0 = acc_a[0], a1 = acc_a[N], b0 = acc_b[0], b1 = acc_b[N];
+        gl_t ra0, ra1, rb0, rb1, unused;
+        glq_ext_mul2(prev0, prev1, al0, al1, a0, a1, al0, al1, 0, 0, ra0, ra1, rb0, rb1, unused);
+        ra0 = glx_add_cc(ra0, co_a[0]); rb0 = glx_add_cc(rb0, co_b[0]);
+        if constexpr (EXT) { ra1 = glx_add_cc(ra1, co_a[N]); rb1 = glx_add_cc(rb1, co_b[N]); }
+        acc.add(T0 + 2 * i, glx_sub_cc(ra0, a0));
+        acc.add(T0 + 2 * i + 1, glx_sub_cc(ra1, a1));
+        if (pair) {
+            acc.add(T0 + 2 * i + 2, glx_sub_cc(rb0, b0));
+            acc.add(T0 + 2 * i + 3, glx_sub_cc(rb1, b1));
+        }
+        prev0 = b0; prev1 = b1;
+    }
+}
+__global__ __launch_bounds__(256) void k_quotient_ext_arith(GlQuotParams p) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t N = size_t(1) << p.lgN;
+    if (i >= N) return;
+    const gl_t* w = p.wires + i;
+    const gl_t* cs = p.cs + i;
+    const gl_t* gc = cs + (size_t)(p.num_selectors + p.num_lookup_selectors) * N;
+    gl_t tot0 = 0, tot1 = 0;
+#pragma unroll 1
+    for (uint32_t g = 0; g < p.num_gates; g++) {
+        if (p.gate_types[g] < 10 || p.gate_types[g] > 13) continue;
+        const gl_t sel = cs[(size_t)p.gate_sel[g] * N];
+        gl_t filter = 1;                                            // gate.rs:277-284
+        for (uint32_t k = p.group_start[g]; k < p.group_end[g]; k++) if (k != g) filter = glx_mul<true>(filter, glx_sub_cc((gl_t)k, sel));
+        if (p.num_selectors > 1) filter = glx_mul<true>(filter, glx_sub_cc((gl_t)0xFFFFFFFFull, sel));
+        GlAlphaAcc acc; acc.start(p.alpha_pows);
+        switch (p.gate_types[g]) {
+            case 10: glq_arithmetic_ext_gate(w, gc, N, acc, p.gate_term0); break;
+            case 11: glq_mul_ext_gate(w, gc, N, acc, p.gate_term0); break;
+            case 12: glq_reducing_gate<false>(w, N, acc, p.gate_term0); break;
+            default: glq_reducing_gate<true>(w, N, acc, p.gate_term0); break;
         }
         gl_t fs0, fs1, unused;
         glx_mul3<true>(filter, acc.sum(0), filter, acc.sum(1), 0, 0, fs0, fs1, unused);

@@ -8,8 +8,9 @@
 // unpinned"); what is checked is a round trip, a second independent writer in the test oracle, and that
 // gl_verify_bytes accepts proofs through data that went through the byte form.
 //
-// Only circuits this library can prove / verify are representable: the five gates of the demo + BaseSumGate<2>, standard_recursion_config's
-// shape (no lookups, no zero-knowledge); anything else is GL_ERR_UNSUPPORTED when reading.
+// Only circuits this library can prove / verify are representable: the gates of host_circuit.hpp's list (Noop, Constant, PublicInput,
+// Arithmetic, Poseidon, BaseSum<2>, Lookup, LookupTable, Exponentiation, RandomAccess, ArithmeticExtension, MulExtension, Reducing,
+// ReducingExtension) in their new_from_config layouts, standard_recursion_config's shape; anything else is GL_ERR_UNSUPPORTED when reading.
 #include "context.hpp"
 #include "host_circuit.hpp"
 #include <algorithm>
@@ -18,7 +19,7 @@
 
 namespace {
 // position of each gate type in DefaultGateSerializer's list (gate_serialization.rs:89-107)
-const uint32_t TAG_ARITHMETIC = 0, TAG_BASE_SUM_2 = 2, TAG_CONSTANT = 3, TAG_EXPONENTIATION = 5, TAG_LOOKUP = 6, TAG_LOOKUP_TABLE = 7, TAG_NOOP = 9, TAG_POSEIDON = 11, TAG_PUBLIC_INPUT = 12, TAG_RANDOM_ACCESS = 13;
+const uint32_t TAG_ARITHMETIC = 0, TAG_ARITHMETIC_EXT = 1, TAG_MUL_EXT = 8, TAG_REDUCING_EXT = 14, TAG_REDUCING = 15, TAG_BASE_SUM_2 = 2, TAG_CONSTANT = 3, TAG_EXPONENTIATION = 5, TAG_LOOKUP = 6, TAG_LOOKUP_TABLE = 7, TAG_NOOP = 9, TAG_POSEIDON = 11, TAG_PUBLIC_INPUT = 12, TAG_RANDOM_ACCESS = 13;
 const uint64_t LOOKUP_SLOTS = 40, LOOKUP_TABLE_SLOTS = 26;     // gates/lookup.rs:41-44, gates/lookup_table.rs:47-50
 const uint64_t BASE_SUM_LIMBS = 63;     // BaseSumGate::<2>::new_from_config under standard_recursion_config (gates/base_sum.rs:31-35)
 // standard_recursion_config (plonk/circuit_data.rs:72-90)
@@ -51,11 +52,15 @@ struct Reader {
 };
 
 uint32_t gate_tag(uint8_t type) {
-    switch (type) { case 0: return TAG_NOOP; case 1: return TAG_CONSTANT; case 2: return TAG_PUBLIC_INPUT; case 3: return TAG_ARITHMETIC; case 5: return TAG_BASE_SUM_2; case 6: return TAG_LOOKUP; case 7: return TAG_LOOKUP_TABLE; case 8: return TAG_EXPONENTIATION; case 9: return TAG_RANDOM_ACCESS; default: return TAG_POSEIDON; }
+    switch (type) { case 0: return TAG_NOOP; case 1: return TAG_CONSTANT; case 2: return TAG_PUBLIC_INPUT; case 3: return TAG_ARITHMETIC; case 5: return TAG_BASE_SUM_2; case 6: return TAG_LOOKUP; case 7: return TAG_LOOKUP_TABLE; case 8: return TAG_EXPONENTIATION; case 9: return TAG_RANDOM_ACCESS;
+                    case 10: return TAG_ARITHMETIC_EXT; case 11: return TAG_MUL_EXT; case 12: return TAG_REDUCING; case 13: return TAG_REDUCING_EXT; default: return TAG_POSEIDON; }
 }
 uint64_t gate_constraints(uint8_t type, uint8_t param, const gl_circuit_desc& d) {
     if (type == 9) return glhost::RandomAccessLayout(param).num_constraints();
-    switch (type) { case 0: case 6: case 7: return 0; case 1: return d.num_constants - d.num_selectors - d.num_lookup_selectors; case 2: return 4; case 3: return d.num_routed_wires / 4; case 5: return 1 + BASE_SUM_LIMBS /* gates/base_sum.rs:144-146 */; case 8: return glhost::EXP_POWER_BITS + 1 /* gates/exponentiation.rs:190-192 */; default: return 123; }   // gates/poseidon.rs:403-409
+    switch (type) { case 0: case 6: case 7: return 0; case 1: return d.num_constants - d.num_selectors - d.num_lookup_selectors; case 2: return 4; case 3: return d.num_routed_wires / 4; case 5: return 1 + BASE_SUM_LIMBS /* gates/base_sum.rs:144-146 */; case 8: return glhost::EXP_POWER_BITS + 1 /* gates/exponentiation.rs:190-192 */;
+                    case 10: return 2 * glhost::ARITH_EXT_OPS /* gates/arithmetic_extension.rs:162-164 */; case 11: return 2 * glhost::MUL_EXT_OPS /* gates/multiplication_extension.rs:149-151 */;
+                    case 12: return 2 * glhost::REDUCING_COEFFS /* gates/reducing.rs:175-177 */; case 13: return 2 * glhost::REDUCING_EXT_COEFFS /* gates/reducing_extension.rs:175-177 */;
+                    default: return 123; }   // gates/poseidon.rs:403-409
 }
 void write_fri_config(Writer& w, const gl_circuit_desc& d) {          // mod.rs:1628-1644
     w.u64(d.rate_bits); w.u64(d.cap_height); w.u64(d.num_query_rounds); w.u32(d.proof_of_work_bits);
@@ -83,7 +88,8 @@ extern "C" int gl_common_data_to_bytes(const gl_circuit_desc* desc, uint8_t* h_o
     // everything the writer indexes or divides by (k_is holds 80 entries)
     GL_REQUIRE(d.num_routed_wires >= 4 && d.num_routed_wires <= 80 && d.quotient_degree_factor >= 1 && d.num_constants >= d.num_selectors, GL_ERR_ARG,
                "bad circuit description: routed wires 4..80, quotient degree factor >= 1, constants >= selectors");
-    for (uint32_t g = 0; g < d.num_gates; g++) GL_REQUIRE(d.gate_types[g] <= glhost::G_LAST, GL_ERR_UNSUPPORTED, "gate type not in {Noop, Constant, PublicInput, Arithmetic, Poseidon, BaseSum<2>, Lookup, LookupTable, Exponentiation, RandomAccess}");
+    for (uint32_t g = 0; g < d.num_gates; g++) GL_REQUIRE(d.gate_types[g] <= glhost::G_LAST, GL_ERR_UNSUPPORTED, "gate type not in " GL_GATE_LIST);
+    { const char* why = glhost::gate_order_error(d); GL_REQUIRE(!why, GL_ERR_UNSUPPORTED, why); }
     { const char* why = glhost::lookup_shape_error(d); GL_REQUIRE(!why, GL_ERR_ARG, why); }
     GL_REQUIRE(d.num_constants >= d.num_selectors + d.num_lookup_selectors, GL_ERR_ARG, "bad lookup description");
     Writer w;
@@ -107,6 +113,10 @@ extern "C" int gl_common_data_to_bytes(const gl_circuit_desc* desc, uint8_t* h_o
         if (d.gate_types[g] == 5) w.u64(BASE_SUM_LIMBS);                           // BaseSumGate<2> { num_limbs } (gates/base_sum.rs:53-55)
         if (d.gate_types[g] == 9) { const glhost::RandomAccessLayout ra(d.gate_params[g]); w.u64(ra.bits); w.u64(ra.num_copies); w.u64(ra.num_extra_constants); }      // random_access.rs:123-128
         if (d.gate_types[g] == 8) w.u64(glhost::EXP_POWER_BITS);                   // ExponentiationGate { num_power_bits } (gates/exponentiation.rs:79-81)
+        if (d.gate_types[g] == 10) w.u64(glhost::ARITH_EXT_OPS);                   // ArithmeticExtensionGate { num_ops } (gates/arithmetic_extension.rs:59-61)
+        if (d.gate_types[g] == 11) w.u64(glhost::MUL_EXT_OPS);                     // MulExtensionGate { num_ops } (gates/multiplication_extension.rs:56-58)
+        if (d.gate_types[g] == 12) w.u64(glhost::REDUCING_COEFFS);                 // ReducingGate { num_coeffs } (gates/reducing.rs:63-66)
+        if (d.gate_types[g] == 13) w.u64(glhost::REDUCING_EXT_COEFFS);             // ReducingExtensionGate { num_coeffs } (gates/reducing_extension.rs:66-69)
         const uint64_t c = gate_constraints(d.gate_types[g], d.gate_params[g], d);
         if (c > max_constraints) max_constraints = c;
     }
@@ -193,6 +203,14 @@ extern "C" int gl_common_data_from_bytes(const uint8_t* h_bytes, size_t num_byte
             const uint64_t bits = r.u64();
             GL_REQUIRE(!r.ok || bits == glhost::EXP_POWER_BITS, GL_ERR_UNSUPPORTED, "ExponentiationGate with a bit count other than new_from_config's 66");
         }
+        else if (tag == TAG_ARITHMETIC_EXT || tag == TAG_MUL_EXT || tag == TAG_REDUCING || tag == TAG_REDUCING_EXT) {
+            // one usize each: num_ops / num_coeffs; only new_from_config's value under standard_recursion_config has a kernel
+            d.gate_types[g] = tag == TAG_ARITHMETIC_EXT ? 10 : tag == TAG_MUL_EXT ? 11 : tag == TAG_REDUCING ? 12 : 13;
+            const uint64_t want = tag == TAG_ARITHMETIC_EXT ? glhost::ARITH_EXT_OPS : tag == TAG_MUL_EXT ? glhost::MUL_EXT_OPS : tag == TAG_REDUCING ? glhost::REDUCING_COEFFS : glhost::REDUCING_EXT_COEFFS;
+            const uint64_t count = r.u64();
+            GL_REQUIRE(!r.ok || count == want, GL_ERR_UNSUPPORTED,
+                       "ArithmeticExtensionGate / MulExtensionGate / ReducingGate / ReducingExtensionGate with a count other than new_from_config's 10 / 13 / 43 / 32");
+        }
         else if (tag == TAG_LOOKUP || tag == TAG_LOOKUP_TABLE) {
             d.gate_types[g] = tag == TAG_LOOKUP ? 6 : 7;
             const uint64_t slots = r.u64(), len = r.u64();
@@ -201,8 +219,9 @@ extern "C" int gl_common_data_from_bytes(const uint8_t* h_bytes, size_t num_byte
             for (uint64_t k = 0; k < 2 * len && r.ok; k++) gate_table[g].push_back(r.u16());
             if (tag == TAG_LOOKUP_TABLE) gate_last_lut_row[g] = r.usize32();
         }
-        else return gl_fail(GL_ERR_UNSUPPORTED, "gate outside {Noop, Constant, PublicInput, Arithmetic, Poseidon, BaseSum<2>, Lookup, LookupTable, Exponentiation, RandomAccess}", __FILE__, __LINE__);
+        else return gl_fail(GL_ERR_UNSUPPORTED, "gate outside " GL_GATE_LIST, __FILE__, __LINE__);
     }
+    if (r.ok) { const char* why = glhost::gate_order_error(d); GL_REQUIRE(!why, GL_ERR_UNSUPPORTED, why); }
     const uint64_t nsel = r.u64();
     GL_REQUIRE(r.ok && nsel == ngates, GL_ERR_ARG, "selector_indices length differs from the number of gates");
     for (uint64_t g = 0; g < ngates; g++) d.gate_selector_index[g] = r.usize32();

@@ -100,6 +100,12 @@ void poseidon_gate_constraints(const E* w, E* out) {
     for (int i = 0; i < 12; i++) out[c++] = e_sub(s[i], w[PW_OUTPUT + i]);
 }
 
+// ExtensionAlgebra<F_p^2, 2> (field/src/extension/algebra.rs:11-26,113-131): a + b X with X^2 = W = 7, the components themselves in F_p^2
+struct Alg { E a, b; };
+inline Alg alg_mul(const Alg& x, const Alg& y) {
+    return Alg{e_add(e_mul(x.a, y.a), e_scale(e_mul(x.b, y.b), glhost::MULT_GEN /* W = 7 */)), e_add(e_mul(x.a, y.b), e_mul(x.b, y.a))};
+}
+
 struct Cursor {                                        // little-endian reader over the proof bytes
     const uint8_t* p; size_t len, pos = 0; bool ok = true;
     Cursor(const uint8_t* b, size_t n) : p(b), len(n) {}
@@ -292,6 +298,45 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
                         tmp[i] = e_sub(e_mul(prev, e_add(e_mul(bit, wires[0]), e_sub(e_of(1), bit))), wires[2 + n + i]);
                     }
                     tmp[n] = e_sub(wires[1 + n], wires[2 + n + n - 1]);
+                    break;
+                }
+                // The extension-field gates: at zeta every wire is itself in F_p^2, so a wire pair is an element (A0, A1) of the ExtensionAlgebra
+                // F_p^2[X]/(X^2 - 7) (field/src/extension/algebra.rs:113-131: W = 7 embedded), and a constraint's two components enter the sum
+                // in order (to_basefield_array).
+                case glhost::G_ARITHMETIC_EXT: {                                                                                                        // arithmetic_extension.rs:68-90
+                    for (int i = 0; i < glhost::ARITH_EXT_OPS; i++) {
+                        const E* w = wires.data() + 8 * i;                                                                                               // m0, m1, addend, output
+                        const Alg prod = alg_mul(Alg{w[0], w[1]}, Alg{w[2], w[3]});
+                        tmp[cnt++] = e_sub(w[6], e_add(e_mul(prod.a, gate_consts[0]), e_mul(w[4], gate_consts[1])));
+                        tmp[cnt++] = e_sub(w[7], e_add(e_mul(prod.b, gate_consts[0]), e_mul(w[5], gate_consts[1])));
+                    }
+                    break;
+                }
+                case glhost::G_MUL_EXT: {                                                                                                               // multiplication_extension.rs:65-84
+                    for (int i = 0; i < glhost::MUL_EXT_OPS; i++) {
+                        const E* w = wires.data() + 6 * i;                                                                                               // m0, m1, output
+                        const Alg prod = alg_mul(Alg{w[0], w[1]}, Alg{w[2], w[3]});
+                        tmp[cnt++] = e_sub(w[4], e_mul(prod.a, gate_consts[0]));
+                        tmp[cnt++] = e_sub(w[5], e_mul(prod.b, gate_consts[0]));
+                    }
+                    break;
+                }
+                case glhost::G_REDUCING: case glhost::G_REDUCING_EXT: {                                                          // reducing.rs:77-103, reducing_extension.rs:80-104
+                    // wires 0-1 output, 2-3 alpha, 4-5 old_acc, the coefficients (one wire each / two wires each), the accumulators; the last
+                    // accumulator is the output
+                    const bool ext = d.gate_types[g] == glhost::G_REDUCING_EXT;
+                    const int nc = ext ? glhost::REDUCING_EXT_COEFFS : glhost::REDUCING_COEFFS, acc0 = 6 + (ext ? 2 : 1) * nc;
+                    const Alg alpha{wires[2], wires[3]};
+                    Alg acc{wires[4], wires[5]};
+                    for (int i = 0; i < nc; i++) {
+                        const int aw = i == nc - 1 ? 0 : acc0 + 2 * i;
+                        const Alg acc_i{wires[aw], wires[aw + 1]};
+                        const Alg coeff = ext ? Alg{wires[6 + 2 * i], wires[7 + 2 * i]} : Alg{wires[6 + i], e_of(0)};
+                        const Alg t = alg_mul(acc, alpha);
+                        tmp[cnt++] = e_sub(e_add(t.a, coeff.a), acc_i.a);
+                        tmp[cnt++] = e_sub(e_add(t.b, coeff.b), acc_i.b);
+                        acc = acc_i;
+                    }
                     break;
                 }
                 default: cnt = 123; poseidon_gate_constraints(wires.data(), tmp); break;

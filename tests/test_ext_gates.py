@@ -1,0 +1,263 @@
+"""ArithmeticExtensionGate, MulExtensionGate, ReducingGate and ReducingExtensionGate (gate types 10..13): circuits built and witnessed by
+the independent model of ext_gate_circuits.py, proved on the GPU, verified by gl_verify.  The CPU oracle has none of these gates, so
+nothing here is byte parity with a Rust proof ("parity unpinned"): acceptance of the model's witnesses shows that the enforced
+constraints vanish on the true relation, the per-constraint tampering that none is missing."""
+import os
+import threading
+
+import numpy as np
+import pytest
+
+import ext_gate_circuits as egc
+from ext_gate_circuits import ARITHMETIC_EXT, MUL_EXT, REDUCING, REDUCING_EXT, P
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+NEW_GATES = [ARITHMETIC_EXT, MUL_EXT, REDUCING, REDUCING_EXT]
+NAMES = {ARITHMETIC_EXT: "arithmetic_ext", MUL_EXT: "mul_ext", REDUCING: "reducing", REDUCING_EXT: "reducing_ext"}
+FIXTURE_SEED = 77
+
+
+def _fixture_circuit():
+    """the n = 8 circuit of the stored proof: one row of each of the four gates, isolated family"""
+    return egc.isolated(NEW_GATES, FIXTURE_SEED, rows_per_gate=1)
+
+
+def _build(p, c, ctx=None):
+    return p.GenericCircuitData.from_classes(c.desc, c.constants, c.classes, ctx=ctx)
+
+
+_NO_PIS = np.zeros(0, dtype=np.uint64)
+
+
+# ------------------------------------------------------------------------------- GPU
+@pytest.mark.gpu
+@pytest.mark.parametrize("gate", NEW_GATES, ids=[NAMES[g] for g in NEW_GATES])
+def test_each_gate_alone_proves_and_verifies(gpu, gate):
+    p, ctx = gpu
+    c = egc.isolated([gate], seed=10 + gate)
+    assert c.n == 8 and [r[0] for r in c.rows[:2]] == [gate, gate]
+    flat = [v for r in c.rows[:2] for v in r[2]] + [v for r in c.rows[:2] for v in r[1]]
+    assert {0, 1, P - 1} <= set(flat)
+    cd = _build(p, c, ctx)
+    proof = cd.prove(c.wires(), _NO_PIS).to_bytes()
+    assert cd.verify(proof) == (True, "")
+    vd = p.api.verifier_data_to_bytes(cd.desc, cd.constants_sigmas_cap, cd.circuit_digest)
+    assert p.api.verify_bytes(vd, proof) == (True, "")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("gate", NEW_GATES, ids=[NAMES[g] for g in NEW_GATES])
+def test_every_constraint_rejects_a_witness_that_breaks_it(gpu, gate):
+    # the gate rows' wires are in no copy constraint, so only the gate constraint can reject; constraint j is broken on gate row j mod 2
+    p, ctx = gpu
+    c = egc.isolated([gate], seed=20 + gate)
+    cd = _build(p, c, ctx)
+    good = c.wires()
+    assert cd.verify(cd.prove(good, _NO_PIS)) == (True, "")
+    accepted = []
+    for j in range(egc.NUM_CONSTRAINTS[gate]):
+        cell, row = egc.constraint_cell(gate, j), j % 2
+        bad = good.copy()
+        bad[cell, row] = (int(bad[cell, row]) + 1) % P
+        ok, _ = cd.verify(cd.prove(bad, _NO_PIS))
+        if ok:
+            accepted.append(j)
+    assert accepted == []
+
+
+def _check_chained(p, ch, ctx):
+    c = ch.circuit
+    for name, got, want in ch.results:
+        assert got == want, name
+    d = c.desc
+    assert d.num_gates == 8 and d.num_selectors == 2 and sorted(d.gate_types[:8]) == [0, 1, 2, 3, 10, 11, 12, 13]
+    assert (c.constants[:2] == egc.UNUSED_SELECTOR).any()
+    cd = _build(p, c, ctx)
+    proof = cd.prove(c.wires(), _NO_PIS).to_bytes()
+    assert cd.verify(proof) == (True, "")
+    return cd, proof
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("degree_bits,hasher", [(4, 0), (6, 0), (4, 1)], ids=["n16", "n64_one_fri_round", "n16_keccak"])
+def test_all_four_gates_chained_in_one_circuit(gpu, degree_bits, hasher):
+    p, ctx = gpu
+    ch = egc.Chained(seed=3, min_degree_bits=degree_bits, hasher=hasher)
+    assert ch.circuit.n == 1 << degree_bits and ch.circuit.desc.num_fri_rounds == (1 if degree_bits == 6 else 0)
+    assert egc.Chained(seed=3, min_degree_bits=5).circuit.desc.num_fri_rounds == 0       # 64 is the smallest n with a FRI reduction
+    cd, proof = _check_chained(p, ch, ctx)
+    bad = ch.circuit.wires()
+    r, col = next((r, 4) for r, row in enumerate(ch.circuit.rows) if row[0] == MUL_EXT)
+    bad[col, r] = (int(bad[col, r]) + 1) % P                           # the first MulExtensionGate output, which later rows copy
+    assert not cd.verify(cd.prove(bad, _NO_PIS))[0]
+
+
+@pytest.mark.gpu
+def test_phase_api_with_external_transcript_on_the_chained_circuit(gpu, orc):
+    # the pattern of test_phase_api_with_external_transcript_reproduces_the_proof: gl_quotient_polys reaches the same launch as gl_prove
+    from test_gpu_parity import _Challenger
+    p, ctx = gpu
+    c = egc.Chained(seed=4).circuit
+    cd = _build(p, c, ctx)
+    wires, d, n = c.wires(), c.desc, c.n
+    N = n << 3
+    d_w = ctx.alloc(wires.nbytes).upload(wires)
+    ch = _Challenger(orc)
+    pi_hash = [0, 0, 0, 0]                                              # hash_no_pad of no public inputs
+    ch.observe(cd.circuit_digest); ch.observe(pi_hash)
+    wires_b = p.PolynomialBatch.from_device(d_w.ptr, 135, n, d.rate_bits, d.cap_height, True)
+    ch.observe(wires_b.cap)
+    betas, gammas = ch.get(2), ch.get(2)
+    zs_b = cd.partial_products(d_w.ptr, betas, gammas)
+    ch.observe(zs_b.cap)
+    alphas = ch.get(2)
+    q_b = cd.quotient_polys(wires_b, zs_b, pi_hash, betas, gammas, alphas)
+    ch.observe(q_b.cap)
+    zeta = ch.get(2)
+    g = orc.primitive_root(d.degree_bits)
+    gzeta = [zeta[0] * g % P, zeta[1] * g % P]
+    cs_b = cd.constants_sigmas_batch
+    o_cs, o_w, o_z, o_q = cs_b.open_at(zeta), wires_b.open_at(zeta), zs_b.open_at(zeta), q_b.open_at(zeta)
+    o_next = zs_b.open_at(gzeta, 0, 2)
+    for o in (o_cs, o_w, o_z, o_q, o_next):
+        ch.observe(o)
+    fri = cd.fri([cs_b, wires_b, zs_b, q_b], zeta, ch.get(2))
+    fri_caps = []
+    for _ in range(d.num_fri_rounds):
+        cap = fri.commit_round()
+        fri_caps.append(cap)
+        ch.observe(cap)
+        fri.fold(ch.get(2))
+    fin = fri.final_poly()
+    ch.observe(fin)
+    w = p.pow_grind(ch.state, ch.inp, d.proof_of_work_bits)
+    ch.observe([w])
+    assert ch.get(1)[0] >> (64 - d.proof_of_work_bits) == 0
+    blob = fri.query([ch.get(1)[0] % N for _ in range(d.num_query_rounds)])
+
+    le = lambda arr: np.ascontiguousarray(np.asarray(arr, dtype="<u8")).tobytes()
+    by = le(wires_b.cap) + le(zs_b.cap) + le(q_b.cap)
+    by += le(o_cs) + le(o_w) + le(o_z[:2]) + le(o_next) + le(o_z[2:]) + le(o_q)       # util/serialization/mod.rs:1409-1423
+    by += b"".join(le(x) for x in fri_caps) + blob + le(fin) + le([w]) + le([0])
+    assert by == cd.prove(wires, _NO_PIS).to_bytes()
+    assert cd.verify(by) == (True, "")
+
+
+@pytest.mark.gpu
+def test_concurrent_proofs_of_the_chained_circuit_on_four_contexts(gpu):
+    p, ctx = gpu
+    c = egc.Chained(seed=5).circuit
+    cd = _build(p, c, ctx)
+    wires = c.wires()
+    want = cd.prove(wires, _NO_PIS).to_bytes()
+    assert cd.verify(want) == (True, "")
+    lanes = [p.api.CircuitView(cd, p.Context(device=0)) for _ in range(4)]
+    results, errors = {}, []
+
+    def work(lane):
+        try:
+            results[lane] = lanes[lane].prove(wires, _NO_PIS).to_bytes()
+        except Exception as e:          # surfaced below: an assertion inside a thread would be lost
+            errors.append(e)
+
+    ths = [threading.Thread(target=work, args=(i,)) for i in range(4)]
+    [t.start() for t in ths]
+    [t.join() for t in ths]
+    assert not errors, errors
+    assert [results[i] == want for i in range(4)] == [True] * 4
+
+
+# ------------------------------------------------------------------------------- CPU
+def _descs():
+    out = [(NAMES[g], egc.isolated([g], seed=30 + g).desc, [g]) for g in NEW_GATES]
+    out.append(("all_four", _fixture_circuit().desc, NEW_GATES))
+    out.append(("chained_two_selector_groups", egc.Chained(seed=6).circuit.desc, NEW_GATES))
+    return out
+
+
+@pytest.mark.parametrize("name,desc,gates", _descs(), ids=[x[0] for x in _descs()])
+def test_common_data_bytes_round_trip_and_gate_entries(name, desc, gates):
+    import plonky2_demo_amd as p
+    from plonky2_demo_amd import api
+    by = api.common_data_to_bytes(desc)
+    back, used = api.common_data_from_bytes(by)
+    assert used == len(by) and bytes(back) == bytes(desc)
+    assert api.common_data_to_bytes(back) == by
+    for g in gates:
+        tag, param = egc.SERIAL_TAG[g]
+        entry = tag.to_bytes(4, "little") + param.to_bytes(8, "little")
+        at = by.find(entry)
+        assert at > 0 and by.find(entry, at + 1) == -1, NAMES[g]
+        for other in (param - 1, param + 1):                          # 9 ops, 44 coefficients, ...
+            bad = by[:at + 4] + other.to_bytes(8, "little") + by[at + 12:]
+            with pytest.raises(p.Plonky2Mi355xError) as e:
+                api.common_data_from_bytes(bad)
+            assert e.value.code == 3, NAMES[g]
+
+
+def test_a_gate_list_out_of_the_builders_order_is_refused():
+    # common_data.gates is sorted by (degree, id) (circuit_builder.rs:987): the byte form represents nothing else.  ReducingGate (degree
+    # 2) swapped with ArithmeticExtensionGate (degree 3), and ReducingExtensionGate with ReducingGate (equal degree, id order)
+    import copy
+    import plonky2_demo_amd as p
+    from plonky2_demo_amd import api
+    good = _fixture_circuit().desc
+    types = list(good.gate_types[:good.num_gates])
+    assert types == [0, 1, 2, REDUCING_EXT, REDUCING, ARITHMETIC_EXT, MUL_EXT]
+    by = api.common_data_to_bytes(good)
+    for i, j in ((4, 5), (3, 4)):
+        d = copy.copy(good)
+        d.gate_types[i], d.gate_types[j] = types[j], types[i]
+        with pytest.raises(p.Plonky2Mi355xError) as e:
+            api.common_data_to_bytes(d)
+        assert e.value.code == 3
+        ea, eb = (b"".join(t.to_bytes(4, "little") + n.to_bytes(8, "little") for t, n in [egc.SERIAL_TAG[types[k]]]) for k in (i, j))
+        at = by.find(ea + eb)
+        assert at > 0
+        with pytest.raises(p.Plonky2Mi355xError) as e:
+            api.common_data_from_bytes(by[:at] + eb + ea + by[at + 24:])
+        assert e.value.code == 3
+
+
+def test_gate_type_constants_are_exported():
+    from plonky2_demo_amd import api
+    assert (api.G_ARITHMETIC_EXT, api.G_MUL_EXT, api.G_REDUCING, api.G_REDUCING_EXT) == (10, 11, 12, 13)
+    assert (ARITHMETIC_EXT, MUL_EXT, REDUCING, REDUCING_EXT) == (10, 11, 12, 13)
+
+
+def _fixture():
+    with open(os.path.join(GOLDEN, "ext_gates_n8_proof.bin"), "rb") as f:
+        proof = f.read()
+    with open(os.path.join(GOLDEN, "ext_gates_n8_verifier_only.bin"), "rb") as f:
+        vo = f.read()
+    return proof, vo
+
+
+def test_cpu_verifier_accepts_the_stored_gpu_proof_and_rejects_flipped_openings():
+    # a GPU-made proof of the n = 8 circuit with one row of each of the four gates (tests/golden/ext_gates_n8_proof.bin, 69 952 bytes,
+    # written by tools/make_ext_gates_fixture.py, with the
+    # VerifierOnlyCircuitData bytes = constants_sigmas_cap + circuit digest beside it); the description is rebuilt by the helper
+    import plonky2_demo_amd as p
+    from plonky2_demo_amd import api
+    proof, vo = _fixture()
+    c = _fixture_circuit()
+    d = c.desc
+    assert c.n == 8 and d.num_selectors == 1 and sorted(d.gate_types[:d.num_gates]) == [0, 1, 2, 10, 11, 12, 13]
+    cap, digest, used = api.verifier_only_from_bytes(vo)
+    assert used == len(vo)
+    buf = np.frombuffer(proof, dtype=np.uint8)
+
+    def verify(by):
+        b = np.frombuffer(bytes(by), dtype=np.uint8)
+        return api._verdict(api.lib.gl_verify(api.ctypes.byref(d), api._p(cap), api._p(digest), api._p(b), b.size))
+
+    assert verify(buf) == (True, "")
+    assert api.verify_bytes(vo + api.common_data_to_bytes(d), proof) == (True, "")
+    # openings: behind the three caps of 16 digests; constants, sigmas, wires, Z, Z(g x), partial products, quotient chunks, 2 words each
+    start, words = 3 * 16 * 4 * 8, 2 * (d.num_constants + 80 + 135 + 2 + 2 + 18 + 16)
+    rs = np.random.RandomState(2024)
+    for _ in range(64):
+        at, bit = start + int(rs.randint(0, 8 * words)), 1 << int(rs.randint(0, 8))
+        bad = bytearray(proof)
+        bad[at] ^= bit
+        assert not verify(bad)[0], (at, bit)
