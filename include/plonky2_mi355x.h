@@ -91,7 +91,11 @@ typedef struct gl_proof gl_proof;      /* ProofWithPublicInputs + the prover's i
  * (CircuitBuilder::arithmetic_extension / mul_extension, ReducingFactorTarget::reduce*).  gl_common_data_to_bytes / _from_bytes refuse
  * (GL_ERR_UNSUPPORTED) a gate list that is not in build()'s order (degree, then id: circuit_builder.rs:987).  `gate_types` is the list
  * `common_data.gates` (sorted by degree, id) and the group arrays are `selectors_info`
- * (plonky2/src/gates/selectors.rs:17-26). */
+ * (plonky2/src/gates/selectors.rs:17-26).
+ * This comment describes; the library itself reads every one of these facts (code, id() name, serialisation tag and parameter words,
+ * degree, number of constraints, quotient launch) from ONE table, GATE_TABLE in plonky2_demo_amd/csrc/gates.hpp.  A new gate type is a
+ * row there, its constraints for the prover (prover_kernels.cuh) and for the verifier (gate_constraints_at, verifier.hip), a line
+ * here and its name in plonky2_demo_amd/_lib.py (and in GL_GATE_LIST beside the table). */
 typedef struct gl_circuit_desc {
     uint32_t degree_bits;              /* log2 of the trace length n                                */
     uint32_t num_wires;                /* 135                                                       */

@@ -174,7 +174,7 @@ SIGNATURES = {
 
 HASHERS = {"poseidon": 0, "keccak": 1}
 
-# gl_circuit_desc.gate_types codes (include/plonky2_mi355x.h)
+# gl_circuit_desc.gate_types codes: the enum of csrc/gates.hpp, spelt out (tests/test_ext_gates.py holds the two against each other)
 (G_NOOP, G_CONSTANT, G_PUBLIC_INPUT, G_ARITHMETIC, G_POSEIDON, G_BASE_SUM, G_LOOKUP, G_LOOKUP_TABLE, G_EXPONENTIATION, G_RANDOM_ACCESS,
  G_ARITHMETIC_EXT, G_MUL_EXT, G_REDUCING, G_REDUCING_EXT) = range(14)
 

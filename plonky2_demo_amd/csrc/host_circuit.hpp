@@ -18,6 +18,7 @@
 #include "gl64.cuh"
 #include "poseidon.cuh"
 #include "keccak.cuh"
+#include "gates.hpp"
 #include "../../include/plonky2_mi355x.h"
 
 namespace glhost {
@@ -26,60 +27,27 @@ static const gl_t MULT_GEN = 7;
 static const gl_t POW2_GEN = 1753635133440165772ULL;
 inline gl_t root_of_unity(unsigned lg) { gl_t r = POW2_GEN; for (unsigned i = lg; i < 32; i++) r = gl_sqr(r); return gl_canon(r); }
 
-// gate type codes shared with the device kernels (order = the reference's sort by (degree, id))
-enum { G_NOOP = 0, G_CONSTANT = 1, G_PUBLIC_INPUT = 2, G_ARITHMETIC = 3, G_POSEIDON = 4, G_BASE_SUM = 5, G_LOOKUP = 6, G_LOOKUP_TABLE = 7, G_EXPONENTIATION = 8,
-       G_RANDOM_ACCESS = 9, G_ARITHMETIC_EXT = 10, G_MUL_EXT = 11, G_REDUCING = 12, G_REDUCING_EXT = 13, G_LAST = G_REDUCING_EXT };
-// the new_from_config parameters of the extension-field gates under standard_recursion_config (D = 2, 80 routed wires, 135 wires):
-// ArithmeticExtensionGate num_ops = 80 / 8 (gates/arithmetic_extension.rs:35-38), MulExtensionGate num_ops = 80 / 6
-// (gates/multiplication_extension.rs:35-38), ReducingGate num_coeffs = min(80 - 6, (135 - 4) / 3) (gates/reducing.rs:29-31),
-// ReducingExtensionGate num_coeffs = min((80 - 6) / 2, (135 - 4) / 4) (gates/reducing_extension.rs:29-33)
-enum { ARITH_EXT_OPS = 10, MUL_EXT_OPS = 13, REDUCING_COEFFS = 43, REDUCING_EXT_COEFFS = 32 };
-#define GL_GATE_LIST "{Noop, Constant, PublicInput, Arithmetic, Poseidon, BaseSum<2>, Lookup, LookupTable, Exponentiation, RandomAccess, ArithmeticExtension, MulExtension, Reducing, ReducingExtension}"
-// RandomAccessGate::new_from_config(standard_recursion_config, bits) (gates/random_access.rs:55-110), bits = gate_params[g] in 1..6: copy c
-// owns wires (2 + 2^bits) c ..: access index, claimed element, the list; then the extra constants; then (unrouted) every copy's index bits
-struct RandomAccessLayout {
-    uint32_t bits, vec_size, num_copies, num_extra_constants;
-    GL_HD explicit RandomAccessLayout(uint32_t b) : bits(b), vec_size(1u << b) {
-        const uint32_t by_routed = 80u / (2u + vec_size), by_wires = 135u / (2u + vec_size + bits);
-        num_copies = by_routed < by_wires ? by_routed : by_wires;
-        const uint32_t left = 80u - (2u + vec_size) * num_copies;
-        num_extra_constants = left < 2u ? left : 2u;
-    }
-    GL_HD uint32_t wire_access_index(uint32_t c) const { return (2u + vec_size) * c; }
-    GL_HD uint32_t wire_claimed_element(uint32_t c) const { return (2u + vec_size) * c + 1u; }
-    GL_HD uint32_t wire_list_item(uint32_t i, uint32_t c) const { return (2u + vec_size) * c + 2u + i; }
-    GL_HD uint32_t wire_extra_constant(uint32_t i) const { return (2u + vec_size) * num_copies + i; }
-    GL_HD uint32_t wire_bit(uint32_t i, uint32_t c) const { return (2u + vec_size) * num_copies + num_extra_constants + c * bits + i; }
-    GL_HD uint32_t num_constraints() const { return num_copies * (bits + 2u) + num_extra_constants; }      // random_access.rs:285-288
-};
-// ExponentiationGate::new_from_config (gates/exponentiation.rs:43-53): min(routed - 2, (wires - 2) / 2) = 66 power bits; wires: 0 base,
-// 1..66 power bits (little-endian), 67 output, 68..133 intermediate values; 67 constraints of degree 4
-enum { EXP_POWER_BITS = 66 };
-enum { LOOKUP_SLOTS = 40, LOOKUP_TABLE_SLOTS = 26, NUM_COINS_LOOKUP = 4 };      // gates/lookup.rs:41-44, gates/lookup_table.rs:47-50, circuit_builder.rs:56-58
+enum { NUM_COINS_LOOKUP = 4 };      // circuit_builder.rs:56-58
 enum { LU_CH_A = 0, LU_CH_B = 1, LU_CH_ALPHA = 2, LU_CH_DELTA = 3 };            // LookupChallenges (circuit_builder.rs:61-71)
 enum { LU_SEL_TRANS_SRE = 0, LU_SEL_TRANS_LDC = 1, LU_SEL_INIT_SRE = 2, LU_SEL_LAST_LDC = 3, LU_SEL_START_END = 4 };      // gates/selectors.rs:34-40
-enum { BASE_SUM_LIMBS = 63 };      // BaseSumGate::<2>::new_from_config (gates/base_sum.rs:31-35): wire 0 = sum, wires 1..=63 = limbs
 static const uint64_t UNUSED_SELECTOR = 0xFFFFFFFFull;        // gates/selectors.rs:14
 
-// common_data.gates is sorted by (degree, id) (circuit_builder.rs:987; selector_polynomials takes the LAST gate's degree for the largest,
-// gates/selectors.rs:118): degree() and the leading type name of id() (the Debug string) per gate type.  Two gates of one type (lookup gates
-// of several tables, RandomAccessGates of equal bits cannot occur) compare by fields this table does not see and pass.  nullptr = in order
-inline unsigned gate_degree(uint8_t type, uint8_t param) {
-    switch (type) {
-        case G_CONSTANT: case G_PUBLIC_INPUT: return 1;
-        case G_BASE_SUM: case G_REDUCING: case G_REDUCING_EXT: return 2;
-        case G_ARITHMETIC: case G_ARITHMETIC_EXT: case G_MUL_EXT: return 3;
-        case G_EXPONENTIATION: return 4;
-        case G_POSEIDON: return 7;
-        case G_RANDOM_ACCESS: return param + 1u;       // gates/random_access.rs:278-280
-        default: return 0;                             // Noop, Lookup, LookupTable
+// the shape of the gate list every entry point needs before it indexes by gate: a known type, and per gate a selector column and a
+// selector group that holds the gate.  The first fault in gate order; the caller maps it to its own error code.  (The serialiser never
+// refused selector fields, which it writes as plain numbers: it keeps its own check of the types.)
+enum GateListFault { GATE_LIST_OK = 0, GATE_LIST_BAD_TYPE, GATE_LIST_BAD_SELECTOR };
+inline GateListFault gate_list_fault(const gl_circuit_desc& d) {
+    for (unsigned g = 0; g < d.num_gates && g < GL_MAX_GATES; g++) {
+        if (d.gate_types[g] > G_LAST) return GATE_LIST_BAD_TYPE;
+        if (!(d.gate_selector_index[g] < d.num_selectors && d.gate_group_start[g] <= g && g < d.gate_group_end[g] && d.gate_group_end[g] <= d.num_gates))
+            return GATE_LIST_BAD_SELECTOR;
     }
+    return GATE_LIST_OK;
 }
-inline const char* gate_id_name(uint8_t type) {
-    static const char* const names[G_LAST + 1] = {"NoopGate", "ConstantGate", "PublicInputGate", "ArithmeticGate", "PoseidonGate", "BaseSumGate", "LookupGate", "LookupTableGate",
-                                                  "ExponentiationGate", "RandomAccessGate", "ArithmeticExtensionGate", "MulExtensionGate", "ReducingGate", "ReducingExtensionGate"};
-    return type <= G_LAST ? names[type] : "";
-}
+// common_data.gates is sorted by (degree, id) (circuit_builder.rs:987; selector_polynomials takes the LAST gate's degree for the largest,
+// gates/selectors.rs:118): degree() and the leading type name of id() (the Debug string) per gate type, from gates.hpp's table.  Two gates
+// of one type (lookup gates of several tables, RandomAccessGates of equal bits cannot occur) compare by fields that table does not see
+// and pass.  nullptr = in order
 inline const char* gate_order_error(const gl_circuit_desc& d) {
     for (unsigned g = 1; g < d.num_gates && g < GL_MAX_GATES; g++) {
         const unsigned da = gate_degree(d.gate_types[g - 1], d.gate_params[g - 1]), db = gate_degree(d.gate_types[g], d.gate_params[g]);
@@ -95,7 +63,7 @@ inline uint32_t lut_rows(const gl_circuit_desc& d, unsigned t) { return (d.lut_l
 // gate_params of the gates that are not lookup gates: 1..6 bits for a RandomAccessGate, 0 otherwise; nullptr = fine
 inline const char* gate_params_error(const gl_circuit_desc& d) {
     for (unsigned g = 0; g < d.num_gates && g < GL_MAX_GATES; g++) {
-        if (d.gate_types[g] == G_RANDOM_ACCESS) { if (d.gate_params[g] < 1 || d.gate_params[g] > 6) return "RandomAccessGate: gate_params must hold 1..6 bits"; }
+        if (d.gate_types[g] == G_RANDOM_ACCESS) { if (d.gate_params[g] < RANDOM_ACCESS_MIN_BITS || d.gate_params[g] > RANDOM_ACCESS_MAX_BITS) return "RandomAccessGate: gate_params must hold 1..6 bits"; }
         else if (d.gate_types[g] != G_LOOKUP && d.gate_types[g] != G_LOOKUP_TABLE && d.gate_params[g] != 0) return "bad gate_params";
     }
     return nullptr;
@@ -130,9 +98,6 @@ inline gl_t lut_poly_at_delta(const gl_circuit_desc& d, unsigned t, gl_t b, gl_t
     for (size_t k = 0; k < deg; k++) f = gl_add(gl_mul(f, delta), k < d.lut_len[t] ? gl_add((gl_t)lut[2 * k], gl_mul(b, (gl_t)lut[2 * k + 1])) : (gl_t)0);
     return gl_canon(f);
 }
-
-// PoseidonGate wire layout (gates/poseidon.rs:36-96)
-enum { PW_INPUT = 0, PW_OUTPUT = 12, PW_SWAP = 24, PW_DELTA = 25, PW_FULL0 = 29, PW_PARTIAL = 65, PW_FULL1 = 87, PW_END = 135 };
 
 inline void host_hash_no_pad(const gl_t* in, size_t n, gl_t* out4) {     // hash/hashing.rs:117-146
     gl_t s[12] = {0};
@@ -300,22 +265,21 @@ inline int build_matmul(size_t m, HostCircuit* hc, bool zero_knowledge = false, 
     d.num_gate_rows = zero_knowledge ? (uint32_t)rows_used : 0;
     d.hasher = hasher;
     // gates present, sorted by (degree, id): Noop(0) < Constant(1) < PublicInput(1) < Arithmetic(3) < Poseidon(7)
-    bool present[5] = {false, false, false, false, false};
+    bool present[G_POSEIDON + 1] = {};
     for (auto g : hc->row_gate) present[g] = true;
-    const unsigned degree_of[5] = {0, 1, 1, 3, 7};
     d.num_gates = 0;
-    for (int g = 0; g < 5; g++) if (present[g]) d.gate_types[d.num_gates++] = (uint8_t)g;
+    for (int g = 0; g <= G_POSEIDON; g++) if (present[g]) d.gate_types[d.num_gates++] = (uint8_t)g;
     // selector groups (gates/selectors.rs:110-185), max_degree = quotient_degree_factor + 1
     const unsigned max_degree = d.quotient_degree_factor + 1, ng = d.num_gates;
     d.num_selectors = 0;
-    if (degree_of[d.gate_types[ng - 1]] + ng - 1 <= max_degree) {
+    if (gate_degree(d.gate_types[ng - 1], 0) + ng - 1 <= max_degree) {
         d.num_selectors = 1;
         for (unsigned i = 0; i < ng; i++) { d.gate_selector_index[i] = 0; d.gate_group_start[i] = 0; d.gate_group_end[i] = ng; }
     } else {
         unsigned start = 0;
         while (start < ng) {
             unsigned size = 0;
-            while (start + size < ng && size + degree_of[d.gate_types[start + size]] < max_degree) size++;
+            while (start + size < ng && size + gate_degree(d.gate_types[start + size], 0) < max_degree) size++;
             for (unsigned i = start; i < start + size; i++) { d.gate_selector_index[i] = d.num_selectors; d.gate_group_start[i] = start; d.gate_group_end[i] = start + size; }
             d.num_selectors++;
             start += size;

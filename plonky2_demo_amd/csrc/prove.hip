@@ -132,10 +132,9 @@ static int validate_desc(const gl_circuit_desc& d) {
     unsigned tot = 0;
     for (unsigned r = 0; r < d.num_fri_rounds; r++) { GL_REQUIRE(d.fri_arity_bits[r] == 4, GL_ERR_UNSUPPORTED, "FRI arity must be 16"); tot += 4; }
     GL_REQUIRE(tot <= d.degree_bits && d.degree_bits + d.rate_bits >= tot + d.cap_height, GL_ERR_ARG, "FRI total reduction arity is too large");   // circuit_builder.rs:977-980
-    for (unsigned g = 0; g < d.num_gates; g++) {
-        GL_REQUIRE(d.gate_types[g] <= glhost::G_LAST, GL_ERR_UNSUPPORTED, "gate type not in " GL_GATE_LIST);
-        GL_REQUIRE(d.gate_selector_index[g] < d.num_selectors && d.gate_group_start[g] <= g && g < d.gate_group_end[g] && d.gate_group_end[g] <= d.num_gates, GL_ERR_ARG, "bad selector group");
-    }
+    const glhost::GateListFault fault = glhost::gate_list_fault(d);
+    GL_REQUIRE(fault != glhost::GATE_LIST_BAD_TYPE, GL_ERR_UNSUPPORTED, "gate type not in " GL_GATE_LIST);
+    GL_REQUIRE(fault != glhost::GATE_LIST_BAD_SELECTOR, GL_ERR_ARG, "bad selector group");
     GL_REQUIRE(d.zero_knowledge <= 1, GL_ERR_ARG, "zero_knowledge is 0 or 1");
     GL_REQUIRE(d.hasher <= GL_HASHER_KECCAK, GL_ERR_ARG, "hasher is 0 (Poseidon) or 1 (Keccak)");
     GL_REQUIRE(!d.zero_knowledge || !d.num_luts, GL_ERR_UNSUPPORTED, "zero knowledge together with lookups is not supported");
@@ -534,17 +533,14 @@ static int commit_quotient(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* w
     }
     for (unsigned g = 0; g < d.num_gates; g++) { q.gate_types[g] = d.gate_types[g]; q.gate_params[g] = d.gate_params[g]; q.gate_sel[g] = d.gate_selector_index[g]; q.group_start[g] = d.gate_group_start[g]; q.group_end[g] = d.gate_group_end[g]; }
     ctx->timing_begin("compute quotient polys");
-    hipLaunchKernelGGL(k_quotient<false>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, q);
-    bool has_poseidon_gate = false;
-    for (unsigned g = 0; g < d.num_gates; g++) has_poseidon_gate |= d.gate_types[g] == 4;
-    if (has_poseidon_gate) hipLaunchKernelGGL(k_quotient<true>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, q);
-    bool has_random_access_gate = false;
-    for (unsigned g = 0; g < d.num_gates; g++) has_random_access_gate |= d.gate_types[g] == glhost::G_RANDOM_ACCESS;
-    if (has_random_access_gate) hipLaunchKernelGGL(k_quotient_random_access, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, q);
-    bool has_ext_arith_gate = false;
-    for (unsigned g = 0; g < d.num_gates; g++) has_ext_arith_gate |= d.gate_types[g] >= glhost::G_ARITHMETIC_EXT && d.gate_types[g] <= glhost::G_REDUCING_EXT;
-    if (has_ext_arith_gate) hipLaunchKernelGGL(k_quotient_ext_arith, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, q);
-    if (d.num_lookup_polys) hipLaunchKernelGGL(k_quotient_lookup, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, q);
+    uint32_t launches = 0;                           // the launch classes (gates.hpp's table) this circuit's gates need
+    for (unsigned g = 0; g < d.num_gates; g++) launches |= 1u << glhost::gate_launch(d.gate_types[g]);
+    const dim3 grid((unsigned)((N + 255) / 256)), block(256);
+    hipLaunchKernelGGL(k_quotient<false>, grid, block, 0, st, q);      // always: it also writes the Z and partial-product terms
+    if ((launches >> glhost::LAUNCH_POSEIDON) & 1) hipLaunchKernelGGL(k_quotient<true>, grid, block, 0, st, q);
+    if ((launches >> glhost::LAUNCH_RANDOM_ACCESS) & 1) hipLaunchKernelGGL(k_quotient_random_access, grid, block, 0, st, q);
+    if ((launches >> glhost::LAUNCH_EXT_ARITH) & 1) hipLaunchKernelGGL(k_quotient_ext_arith, grid, block, 0, st, q);
+    if (d.num_lookup_polys) hipLaunchKernelGGL(k_quotient_lookup, grid, block, 0, st, q);
     ctx->timing_end();
     GL_CHECK_HIP(hipGetLastError());
     // coset_ifft(7) of each quotient (prover.rs:739-743); the 8n coefficients ARE the 8 chunks of n (prover.rs:245-258)

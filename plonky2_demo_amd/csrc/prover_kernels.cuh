@@ -16,6 +16,7 @@
 #include "gl64.cuh"
 #include "poseidon.cuh"
 #include "keccak.cuh"
+#include "gates.hpp"
 #include "../../include/plonky2_mi355x.h"
 
 #define GLP_MAX_ROUTED 80
@@ -181,8 +182,8 @@ struct GlQuotParams {
 // per challenge: last LDC, initial Sum, initial RE, final RE (one per table), RE transition, 6 x (Sum, LDC) transitions
 #define GLQ_LOOKUP_TERMS(num_luts) (16u + (num_luts))
 // the alpha-power table holds the terms of every supported circuit: Z and partial-product checks, the lookup terms of GL_MAX_LUTS tables,
-// then the widest gate (PoseidonGate 123; ReducingGate 86, ExponentiationGate 67, ReducingExtensionGate 64, ...)
-static_assert(2 + 2 * GLP_CHUNKS + 2 * GLQ_LOOKUP_TERMS(GL_MAX_LUTS) + 123 <= GLQ_MAX_TERMS, "alpha-power table too small");
+// then the widest gate of gates.hpp's table (PoseidonGate 123; ReducingGate 86, ExponentiationGate 67, ReducingExtensionGate 64, ...)
+static_assert(2 + 2 * GLP_CHUNKS + 2 * GLQ_LOOKUP_TERMS(GL_MAX_LUTS) + GL_MAX_GATE_CONSTRAINTS <= GLQ_MAX_TERMS, "alpha-power table too small");
 
 // running alpha-weighted sums for the two alphas: unreduced (GlxWideAcc2: 16 instructions per term for both), one reduction
 // when the sum is used
@@ -193,6 +194,10 @@ struct GlAlphaAcc {
     __device__ __forceinline__ void add(uint32_t t, gl_t term) { w.mac(term, ap[t], ap[GLQ_MAX_TERMS + t]); }
     __device__ __forceinline__ gl_t sum(int b) const { return w.sum(b); }
 };
+
+// The four gate kernels below (k_quotient<false / true>, k_quotient_random_access, k_quotient_ext_arith) each write out the loop over the
+// gate list, the selector filter (gate.rs:277-284), filter x sums and the final x 1/Z_H store.  Keep them in the kernels: shared as
+// inlined functions the same text compiles to other code, with more registers in k_quotient<false> (profiles/README.md).
 
 // PoseidonGate constraints (gates/poseidon.rs:193-272), term index base `t0`.  Wire k of the point lives at w[k * N]; the
 // wires are read through WALKING pointers (p += N) in the order the gate consumes them: with closed-form addresses the
@@ -343,7 +348,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
     const gl_t* gc = cs + (size_t)(p.num_selectors + p.num_lookup_selectors) * N;      // the gate's own constants (gate.rs:129-133)
 #pragma unroll 1
     for (uint32_t g = 0; g < p.num_gates; g++) {
-        if ((p.gate_types[g] == 4) != POSEIDON_PART) continue;
+        if ((p.gate_types[g] == glhost::G_POSEIDON) != POSEIDON_PART) continue;
         const gl_t sel = cs[(size_t)p.gate_sel[g] * N];
         gl_t filter = 1;                                            // gate.rs:277-284
         for (uint32_t k = p.group_start[g]; k < p.group_end[g]; k++) if (k != g) filter = glx_mul<true>(filter, glx_sub_cc((gl_t)k, sel));
@@ -351,15 +356,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
         GlAlphaAcc acc; acc.start(p.alpha_pows);
         if constexpr (POSEIDON_PART) glq_poseidon_gate(w, N, acc, T0);
         else switch (p.gate_types[g]) {
-            case 1:     // ConstantGate (gates/constant.rs:59-66)
+            case glhost::G_CONSTANT:     // ConstantGate (gates/constant.rs:59-66)
                 acc.add(T0, glx_sub_cc(gc[0], w[0]));
                 acc.add(T0 + 1, glx_sub_cc(gc[N], w[N]));
                 break;
-            case 2:     // PublicInputGate (gates/public_input.rs:44-49)
+            case glhost::G_PUBLIC_INPUT:     // PublicInputGate (gates/public_input.rs:44-49)
 #pragma unroll
                 for (int k = 0; k < 4; k++) acc.add(T0 + k, glx_sub_cc(w[(size_t)k * N], p.pi_hash[k]));
                 break;
-            case 3: {   // ArithmeticGate (gates/arithmetic_base.rs:163-181): two operations at a time, six products in two groups
+            case glhost::G_ARITHMETIC: {   // ArithmeticGate (gates/arithmetic_base.rs:163-181): two operations at a time, six products in two groups
                 const gl_t c0 = gc[0], c1 = gc[N];
 #pragma unroll 2
                 for (int k = 0; k < 20; k += 2) {
@@ -373,7 +378,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
                 }
                 break;
             }
-            case 5: {   // BaseSumGate<2>, 63 limbs (gates/base_sum.rs:153-170): sum of limb_i 2^i - sum, then limb (limb - 1) per limb
+            case glhost::G_BASE_SUM: {   // BaseSumGate<2>, 63 limbs (gates/base_sum.rs:153-170): sum of limb_i 2^i - sum, then limb (limb - 1) per limb
                 gl_t computed = 0;                                   // reduce_with_powers(limbs, 2): Horner from the top limb
 #pragma unroll 1
                 for (int k = 63; k >= 1; k -= 3) {                   // wires 1..63 = limbs 0..62, three range checks per step
@@ -388,7 +393,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
                 acc.add(T0, glx_sub_cc(computed, w[0]));
                 break;
             }
-            case 8: {   // ExponentiationGate, 66 power bits (gates/exponentiation.rs:196-228): square-and-multiply, bits big-endian; wires:
+            case glhost::G_EXPONENTIATION: {   // ExponentiationGate, 66 power bits (gates/exponentiation.rs:196-228): square-and-multiply, bits big-endian; wires:
                         // 0 base, 1..66 bits, 67 output, 68..133 intermediate values.  Three steps at a time (their six products in two groups).
                 const gl_t base = w[0];
                 const gl_t* iv = w + (size_t)68 * N;                 // intermediate value i at iv[i * N]
@@ -409,7 +414,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
                 acc.add(T0 + 66, glx_sub_cc(w[(size_t)67 * N], last));
                 break;
             }
-            default: break;   // NoopGate
+            default: break;   // NoopGate; the gates of the other launches (they add nothing here)
         }
         gl_t fs0, fs1, unused;
         glx_mul3<true>(filter, acc.sum(0), filter, acc.sum(1), 0, 0, fs0, fs1, unused);
@@ -532,7 +537,7 @@ __global__ __launch_bounds__(256) void k_quotient_random_access(GlQuotParams p) 
     gl_t tot0 = 0, tot1 = 0;
 #pragma unroll 1
     for (uint32_t g = 0; g < p.num_gates; g++) {
-        if (p.gate_types[g] != 9) continue;
+        if (p.gate_types[g] != glhost::G_RANDOM_ACCESS) continue;
         const gl_t sel = cs[(size_t)p.gate_sel[g] * N];
         gl_t filter = 1;                                            // gate.rs:277-284
         for (uint32_t k = p.group_start[g]; k < p.group_end[g]; k++) if (k != g) filter = glx_mul<true>(filter, glx_sub_cc((gl_t)k, sel));
@@ -660,16 +665,16 @@ __global__ __launch_bounds__(256) void k_quotient_ext_arith(GlQuotParams p) {
     gl_t tot0 = 0, tot1 = 0;
 #pragma unroll 1
     for (uint32_t g = 0; g < p.num_gates; g++) {
-        if (p.gate_types[g] < 10 || p.gate_types[g] > 13) continue;
+        if (p.gate_types[g] < glhost::G_ARITHMETIC_EXT || p.gate_types[g] > glhost::G_REDUCING_EXT) continue;
         const gl_t sel = cs[(size_t)p.gate_sel[g] * N];
         gl_t filter = 1;                                            // gate.rs:277-284
         for (uint32_t k = p.group_start[g]; k < p.group_end[g]; k++) if (k != g) filter = glx_mul<true>(filter, glx_sub_cc((gl_t)k, sel));
         if (p.num_selectors > 1) filter = glx_mul<true>(filter, glx_sub_cc((gl_t)0xFFFFFFFFull, sel));
         GlAlphaAcc acc; acc.start(p.alpha_pows);
         switch (p.gate_types[g]) {
-            case 10: glq_arithmetic_ext_gate(w, gc, N, acc, p.gate_term0); break;
-            case 11: glq_mul_ext_gate(w, gc, N, acc, p.gate_term0); break;
-            case 12: glq_reducing_gate<false>(w, N, acc, p.gate_term0); break;
+            case glhost::G_ARITHMETIC_EXT: glq_arithmetic_ext_gate(w, gc, N, acc, p.gate_term0); break;
+            case glhost::G_MUL_EXT: glq_mul_ext_gate(w, gc, N, acc, p.gate_term0); break;
+            case glhost::G_REDUCING: glq_reducing_gate<false>(w, N, acc, p.gate_term0); break;
             default: glq_reducing_gate<true>(w, N, acc, p.gate_term0); break;
         }
         gl_t fs0, fs1, unused;

@@ -8,9 +8,9 @@
 // unpinned"); what is checked is a round trip, a second independent writer in the test oracle, and that
 // gl_verify_bytes accepts proofs through data that went through the byte form.
 //
-// Only circuits this library can prove / verify are representable: the gates of host_circuit.hpp's list (Noop, Constant, PublicInput,
-// Arithmetic, Poseidon, BaseSum<2>, Lookup, LookupTable, Exponentiation, RandomAccess, ArithmeticExtension, MulExtension, Reducing,
-// ReducingExtension) in their new_from_config layouts, standard_recursion_config's shape; anything else is GL_ERR_UNSUPPORTED when reading.
+// Only circuits this library can prove / verify are representable: the gates of gates.hpp's table in their new_from_config layouts,
+// standard_recursion_config's shape; anything else is GL_ERR_UNSUPPORTED when reading.  A gate's tag, the words behind it and the values
+// accepted for them are its row of that table.
 #include "context.hpp"
 #include "host_circuit.hpp"
 #include <algorithm>
@@ -18,12 +18,8 @@
 #include <vector>
 
 namespace {
-// position of each gate type in DefaultGateSerializer's list (gate_serialization.rs:89-107)
-const uint32_t TAG_ARITHMETIC = 0, TAG_ARITHMETIC_EXT = 1, TAG_MUL_EXT = 8, TAG_REDUCING_EXT = 14, TAG_REDUCING = 15, TAG_BASE_SUM_2 = 2, TAG_CONSTANT = 3, TAG_EXPONENTIATION = 5, TAG_LOOKUP = 6, TAG_LOOKUP_TABLE = 7, TAG_NOOP = 9, TAG_POSEIDON = 11, TAG_PUBLIC_INPUT = 12, TAG_RANDOM_ACCESS = 13;
-const uint64_t LOOKUP_SLOTS = 40, LOOKUP_TABLE_SLOTS = 26;     // gates/lookup.rs:41-44, gates/lookup_table.rs:47-50
-const uint64_t BASE_SUM_LIMBS = 63;     // BaseSumGate::<2>::new_from_config under standard_recursion_config (gates/base_sum.rs:31-35)
 // standard_recursion_config (plonk/circuit_data.rs:72-90)
-const uint64_t STD_SECURITY_BITS = 100, STD_CONFIG_NUM_CONSTANTS = 2, STD_FINAL_POLY_BITS = 5, STD_ARITY_BITS = 4;
+const uint64_t STD_SECURITY_BITS = 100, STD_FINAL_POLY_BITS = 5, STD_ARITY_BITS = 4;
 
 struct Writer {
     std::vector<uint8_t> b;
@@ -51,16 +47,14 @@ struct Reader {
     bool wide = false;
 };
 
-uint32_t gate_tag(uint8_t type) {
-    switch (type) { case 0: return TAG_NOOP; case 1: return TAG_CONSTANT; case 2: return TAG_PUBLIC_INPUT; case 3: return TAG_ARITHMETIC; case 5: return TAG_BASE_SUM_2; case 6: return TAG_LOOKUP; case 7: return TAG_LOOKUP_TABLE; case 8: return TAG_EXPONENTIATION; case 9: return TAG_RANDOM_ACCESS;
-                    case 10: return TAG_ARITHMETIC_EXT; case 11: return TAG_MUL_EXT; case 12: return TAG_REDUCING; case 13: return TAG_REDUCING_EXT; default: return TAG_POSEIDON; }
+// the word of the two WORDS_CONFIG_COUNT gates, ArithmeticGate { num_ops } and ConstantGate { num_consts }, as this description implies
+// it; either gate has one constraint per count
+uint64_t config_count(const gl_circuit_desc& d, uint8_t type) {
+    return type == glhost::G_ARITHMETIC ? d.num_routed_wires / 4 : d.num_constants - d.num_selectors - d.num_lookup_selectors;
 }
-uint64_t gate_constraints(uint8_t type, uint8_t param, const gl_circuit_desc& d) {
-    if (type == 9) return glhost::RandomAccessLayout(param).num_constraints();
-    switch (type) { case 0: case 6: case 7: return 0; case 1: return d.num_constants - d.num_selectors - d.num_lookup_selectors; case 2: return 4; case 3: return d.num_routed_wires / 4; case 5: return 1 + BASE_SUM_LIMBS /* gates/base_sum.rs:144-146 */; case 8: return glhost::EXP_POWER_BITS + 1 /* gates/exponentiation.rs:190-192 */;
-                    case 10: return 2 * glhost::ARITH_EXT_OPS /* gates/arithmetic_extension.rs:162-164 */; case 11: return 2 * glhost::MUL_EXT_OPS /* gates/multiplication_extension.rs:149-151 */;
-                    case 12: return 2 * glhost::REDUCING_COEFFS /* gates/reducing.rs:175-177 */; case 13: return 2 * glhost::REDUCING_EXT_COEFFS /* gates/reducing_extension.rs:175-177 */;
-                    default: return 123; }   // gates/poseidon.rs:403-409
+uint64_t gate_constraints(const gl_circuit_desc& d, unsigned g) {
+    const uint8_t type = d.gate_types[g];
+    return glhost::gate_row(type).words == glhost::WORDS_CONFIG_COUNT ? config_count(d, type) : glhost::gate_num_constraints(type, d.gate_params[g]);
 }
 void write_fri_config(Writer& w, const gl_circuit_desc& d) {          // mod.rs:1628-1644
     w.u64(d.rate_bits); w.u64(d.cap_height); w.u64(d.num_query_rounds); w.u32(d.proof_of_work_bits);
@@ -94,7 +88,7 @@ extern "C" int gl_common_data_to_bytes(const gl_circuit_desc* desc, uint8_t* h_o
     GL_REQUIRE(d.num_constants >= d.num_selectors + d.num_lookup_selectors, GL_ERR_ARG, "bad lookup description");
     Writer w;
     // CircuitConfig (mod.rs:1662-1686)
-    w.u64(d.num_wires); w.u64(d.num_routed_wires); w.u64(STD_CONFIG_NUM_CONSTANTS); w.u64(STD_SECURITY_BITS); w.u64(d.num_challenges);
+    w.u64(d.num_wires); w.u64(d.num_routed_wires); w.u64(glhost::STD_NUM_CONSTANTS); w.u64(STD_SECURITY_BITS); w.u64(d.num_challenges);
     w.u64(d.quotient_degree_factor); w.u8(1 /* use_base_arithmetic_gate */); w.u8(d.zero_knowledge ? 1 : 0);
     write_fri_config(w, d);
     // FriParams (mod.rs:1646-1660)
@@ -105,19 +99,19 @@ extern "C" int gl_common_data_to_bytes(const gl_circuit_desc* desc, uint8_t* h_o
     w.u64(d.num_gates);
     uint64_t max_constraints = 0;
     for (uint32_t g = 0; g < d.num_gates; g++) {
-        w.u32(gate_tag(d.gate_types[g]));
-        if (d.gate_types[g] == 3) w.u64(d.num_routed_wires / 4);                   // ArithmeticGate { num_ops }
-        if (d.gate_types[g] == 1) w.u64(d.num_constants - d.num_selectors - d.num_lookup_selectors);      // ConstantGate { num_consts }
-        if (d.gate_types[g] == 6) { w.u64(LOOKUP_SLOTS); w.lut(d, d.gate_params[g]); }                // LookupGate { num_slots, lut } (gates/lookup.rs:59-62)
-        if (d.gate_types[g] == 7) { w.u64(LOOKUP_TABLE_SLOTS); w.lut(d, d.gate_params[g]); w.u64(d.last_lut_row[d.gate_params[g]]); }      // LookupTableGate (gates/lookup_table.rs:70-74)
-        if (d.gate_types[g] == 5) w.u64(BASE_SUM_LIMBS);                           // BaseSumGate<2> { num_limbs } (gates/base_sum.rs:53-55)
-        if (d.gate_types[g] == 9) { const glhost::RandomAccessLayout ra(d.gate_params[g]); w.u64(ra.bits); w.u64(ra.num_copies); w.u64(ra.num_extra_constants); }      // random_access.rs:123-128
-        if (d.gate_types[g] == 8) w.u64(glhost::EXP_POWER_BITS);                   // ExponentiationGate { num_power_bits } (gates/exponentiation.rs:79-81)
-        if (d.gate_types[g] == 10) w.u64(glhost::ARITH_EXT_OPS);                   // ArithmeticExtensionGate { num_ops } (gates/arithmetic_extension.rs:59-61)
-        if (d.gate_types[g] == 11) w.u64(glhost::MUL_EXT_OPS);                     // MulExtensionGate { num_ops } (gates/multiplication_extension.rs:56-58)
-        if (d.gate_types[g] == 12) w.u64(glhost::REDUCING_COEFFS);                 // ReducingGate { num_coeffs } (gates/reducing.rs:63-66)
-        if (d.gate_types[g] == 13) w.u64(glhost::REDUCING_EXT_COEFFS);             // ReducingExtensionGate { num_coeffs } (gates/reducing_extension.rs:66-69)
-        const uint64_t c = gate_constraints(d.gate_types[g], d.gate_params[g], d);
+        const glhost::GateRow& row = glhost::gate_row(d.gate_types[g]);
+        w.u32(row.tag);
+        switch (row.words) {
+            case glhost::WORDS_NONE: break;
+            case glhost::WORDS_COUNT: w.u64(row.count); break;
+            case glhost::WORDS_CONFIG_COUNT: w.u64(config_count(d, row.type)); break;
+            case glhost::WORDS_RANDOM_ACCESS: { const glhost::RandomAccessLayout ra(d.gate_params[g]); w.u64(ra.bits); w.u64(ra.num_copies); w.u64(ra.num_extra_constants); break; }
+            case glhost::WORDS_LOOKUP: case glhost::WORDS_LOOKUP_TABLE:      // the gate carries its whole table
+                w.u64(row.count); w.lut(d, d.gate_params[g]);
+                if (row.words == glhost::WORDS_LOOKUP_TABLE) w.u64(d.last_lut_row[d.gate_params[g]]);
+                break;
+        }
+        const uint64_t c = gate_constraints(d, g);
         if (c > max_constraints) max_constraints = c;
     }
     // SelectorsInfo (mod.rs:1700-1713): selector_indices, then the distinct groups in order
@@ -178,48 +172,36 @@ extern "C" int gl_common_data_from_bytes(const uint8_t* h_bytes, size_t num_byte
     uint32_t gate_last_lut_row[GL_MAX_GATES] = {0};
     for (uint64_t g = 0; g < ngates; g++) {
         const uint32_t tag = r.u32();
-        if (tag == TAG_NOOP) d.gate_types[g] = 0;
-        else if (tag == TAG_CONSTANT) { d.gate_types[g] = 1; const_consts = r.u64(); }
-        else if (tag == TAG_PUBLIC_INPUT) d.gate_types[g] = 2;
-        else if (tag == TAG_ARITHMETIC) { d.gate_types[g] = 3; arith_ops = r.u64(); }
-        else if (tag == TAG_POSEIDON) d.gate_types[g] = 4;
-        else if (tag == TAG_BASE_SUM_2) {
-            d.gate_types[g] = 5;
-            const uint64_t limbs = r.u64();
-            GL_REQUIRE(!r.ok || limbs == BASE_SUM_LIMBS, GL_ERR_UNSUPPORTED, "BaseSumGate<2> with a limb count other than new_from_config's 63");
-        }
-        else if (tag == TAG_RANDOM_ACCESS) {
-            d.gate_types[g] = 9;
-            const uint64_t bits = r.u64(), copies = r.u64(), extra = r.u64();
-            GL_REQUIRE(!r.ok || (bits >= 1 && bits <= 6), GL_ERR_UNSUPPORTED, "RandomAccessGate: 1..6 index bits");
-            if (r.ok) {
-                const glhost::RandomAccessLayout ra((uint32_t)bits);
-                GL_REQUIRE(copies == ra.num_copies && extra == ra.num_extra_constants, GL_ERR_UNSUPPORTED, "RandomAccessGate with a layout other than new_from_config's");
-                d.gate_params[g] = (uint8_t)bits;
+        const int type = glhost::gate_from_tag(tag);
+        if (type < 0) return gl_fail(GL_ERR_UNSUPPORTED, "gate outside " GL_GATE_LIST, __FILE__, __LINE__);
+        d.gate_types[g] = (uint8_t)type;
+        const glhost::GateRow& row = glhost::gate_row((uint8_t)type);
+        switch (row.words) {
+            case glhost::WORDS_NONE: break;
+            case glhost::WORDS_COUNT: {     // only new_from_config's value under standard_recursion_config has a kernel
+                const uint64_t count = r.u64();
+                GL_REQUIRE(!r.ok || count == row.count, GL_ERR_UNSUPPORTED, row.refusal);
+                break;
+            }
+            case glhost::WORDS_CONFIG_COUNT: (type == glhost::G_ARITHMETIC ? arith_ops : const_consts) = r.u64(); break;      // checked against the config below
+            case glhost::WORDS_RANDOM_ACCESS: {
+                const uint64_t bits = r.u64(), copies = r.u64(), extra = r.u64();
+                GL_REQUIRE(!r.ok || (bits >= glhost::RANDOM_ACCESS_MIN_BITS && bits <= glhost::RANDOM_ACCESS_MAX_BITS), GL_ERR_UNSUPPORTED, "RandomAccessGate: 1..6 index bits");
+                if (r.ok) {
+                    const glhost::RandomAccessLayout ra((uint32_t)bits);
+                    GL_REQUIRE(copies == ra.num_copies && extra == ra.num_extra_constants, GL_ERR_UNSUPPORTED, "RandomAccessGate with a layout other than new_from_config's");
+                    d.gate_params[g] = (uint8_t)bits;
+                }
+                break;
+            }
+            case glhost::WORDS_LOOKUP: case glhost::WORDS_LOOKUP_TABLE: {
+                const uint64_t slots = r.u64(), len = r.u64();
+                GL_REQUIRE(!r.ok || (slots == row.count && len >= 1 && len <= GL_MAX_LUT_ENTRIES), GL_ERR_UNSUPPORTED, row.refusal);
+                for (uint64_t k = 0; k < 2 * len && r.ok; k++) gate_table[g].push_back(r.u16());
+                if (row.words == glhost::WORDS_LOOKUP_TABLE) gate_last_lut_row[g] = r.usize32();
+                break;
             }
         }
-        else if (tag == TAG_EXPONENTIATION) {
-            d.gate_types[g] = 8;
-            const uint64_t bits = r.u64();
-            GL_REQUIRE(!r.ok || bits == glhost::EXP_POWER_BITS, GL_ERR_UNSUPPORTED, "ExponentiationGate with a bit count other than new_from_config's 66");
-        }
-        else if (tag == TAG_ARITHMETIC_EXT || tag == TAG_MUL_EXT || tag == TAG_REDUCING || tag == TAG_REDUCING_EXT) {
-            // one usize each: num_ops / num_coeffs; only new_from_config's value under standard_recursion_config has a kernel
-            d.gate_types[g] = tag == TAG_ARITHMETIC_EXT ? 10 : tag == TAG_MUL_EXT ? 11 : tag == TAG_REDUCING ? 12 : 13;
-            const uint64_t want = tag == TAG_ARITHMETIC_EXT ? glhost::ARITH_EXT_OPS : tag == TAG_MUL_EXT ? glhost::MUL_EXT_OPS : tag == TAG_REDUCING ? glhost::REDUCING_COEFFS : glhost::REDUCING_EXT_COEFFS;
-            const uint64_t count = r.u64();
-            GL_REQUIRE(!r.ok || count == want, GL_ERR_UNSUPPORTED,
-                       "ArithmeticExtensionGate / MulExtensionGate / ReducingGate / ReducingExtensionGate with a count other than new_from_config's 10 / 13 / 43 / 32");
-        }
-        else if (tag == TAG_LOOKUP || tag == TAG_LOOKUP_TABLE) {
-            d.gate_types[g] = tag == TAG_LOOKUP ? 6 : 7;
-            const uint64_t slots = r.u64(), len = r.u64();
-            GL_REQUIRE(!r.ok || (slots == (tag == TAG_LOOKUP ? LOOKUP_SLOTS : LOOKUP_TABLE_SLOTS) && len >= 1 && len <= GL_MAX_LUT_ENTRIES), GL_ERR_UNSUPPORTED,
-                       "lookup gate: slot count of standard_recursion_config and a table of at most 1024 entries");
-            for (uint64_t k = 0; k < 2 * len && r.ok; k++) gate_table[g].push_back(r.u16());
-            if (tag == TAG_LOOKUP_TABLE) gate_last_lut_row[g] = r.usize32();
-        }
-        else return gl_fail(GL_ERR_UNSUPPORTED, "gate outside " GL_GATE_LIST, __FILE__, __LINE__);
     }
     if (r.ok) { const char* why = glhost::gate_order_error(d); GL_REQUIRE(!why, GL_ERR_UNSUPPORTED, why); }
     const uint64_t nsel = r.u64();
@@ -259,7 +241,7 @@ extern "C" int gl_common_data_from_bytes(const uint8_t* h_bytes, size_t num_byte
     GL_REQUIRE(r.ok, GL_ERR_ARG, "truncated CommonCircuitData");
     bool has_table_gate[GL_MAX_LUTS] = {false};
     for (uint64_t g = 0; g < ngates; g++) {
-        if (d.gate_types[g] != 6 && d.gate_types[g] != 7) continue;
+        if (d.gate_types[g] != glhost::G_LOOKUP && d.gate_types[g] != glhost::G_LOOKUP_TABLE) continue;
         unsigned t = 0;                 // the tables of `luts` are distinct (circuit_builder.rs is_stored): the first equal one is the gate's
         for (; t < nluts; t++) {
             const uint16_t* e = d.lut + 2 * (size_t)glhost::lut_offset(d, t);
@@ -267,7 +249,7 @@ extern "C" int gl_common_data_from_bytes(const uint8_t* h_bytes, size_t num_byte
         }
         GL_REQUIRE(t < nluts, GL_ERR_ARG, "a lookup gate's table is not one of CommonCircuitData's luts");
         d.gate_params[g] = (uint8_t)t;
-        if (d.gate_types[g] == 7) {
+        if (d.gate_types[g] == glhost::G_LOOKUP_TABLE) {
             // LookupWire is prover data (circuit_data.rs:296-299), not part of these bytes: last_lut_row is the LookupTableGate's field,
             // first_lut_row follows from the table length; last_lu_row is unknown here and left 0 (the verifier does not need it; build()
             // reads it from the lookup selector columns)
@@ -281,7 +263,7 @@ extern "C" int gl_common_data_from_bytes(const uint8_t* h_bytes, size_t num_byte
     GL_REQUIRE((!arith_ops || arith_ops == d.num_routed_wires / 4) && (!const_consts || const_consts == cfg_consts), GL_ERR_UNSUPPORTED, "gate parameters");
     {   // the two redundant fields must say what the rest implies (the writer derives them the same way)
         uint64_t max_constraints = 0;
-        for (uint32_t g = 0; g < d.num_gates; g++) max_constraints = std::max<uint64_t>(max_constraints, gate_constraints(d.gate_types[g], d.gate_params[g], d));
+        for (uint32_t g = 0; g < d.num_gates; g++) max_constraints = std::max<uint64_t>(max_constraints, gate_constraints(d, g));
         GL_REQUIRE(d.quotient_degree_factor >= 1 && num_gate_constraints == max_constraints &&
                    num_partial_products == (d.num_routed_wires + d.quotient_degree_factor - 1) / d.quotient_degree_factor - 1, GL_ERR_ARG,
                    "num_gate_constraints / num_partial_products differ from what the gates and the routed wires imply");

@@ -55,7 +55,7 @@ void ext_mds(E (&s)[12]) {
 }
 void ext_add_round_constants(E (&s)[12], int round) { for (int i = 0; i < 12; i++) s[i] = e_add(s[i], e_of(POSEIDON_RC[12 * round + i])); }
 
-// 123 constraints of gates/poseidon.rs:113-191 on the row `w` (135 extension values); returns them in order
+// the POSEIDON_GATE_CONSTRAINTS constraints of gates/poseidon.rs:113-191 on the row `w` (135 extension values); returns them in order
 void poseidon_gate_constraints(const E* w, E* out) {
     using namespace glhost;
     int c = 0;
@@ -106,6 +106,100 @@ inline Alg alg_mul(const Alg& x, const Alg& y) {
     return Alg{e_add(e_mul(x.a, y.a), e_scale(e_mul(x.b, y.b), glhost::MULT_GEN /* W = 7 */)), e_add(e_mul(x.a, y.b), e_mul(x.b, y.a))};
 }
 
+// The constraints of one gate of `type` (`param`: gl_circuit_desc.gate_params) on the row `wires` (135 extension values), in order, into
+// tmp[GL_MAX_GATE_CONSTRAINTS]; returns their number, which gl_verify holds against gate_num_constraints.  An unknown type has none
+// (gl_verify refuses it beforehand).
+size_t gate_constraints_at(uint8_t type, uint8_t param, const E* wires, const E* gate_consts, const gl_t* pi_hash, E* tmp) {
+    size_t cnt = 0;
+    switch (type) {
+        case glhost::G_NOOP: case glhost::G_LOOKUP: case glhost::G_LOOKUP_TABLE: break;          // no main-trace constraints (lookup.rs:72-75)
+        case glhost::G_CONSTANT: cnt = 2; for (int i = 0; i < 2; i++) tmp[i] = e_sub(gate_consts[i], wires[i]); break;                        // constant.rs:59-66
+        case glhost::G_PUBLIC_INPUT: cnt = 4; for (int i = 0; i < 4; i++) tmp[i] = e_sub(wires[i], e_of(pi_hash[i])); break;                     // public_input.rs:44-49
+        case glhost::G_ARITHMETIC: cnt = 20;                                                                                                    // arithmetic_base.rs:72-92
+            for (int i = 0; i < 20; i++) tmp[i] = e_sub(wires[4 * i + 3], e_add(e_mul(e_mul(wires[4 * i], wires[4 * i + 1]), gate_consts[0]), e_mul(wires[4 * i + 2], gate_consts[1])));
+            break;
+        case glhost::G_BASE_SUM: {                                                                                                              // base_sum.rs:63-76, B = 2
+            cnt = 1 + glhost::BASE_SUM_LIMBS;
+            E computed = e_of(0);                                                                                                                // reduce_with_powers(limbs, 2)
+            for (int i = glhost::BASE_SUM_LIMBS; i-- > 0;) computed = e_add(e_add(computed, computed), wires[1 + i]);
+            tmp[0] = e_sub(computed, wires[0]);
+            for (int i = 0; i < glhost::BASE_SUM_LIMBS; i++) tmp[1 + i] = e_mul(wires[1 + i], e_sub(wires[1 + i], e_of(1)));
+            break;
+        }
+        case glhost::G_RANDOM_ACCESS: {                                                                                                         // random_access.rs:139-184
+            const glhost::RandomAccessLayout ra(param);
+            for (uint32_t copy = 0; copy < ra.num_copies; copy++) {
+                std::vector<E> items(ra.vec_size);
+                for (uint32_t i = 0; i < ra.vec_size; i++) items[i] = wires[ra.wire_list_item(i, copy)];
+                for (uint32_t i = 0; i < ra.bits; i++) { const E b = wires[ra.wire_bit(i, copy)]; tmp[cnt++] = e_mul(b, e_sub(b, e_of(1))); }
+                E rec = e_of(0);
+                for (uint32_t i = ra.bits; i-- > 0;) rec = e_add(e_add(rec, rec), wires[ra.wire_bit(i, copy)]);
+                tmp[cnt++] = e_sub(rec, wires[ra.wire_access_index(copy)]);
+                for (uint32_t i = 0; i < ra.bits; i++) {                                                                                         // fold the list by bit i
+                    const E b = wires[ra.wire_bit(i, copy)];
+                    for (size_t j = 0; 2 * j + 1 < items.size(); j++) items[j] = e_add(items[2 * j], e_mul(b, e_sub(items[2 * j + 1], items[2 * j])));
+                    items.resize(items.size() / 2);
+                }
+                tmp[cnt++] = e_sub(items[0], wires[ra.wire_claimed_element(copy)]);
+            }
+            for (uint32_t i = 0; i < ra.num_extra_constants; i++) tmp[cnt++] = e_sub(gate_consts[i], wires[ra.wire_extra_constant(i)]);
+            break;
+        }
+        case glhost::G_EXPONENTIATION: {                                                                                                        // exponentiation.rs:88-124
+            const int n = glhost::EXP_POWER_BITS;
+            cnt = n + 1;
+            for (int i = 0; i < n; i++) {                                                                                                        // square-and-multiply, bits big-endian
+                const E prev = i == 0 ? e_of(1) : e_mul(wires[2 + n + i - 1], wires[2 + n + i - 1]);
+                const E bit = wires[1 + (n - 1 - i)];
+                tmp[i] = e_sub(e_mul(prev, e_add(e_mul(bit, wires[0]), e_sub(e_of(1), bit))), wires[2 + n + i]);
+            }
+            tmp[n] = e_sub(wires[1 + n], wires[2 + n + n - 1]);
+            break;
+        }
+        // The extension-field gates: at zeta every wire is itself in F_p^2, so a wire pair is an element (A0, A1) of the ExtensionAlgebra
+        // F_p^2[X]/(X^2 - 7) (field/src/extension/algebra.rs:113-131: W = 7 embedded), and a constraint's two components enter the sum
+        // in order (to_basefield_array).
+        case glhost::G_ARITHMETIC_EXT: {                                                                                                        // arithmetic_extension.rs:68-90
+            for (int i = 0; i < glhost::ARITH_EXT_OPS; i++) {
+                const E* w = wires + 8 * i;                                                                                               // m0, m1, addend, output
+                const Alg prod = alg_mul(Alg{w[0], w[1]}, Alg{w[2], w[3]});
+                tmp[cnt++] = e_sub(w[6], e_add(e_mul(prod.a, gate_consts[0]), e_mul(w[4], gate_consts[1])));
+                tmp[cnt++] = e_sub(w[7], e_add(e_mul(prod.b, gate_consts[0]), e_mul(w[5], gate_consts[1])));
+            }
+            break;
+        }
+        case glhost::G_MUL_EXT: {                                                                                                               // multiplication_extension.rs:65-84
+            for (int i = 0; i < glhost::MUL_EXT_OPS; i++) {
+                const E* w = wires + 6 * i;                                                                                               // m0, m1, output
+                const Alg prod = alg_mul(Alg{w[0], w[1]}, Alg{w[2], w[3]});
+                tmp[cnt++] = e_sub(w[4], e_mul(prod.a, gate_consts[0]));
+                tmp[cnt++] = e_sub(w[5], e_mul(prod.b, gate_consts[0]));
+            }
+            break;
+        }
+        case glhost::G_REDUCING: case glhost::G_REDUCING_EXT: {                                                          // reducing.rs:77-103, reducing_extension.rs:80-104
+            // wires 0-1 output, 2-3 alpha, 4-5 old_acc, the coefficients (one wire each / two wires each), the accumulators; the last
+            // accumulator is the output
+            const bool ext = type == glhost::G_REDUCING_EXT;
+            const int nc = ext ? glhost::REDUCING_EXT_COEFFS : glhost::REDUCING_COEFFS, acc0 = 6 + (ext ? 2 : 1) * nc;
+            const Alg alpha{wires[2], wires[3]};
+            Alg acc{wires[4], wires[5]};
+            for (int i = 0; i < nc; i++) {
+                const int aw = i == nc - 1 ? 0 : acc0 + 2 * i;
+                const Alg acc_i{wires[aw], wires[aw + 1]};
+                const Alg coeff = ext ? Alg{wires[6 + 2 * i], wires[7 + 2 * i]} : Alg{wires[6 + i], e_of(0)};
+                const Alg t = alg_mul(acc, alpha);
+                tmp[cnt++] = e_sub(e_add(t.a, coeff.a), acc_i.a);
+                tmp[cnt++] = e_sub(e_add(t.b, coeff.b), acc_i.b);
+                acc = acc_i;
+            }
+            break;
+        }
+        case glhost::G_POSEIDON: cnt = glhost::POSEIDON_GATE_CONSTRAINTS; poseidon_gate_constraints(wires, tmp); break;
+    }
+    return cnt;
+}
+
 struct Cursor {                                        // little-endian reader over the proof bytes
     const uint8_t* p; size_t len, pos = 0; bool ok = true;
     Cursor(const uint8_t* b, size_t n) : p(b), len(n) {}
@@ -140,9 +234,7 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
     // wrong one must be refused, not turned into a 2^40-byte allocation: tools/sanitizer/data_fuzz.cpp)
     GL_REQUIRE(d.num_selectors <= GL_MAX_GATES && d.cap_height <= 16 && d.num_query_rounds <= num_bytes / 8 && d.num_public_inputs <= num_bytes / 8,
                GL_ERR_ARG, "gl_verify: a count of the description exceeds what the proof bytes can hold");
-    for (unsigned g = 0; g < d.num_gates; g++)
-        GL_REQUIRE(d.gate_types[g] <= glhost::G_LAST && d.gate_selector_index[g] < d.num_selectors && d.gate_group_start[g] <= g && g < d.gate_group_end[g] && d.gate_group_end[g] <= d.num_gates,
-                   GL_ERR_ARG, "gl_verify: bad gate / selector description");
+    GL_REQUIRE(!glhost::gate_list_fault(d), GL_ERR_ARG, "gl_verify: bad gate / selector description");
     const size_t nch = 2, R = 80, W = 135, QF = 8, NPP = 9;            // partial products per challenge: ceil(80 / 8) - 1
     const size_t ncap = size_t(1) << d.cap_height, ncs = d.num_constants + R;
     const unsigned lgn = d.degree_bits, lgN = lgn + d.rate_bits;
@@ -245,102 +337,17 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
         // L_0(zeta) = (zeta^n - 1) / (n (zeta - 1))  (plonk_common.rs:61-71)
         const E l0 = e_eq(zeta, e_of(1)) ? e_of(1) : e_mul(z_h, gl2_inv(e_scale(e_sub(zeta, e_of(1)), (gl_t)n)));
         // gate constraints, summed slot-wise with each gate's selector filter (vanishing_poly.rs:671-699, gate.rs:277-284)
-        const size_t NGC = 123;
-        std::vector<E> gate_terms(NGC, e_of(0));
+        std::vector<E> gate_terms(GL_MAX_GATE_CONSTRAINTS, e_of(0));
         const E* gate_consts = consts.data() + d.num_selectors + d.num_lookup_selectors;      // gate.rs:129-133
-        E tmp[123];
+        E tmp[GL_MAX_GATE_CONSTRAINTS];
         for (unsigned g = 0; g < d.num_gates; g++) {
             const E sel = consts[d.gate_selector_index[g]];
             E filter = e_of(1);
             for (unsigned i = d.gate_group_start[g]; i < d.gate_group_end[g]; i++) if (i != g) filter = e_mul(filter, e_sub(e_of(i), sel));
             if (d.num_selectors > 1) filter = e_mul(filter, e_sub(e_of(glhost::UNUSED_SELECTOR), sel));
-            size_t cnt = 0;
-            switch (d.gate_types[g]) {
-                case glhost::G_NOOP: case glhost::G_LOOKUP: case glhost::G_LOOKUP_TABLE: break;          // no main-trace constraints (lookup.rs:72-75)
-                case glhost::G_CONSTANT: cnt = 2; for (int i = 0; i < 2; i++) tmp[i] = e_sub(gate_consts[i], wires[i]); break;                        // constant.rs:59-66
-                case glhost::G_PUBLIC_INPUT: cnt = 4; for (int i = 0; i < 4; i++) tmp[i] = e_sub(wires[i], e_of(pi_hash[i])); break;                     // public_input.rs:44-49
-                case glhost::G_ARITHMETIC: cnt = 20;                                                                                                    // arithmetic_base.rs:72-92
-                    for (int i = 0; i < 20; i++) tmp[i] = e_sub(wires[4 * i + 3], e_add(e_mul(e_mul(wires[4 * i], wires[4 * i + 1]), gate_consts[0]), e_mul(wires[4 * i + 2], gate_consts[1])));
-                    break;
-                case glhost::G_BASE_SUM: {                                                                                                              // base_sum.rs:63-76, B = 2
-                    cnt = 1 + glhost::BASE_SUM_LIMBS;
-                    E computed = e_of(0);                                                                                                                // reduce_with_powers(limbs, 2)
-                    for (int i = glhost::BASE_SUM_LIMBS; i-- > 0;) computed = e_add(e_add(computed, computed), wires[1 + i]);
-                    tmp[0] = e_sub(computed, wires[0]);
-                    for (int i = 0; i < glhost::BASE_SUM_LIMBS; i++) tmp[1 + i] = e_mul(wires[1 + i], e_sub(wires[1 + i], e_of(1)));
-                    break;
-                }
-                case glhost::G_RANDOM_ACCESS: {                                                                                                         // random_access.rs:139-184
-                    const glhost::RandomAccessLayout ra(d.gate_params[g]);
-                    for (uint32_t copy = 0; copy < ra.num_copies; copy++) {
-                        std::vector<E> items(ra.vec_size);
-                        for (uint32_t i = 0; i < ra.vec_size; i++) items[i] = wires[ra.wire_list_item(i, copy)];
-                        for (uint32_t i = 0; i < ra.bits; i++) { const E b = wires[ra.wire_bit(i, copy)]; tmp[cnt++] = e_mul(b, e_sub(b, e_of(1))); }
-                        E rec = e_of(0);
-                        for (uint32_t i = ra.bits; i-- > 0;) rec = e_add(e_add(rec, rec), wires[ra.wire_bit(i, copy)]);
-                        tmp[cnt++] = e_sub(rec, wires[ra.wire_access_index(copy)]);
-                        for (uint32_t i = 0; i < ra.bits; i++) {                                                                                         // fold the list by bit i
-                            const E b = wires[ra.wire_bit(i, copy)];
-                            for (size_t j = 0; 2 * j + 1 < items.size(); j++) items[j] = e_add(items[2 * j], e_mul(b, e_sub(items[2 * j + 1], items[2 * j])));
-                            items.resize(items.size() / 2);
-                        }
-                        tmp[cnt++] = e_sub(items[0], wires[ra.wire_claimed_element(copy)]);
-                    }
-                    for (uint32_t i = 0; i < ra.num_extra_constants; i++) tmp[cnt++] = e_sub(gate_consts[i], wires[ra.wire_extra_constant(i)]);
-                    break;
-                }
-                case glhost::G_EXPONENTIATION: {                                                                                                        // exponentiation.rs:88-124
-                    const int n = glhost::EXP_POWER_BITS;
-                    cnt = n + 1;
-                    for (int i = 0; i < n; i++) {                                                                                                        // square-and-multiply, bits big-endian
-                        const E prev = i == 0 ? e_of(1) : e_mul(wires[2 + n + i - 1], wires[2 + n + i - 1]);
-                        const E bit = wires[1 + (n - 1 - i)];
-                        tmp[i] = e_sub(e_mul(prev, e_add(e_mul(bit, wires[0]), e_sub(e_of(1), bit))), wires[2 + n + i]);
-                    }
-                    tmp[n] = e_sub(wires[1 + n], wires[2 + n + n - 1]);
-                    break;
-                }
-                // The extension-field gates: at zeta every wire is itself in F_p^2, so a wire pair is an element (A0, A1) of the ExtensionAlgebra
-                // F_p^2[X]/(X^2 - 7) (field/src/extension/algebra.rs:113-131: W = 7 embedded), and a constraint's two components enter the sum
-                // in order (to_basefield_array).
-                case glhost::G_ARITHMETIC_EXT: {                                                                                                        // arithmetic_extension.rs:68-90
-                    for (int i = 0; i < glhost::ARITH_EXT_OPS; i++) {
-                        const E* w = wires.data() + 8 * i;                                                                                               // m0, m1, addend, output
-                        const Alg prod = alg_mul(Alg{w[0], w[1]}, Alg{w[2], w[3]});
-                        tmp[cnt++] = e_sub(w[6], e_add(e_mul(prod.a, gate_consts[0]), e_mul(w[4], gate_consts[1])));
-                        tmp[cnt++] = e_sub(w[7], e_add(e_mul(prod.b, gate_consts[0]), e_mul(w[5], gate_consts[1])));
-                    }
-                    break;
-                }
-                case glhost::G_MUL_EXT: {                                                                                                               // multiplication_extension.rs:65-84
-                    for (int i = 0; i < glhost::MUL_EXT_OPS; i++) {
-                        const E* w = wires.data() + 6 * i;                                                                                               // m0, m1, output
-                        const Alg prod = alg_mul(Alg{w[0], w[1]}, Alg{w[2], w[3]});
-                        tmp[cnt++] = e_sub(w[4], e_mul(prod.a, gate_consts[0]));
-                        tmp[cnt++] = e_sub(w[5], e_mul(prod.b, gate_consts[0]));
-                    }
-                    break;
-                }
-                case glhost::G_REDUCING: case glhost::G_REDUCING_EXT: {                                                          // reducing.rs:77-103, reducing_extension.rs:80-104
-                    // wires 0-1 output, 2-3 alpha, 4-5 old_acc, the coefficients (one wire each / two wires each), the accumulators; the last
-                    // accumulator is the output
-                    const bool ext = d.gate_types[g] == glhost::G_REDUCING_EXT;
-                    const int nc = ext ? glhost::REDUCING_EXT_COEFFS : glhost::REDUCING_COEFFS, acc0 = 6 + (ext ? 2 : 1) * nc;
-                    const Alg alpha{wires[2], wires[3]};
-                    Alg acc{wires[4], wires[5]};
-                    for (int i = 0; i < nc; i++) {
-                        const int aw = i == nc - 1 ? 0 : acc0 + 2 * i;
-                        const Alg acc_i{wires[aw], wires[aw + 1]};
-                        const Alg coeff = ext ? Alg{wires[6 + 2 * i], wires[7 + 2 * i]} : Alg{wires[6 + i], e_of(0)};
-                        const Alg t = alg_mul(acc, alpha);
-                        tmp[cnt++] = e_sub(e_add(t.a, coeff.a), acc_i.a);
-                        tmp[cnt++] = e_sub(e_add(t.b, coeff.b), acc_i.b);
-                        acc = acc_i;
-                    }
-                    break;
-                }
-                default: cnt = 123; poseidon_gate_constraints(wires.data(), tmp); break;
-            }
+            const size_t cnt = gate_constraints_at(d.gate_types[g], d.gate_params[g], wires.data(), gate_consts, pi_hash, tmp);
+            // the function and the table are two statements of one fact
+            GL_REQUIRE(cnt == glhost::gate_num_constraints(d.gate_types[g], d.gate_params[g]), GL_ERR_INTERNAL, "gl_verify: a gate's constraint count differs from its row of the gate table");
             for (size_t j = 0; j < cnt; j++) gate_terms[j] = e_add(gate_terms[j], e_mul(filter, tmp[j]));
         }
         for (size_t c = 0; c < nch; c++) {

@@ -220,9 +220,78 @@ def test_a_gate_list_out_of_the_builders_order_is_refused():
 
 
 def test_gate_type_constants_are_exported():
-    from plonky2_demo_amd import api
+    # all fourteen codes of the C enum (csrc/gates.hpp, the one place that defines them) against the names _lib.py spells out
+    import re
+    from plonky2_demo_amd import _lib, api
     assert (api.G_ARITHMETIC_EXT, api.G_MUL_EXT, api.G_REDUCING, api.G_REDUCING_EXT) == (10, 11, 12, 13)
     assert (ARITHMETIC_EXT, MUL_EXT, REDUCING, REDUCING_EXT) == (10, 11, 12, 13)
+    with open(os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "csrc", "gates.hpp")) as f:
+        enum = re.search(r"enum \{ (G_NOOP = 0,.*?G_LAST = (\w+)) \};", f.read(), re.S)
+    codes = {name: int(value) for name, value in re.findall(r"(G_\w+) = (\d+)", enum.group(1))}
+    assert len(codes) == 14 and sorted(codes.values()) == list(range(14)) and codes[enum.group(2)] == 13
+    assert {name: getattr(_lib, name) for name in codes} == codes
+    assert sorted(n for n in vars(_lib) if re.fullmatch(r"G_[A-Z_]+", n)) == sorted(codes)
+
+
+# ---- the gate table (csrc/gates.hpp) against counts written from the reference, one gate type at a time ----
+NOOP, CONSTANT, PUBLIC_INPUT, ARITHMETIC, POSEIDON, BASE_SUM, LOOKUP, LOOKUP_TABLE, EXPONENTIATION, RANDOM_ACCESS = range(10)
+
+
+def _random_access_constraints(bits):
+    # RandomAccessGate::new_from_config and num_constraints (gates/random_access.rs:55-72, 285-288) under standard_recursion_config
+    vec = 1 << bits
+    copies = min(80 // (2 + vec), 135 // (2 + vec + bits))
+    return copies * (bits + 2) + min(80 - (2 + vec) * copies, 2)
+
+
+# num_constraints() of every gate in its new_from_config layout: constant.rs:88-90 (num_consts = 2), public_input.rs:89-91,
+# arithmetic_base.rs:119-121 (num_ops = 80 / 4), poseidon.rs:403-409 (12 x 7 full-round and 22 partial-round S-box inputs, 12 outputs, the
+# swap bit and its 4 deltas), base_sum.rs:144-146 (1 + 63 limbs), lookup.rs:72-75 and lookup_table.rs (none on the main trace),
+# exponentiation.rs:190-192 (66 + 1); the four extension gates from the model's own table.  The oracle has no call that returns a gate's
+# count (its gates answer num_constraints() only inside its own circuits), so the numbers are written out here from the reference's
+# source, a statement independent of the C++ table.  For the Constant and Arithmetic gates the serialiser takes the count from the
+# description, not from the row: the row's figure for those two is held by gl_verify's count check alone
+_NUM_CONSTRAINTS = {NOOP: 0, CONSTANT: 2, PUBLIC_INPUT: 4, ARITHMETIC: 80 // 4, POSEIDON: 12 * 7 + 22 + 12 + 1 + 4, BASE_SUM: 1 + 63, LOOKUP: 0,
+                    LOOKUP_TABLE: 0, EXPONENTIATION: 66 + 1, **egc.NUM_CONSTRAINTS}
+_TABLE_CASES = [(g, 0) for g in range(14) if g != RANDOM_ACCESS] + [(RANDOM_ACCESS, bits) for bits in range(1, 7)]
+
+
+def _one_gate_desc(gate, param):
+    """NoopGate and `gate` alone, one selector group, n = 8; a lookup gate brings its table and the table's other gate (the byte form
+    has no table without both).  In build()'s order: degree, then id ("LookupGate" < "LookupTableGate" < "NoopGate")."""
+    import copy
+    d = copy.copy(egc.isolated([ARITHMETIC_EXT], seed=1, rows_per_gate=1).desc)
+    lookups = gate in (LOOKUP, LOOKUP_TABLE)
+    gates = [LOOKUP, LOOKUP_TABLE, NOOP] if lookups else [NOOP] if gate == NOOP else [NOOP, gate]
+    d.num_gates, d.num_selectors = len(gates), 1
+    for i in range(16):
+        live = i < len(gates)
+        d.gate_types[i], d.gate_params[i] = (gates[i], param if gates[i] == gate else 0) if live else (0, 0)
+        d.gate_selector_index[i], d.gate_group_start[i], d.gate_group_end[i] = 0, 0, len(gates) if live else 0
+    if lookups:
+        d.num_luts, d.num_lookup_polys, d.num_lookup_selectors, d.lut_len[0] = 1, 7, 5, 3
+        for j, v in enumerate((0, 5, 1, 6, 2, 7)):
+            d.lut[j] = v
+        d.last_lut_row[0] = d.first_lut_row[0] = 4          # three entries fill one LookupTableGate row
+    d.num_constants = d.num_selectors + d.num_lookup_selectors + 2
+    return d
+
+
+@pytest.mark.parametrize("gate,param", _TABLE_CASES, ids=["type%d_param%d" % c for c in _TABLE_CASES])
+def test_gate_table_round_trips_and_counts_constraints_like_the_reference(gate, param):
+    from plonky2_demo_amd import api
+    d = _one_gate_desc(gate, param)
+    by = api.common_data_to_bytes(d)
+    back, used = api.common_data_from_bytes(by)
+    assert used == len(by) and api.common_data_to_bytes(back) == by
+    types = list(back.gate_types[:back.num_gates])
+    assert types == list(d.gate_types[:d.num_gates]) and gate in types and back.gate_params[types.index(gate)] == param
+    # num_gate_constraints: behind it come num_constants, num_public_inputs, the 80 k_is with their length, num_partial_products, the three
+    # lookup counts and the tables (a length and four bytes per entry each)
+    tail = 8 * (2 + 81 + 1 + 3) + sum(8 + 4 * d.lut_len[t] for t in range(d.num_luts))
+    want = _random_access_constraints(param) if gate == RANDOM_ACCESS else _NUM_CONSTRAINTS[gate]
+    assert int.from_bytes(by[-tail - 8:-tail], "little") == want
+    assert int.from_bytes(by[-tail - 16:-tail - 8], "little") == d.quotient_degree_factor      # (the word before it: the offset is right)
 
 
 def _fixture():

@@ -241,7 +241,8 @@ def test_common_data_writer_validates_its_description():
         with pytest.raises(p.Plonky2Mi355xError):
             api.common_data_to_bytes(d)
     d = copy.copy(hc.desc)
-    d.gate_types[0] = 10                                  # 0..9 are the supported gate types
+    from plonky2_demo_amd import _lib
+    d.gate_types[0] = max(v for n, v in vars(_lib).items() if n.startswith("G_")) + 1      # G_LAST + 1: the first code past the gate types
     with pytest.raises(p.Plonky2Mi355xError) as e:
         api.common_data_to_bytes(d)
     assert e.value.code == 3
