@@ -188,6 +188,22 @@ def test_ntt_large_sizes_round_trip(gpu, orc):
             assert (f == orc.fft(x)).all()
 
 
+@pytest.mark.parametrize("lg", [19, 21])
+def test_ntt_2_19_and_2_21_by_value_against_the_oracle(gpu, orc, lg):
+    # the two two-pass sizes above 2^18 that the round trip above checks only against themselves: 2^21 is the m = 128 LDE size and the only
+    # user of ntt_row_pass<11>.  Forward, inverse and coset forms on two columns, and at 2^21 the LDE from 2^18 with its zero padding.
+    p, ctx = gpu
+    x = rand_field(700 + lg, (2, 1 << lg))
+    assert (p.fft(x) == orc.fft(x)).all()
+    assert (p.ifft(x) == orc.ifft(x)).all()
+    s = 0x123456789ABCDEF % P
+    assert (p.coset_fft(x, s) == orc.coset_fft(x, s)).all()
+    assert (p.coset_fft(x) == orc.coset_fft(x, 7)).all()
+    if lg == 21:
+        c = rand_field(750 + lg, (2, 1 << (lg - 3)))
+        assert (p.lde_onto_coset(c, 3) == orc.lde(c, 3, threads=8)).all()
+
+
 @pytest.mark.parametrize("lg", [22, 23, 24])
 def test_ntt_three_pass_sizes_against_the_oracle(gpu, orc, lg):
     # from 2^22 points on the transform is nested: 2^9 / 2^10-point columns, then the M-point rows as a two-pass transform whose row pass
