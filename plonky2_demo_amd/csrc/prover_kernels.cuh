@@ -773,14 +773,8 @@ __global__ __launch_bounds__(256) void k_eval_at_ext(const gl_t* coeffs, uint32_
     if (t == 0) { out[2 * poly] = gl_canon(sha[0]); out[2 * poly + 1] = gl_canon(shb[0]); }
 }
 
-// table of powers of an extension element: out_a[i], out_b[i] = z^i, i < n
-__global__ __launch_bounds__(256) void k_ext_powers(gl_t za, gl_t zb, uint32_t n, gl_t* out_a, gl_t* out_b) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const gl2_t v = gl2_canon(gl2_exp(gl2_make(za, zb), i));
-    out_a[i] = v.a; out_b[i] = v.b;
-}
-// two points in one launch (grid.y = 2): out = [a(z0) | b(z0) | a(z1) | b(z1)], n entries each
+// tables of powers of two extension elements in one launch (grid.y = 2): out = [a(z0) | b(z0) | a(z1) | b(z1)], n entries each,
+// plane a / b of z^i at index i
 __global__ __launch_bounds__(256) void k_ext_powers2(gl_t z0a, gl_t z0b, gl_t z1a, gl_t z1b, uint32_t n, gl_t* out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -790,36 +784,9 @@ __global__ __launch_bounds__(256) void k_ext_powers2(gl_t z0a, gl_t z0b, gl_t z1
     o[i] = v.a; o[n + i] = v.b;
 }
 // p(z) = sum_i c_i z^i with the powers tabulated once per proof: two base-field multiply-adds per coefficient, coalesced
-// reads (thread t takes i = t, t + 256, ...).  grid = (npolys); block = 256.
-__global__ __launch_bounds__(256) void k_eval_with_powers(const gl_t* coeffs, uint32_t n, uint64_t stride, const gl_t* __restrict__ pa,
-                                                          const gl_t* __restrict__ pb, gl_t* out /* [npolys][2] */) {
-    __shared__ gl_t sha[256], shb[256];
-    const uint32_t poly = blockIdx.x, t = threadIdx.x;
-    const gl_t* c = coeffs + (uint64_t)poly * stride;
-    // four independent accumulator pairs and all loads of a step issued before the arithmetic: the chain is latency-bound otherwise
-    gl_t a0 = 0, b0 = 0, a1 = 0, b1 = 0, a2 = 0, b2 = 0, a3 = 0, b3 = 0;
-    uint32_t i = t;
-    for (; i + 768 < n; i += 1024) {
-        const gl_t c0 = c[i], c1 = c[i + 256], c2 = c[i + 512], c3 = c[i + 768];
-        const gl_t x0 = pa[i], x1 = pa[i + 256], x2 = pa[i + 512], x3 = pa[i + 768];
-        const gl_t y0 = pb[i], y1 = pb[i + 256], y2 = pb[i + 512], y3 = pb[i + 768];
-        a0 = gl_mul_add(a0, c0, x0); b0 = gl_mul_add(b0, c0, y0);
-        a1 = gl_mul_add(a1, c1, x1); b1 = gl_mul_add(b1, c1, y1);
-        a2 = gl_mul_add(a2, c2, x2); b2 = gl_mul_add(b2, c2, y2);
-        a3 = gl_mul_add(a3, c3, x3); b3 = gl_mul_add(b3, c3, y3);
-    }
-    for (; i < n; i += 256) { const gl_t ci = c[i]; a0 = gl_mul_add(a0, ci, pa[i]); b0 = gl_mul_add(b0, ci, pb[i]); }
-    sha[t] = gl_add(gl_add(a0, a1), gl_add(a2, a3)); shb[t] = gl_add(gl_add(b0, b1), gl_add(b2, b3));
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < (uint32_t)s) { sha[t] = gl_add(sha[t], sha[t + s]); shb[t] = gl_add(shb[t], shb[t + s]); }
-        __syncthreads();
-    }
-    if (t == 0) { out[2 * poly] = gl_canon(sha[0]); out[2 * poly + 1] = gl_canon(shb[0]); }
-}
-
-// the same for a LIST of polynomials in one launch: block j evaluates cols[j]; the first `n_first` at the point whose powers
-// are (pa, pb), the rest at the point of (pa2, pb2) -- all openings of a proof (255 at zeta, 2 at g zeta) behind one launch
+// reads (thread t takes i = t, t + 256, ...), for a LIST of polynomials in one launch.  grid = (npolys); block = 256: block j
+// evaluates cols[j]; the first `n_first` at the point whose powers are (pa, pb), the rest at the point of (pa2, pb2) -- all
+// openings of a proof (255 at zeta, 2 at g zeta) behind one launch
 __global__ __launch_bounds__(256) void k_eval_list_with_powers(const gl_t* const* __restrict__ cols, uint32_t n, uint32_t n_first,
                                                                const gl_t* __restrict__ pa, const gl_t* __restrict__ pb,
                                                                const gl_t* __restrict__ pa2, const gl_t* __restrict__ pb2, gl_t* out /* [npolys][2] */) {
@@ -827,6 +794,7 @@ __global__ __launch_bounds__(256) void k_eval_list_with_powers(const gl_t* const
     const uint32_t poly = blockIdx.x, t = threadIdx.x;
     const gl_t* c = cols[poly];
     if (poly >= n_first) { pa = pa2; pb = pb2; }
+    // four independent accumulator pairs and all loads of a step issued before the arithmetic: the chain is latency-bound otherwise
     gl_t a0 = 0, b0 = 0, a1 = 0, b1 = 0, a2 = 0, b2 = 0, a3 = 0, b3 = 0;
     uint32_t i = t;
     for (; i + 768 < n; i += 1024) {
