@@ -10,6 +10,7 @@ import pytest
 
 import ext_gate_circuits as egc
 from ext_gate_circuits import ARITHMETIC_EXT, MUL_EXT, REDUCING, REDUCING_EXT, P
+from transcript import drive_phase_api, poseidon_challenger
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 NEW_GATES = [ARITHMETIC_EXT, MUL_EXT, REDUCING, REDUCING_EXT]
@@ -94,53 +95,13 @@ def test_all_four_gates_chained_in_one_circuit(gpu, degree_bits, hasher):
 
 @pytest.mark.gpu
 def test_phase_api_with_external_transcript_on_the_chained_circuit(gpu, orc):
-    # the pattern of test_phase_api_with_external_transcript_reproduces_the_proof: gl_quotient_polys reaches the same launch as gl_prove
-    from test_gpu_parity import _Challenger
+    # gl_quotient_polys reaches the same launch as gl_prove
     p, ctx = gpu
     c = egc.Chained(seed=4).circuit
     cd = _build(p, c, ctx)
-    wires, d, n = c.wires(), c.desc, c.n
-    N = n << 3
-    d_w = ctx.alloc(wires.nbytes).upload(wires)
-    ch = _Challenger(orc)
-    pi_hash = [0, 0, 0, 0]                                              # hash_no_pad of no public inputs
-    ch.observe(cd.circuit_digest); ch.observe(pi_hash)
-    wires_b = p.PolynomialBatch.from_device(d_w.ptr, 135, n, d.rate_bits, d.cap_height, True)
-    ch.observe(wires_b.cap)
-    betas, gammas = ch.get(2), ch.get(2)
-    zs_b = cd.partial_products(d_w.ptr, betas, gammas)
-    ch.observe(zs_b.cap)
-    alphas = ch.get(2)
-    q_b = cd.quotient_polys(wires_b, zs_b, pi_hash, betas, gammas, alphas)
-    ch.observe(q_b.cap)
-    zeta = ch.get(2)
-    g = orc.primitive_root(d.degree_bits)
-    gzeta = [zeta[0] * g % P, zeta[1] * g % P]
-    cs_b = cd.constants_sigmas_batch
-    o_cs, o_w, o_z, o_q = cs_b.open_at(zeta), wires_b.open_at(zeta), zs_b.open_at(zeta), q_b.open_at(zeta)
-    o_next = zs_b.open_at(gzeta, 0, 2)
-    for o in (o_cs, o_w, o_z, o_q, o_next):
-        ch.observe(o)
-    fri = cd.fri([cs_b, wires_b, zs_b, q_b], zeta, ch.get(2))
-    fri_caps = []
-    for _ in range(d.num_fri_rounds):
-        cap = fri.commit_round()
-        fri_caps.append(cap)
-        ch.observe(cap)
-        fri.fold(ch.get(2))
-    fin = fri.final_poly()
-    ch.observe(fin)
-    w = p.pow_grind(ch.state, ch.inp, d.proof_of_work_bits)
-    ch.observe([w])
-    assert ch.get(1)[0] >> (64 - d.proof_of_work_bits) == 0
-    blob = fri.query([ch.get(1)[0] % N for _ in range(d.num_query_rounds)])
-
-    le = lambda arr: np.ascontiguousarray(np.asarray(arr, dtype="<u8")).tobytes()
-    by = le(wires_b.cap) + le(zs_b.cap) + le(q_b.cap)
-    by += le(o_cs) + le(o_w) + le(o_z[:2]) + le(o_next) + le(o_z[2:]) + le(o_q)       # util/serialization/mod.rs:1409-1423
-    by += b"".join(le(x) for x in fri_caps) + blob + le(fin) + le([w]) + le([0])
-    assert by == cd.prove(wires, _NO_PIS).to_bytes()
-    assert cd.verify(by) == (True, "")
+    r = drive_phase_api(p, ctx, orc, cd, poseidon_challenger(orc), c.wires(), _NO_PIS)
+    assert r.bytes == cd.prove(c.wires(), _NO_PIS).to_bytes()
+    assert cd.verify(r.bytes) == (True, "")
 
 
 @pytest.mark.gpu

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from oracle_lib import P, rand_field
+from transcript import LibraryChallenger, drive_phase_api, poseidon_challenger
 
 pytestmark = pytest.mark.gpu
 
@@ -528,123 +529,30 @@ def test_prove_m256_the_largest_size_the_abi_takes(gpu):
 
 
 # ------------------------------------------------------------------------------- phase-level ABI (SURVEY 8b seam)
-class _ProductChallenger:
-    """The same interface over the library's own gl_challenger_* (for callers without a transcript implementation)."""
-
-    def __init__(self, p):
-        self.ch = p.Challenger()
-
-    def observe(self, xs):
-        self.ch.observe_elements(xs)
-
-    def get(self, k):
-        return self.ch.get_n_challenges(k)
-
-    @property
-    def state(self):
-        return self.ch.state()[0]
-
-    @property
-    def inp(self):
-        return self.ch.state()[1]
-
-
-class _Challenger:
-    """iop/challenger.rs:30-153 as the reference-side caller would keep it (here in Python, permutation from the oracle)."""
-
-    def __init__(self, orc):
-        self.orc, self.state, self.inp, self.out = orc, [0] * 12, [], []
-
-    def _duplex(self):
-        for i, x in enumerate(self.inp):
-            self.state[i] = x
-        self.inp = []
-        self.state = [int(x) for x in self.orc.poseidon(np.array(self.state, dtype=np.uint64))]
-        self.out = self.state[:8]
-
-    def observe(self, xs):
-        for x in np.asarray(xs, dtype=np.uint64).reshape(-1):
-            self.out = []
-            self.inp.append(int(x))
-            if len(self.inp) == 8:
-                self._duplex()
-
-    def get(self, k):
-        r = []
-        for _ in range(k):
-            if self.inp or not self.out:
-                self._duplex()
-            r.append(self.out.pop() % P)
-        return r
-
-
 @pytest.mark.parametrize("m,own", [(2, False), (8, False), (20, False), (8, True), (20, True)])
 def test_phase_api_with_external_transcript_reproduces_the_proof(gpu, orc, m, own):
-    # every phase entry point of include/plonky2_mi355x.h driven by a caller-side Challenger, in the order of
-    # plonk/prover.rs:102-329; the assembled ProofWithPublicInputs bytes equal the oracle's (and gl_prove's)
+    # the phase entry points driven by a caller-side Challenger (the model, or the library's own): the assembled ProofWithPublicInputs
+    # bytes equal the oracle's (and gl_prove's)
     p, ctx = gpu
     hc = p.MatmulCircuit(m)
-    n, N, d = hc.n, hc.n << 3, hc.desc
     a, b = rand_field(7000 + m, m * m) % (2**32 - 1), rand_field(7001 + m, m * m) % (2**32 - 1)
     wires, pis = hc.witness(a, b, filler_seed=m)
     cd = hc.build()
     op = orc.circuit(m, threads=8).witness(a, b, filler_seed=m).prove(threads=8)
 
-    d_w = ctx.alloc(wires.nbytes).upload(wires)
-    ch = _ProductChallenger(p) if own else _Challenger(orc)
-    pi_hash = orc.hash_no_pad(pis)
-    ch.observe(cd.circuit_digest); ch.observe(pi_hash)
-    wires_b = p.PolynomialBatch.from_device(d_w.ptr, 135, n, d.rate_bits, d.cap_height, True)
-    ch.observe(wires_b.cap)
-    betas, gammas = ch.get(2), ch.get(2)
-    zs_b = cd.partial_products(d_w.ptr, betas, gammas)
-    assert (d_w.download(wires.shape) == wires).all()                  # the witness matrix is left untouched
-    ch.observe(zs_b.cap)
-    alphas = ch.get(2)
-    q_b = cd.quotient_polys(wires_b, zs_b, pi_hash, betas, gammas, alphas)
-    assert (q_b.polynomials == op.quotient_chunks()).all()
-    ch.observe(q_b.cap)
-    zeta = ch.get(2)
-    g = orc.primitive_root(hc.degree_bits)
-    gzeta = [zeta[0] * g % P, zeta[1] * g % P]
-    cs_b = cd.constants_sigmas_batch
-    o_cs, o_w, o_z, o_q = cs_b.open_at(zeta), wires_b.open_at(zeta), zs_b.open_at(zeta), q_b.open_at(zeta)
-    o_next = zs_b.open_at(gzeta, 0, 2)
-    assert (zs_b.open_at(zeta, 2, 18) == o_z[2:]).all()
-    for o in (o_cs, o_w, o_z, o_q, o_next):
-        ch.observe(o)
-    fri_alpha = ch.get(2)
-    fri = cd.fri([cs_b, wires_b, zs_b, q_b], zeta, fri_alpha)
-    fri_caps = []
+    r = drive_phase_api(p, ctx, orc, cd, LibraryChallenger(p) if own else poseidon_challenger(orc), wires, pis)
+    assert (r.d_wires.download(wires.shape) == wires).all()            # the witness matrix is left untouched
+    assert (r.q_b.polynomials == op.quotient_chunks()).all()
+    assert (r.zs_b.open_at(r.zeta, 2, 18) == r.openings["pp"]).all()
     with pytest.raises(p.Plonky2Mi355xError):
-        fri.fold([1, 0])                                                    # fold before commit
-    for _ in range(d.num_fri_rounds):
-        cap = fri.commit_round()
-        fri_caps.append(cap)
-        ch.observe(cap)
-        fri.fold(ch.get(2))
+        cd.fri(r.batches, r.zeta, r.fri_alpha).fold([1, 0])                # fold before commit
     with pytest.raises(p.Plonky2Mi355xError):
-        fri.commit_round()                                                  # no round left
-    fin = fri.final_poly()
-    ch.observe(fin)
-    w = p.pow_grind(ch.state, ch.inp, d.proof_of_work_bits)
-    ch.observe([w])
-    resp = ch.get(1)[0]
-    assert resp >> (64 - d.proof_of_work_bits) == 0
-    x_index = [ch.get(1)[0] % N for _ in range(d.num_query_rounds)]
-    blob = fri.query(x_index)
-
-    le = lambda arr: np.ascontiguousarray(np.asarray(arr, dtype="<u8")).tobytes()
-    by = le(wires_b.cap) + le(zs_b.cap) + le(q_b.cap)
-    by += le(o_cs) + le(o_w) + le(o_z[:2]) + le(o_next) + le(o_z[2:]) + le(o_q)       # util/serialization/mod.rs:1409-1423
-    by += b"".join(le(c) for c in fri_caps) + blob + le(fin) + le([w]) + le([pis.size]) + le(pis)
+        r.fri.commit_round()                                                # no round left
     ob = op.to_bytes()
-    assert len(by) == len(ob)
-    assert by == ob
-    assert by == cd.prove(wires, pis).to_bytes()
-    assert op.challenges()["pow_witness"] == w and op.query_indices() == x_index
-    for h in (fri, q_b, zs_b, wires_b):
-        del h
+    assert len(r.bytes) == len(ob)
+    assert r.bytes == ob
+    assert r.bytes == cd.prove(wires, pis).to_bytes()
+    assert op.challenges()["pow_witness"] == r.pow_witness and op.query_indices() == r.x_index
 
 
 # ------------------------------------------------------------------------------- witness generation in HBM (SURVEY 8f-3)
@@ -1165,67 +1073,22 @@ def test_lookup_rows_come_from_the_selector_columns(gpu, orc):
 
 
 def test_phase_api_on_a_lookup_circuit_with_an_external_transcript(gpu, orc):
-    # the phase-level seam for a circuit WITH lookups: gl_partial_products_lookups / gl_quotient_polys_lookups take the delta challenges
-    # ([betas | gammas | 4 drawn after them], prover.rs:166-184); openings in FriOpenings order with the lookup polynomials last in both
-    # batches (proof.rs:346-380); OpeningSet bytes with the lookup vectors between zs_next and the partial products (mod.rs:1409-1423).
+    # the phase-level seam for a circuit WITH lookups: gl_partial_products_lookups / gl_quotient_polys_lookups take the delta challenges.
     # The bytes assembled by the caller equal gl_prove's and the oracle's.
     p, ctx = gpu
     oc = orc.circuit_of_kind(8, 50, threads=8)
     w = oc.witness(np.arange(3, 53, dtype=np.uint64), np.zeros(0, dtype=np.uint64), filler_seed=9)
     wires, pis = w.wires(), w.public_inputs()
     op = w.prove(threads=8)
-    d = oc.product_desc()
-    cd = p.GenericCircuitData(d, oc.constants_sigmas())
-    n, N = 1 << d.degree_bits, 1 << (d.degree_bits + 3)
-    d_w = ctx.alloc(wires.nbytes).upload(wires)
-    ch = _Challenger(orc)
-    pi_hash = orc.hash_no_pad(pis)
-    ch.observe(cd.circuit_digest); ch.observe(pi_hash)
-    wires_b = p.PolynomialBatch.from_device(d_w.ptr, 135, n, d.rate_bits, d.cap_height, True)
-    ch.observe(wires_b.cap)
-    betas, gammas = ch.get(2), ch.get(2)
-    deltas = list(betas) + list(gammas) + list(ch.get(4))
+    cd = p.GenericCircuitData(oc.product_desc(), oc.constants_sigmas())
+    r = drive_phase_api(p, ctx, orc, cd, poseidon_challenger(orc), wires, pis)
     with pytest.raises(p.Plonky2Mi355xError):
-        cd.partial_products(d_w.ptr, betas, gammas)                        # a lookup circuit needs the deltas
-    zs_b = cd.partial_products(d_w.ptr, betas, gammas, deltas=deltas)
-    assert zs_b.polynomials.shape[0] == 34
-    ch.observe(zs_b.cap)
-    alphas = ch.get(2)
-    q_b = cd.quotient_polys(wires_b, zs_b, pi_hash, betas, gammas, alphas, deltas=deltas)
-    assert (q_b.polynomials == op.quotient_chunks()).all()
-    ch.observe(q_b.cap)
-    zeta = ch.get(2)
-    g = orc.primitive_root(d.degree_bits)
-    gzeta = [zeta[0] * g % P, zeta[1] * g % P]
-    cs_b = cd.constants_sigmas_batch
-    o_cs, o_w, o_z, o_q = cs_b.open_at(zeta), wires_b.open_at(zeta), zs_b.open_at(zeta), q_b.open_at(zeta)
-    o_next = zs_b.open_at(gzeta)
-    for o in (o_cs, o_w, o_z[:20], o_q, o_z[20:], o_next[:2], o_next[20:]):
-        ch.observe(o)
-    fri_alpha = ch.get(2)
-    fri = cd.fri([cs_b, wires_b, zs_b, q_b], zeta, fri_alpha)
-    fri_caps = []
-    for _ in range(d.num_fri_rounds):
-        cap = fri.commit_round()
-        fri_caps.append(cap)
-        ch.observe(cap)
-        fri.fold(ch.get(2))
-    fin = fri.final_poly()
-    ch.observe(fin)
-    pw = p.pow_grind(ch.state, ch.inp, d.proof_of_work_bits)
-    ch.observe([pw])
-    assert ch.get(1)[0] >> (64 - d.proof_of_work_bits) == 0
-    x_index = [ch.get(1)[0] % N for _ in range(d.num_query_rounds)]
-    blob = fri.query(x_index)
-    le = lambda arr: np.ascontiguousarray(np.asarray(arr, dtype="<u8")).tobytes()
-    by = le(wires_b.cap) + le(zs_b.cap) + le(q_b.cap)
-    by += le(o_cs) + le(o_w) + le(o_z[:2]) + le(o_next[:2]) + le(o_z[20:]) + le(o_next[20:]) + le(o_z[2:20]) + le(o_q)
-    by += b"".join(le(c) for c in fri_caps) + blob + le(fin) + le([pw]) + le([pis.size]) + le(pis)
-    assert by == op.to_bytes()
-    assert by == cd.prove(wires, pis).to_bytes()
-    assert cd.verify(by) == (True, "")
-    for h in (fri, q_b, zs_b, wires_b):
-        del h
+        cd.partial_products(r.d_wires.ptr, r.betas, r.gammas)              # a lookup circuit needs the deltas
+    assert r.zs_b.polynomials.shape[0] == 34
+    assert (r.q_b.polynomials == op.quotient_chunks()).all()
+    assert r.bytes == op.to_bytes()
+    assert r.bytes == cd.prove(wires, pis).to_bytes()
+    assert cd.verify(r.bytes) == (True, "")
 
 
 def test_prover_pool_matches_individual_proofs(gpu):

@@ -4,7 +4,7 @@ transcript and proof of work.
 PARITY UNPINNED against Rust: the reference holds no Keccak known-answer vector and there is no Rust toolchain, so what stands in for the
 oracle is the independent model in THIS file -- a numpy Keccak-f[1600] sponge (round constants from the LFSR, rotation offsets from the
 (x, y) walk: no table shared with csrc/keccak.cuh), checked against hashlib.sha3_256 and the two published Keccak-256 digests, and on top
-of it hash_or_noop, two_to_one, hash_pad, Merkle trees, KeccakPermutation and a Challenger restated from the reference's sources."""
+of it hash_or_noop, two_to_one, hash_pad, Merkle trees, KeccakPermutation and (over the duplex model of tests/transcript.py) a Challenger restated from the reference's sources."""
 import ctypes
 import hashlib
 import json
@@ -15,7 +15,8 @@ import numpy as np
 import pytest
 
 from oracle_lib import P, rand_field
-from proof_parser import ParsedProof
+from proof_parser import NUM_WIRES, ParsedProof, leaf_lens, opening_columns
+from transcript import DuplexChallenger, LibraryChallenger, drive_phase_api, public_inputs_hash, replay_transcript
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U64 = np.uint64
@@ -199,37 +200,9 @@ def model_permute(state):
     return filter_words(words, 12)[0]
 
 
-class ModelChallenger:
-    """iop/challenger.rs:30-153 over KeccakPermutation."""
-
-    def __init__(self):
-        self.state, self.inp, self.out = [0] * 12, [], []
-
-    def dup(self):
-        for i, x in enumerate(self.inp):
-            self.state[i] = x
-        self.inp = []
-        self.state = model_permute(self.state)
-        self.out = self.state[:8]
-
-    def observe(self, xs):
-        for x in np.asarray(xs, dtype=U64).reshape(-1):
-            self.out = []
-            self.inp.append(int(x) % P)
-            if len(self.inp) == 8:
-                self.dup()
-
-    def observe_hashes(self, digests):
-        for h in model_hash_elements(digests):
-            self.observe(np.array(h, dtype=U64))
-
-    def get(self, k):
-        r = []
-        for _ in range(k):
-            if self.inp or not self.out:
-                self.dup()
-            r.append(self.out.pop())
-        return r
+def model_challenger():
+    """iop/challenger.rs:30-153 over KeccakPermutation; a BytesHash<25> is observed as its four chunks."""
+    return DuplexChallenger(model_permute, model_hash_elements)
 
 
 def model_pow_responses(state, pos, candidates):
@@ -312,7 +285,7 @@ def test_keccak_challenger_matches_the_model():
     # a script that crosses the rate several times, mixes elements, a Poseidon hash (4 elements) and Keccak hashes (7/7/7/4 bytes), and
     # asks for more than 8 challenges in a row
     import plonky2_demo_amd as p
-    ch, mo = p.Challenger(hasher=KECCAK), ModelChallenger()
+    ch, mo = p.Challenger(hasher=KECCAK), model_challenger()
     rng = np.random.default_rng(7)
     pi_hash = rand_field(9, 4)
     cap = model_hash_no_pad(noncanonical_rows(11, 16, 30))
@@ -482,7 +455,7 @@ def test_gpu_pow_grind_finds_the_smallest_witness(gpu):
             valid += [int(c) for c, r in zip(cand, resp) if int(r) >> (64 - bits) == 0]
         assert valid == [w], (nbuf, bits, w, valid[:3])
         # the Challenger agrees: observing the witness yields a response with the leading zeros
-        mo = ModelChallenger()
+        mo = model_challenger()
         mo.state, mo.inp = [x % P for x in [int(v) for v in state]], [int(x) % P for x in buf]
         mo.observe(np.array([w], dtype=U64))
         assert mo.get(1)[0] >> (64 - bits) == 0
@@ -500,43 +473,10 @@ def num_hashes(d):
 
 
 def poseidon_proof_len(d, npis):
-    lgN, nlp, salt = d.degree_bits + d.rate_bits, d.num_lookup_polys, 4 if d.zero_knowledge else 0
-    openings = d.num_constants + 80 + 135 + 2 + 2 + 4 * nlp + 18 + 16
-    leaf_words = (d.num_constants + 80) + (135 + salt) + (20 + 2 * nlp + salt) + (16 + salt)
+    openings, leaf_words = sum(k for _, k in opening_columns(d)), sum(leaf_lens(d))
     final_len = (1 << d.degree_bits) >> sum(d.fri_arity_bits[r] for r in range(d.num_fri_rounds))
     per_query = 8 * leaf_words + 4 + sum(8 * (2 << d.fri_arity_bits[r]) + 1 for r in range(d.num_fri_rounds))
     return 32 * num_hashes(d) + 16 * openings + d.num_query_rounds * per_query + 16 * final_len + 8 + 8 + 8 * npis
-
-
-def replay_transcript(d, digest, pi_hash, pp):
-    """prover.rs:158-227,273,298 / fri/prover.rs:91-93,111,153 on the MODEL Challenger: (challenges as Proof.challenges() gives them, PoW
-    response, query indices).  The native verifier shares HostChallenger with the prover, so this replay is what pins the transcript."""
-    ch = ModelChallenger()
-    ch.observe_hashes(digest)
-    ch.observe(pi_hash)                                              # C::InnerHasher = Poseidon: four elements
-    ch.observe_hashes(pp.caps[0])
-    betas, gammas = ch.get(2), ch.get(2)
-    if d.num_lookup_polys:
-        ch.get(4)
-    ch.observe_hashes(pp.caps[1])
-    alphas = ch.get(2)
-    ch.observe_hashes(pp.caps[2])
-    zeta = ch.get(2)
-    o = pp.openings
-    for name in ("constants", "sigmas", "wires", "zs", "pp", "quotient", "lookups", "zs_next", "lookups_next"):      # FriOpenings order (proof.rs:346-380)
-        ch.observe(o[name])
-    fri_alpha = ch.get(2)
-    fri_betas = []
-    for cap in pp.fri_caps:
-        ch.observe_hashes(cap)
-        fri_betas.append(ch.get(2))
-    ch.observe(pp.final_poly)
-    ch.observe(np.array([pp.pow_witness], dtype=U64))
-    response = ch.get(1)[0]
-    N = 1 << (d.degree_bits + d.rate_bits)
-    x_index = [ch.get(1)[0] % N for _ in range(d.num_query_rounds)]
-    return {"betas": betas, "gammas": gammas, "alphas": alphas, "zeta": zeta, "fri_alpha": fri_alpha, "pow_witness": pp.pow_witness,
-            "public_inputs_hash": [int(x) for x in pi_hash], "fri_betas": fri_betas}, response, x_index
 
 
 def check_query_paths(d, pp, cs_cap, x_index, rounds):
@@ -568,8 +508,7 @@ def check_keccak_proof(p, orc, cd, d, proof, pis, wires=None, expect_caps=True):
     # 2. independent transcript
     pp = ParsedProof(d, by)
     assert (pp.public_inputs == np.asarray(pis, dtype=U64)).all() and all((pp.caps[i] == proof.caps()[i]).all() for i in range(3))
-    pi_hash = orc.hash_no_pad(pis) if len(pis) else np.zeros(4, dtype=U64)
-    chal, response, x_index = replay_transcript(d, cd.circuit_digest, pi_hash, pp)
+    chal, response, x_index, _ = replay_transcript(d, model_challenger(), cd.circuit_digest, public_inputs_hash(orc, pis), pp)
     assert chal == proof.challenges()
     assert response >> (64 - d.proof_of_work_bits) == 0
     assert x_index == proof.query_indices()
@@ -663,10 +602,10 @@ def test_keccak_proof_tampering_is_rejected_with_the_check_named(gpu, orc):
     assert cd.verify(by) == (True, "")
     ncap, lgN = 1 << d.cap_height, d.degree_bits + d.rate_bits
     o_open = 3 * ncap * 25
-    o_fcaps = o_open + 16 * (d.num_constants + 80 + 135 + 2 + 2 + 18 + 16)
+    o_fcaps = o_open + 16 * sum(k for _, k in opening_columns(d))
     o_query = o_fcaps + d.num_fri_rounds * ncap * 25
     o_leaf0 = o_query                                                # first initial leaf (constants || sigmas row)
-    o_sib0 = o_leaf0 + 8 * (d.num_constants + 80) + 1                # its first sibling
+    o_sib0 = o_leaf0 + 8 * leaf_lens(d)[0] + 1                       # its first sibling
     o_pow = len(by) - 8 * len(pis) - 16
 
     def verdict(pos, bit=0):
@@ -697,65 +636,23 @@ def test_keccak_proof_tampering_is_rejected_with_the_check_named(gpu, orc):
 
 @pytest.mark.gpu
 def test_keccak_phase_api_with_an_external_transcript(gpu, orc):
-    # the shape of test_phase_api_on_a_lookup_circuit_with_an_external_transcript with the new challenger and grind entries: the bytes
-    # assembled by the caller equal gl_prove's
+    # the lookup circuit of test_phase_api_on_a_lookup_circuit_with_an_external_transcript under desc.hasher = 1, with the library's
+    # challenger and the Keccak grind entry: the bytes assembled by the caller equal gl_prove's
     p, ctx = gpu
     oc, w = oracle_case(orc, 8, 50)
     d = oc.product_desc()
     d.hasher = 1
     cd = p.GenericCircuitData(d, oc.constants_sigmas(), ctx)
     wires, pis = w.wires(), w.public_inputs()
-    n, N = 1 << d.degree_bits, 1 << (d.degree_bits + 3)
-    d_w = ctx.alloc(wires.nbytes).upload(wires)
-    ch = p.Challenger(hasher=KECCAK)
-    pi_hash = orc.hash_no_pad(pis)
-    ch.observe_hashes(cd.circuit_digest); ch.observe_hashes(pi_hash, hasher="poseidon")
-    poseidon_wires = p.PolynomialBatch.from_device(d_w.ptr, 135, n, d.rate_bits, d.cap_height, True, ctx=ctx)
-    wires_b = p.PolynomialBatch.from_device(d_w.ptr, 135, n, d.rate_bits, d.cap_height, True, ctx=ctx, hasher=KECCAK)
-    ch.observe_hashes(wires_b.cap)
-    betas, gammas = ch.get_n_challenges(2), ch.get_n_challenges(2)
-    deltas = betas + gammas + ch.get_n_challenges(4)
-    zs_b = cd.partial_products(d_w.ptr, betas, gammas, deltas=deltas)
-    assert zs_b.hasher == 1
-    ch.observe_hashes(zs_b.cap)
-    alphas = ch.get_n_challenges(2)
+    r = drive_phase_api(p, ctx, orc, cd, LibraryChallenger(p, KECCAK), wires, pis)
+    assert r.zs_b.hasher == 1
+    poseidon_wires = p.PolynomialBatch.from_device(r.d_wires.ptr, NUM_WIRES, cd.n, d.rate_bits, d.cap_height, True, ctx=ctx)
     with pytest.raises(p.Plonky2Mi355xError):                         # mixing hashers is GL_ERR_ARG
-        cd.quotient_polys(poseidon_wires, zs_b, pi_hash, betas, gammas, alphas, deltas=deltas)
-    q_b = cd.quotient_polys(wires_b, zs_b, pi_hash, betas, gammas, alphas, deltas=deltas)
-    ch.observe_hashes(q_b.cap)
-    zeta = ch.get_n_challenges(2)
-    g = orc.primitive_root(d.degree_bits)
-    gzeta = [zeta[0] * g % P, zeta[1] * g % P]
-    cs_b = cd.constants_sigmas_batch
-    o_cs, o_w, o_z, o_q = cs_b.open_at(zeta), wires_b.open_at(zeta), zs_b.open_at(zeta), q_b.open_at(zeta)
-    o_next = zs_b.open_at(gzeta)
-    for o in (o_cs, o_w, o_z[:20], o_q, o_z[20:], o_next[:2], o_next[20:]):
-        ch.observe_elements(o)
-    fri_alpha = ch.get_n_challenges(2)
+        cd.quotient_polys(poseidon_wires, r.zs_b, r.pi_hash, r.betas, r.gammas, r.alphas, deltas=r.deltas)
     with pytest.raises(p.Plonky2Mi355xError):
-        cd.fri([cs_b, poseidon_wires, zs_b, q_b], zeta, fri_alpha)
-    fri = cd.fri([cs_b, wires_b, zs_b, q_b], zeta, fri_alpha)
-    fri_caps = []
-    for _ in range(d.num_fri_rounds):
-        cap = fri.commit_round()
-        fri_caps.append(cap)
-        ch.observe_hashes(cap)
-        fri.fold(ch.get_n_challenges(2))
-    fin = fri.final_poly()
-    ch.observe_elements(fin)
-    st, buf = ch.state()
-    pw = p.pow_grind(st, buf, d.proof_of_work_bits, ctx=ctx, hasher=KECCAK)
-    ch.observe_elements([pw])
-    assert ch.get_n_challenges(1)[0] >> (64 - d.proof_of_work_bits) == 0
-    x_index = [ch.get_n_challenges(1)[0] % N for _ in range(d.num_query_rounds)]
-    blob = fri.query(x_index)
-    le = lambda arr: np.ascontiguousarray(np.asarray(arr, dtype="<u8")).tobytes()
-    hb = lambda caps: b"".join(p.hash_to_bytes(caps, KECCAK))
-    by = hb(wires_b.cap) + hb(zs_b.cap) + hb(q_b.cap)
-    by += le(o_cs) + le(o_w) + le(o_z[:2]) + le(o_next[:2]) + le(o_z[20:]) + le(o_next[20:]) + le(o_z[2:20]) + le(o_q)
-    by += b"".join(hb(c) for c in fri_caps) + blob + le(fin) + le([pw]) + le([pis.size]) + le(pis)
-    assert by == cd.prove(wires, pis).to_bytes()
-    assert cd.verify(by) == (True, "")
+        cd.fri([r.batches[0], poseidon_wires, r.zs_b, r.q_b], r.zeta, r.fri_alpha)
+    assert r.bytes == cd.prove(wires, pis).to_bytes()
+    assert cd.verify(r.bytes) == (True, "")
 
 
 @pytest.mark.gpu

@@ -11,22 +11,19 @@ import pytest
 import ext_gate_circuits as egc
 import vanishing_model as vm
 from oracle_lib import rand_field
+from proof_parser import ParsedProof
+from transcript import poseidon_challenger, replay_transcript
 
 P = vm.P
 
 
 def oracle_inputs(orc, oc, w):
     """-> (desc, the three value batches, pi_hash, betas, gammas, alphas, deltas or None, the proof) of the oracle's proof of `w`"""
-    from test_gpu_parity import _Challenger
     op = w.prove(threads=4)
     d, ch = oc.product_desc(), op.challenges()
-    deltas = None
-    if d.num_lookup_polys:                                # the lookup challenges are not in challenges(): replay the transcript up to them
-        t = _Challenger(orc)
-        t.observe(oc.digest); t.observe(ch["public_inputs_hash"]); t.observe(op.caps()[0])
-        betas, gammas = t.get(2), t.get(2)
-        assert betas == ch["betas"] and gammas == ch["gammas"]
-        deltas = betas + gammas + t.get(4)
+    # the lookup challenges are not in challenges(): the replay of the proof's transcript draws them
+    replayed, _, _, deltas = replay_transcript(d, poseidon_challenger(orc), oc.digest, ch["public_inputs_hash"], ParsedProof(d, op.to_bytes()))
+    assert replayed == ch
     return d, (oc.constants_sigmas(), w.wires(), op.zs_partial_products()), ch["public_inputs_hash"], ch["betas"], ch["gammas"], ch["alphas"], deltas, op
 
 
