@@ -25,7 +25,12 @@
  *    context's device.  Opaque handles own device memory and are released with their *_free.
  *  - All functions return GL_OK (0) or a GL_ERR_* code and never unwind; gl_last_error() gives the
  *    text for the calling thread.  The reference panics on shape errors (oracle.rs:114,
- *    merkle_tree.rs:137-143, fft.rs:175-181); here they are GL_ERR_ARG.
+ *    merkle_tree.rs:137-143, fft.rs:175-181); here they are GL_ERR_ARG.  A C++ exception inside the
+ *    library (in practice std::bad_alloc: out of host memory; std::system_error: a thread could not be
+ *    started) is caught at the entry point and becomes GL_ERR_INTERNAL with its text in gl_last_error();
+ *    gl_challenger_new / gl_challenger_new_h return NULL for it, with the last error set.  The functions
+ *    marked GL_NOEXCEPT (the *_free functions and the plain getters) contain nothing that can throw.  After
+ *    such an error every out-handle is NULL, nothing is leaked, and the handles passed in stay usable or freeable.
  *  - A gl_ctx is bound to one device and one HIP stream; calls on one ctx are issued in order on that
  *    stream.  Different ctxs may be used concurrently from different threads; ONE ctx runs one computing call at a
  *    time.  The plain copies out of a handle -- gl_batch_cap / gl_batch_coeffs / gl_batch_lde, gl_merkle_cap,
@@ -50,6 +55,9 @@
 
 #ifdef __cplusplus
 extern "C" {
+#define GL_NOEXCEPT noexcept  /* the *_free functions and plain getters: nothing in them can throw */
+#else
+#define GL_NOEXCEPT
 #endif
 
 #define GL_OK 0
@@ -145,11 +153,11 @@ typedef struct gl_circuit_desc {
  * the context create its own non-blocking stream. */
 int gl_ctx_create(int device, void* stream, gl_ctx** out);
 /* drops the creator's reference (see "Lifetime" above); synchronises the stream first */
-void gl_ctx_destroy(gl_ctx* ctx);
+void gl_ctx_destroy(gl_ctx* ctx) GL_NOEXCEPT;
 int gl_ctx_synchronize(gl_ctx* ctx);
 /* scratch used between the two NTT passes (elements); default 2^24 (128 MiB). */
 int gl_ctx_set_scratch_elems(gl_ctx* ctx, size_t elems);
-const char* gl_last_error(void);
+const char* gl_last_error(void) GL_NOEXCEPT;
 /* Per-scope device timings (HIP events on the context's stream), the analogue of the reference's TimingTree
  * (plonky2/src/util/timing.rs:8-192; scopes as in fri/oracle.rs:51-89, plonk/prover.rs:118-316).
  * Off by default; gl_ctx_timing_report synchronises and writes a JSON object into buf. */
@@ -216,7 +224,7 @@ int gl_merkle_new_h(gl_ctx* ctx, uint32_t hasher, const uint64_t* h_leaves, size
 int gl_merkle_cap(const gl_merkle* t, uint64_t* h_out);
 /* MerkleTree::prove (merkle_tree.rs:171-207): siblings bottom-up, h_out[log2(n) - cap_height][4] */
 int gl_merkle_prove(const gl_merkle* t, size_t leaf_index, uint64_t* h_out, uint32_t* n_siblings);
-void gl_merkle_free(gl_merkle* t);
+void gl_merkle_free(gl_merkle* t) GL_NOEXCEPT;
 
 /* ---- PolynomialBatch -----------------------------------------------------------------------------*/
 /* PolynomialBatch::from_values(values, rate_bits, blinding, cap_height, timing, fft_root_table)
@@ -250,7 +258,7 @@ int gl_batch_from_coeffs_blinded_h(gl_ctx* ctx, uint32_t hasher, const uint64_t*
                                    uint32_t cap_height, const uint8_t seed[32], gl_batch** out);
 int gl_batch_from_device_h(gl_ctx* ctx, uint32_t hasher, const uint64_t* d_cols, size_t ncols, size_t n, uint32_t rate_bits,
                            uint32_t cap_height, int is_values, gl_batch** out);
-uint32_t gl_batch_hasher(const gl_batch* b);
+uint32_t gl_batch_hasher(const gl_batch* b) GL_NOEXCEPT;
 /* field `merkle_tree.cap` (used at prover.rs:164,225,273,319-321): h_out[2^cap_height][4] */
 int gl_batch_cap(const gl_batch* b, uint64_t* h_out);
 /* merkle_tree.get(i) (merkle_tree.rs:167-169): the leaf at Merkle index i, h_out[ncols] (h_out[ncols + 4] with blinding: the salt last) */
@@ -263,11 +271,11 @@ int gl_batch_prove(const gl_batch* b, size_t leaf_index, uint64_t* h_out, uint32
 int gl_batch_coeffs(const gl_batch* b, uint64_t* h_out);
 /* all LDE values in natural order, column-major h_out[ncols][n << rate_bits] (index i <-> 7*w^i) */
 int gl_batch_lde(const gl_batch* b, uint64_t* h_out);
-size_t gl_batch_ncols(const gl_batch* b);
-size_t gl_batch_degree(const gl_batch* b);
-const uint64_t* gl_batch_dev_coeffs(const gl_batch* b);   /* d [ncols][n]  */
-const uint64_t* gl_batch_dev_lde(const gl_batch* b);      /* d [ncols][N]  */
-void gl_batch_free(gl_batch* b);
+size_t gl_batch_ncols(const gl_batch* b) GL_NOEXCEPT;
+size_t gl_batch_degree(const gl_batch* b) GL_NOEXCEPT;
+const uint64_t* gl_batch_dev_coeffs(const gl_batch* b) GL_NOEXCEPT;   /* d [ncols][n]  */
+const uint64_t* gl_batch_dev_lde(const gl_batch* b) GL_NOEXCEPT;      /* d [ncols][N]  */
+void gl_batch_free(gl_batch* b) GL_NOEXCEPT;
 
 /* ---- randomness of zero-knowledge proving ------------------------------------------------------------
  * A keyed counter-based generator: ChaCha20's block function (RFC 8439 section 2.3) with key = the 32-byte seed, nonce =
@@ -303,7 +311,7 @@ int gl_host_circuit_constants_sigmas(const gl_host_circuit* hc, uint64_t* h_out)
  * (circuit_builder.rs:904-910) come from splitmix64(filler_seed).  h_wires[135][n], h_public_inputs[3 m^2]. */
 int gl_matmul_witness(const gl_host_circuit* hc, const uint64_t* h_a, const uint64_t* h_b, uint64_t filler_seed,
                       uint64_t* h_wires, uint64_t* h_public_inputs);
-void gl_host_circuit_free(gl_host_circuit* hc);
+void gl_host_circuit_free(gl_host_circuit* hc) GL_NOEXCEPT;
 /* The same witness produced directly in HBM: the m^3 ArithmeticGate operations are filled by the GPU, the sequential
  * public-input hash sponge (PoseidonGate rows) by the calling host thread meanwhile.  d_wires[135][n] is overwritten;
  * h_public_inputs[3 m^2].  The generator borrows `hc` and belongs to `ctx` (one per context / stream). */
@@ -311,7 +319,7 @@ typedef struct gl_matmul_witgen gl_matmul_witgen;
 int gl_matmul_witgen_create(gl_ctx* ctx, const gl_host_circuit* hc, gl_matmul_witgen** out);
 int gl_matmul_witgen_run(gl_matmul_witgen* g, const uint64_t* a, const uint64_t* b, uint64_t filler_seed,
                          uint64_t* d_wires, uint64_t* h_public_inputs, uint64_t* h_public_inputs_hash /* [4], may be null */);
-void gl_matmul_witgen_free(gl_matmul_witgen* g);
+void gl_matmul_witgen_free(gl_matmul_witgen* g) GL_NOEXCEPT;
 
 /* The device half of build(): PolynomialBatch::from_values(constants || sigmas) (circuit_builder.rs:1020-1028),
  * circuit_digest (:1089-1100), sigma / subgroup tables.  h_constants_sigmas[(num_constants + 80)][n]. */
@@ -341,8 +349,8 @@ int gl_circuit_warm_up(gl_ctx* ctx, const gl_circuit* c);
 int gl_witness_blind(gl_ctx* ctx, const gl_circuit* c, uint64_t* d_wires, const uint8_t seed[32]);
 int gl_circuit_digest(const gl_circuit* c, uint64_t h_out[4]);                 /* verifier_only.circuit_digest */
 int gl_circuit_constants_sigmas_cap(const gl_circuit* c, uint64_t* h_out);     /* [2^cap_height][4]            */
-const gl_batch* gl_circuit_constants_sigmas_batch(const gl_circuit* c);
-void gl_circuit_free(gl_circuit* c);
+const gl_batch* gl_circuit_constants_sigmas_batch(const gl_circuit* c) GL_NOEXCEPT;
+void gl_circuit_free(gl_circuit* c) GL_NOEXCEPT;
 
 /* ---- prover phases ---------------------------------------------------------------------------------*/
 /* Not for zero-knowledge circuits (GL_ERR_UNSUPPORTED): they are proved by gl_prove* only. */
@@ -399,7 +407,7 @@ int gl_pow_grind_h(gl_ctx* ctx, uint32_t hasher, const uint64_t sponge_state[12]
  * serialised Vec<FriQueryRound> body (util/serialization/mod.rs:1477-1546).  h_blob may be null to query the size. */
 int gl_fri_query(gl_fri* f, const uint32_t* x_index, uint32_t num_queries, uint8_t* h_blob, size_t cap_bytes,
                  size_t* num_bytes);
-void gl_fri_free(gl_fri* f);
+void gl_fri_free(gl_fri* f) GL_NOEXCEPT;
 
 /* A Challenger (iop/challenger.rs:30-153: duplex sponge, challenges pop from the end of the rate) for callers of the
  * phase API that have no transcript of their own.  Host code.  `gl_challenger_state` exposes sponge_state / input_buffer
@@ -414,7 +422,7 @@ int gl_challenger_observe_hashes(gl_challenger* c, uint32_t oh, const uint64_t* 
 int gl_challenger_observe(gl_challenger* c, const uint64_t* h_elements, size_t count);
 int gl_challenger_get_challenges(gl_challenger* c, uint64_t* h_out, size_t count);
 int gl_challenger_state(const gl_challenger* c, uint64_t h_sponge_state[12], uint64_t h_input_buffer[8], uint32_t* input_len);
-void gl_challenger_free(gl_challenger* c);
+void gl_challenger_free(gl_challenger* c) GL_NOEXCEPT;
 
 /* ---- prove() ---------------------------------------------------------------------------------------*/
 /* plonk::prover::prove (plonky2/src/plonk/prover.rs:102-329) from step 4 on, i.e. given the FULL witness matrix
@@ -444,8 +452,8 @@ int gl_prove_device_seeded(gl_ctx* ctx, const gl_circuit* c, const uint64_t* d_w
  * generator each); item i is proved on lane i % lanes by `lanes` host threads inside the call.  `hc` is borrowed. */
 typedef struct gl_prover_pool gl_prover_pool;
 int gl_prover_pool_create(int device, const gl_host_circuit* hc, uint32_t lanes, gl_prover_pool** out);
-uint32_t gl_prover_pool_lanes(const gl_prover_pool* p);
-const gl_circuit* gl_prover_pool_circuit(const gl_prover_pool* p);     /* for gl_circuit_digest / _constants_sigmas_cap */
+uint32_t gl_prover_pool_lanes(const gl_prover_pool* p) GL_NOEXCEPT;
+const gl_circuit* gl_prover_pool_circuit(const gl_prover_pool* p) GL_NOEXCEPT;     /* for gl_circuit_digest / _constants_sigmas_cap */
 /* a[i], b[i]: row-major m x m operands on the host; filler_seeds may be null (seed i); out_proofs[count] */
 int gl_prover_pool_prove_matmul(gl_prover_pool* p, size_t count, const uint64_t* const* a, const uint64_t* const* b,
                                 const uint64_t* filler_seeds, gl_proof** out_proofs);
@@ -456,21 +464,21 @@ int gl_prover_pool_prove_matmul(gl_prover_pool* p, size_t count, const uint64_t*
 int gl_prover_pool_create_generic(int device, const gl_circuit_desc* desc, const uint64_t* h_constants_sigmas, uint32_t lanes, gl_prover_pool** out);
 int gl_prover_pool_prove_columns(gl_prover_pool* p, size_t count, const uint64_t* const* const* columns, const uint64_t* const* public_inputs,
                                  gl_proof** out_proofs);
-void gl_prover_pool_free(gl_prover_pool* p);
+void gl_prover_pool_free(gl_prover_pool* p) GL_NOEXCEPT;
 
 /* ProofWithPublicInputs::to_bytes (plonk/proof.rs:104-110; util/serialization/mod.rs:1939-1981) */
-size_t gl_proof_num_bytes(const gl_proof* p);
+size_t gl_proof_num_bytes(const gl_proof* p) GL_NOEXCEPT;
 int gl_proof_bytes(const gl_proof* p, uint8_t* h_out, size_t cap);
 /* intermediates, for parity tests: betas[2] gammas[2] alphas[2] zeta[2] fri_alpha[2] pow_witness pi_hash[4],
  * then the FRI betas (2 words each); returns the number of words written */
-size_t gl_proof_challenges(const gl_proof* p, uint64_t* h_out);
+size_t gl_proof_challenges(const gl_proof* p, uint64_t* h_out) GL_NOEXCEPT;
 int gl_proof_caps(const gl_proof* p, uint64_t* h_out /* [3][2^cap_height][4]: wires, zs_pp, quotient */);
 /* the next two need gl_ctx_capture_intermediates(ctx, 1) before proving (two extra device->host copies per proof) */
 int gl_ctx_capture_intermediates(gl_ctx* ctx, int enable);
 int gl_proof_zs_partial_products(const gl_proof* p, uint64_t* h_out /* [20][n] values; [34][n] with lookups: the 14 lookup polynomials follow */);
 int gl_proof_quotient_chunks(const gl_proof* p, uint64_t* h_out /* [16][n] coefficients */);
-size_t gl_proof_query_indices(const gl_proof* p, uint64_t* h_out);
-void gl_proof_free(gl_proof* p);
+size_t gl_proof_query_indices(const gl_proof* p, uint64_t* h_out) GL_NOEXCEPT;
+void gl_proof_free(gl_proof* p) GL_NOEXCEPT;
 
 /* ---- verify() --------------------------------------------------------------------------------------*/
 /* VerifierCircuitData::verify (plonky2/src/plonk/circuit_data.rs:208-215 -> plonk/verifier.rs:15-115, fri/verifier.rs:

@@ -10,6 +10,7 @@
 #include "context.hpp"
 #include "rng.cuh"
 #include <cstring>
+#include <memory>
 
 
 // `values`: column-major VALUES to interpolate into b->coeffs (may be b->coeffs itself), or null when b->coeffs already
@@ -36,9 +37,11 @@ static int batch_commit(gl_ctx* c, gl_batch* b, const gl_t* values, const uint8_
     return GL_OK;
 }
 
-extern "C" void gl_batch_free(gl_batch* b);
-static int batch_alloc(gl_ctx* c, size_t ncols, size_t n, uint32_t rate_bits, uint32_t cap_height, uint32_t salt, uint32_t hasher, gl_batch** out) {
-    GL_REQUIRE(c && out && ncols >= 1 && n >= 1, GL_ERR_ARG, "PolynomialBatch: bad argument");
+extern "C" void gl_batch_free(gl_batch* b) noexcept;
+// a batch under construction: freed on every path that does not hand it out, unwinding included
+struct BatchPtr : std::unique_ptr<gl_batch, void (*)(gl_batch*) noexcept> { BatchPtr() : unique_ptr(nullptr, gl_batch_free) {} };
+static int batch_alloc(gl_ctx* c, size_t ncols, size_t n, uint32_t rate_bits, uint32_t cap_height, uint32_t salt, uint32_t hasher, BatchPtr& b) {
+    GL_REQUIRE(c && ncols >= 1 && n >= 1, GL_ERR_ARG, "PolynomialBatch: bad argument");
     GL_REQUIRE(hasher <= 1, GL_ERR_ARG, "PolynomialBatch: hasher is 0 (Poseidon) or 1 (Keccak)");
     uint32_t lg = 0;
     while ((size_t(1) << lg) < n) lg++;
@@ -46,13 +49,11 @@ static int batch_alloc(gl_ctx* c, size_t ncols, size_t n, uint32_t rate_bits, ui
     GL_REQUIRE(lg + rate_bits <= 24, GL_ERR_ARG, "LDE size unsupported");
     GL_REQUIRE(cap_height <= lg + rate_bits, GL_ERR_ARG, "cap_height should be at most log2(leaves.len())");
     GL_TRY(c->activate());
-    gl_batch* b = new gl_batch();
+    b.reset(new gl_batch());
     b->ctx = c; c->retain(); b->ncols = ncols; b->n = n; b->degree_log = lg; b->rate_bits = rate_bits; b->cap_height = cap_height;
     b->salt = salt; b->hasher = hasher;
-    int st = c->pool_alloc(ncols * n * sizeof(gl_t), (void**)&b->coeffs);
-    if (st == GL_OK) st = c->pool_alloc(b->leaf_len() * b->N() * sizeof(gl_t), (void**)&b->lde);
-    if (st != GL_OK) { gl_batch_free(b); return st; }      // nothing leaks when the device is out of memory
-    *out = b;
+    GL_TRY(c->pool_alloc(ncols * n * sizeof(gl_t), (void**)&b->coeffs));      // (nothing leaks when the device is out of memory)
+    GL_TRY(c->pool_alloc(b->leaf_len() * b->N() * sizeof(gl_t), (void**)&b->lde));
     return GL_OK;
 }
 
@@ -60,90 +61,87 @@ static int batch_alloc(gl_ctx* c, size_t ncols, size_t n, uint32_t rate_bits, ui
 static int batch_from_host(gl_ctx* c, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits, bool blinding,
                            const uint8_t* seed_in, uint32_t cap_height, bool is_values, gl_batch** out, uint32_t hasher = 0) {
     GL_REQUIRE(h_cols, GL_ERR_ARG, "PolynomialBatch: null columns");
+    GL_REQUIRE(out, GL_ERR_ARG, "PolynomialBatch: bad argument");
     uint8_t seed[32];
     if (blinding && seed_in) memcpy(seed, seed_in, 32);
     else if (blinding) GL_TRY(gl_os_seed(seed));
-    gl_batch* b = nullptr;
-    GL_TRY(batch_alloc(c, ncols, n, rate_bits, cap_height, blinding ? GL_SALT_SIZE : 0, hasher, &b));
+    BatchPtr b;
+    GL_TRY(batch_alloc(c, ncols, n, rate_bits, cap_height, blinding ? GL_SALT_SIZE : 0, hasher, b));
     for (size_t col = 0; col < ncols; col++) {
-        if (!h_cols[col]) { gl_batch_free(b); return gl_fail(GL_ERR_ARG, "null column", __FILE__, __LINE__); }
-        hipError_t e = hipMemcpyAsync(b->coeffs + col * n, h_cols[col], n * sizeof(gl_t), hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { gl_batch_free(b); return gl_fail(GL_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__); }
+        GL_REQUIRE(h_cols[col], GL_ERR_ARG, "null column");
+        GL_CHECK_HIP(hipMemcpyAsync(b->coeffs + col * n, h_cols[col], n * sizeof(gl_t), hipMemcpyHostToDevice, c->stream));
     }
     GL_CHECK_HIP(gl_stream_wait(c->stream));   // caller-owned pageable columns
-    int st = batch_commit(c, b, is_values ? b->coeffs : nullptr, seed);
-    if (st != GL_OK) { gl_batch_free(b); return st; }
-    *out = b;
+    GL_TRY(batch_commit(c, b.get(), is_values ? b->coeffs : nullptr, seed));
+    *out = b.release();
     return GL_OK;
 }
 
 #define GL_BLINDED_ENTRY "blinding: use gl_batch_from_values_blinded / gl_batch_from_coeffs_blinded (salted leaves)"
 extern "C" int gl_batch_from_values(gl_ctx* c, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
-                                    uint32_t blinding, uint32_t cap_height, gl_batch** out) {
+                                    uint32_t blinding, uint32_t cap_height, gl_batch** out) try {
     GL_REQUIRE(blinding == 0, GL_ERR_UNSUPPORTED, GL_BLINDED_ENTRY);
     return batch_from_host(c, h_cols, ncols, n, rate_bits, false, nullptr, cap_height, true, out);
-}
+} catch (...) { return gl_caught(); }
 extern "C" int gl_batch_from_coeffs(gl_ctx* c, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
-                                    uint32_t blinding, uint32_t cap_height, gl_batch** out) {
+                                    uint32_t blinding, uint32_t cap_height, gl_batch** out) try {
     GL_REQUIRE(blinding == 0, GL_ERR_UNSUPPORTED, GL_BLINDED_ENTRY);
     return batch_from_host(c, h_cols, ncols, n, rate_bits, false, nullptr, cap_height, false, out);
-}
+} catch (...) { return gl_caught(); }
 extern "C" int gl_batch_from_values_blinded(gl_ctx* c, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
-                                            uint32_t cap_height, const uint8_t seed[32], gl_batch** out) {
+                                            uint32_t cap_height, const uint8_t seed[32], gl_batch** out) try {
     return batch_from_host(c, h_cols, ncols, n, rate_bits, true, seed, cap_height, true, out);
-}
+} catch (...) { return gl_caught(); }
 extern "C" int gl_batch_from_coeffs_blinded(gl_ctx* c, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
-                                            uint32_t cap_height, const uint8_t seed[32], gl_batch** out) {
+                                            uint32_t cap_height, const uint8_t seed[32], gl_batch** out) try {
     return batch_from_host(c, h_cols, ncols, n, rate_bits, true, seed, cap_height, false, out);
-}
+} catch (...) { return gl_caught(); }
 int gl_batch_from_device_salted(gl_ctx* c, const uint64_t* d_cols, size_t ncols, size_t n, uint32_t rate_bits, uint32_t cap_height,
                                 int is_values, const uint8_t* seed, uint32_t oracle, gl_batch** out, uint32_t hasher) {
     GL_REQUIRE(d_cols, GL_ERR_ARG, "PolynomialBatch: null device columns");
-    gl_batch* b = nullptr;
-    GL_TRY(batch_alloc(c, ncols, n, rate_bits, cap_height, seed ? GL_SALT_SIZE : 0, hasher, &b));
-    if (!is_values) {      // coefficients are kept: copy; values are interpolated straight out of the caller's matrix (left untouched)
-        hipError_t e = hipMemcpyAsync(b->coeffs, d_cols, ncols * n * sizeof(gl_t), hipMemcpyDeviceToDevice, c->stream);
-        if (e != hipSuccess) { gl_batch_free(b); return gl_fail(GL_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__); }
-    }
-    int st = batch_commit(c, b, is_values ? (const gl_t*)d_cols : nullptr, seed, oracle);
-    if (st != GL_OK) { gl_batch_free(b); return st; }
-    *out = b;
+    GL_REQUIRE(out, GL_ERR_ARG, "PolynomialBatch: bad argument");
+    BatchPtr b;
+    GL_TRY(batch_alloc(c, ncols, n, rate_bits, cap_height, seed ? GL_SALT_SIZE : 0, hasher, b));
+    // coefficients are kept: copy; values are interpolated straight out of the caller's matrix (left untouched)
+    if (!is_values) GL_CHECK_HIP(hipMemcpyAsync(b->coeffs, d_cols, ncols * n * sizeof(gl_t), hipMemcpyDeviceToDevice, c->stream));
+    GL_TRY(batch_commit(c, b.get(), is_values ? (const gl_t*)d_cols : nullptr, seed, oracle));
+    *out = b.release();
     return GL_OK;
 }
 extern "C" int gl_batch_from_device(gl_ctx* c, const uint64_t* d_cols, size_t ncols, size_t n, uint32_t rate_bits,
-                                    uint32_t cap_height, int is_values, gl_batch** out) {
+                                    uint32_t cap_height, int is_values, gl_batch** out) try {
     return gl_batch_from_device_salted(c, d_cols, ncols, n, rate_bits, cap_height, is_values, nullptr, 0, out);
-}
+} catch (...) { return gl_caught(); }
 // the constructors for PolynomialBatch<F, C, D> with C::Hasher = `hasher` (fri/oracle.rs:43-125)
 extern "C" int gl_batch_from_values_h(gl_ctx* c, uint32_t hasher, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
-                                      uint32_t blinding, uint32_t cap_height, gl_batch** out) {
+                                      uint32_t blinding, uint32_t cap_height, gl_batch** out) try {
     GL_REQUIRE(blinding == 0, GL_ERR_UNSUPPORTED, GL_BLINDED_ENTRY);
     return batch_from_host(c, h_cols, ncols, n, rate_bits, false, nullptr, cap_height, true, out, hasher);
-}
+} catch (...) { return gl_caught(); }
 extern "C" int gl_batch_from_coeffs_h(gl_ctx* c, uint32_t hasher, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
-                                      uint32_t blinding, uint32_t cap_height, gl_batch** out) {
+                                      uint32_t blinding, uint32_t cap_height, gl_batch** out) try {
     GL_REQUIRE(blinding == 0, GL_ERR_UNSUPPORTED, GL_BLINDED_ENTRY);
     return batch_from_host(c, h_cols, ncols, n, rate_bits, false, nullptr, cap_height, false, out, hasher);
-}
+} catch (...) { return gl_caught(); }
 extern "C" int gl_batch_from_values_blinded_h(gl_ctx* c, uint32_t hasher, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
-                                              uint32_t cap_height, const uint8_t seed[32], gl_batch** out) {
+                                              uint32_t cap_height, const uint8_t seed[32], gl_batch** out) try {
     return batch_from_host(c, h_cols, ncols, n, rate_bits, true, seed, cap_height, true, out, hasher);
-}
+} catch (...) { return gl_caught(); }
 extern "C" int gl_batch_from_coeffs_blinded_h(gl_ctx* c, uint32_t hasher, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
-                                              uint32_t cap_height, const uint8_t seed[32], gl_batch** out) {
+                                              uint32_t cap_height, const uint8_t seed[32], gl_batch** out) try {
     return batch_from_host(c, h_cols, ncols, n, rate_bits, true, seed, cap_height, false, out, hasher);
-}
+} catch (...) { return gl_caught(); }
 extern "C" int gl_batch_from_device_h(gl_ctx* c, uint32_t hasher, const uint64_t* d_cols, size_t ncols, size_t n, uint32_t rate_bits,
-                                      uint32_t cap_height, int is_values, gl_batch** out) {
+                                      uint32_t cap_height, int is_values, gl_batch** out) try {
     return gl_batch_from_device_salted(c, d_cols, ncols, n, rate_bits, cap_height, is_values, nullptr, 0, out, hasher);
-}
-extern "C" uint32_t gl_batch_hasher(const gl_batch* b) { return b ? b->hasher : 0; }
+} catch (...) { return gl_caught(); }
+extern "C" uint32_t gl_batch_hasher(const gl_batch* b) noexcept { return b ? b->hasher : 0; }
 
-extern "C" int gl_batch_cap(const gl_batch* b, uint64_t* h_out) {
+extern "C" int gl_batch_cap(const gl_batch* b, uint64_t* h_out) try {
     GL_REQUIRE(b && h_out, GL_ERR_ARG, "null argument");
     const GlMerkle& m = b->tree;
     return gl_copy_d2h(b->ctx, h_out, m.level_ptr(m.num_levels() - 1), (size_t(4) << m.cap_height) * sizeof(gl_t));
-}
+} catch (...) { return gl_caught(); }
 
 // out[c] = lde[c][row]
 __global__ void k_gather_row(const gl_t* lde, uint64_t stride, uint32_t ncols, uint64_t row, gl_t* out) {
@@ -165,32 +163,32 @@ static int batch_row(const gl_batch* b, size_t natural_row, size_t ncols, uint64
     GL_CHECK_HIP(hipGetLastError());
     return gl_copy_d2h(c, h_out, c->dev_small, ncols * sizeof(gl_t));
 }
-extern "C" int gl_batch_get_leaf(const gl_batch* b, size_t leaf_index, uint64_t* h_out) {
+extern "C" int gl_batch_get_leaf(const gl_batch* b, size_t leaf_index, uint64_t* h_out) try {
     GL_REQUIRE(b && h_out && leaf_index < b->N(), GL_ERR_ARG, "bad leaf index");
     return batch_row(b, host_bitrev(leaf_index, b->degree_log + b->rate_bits), b->leaf_len(), h_out);
-}
-extern "C" int gl_batch_get_lde_values(const gl_batch* b, size_t index, size_t step, uint64_t* h_out) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_batch_get_lde_values(const gl_batch* b, size_t index, size_t step, uint64_t* h_out) try {
     GL_REQUIRE(b && h_out && index * step < b->N(), GL_ERR_ARG, "bad LDE index");
     // oracle.rs:128-133 reads leaves[reverse_bits(index*step)] without its salt; leaf j is LDE row bitrev(j), so this is row index*step
     return batch_row(b, index * step, b->ncols, h_out);
-}
-extern "C" int gl_batch_prove(const gl_batch* b, size_t leaf_index, uint64_t* h_out, uint32_t* n_siblings) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_batch_prove(const gl_batch* b, size_t leaf_index, uint64_t* h_out, uint32_t* n_siblings) try {
     GL_REQUIRE(b && h_out, GL_ERR_ARG, "null argument");
     return gl_merkle_prove_impl(b->ctx, b->tree, leaf_index, h_out, n_siblings);
-}
-extern "C" int gl_batch_coeffs(const gl_batch* b, uint64_t* h_out) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_batch_coeffs(const gl_batch* b, uint64_t* h_out) try {
     GL_REQUIRE(b && h_out, GL_ERR_ARG, "null argument");
     return gl_copy_d2h(b->ctx, h_out, b->coeffs, b->ncols * b->n * sizeof(gl_t));
-}
-extern "C" int gl_batch_lde(const gl_batch* b, uint64_t* h_out) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_batch_lde(const gl_batch* b, uint64_t* h_out) try {
     GL_REQUIRE(b && h_out, GL_ERR_ARG, "null argument");
     return gl_copy_d2h(b->ctx, h_out, b->lde, b->ncols * b->N() * sizeof(gl_t));
-}
-extern "C" size_t gl_batch_ncols(const gl_batch* b) { return b ? b->ncols : 0; }
-extern "C" size_t gl_batch_degree(const gl_batch* b) { return b ? b->n : 0; }
-extern "C" const uint64_t* gl_batch_dev_coeffs(const gl_batch* b) { return b ? b->coeffs : nullptr; }
-extern "C" const uint64_t* gl_batch_dev_lde(const gl_batch* b) { return b ? b->lde : nullptr; }
-extern "C" void gl_batch_free(gl_batch* b) {
+} catch (...) { return gl_caught(); }
+extern "C" size_t gl_batch_ncols(const gl_batch* b) noexcept { return b ? b->ncols : 0; }
+extern "C" size_t gl_batch_degree(const gl_batch* b) noexcept { return b ? b->n : 0; }
+extern "C" const uint64_t* gl_batch_dev_coeffs(const gl_batch* b) noexcept { return b ? b->coeffs : nullptr; }
+extern "C" const uint64_t* gl_batch_dev_lde(const gl_batch* b) noexcept { return b ? b->lde : nullptr; }
+extern "C" void gl_batch_free(gl_batch* b) noexcept {
     if (!b) return;
     gl_merkle_release(b->ctx, &b->tree);
     if (b->coeffs) b->ctx->pool_release(b->coeffs);

@@ -9,15 +9,6 @@
 #include <cstring>
 #include <cstdlib>
 
-thread_local std::string g_gl_last_error;
-
-int gl_fail(int code, const char* what, const char* file, int line) {
-    char buf[512];
-    snprintf(buf, sizeof buf, "%s (%s:%d)", what, file, line);
-    g_gl_last_error = buf;
-    return code;
-}
-
 // ------------------------------------------------------------------------------------------ context
 int gl_ctx::activate() {
     int cur = -1;
@@ -37,15 +28,20 @@ int gl_ctx::pin_acquire(size_t bytes, void** out, size_t* cap) {
         std::lock_guard<std::mutex> lk(pin_mu);
         for (size_t i = 0; i < pin_free.size(); i++)
             if (pin_free[i].second >= bytes) { *out = pin_free[i].first; *cap = pin_free[i].second; pin_free.erase(pin_free.begin() + i); return GL_OK; }
+        // room in the list for every buffer that exists, the new one included: pin_release never allocates, so it cannot fail
+        if (pin_free.capacity() <= pin_count) pin_free.reserve(2 * pin_count + 4);
+        pin_count++;
     }
     const size_t sz = bytes < (size_t(1) << 20) ? (size_t(1) << 20) : bytes;
-    GL_CHECK_HIP(hipHostMalloc(out, sz, hipHostMallocDefault));
+    const hipError_t e = hipHostMalloc(out, sz, hipHostMallocDefault);
+    if (e != hipSuccess) { std::lock_guard<std::mutex> lk(pin_mu); pin_count--; }
+    GL_CHECK_HIP(e);
     *cap = sz;
     return GL_OK;
 }
-void gl_ctx::pin_release(void* p, size_t cap) {
+void gl_ctx::pin_release(void* p, size_t cap) noexcept {
     std::lock_guard<std::mutex> lk(pin_mu);
-    pin_free.emplace_back(p, cap);
+    pin_free.emplace_back(p, cap);             // (within the capacity pin_acquire reserved)
 }
 int gl_ctx::ensure_dev_small(size_t bytes) {
     if (bytes <= dev_small_bytes) return GL_OK;
@@ -75,19 +71,21 @@ int gl_ctx::pool_alloc(size_t bytes, void** out) {
     }
     if (e != hipSuccess) return gl_fail(GL_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
     std::lock_guard<std::mutex> lk(pool_mu);
-    pool_block_size[p] = want;
+    try { pool_block_size[p] = want; }
+    catch (...) { (void)hipFree(p); throw; }      // a block the pool cannot count is not lost
     pool_bytes += want;
     *out = p;
     return GL_OK;
 }
-void gl_ctx::pool_release(void* p) {
+void gl_ctx::pool_release(void* p) noexcept {
     if (!p) return;
     std::lock_guard<std::mutex> lk(pool_mu);
     auto it = pool_block_size.find(p);
     if (it == pool_block_size.end()) { (void)hipFree(p); return; }
-    pool_free_blocks.emplace(it->second, p);
+    try { pool_free_blocks.emplace(it->second, p); }
+    catch (...) { pool_bytes -= it->second; pool_block_size.erase(it); (void)hipFree(p); }      // no node for the free list: back to the runtime (hipFree waits for the device)
 }
-void gl_ctx::pool_trim() {
+void gl_ctx::pool_trim() noexcept {
     std::lock_guard<std::mutex> lk(pool_mu);
     (void)gl_stream_wait(stream);
     for (auto& kv : pool_free_blocks) { pool_bytes -= kv.first; pool_block_size.erase(kv.second); (void)hipFree(kv.second); }
@@ -98,9 +96,11 @@ void gl_ctx::timing_begin(const char* name) {
     if (!timing_enabled) return;
     TimingRec r; r.name = name;
     if (hipEventCreate(&r.start) != hipSuccess || hipEventCreate(&r.stop) != hipSuccess) return;
+    // (the stack is as deep as the scopes nest: its reserve is a no-op after the first few scopes)
+    try { timing_stack.reserve(timing_stack.size() + 1); timing_recs.push_back(r); }
+    catch (...) { (void)hipEventDestroy(r.start); (void)hipEventDestroy(r.stop); return; }      // as when the events cannot be created: the scope goes untimed
     (void)hipEventRecord(r.start, stream);
-    timing_stack.push_back(timing_recs.size());
-    timing_recs.push_back(r);
+    timing_stack.push_back(timing_recs.size() - 1);
 }
 void gl_ctx::timing_end() {
     if (!timing_enabled || timing_stack.empty()) return;
@@ -108,12 +108,12 @@ void gl_ctx::timing_end() {
     timing_stack.pop_back();
 }
 
-extern "C" int gl_ctx_timing_enable(gl_ctx* c, int on) {
+extern "C" int gl_ctx_timing_enable(gl_ctx* c, int on) try {
     GL_REQUIRE(c, GL_ERR_ARG, "null ctx");
     c->timing_enabled = on != 0;
     return GL_OK;
-}
-extern "C" int gl_ctx_timing_reset(gl_ctx* c) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_ctx_timing_reset(gl_ctx* c) try {
     GL_REQUIRE(c, GL_ERR_ARG, "null ctx");
     GL_TRY(c->activate());
     GL_CHECK_HIP(gl_stream_wait(c->stream));
@@ -121,9 +121,9 @@ extern "C" int gl_ctx_timing_reset(gl_ctx* c) {
     c->timing_recs.clear();
     c->timing_stack.clear();
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 // writes a JSON object {"scope": {"count": n, "ms": total}, ...} into buf (NUL-terminated)
-extern "C" int gl_ctx_timing_report(gl_ctx* c, char* buf, size_t cap) {
+extern "C" int gl_ctx_timing_report(gl_ctx* c, char* buf, size_t cap) try {
     GL_REQUIRE(c && buf && cap > 2, GL_ERR_ARG, "bad argument");
     GL_TRY(c->activate());
     GL_CHECK_HIP(gl_stream_wait(c->stream));
@@ -147,7 +147,7 @@ extern "C" int gl_ctx_timing_report(gl_ctx* c, char* buf, size_t cap) {
     GL_REQUIRE(out.size() + 1 <= cap, GL_ERR_ARG, "timing report buffer too small");
     memcpy(buf, out.c_str(), out.size() + 1);
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 
 int gl_ctx::get_offsets_table(const uint64_t* host, size_t len, const uint64_t** d_out) {
     std::vector<uint64_t> key(host, host + len);
@@ -157,10 +157,29 @@ int gl_ctx::get_offsets_table(const uint64_t* host, size_t len, const uint64_t**
     GL_CHECK_HIP(hipMalloc((void**)&d, len * sizeof(uint64_t)));
     GL_CHECK_HIP(hipMemcpyAsync(d, host, len * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
     GL_CHECK_HIP(gl_stream_wait(stream));   // first use only
-    offset_tables[key] = d;
+    try { offset_tables[key] = d; }
+    catch (...) { (void)hipFree(d); throw; }
     *d_out = d;
     return GL_OK;
 }
+
+extern "C" int gl_ctx_create(int device, void* stream, gl_ctx** out) try {
+    GL_REQUIRE(out != nullptr, GL_ERR_ARG, "gl_ctx_create: out is null");
+    int count = 0;
+    hipError_t e = hipGetDeviceCount(&count);
+    if (e != hipSuccess || count == 0) return gl_fail(GL_ERR_HIP, "no HIP device available (this library has no CPU fallback)", __FILE__, __LINE__);
+    GL_REQUIRE(device >= 0 && device < count, GL_ERR_ARG, "gl_ctx_create: bad device index");
+    GL_CHECK_HIP(hipSetDevice(device));
+    std::unique_ptr<gl_ctx, void (*)(gl_ctx*)> holder(new gl_ctx(), gl_ctx_release);      // nothing leaks on an error path
+    gl_ctx* c = holder.get();
+    c->device = device;
+    if (const char* e = getenv("GL_NTT_SCRATCH_LOG")) { const int lg = atoi(e); if (lg >= 16 && lg <= 32) c->scratch_target = size_t(1) << lg; }      // tuning knob
+    if (stream) { c->stream = (hipStream_t)stream; c->own_stream = false; }
+    else { GL_CHECK_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
+    GL_TRY(gl_ntt_local_tables(c));      // ntt.hip: the one step of creation that launches kernels
+    *out = holder.release();
+    return GL_OK;
+} catch (...) { return gl_caught(); }
 
 // the last reference is gone: nothing points at the context any more
 static void gl_ctx_teardown(gl_ctx* c) {
@@ -185,31 +204,31 @@ void gl_ctx_release(gl_ctx* c) {
 }
 // Drops the creator's reference.  Handles created on the context keep it alive (and usable through them) until the last of
 // them is freed; the caller must not pass `c` to any entry point after this call.
-extern "C" void gl_ctx_destroy(gl_ctx* c) {
+extern "C" void gl_ctx_destroy(gl_ctx* c) noexcept {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)gl_stream_wait(c->stream);
     gl_ctx_release(c);
 }
-extern "C" int gl_ctx_synchronize(gl_ctx* c) {
+extern "C" int gl_ctx_synchronize(gl_ctx* c) try {
     GL_REQUIRE(c, GL_ERR_ARG, "null ctx");
     GL_TRY(c->activate());
     GL_CHECK_HIP(gl_stream_wait(c->stream));
     return GL_OK;
-}
-extern "C" int gl_ctx_set_scratch_elems(gl_ctx* c, size_t elems) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_ctx_set_scratch_elems(gl_ctx* c, size_t elems) try {
     GL_REQUIRE(c && elems >= (size_t(1) << 13), GL_ERR_ARG, "bad scratch size");      // at least one NTT tile (ntt.cuh NTT_TILE_LOG)
     c->scratch_target = elems;
     return GL_OK;
-}
-extern "C" const char* gl_last_error(void) { return g_gl_last_error.c_str(); }
-extern "C" int gl_dev_alloc(gl_ctx* c, size_t bytes, void** d_out) {
+} catch (...) { return gl_caught(); }
+extern "C" const char* gl_last_error(void) noexcept { return g_gl_last_error; }
+extern "C" int gl_dev_alloc(gl_ctx* c, size_t bytes, void** d_out) try {
     GL_REQUIRE(c && d_out, GL_ERR_ARG, "null argument");
     GL_TRY(c->activate());
     GL_CHECK_HIP(hipMalloc(d_out, bytes ? bytes : 8));
     return GL_OK;
-}
-extern "C" int gl_dev_free(gl_ctx* c, void* d_ptr) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_dev_free(gl_ctx* c, void* d_ptr) try {
     // plain device memory: a null context (already destroyed by the caller) is accepted, the whole device is drained instead
     if (!d_ptr) return GL_OK;
     if (c) { GL_TRY(c->activate()); GL_CHECK_HIP(gl_stream_wait(c->stream)); }
@@ -228,15 +247,15 @@ extern "C" int gl_dev_free(gl_ctx* c, void* d_ptr) {
     }
     GL_CHECK_HIP(hipFree(d_ptr));
     return GL_OK;
-}
-extern "C" int gl_copy_h2d(gl_ctx* c, void* d_dst, const void* h_src, size_t bytes) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_copy_h2d(gl_ctx* c, void* d_dst, const void* h_src, size_t bytes) try {
     GL_REQUIRE(c && d_dst && h_src, GL_ERR_ARG, "null argument");
     GL_TRY(c->activate());
     GL_CHECK_HIP(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, c->stream));
     GL_CHECK_HIP(gl_stream_wait(c->stream));   // pageable source must not be reused before the copy lands
     return GL_OK;
-}
-extern "C" int gl_copy_d2h(gl_ctx* c, void* h_dst, const void* d_src, size_t bytes) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_copy_d2h(gl_ctx* c, void* h_dst, const void* d_src, size_t bytes) try {
     GL_REQUIRE(c && h_dst && d_src, GL_ERR_ARG, "null argument");
     GL_TRY(c->activate());
     // A copy to pageable memory makes the runtime wait for the stream INSIDE hipMemcpyAsync, spinning (measured: each of 16
@@ -256,5 +275,5 @@ extern "C" int gl_copy_d2h(gl_ctx* c, void* h_dst, const void* d_src, size_t byt
     GL_CHECK_HIP(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
     GL_CHECK_HIP(gl_stream_wait(c->stream));
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 

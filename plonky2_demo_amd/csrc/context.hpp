@@ -7,7 +7,10 @@
 #include <chrono>
 #include <time.h>
 #include <sys/prctl.h>
+#include <cstdio>
+#include <exception>
 #include <map>
+#include <new>
 #include <tuple>
 #include <mutex>
 #include <unordered_map>
@@ -18,9 +21,26 @@
 #include "../../include/plonky2_mi355x.h"
 
 struct gl_ctx;
-void gl_ctx_release(gl_ctx* c);      // drops one reference (ntt.hip)
-extern thread_local std::string g_gl_last_error;
-int gl_fail(int code, const char* what, const char* file, int line);
+void gl_ctx_release(gl_ctx* c);      // drops one reference (context.hip)
+
+// ---- errors: the C ABI never unwinds ----------------------------------------------------------------------
+// The calling thread's last error text.  A fixed buffer, so that reporting an error allocates nothing: the path that
+// reports "out of host memory" must not need any.  `what` must not point into the buffer itself.
+inline thread_local char g_gl_last_error[512] = "";
+inline int gl_fail(int code, const char* what, const char* file, int line) noexcept {
+    snprintf(g_gl_last_error, sizeof g_gl_last_error, "%s (%s:%d)", what, file, line);
+    return code;
+}
+// The one exception boundary.  Every extern "C" definition whose body can throw is a function-try-block
+//     extern "C" int gl_foo(...) try { body } catch (...) { return gl_caught(); }
+// (a pointer return: `(void)gl_caught(); return nullptr;`); the ones whose body cannot throw -- the *_free functions
+// and plain getters -- are declared noexcept instead.  tests/test_abi.py checks that every definition is one or the other.
+inline int gl_caught() noexcept {
+    try { throw; }
+    catch (const std::bad_alloc&) { return gl_fail(GL_ERR_INTERNAL, "out of host memory", __FILE__, __LINE__); }
+    catch (const std::exception& e) { return gl_fail(GL_ERR_INTERNAL, e.what(), __FILE__, __LINE__); }
+    catch (...) { return gl_fail(GL_ERR_INTERNAL, "unknown C++ exception", __FILE__, __LINE__); }
+}
 
 #define GL_CHECK_HIP(expr)                                                                   \
     do {                                                                                     \
@@ -31,6 +51,7 @@ int gl_fail(int code, const char* what, const char* file, int line);
     do {                                                                 \
         if (!(cond)) return gl_fail(code, msg, __FILE__, __LINE__);      \
     } while (0)
+#define GL_REQUIRE_HASHER(h, who) GL_REQUIRE((h) == GL_HASHER_POSEIDON || (h) == GL_HASHER_KECCAK, GL_ERR_ARG, who ": hasher is 0 (Poseidon) or 1 (Keccak)")
 #define GL_TRY(expr)                 \
     do {                             \
         int _s = (expr);             \
@@ -111,8 +132,9 @@ struct gl_ctx {
     // buffer is taken from this list for one copy and handed back afterwards
     std::mutex pin_mu;
     std::vector<std::pair<void*, size_t>> pin_free;
+    size_t pin_count = 0;                                         // buffers that exist, free or in use (pin_free has room for all of them)
     int pin_acquire(size_t bytes, void** out, size_t* cap);
-    void pin_release(void* p, size_t cap);
+    void pin_release(void* p, size_t cap) noexcept;
     gl_t* dev_small = nullptr;                                    // 1 MiB device staging
     size_t dev_small_bytes = 0;
 
@@ -134,8 +156,8 @@ struct gl_ctx {
     std::unordered_map<void*, size_t> pool_block_size;
     size_t pool_bytes = 0;
     int pool_alloc(size_t bytes, void** out);
-    void pool_release(void* p);
-    void pool_trim();
+    void pool_release(void* p) noexcept;      // (destructors and *_free call it)
+    void pool_trim() noexcept;
 
     // parity tests: keep the Z / partial-product values and the quotient chunks of each proof on the host
     bool capture_intermediates = false;
@@ -158,6 +180,7 @@ struct GlTimed {
 };
 
 // ---- NTT launcher (ntt.hip) ---------------------------------------------------------------------------
+int gl_ntt_local_tables(gl_ctx* c);      // fills c->tw_local on c->stream: the part of gl_ctx_create that needs kernels
 // dst[b][k] = post_const * post_shift^k * sum_i (pre_shift^i * src[b][i]) * w^(+-ik),  i < n_in, k < 2^lgN
 // pre_shift / post_shift == 0 mean "no scaling".  src may equal dst.  Output canonical.
 int gl_ntt_run(gl_ctx* ctx, const gl_t* src, uint64_t src_stride, uint32_t n_in, gl_t* dst, uint64_t dst_stride,

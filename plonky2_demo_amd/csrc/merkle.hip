@@ -19,7 +19,6 @@ struct gl_merkle {
     gl_t* leaves = nullptr;      // device copy, row-major [num_leaves][leaf_len] in Merkle order
     size_t num_leaves = 0, leaf_len = 0;
 };
-#define GL_REQUIRE_HASHER(h, who) GL_REQUIRE((h) == GL_HASHER_POSEIDON || (h) == GL_HASHER_KECCAK, GL_ERR_ARG, who ": hasher is 0 (Poseidon) or 1 (Keccak)")
 
 #define GL_COOP_MAX_NODES_DEFAULT 8192u      // 8192 hashes x 16 lanes = 2048 waves = 2 per SIMD
 #define GL_COOP_MAX_NODES_THROUGHPUT 1024u   // with more than two proofs in flight
@@ -325,15 +324,15 @@ void gl_merkle_release(gl_ctx* c, GlMerkle* m) {
 }
 
 // --------------------------------------------------------------------------------------------- C ABI
-extern "C" int gl_poseidon_permute(gl_ctx* c, uint64_t* d_states, size_t count) {
+extern "C" int gl_poseidon_permute(gl_ctx* c, uint64_t* d_states, size_t count) try {
     GL_REQUIRE(c && d_states, GL_ERR_ARG, "null argument");
     if (!count) return GL_OK;
     GL_TRY(c->activate());
     hipLaunchKernelGGL((k_poseidon_states<PSD_LAYER_HASH, true>), dim3((unsigned)((count + 63) / 64)), dim3(64), 0, c->stream, d_states, count);
     GL_CHECK_HIP(hipGetLastError());
     return GL_OK;
-}
-extern "C" int gl_poseidon_permute_raw(gl_ctx* c, uint64_t* d_states, size_t count, int layer) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_poseidon_permute_raw(gl_ctx* c, uint64_t* d_states, size_t count, int layer) try {
     GL_REQUIRE(c && d_states && (layer == PSD_LAYER_VALU || layer == PSD_LAYER_MFMA), GL_ERR_ARG, "bad argument");
     if (!count) return GL_OK;
     GL_TRY(c->activate());
@@ -343,9 +342,9 @@ extern "C" int gl_poseidon_permute_raw(gl_ctx* c, uint64_t* d_states, size_t cou
         hipLaunchKernelGGL((k_poseidon_states<PSD_LAYER_VALU, false>), dim3((unsigned)((count + 63) / 64)), dim3(64), 0, c->stream, d_states, count);
     GL_CHECK_HIP(hipGetLastError());
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 // KeccakHash<25> / PoseidonHash ::hash_or_noop (plonk/config.rs:55-66) of rows, by hasher
-extern "C" int gl_hash_rows_h(gl_ctx* c, uint32_t hasher, const uint64_t* d_rows, size_t count, size_t len, uint64_t* d_out) {
+extern "C" int gl_hash_rows_h(gl_ctx* c, uint32_t hasher, const uint64_t* d_rows, size_t count, size_t len, uint64_t* d_out) try {
     GL_REQUIRE_HASHER(hasher, "gl_hash_rows_h");
     if (hasher == GL_HASHER_POSEIDON) return gl_hash_rows(c, d_rows, count, len, d_out);
     GL_REQUIRE(c && d_rows && d_out && len >= 1 && len <= 0xFFFFFFFFu, GL_ERR_ARG, "bad argument");
@@ -354,33 +353,15 @@ extern "C" int gl_hash_rows_h(gl_ctx* c, uint32_t hasher, const uint64_t* d_rows
     hipLaunchKernelGGL(k_kck_hash_rows, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, c->stream, d_rows, count, (uint32_t)len, d_out);
     GL_CHECK_HIP(hipGetLastError());
     return GL_OK;
-}
-// the same two functions on the host (no GPU needed), `count` rows / pairs: hash_or_noop (plonk/config.rs:55-66) and two_to_one
-// (hash/hashing.rs:98-115, hash/keccak.rs:119-126)
-extern "C" int gl_hash_or_noop_host(uint32_t hasher, const uint64_t* h_rows, size_t count, size_t len, uint64_t* h_out) {
-    GL_REQUIRE_HASHER(hasher, "gl_hash_or_noop_host");
-    GL_REQUIRE((h_rows || !count || !len) && (h_out || !count), GL_ERR_ARG, "gl_hash_or_noop_host: null argument");
-    for (size_t r = 0; r < count; r++) glhost::hash_or_noop(hasher, h_rows + r * len, len, h_out + 4 * r);
-    return GL_OK;
-}
-extern "C" int gl_two_to_one_host(uint32_t hasher, const uint64_t* h_left, const uint64_t* h_right, size_t count, uint64_t* h_out) {
-    GL_REQUIRE_HASHER(hasher, "gl_two_to_one_host");
-    GL_REQUIRE((h_left && h_right && h_out) || !count, GL_ERR_ARG, "gl_two_to_one_host: null argument");
-    for (size_t i = 0; i < count; i++) {
-        if (hasher == GL_HASHER_KECCAK)
-            GL_REQUIRE(kck_hash_is_padded(h_left + 4 * i) && kck_hash_is_padded(h_right + 4 * i), GL_ERR_ARG, "a BytesHash<25> slot with non-zero padding bytes");
-        glhost::two_to_one(hasher, h_left + 4 * i, h_right + 4 * i, h_out + 4 * i);
-    }
-    return GL_OK;
-}
-extern "C" int gl_hash_rows(gl_ctx* c, const uint64_t* d_rows, size_t count, size_t len, uint64_t* d_out) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_hash_rows(gl_ctx* c, const uint64_t* d_rows, size_t count, size_t len, uint64_t* d_out) try {
     GL_REQUIRE(c && d_rows && d_out && len >= 1, GL_ERR_ARG, "bad argument");
     if (!count) return GL_OK;
     GL_TRY(c->activate());
     hipLaunchKernelGGL(k_hash_rows, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, c->stream, d_rows, count, (uint32_t)len, d_out);
     GL_CHECK_HIP(hipGetLastError());
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 
 // row-major [rows][cols] -> column-major [cols][rows] with the row index bit-reversed
 __global__ void k_rows_to_natural_cols(const gl_t* rows, uint32_t lg_rows, uint32_t cols, gl_t* out) {
@@ -391,11 +372,11 @@ __global__ void k_rows_to_natural_cols(const gl_t* rows, uint32_t lg_rows, uint3
     out[idx] = rows[(uint64_t)d_bitrev(r, lg_rows) * cols + c];
 }
 
-extern "C" int gl_merkle_new(gl_ctx* c, const uint64_t* h_leaves, size_t num_leaves, size_t leaf_len, uint32_t cap_height, gl_merkle** out) {
+extern "C" int gl_merkle_new(gl_ctx* c, const uint64_t* h_leaves, size_t num_leaves, size_t leaf_len, uint32_t cap_height, gl_merkle** out) try {
     return gl_merkle_new_h(c, GL_HASHER_POSEIDON, h_leaves, num_leaves, leaf_len, cap_height, out);
-}
+} catch (...) { return gl_caught(); }
 // MerkleTree::<F, C::Hasher>::new (hash/merkle_tree.rs:135-165) for either hasher
-extern "C" int gl_merkle_new_h(gl_ctx* c, uint32_t hasher, const uint64_t* h_leaves, size_t num_leaves, size_t leaf_len, uint32_t cap_height, gl_merkle** out) {
+extern "C" int gl_merkle_new_h(gl_ctx* c, uint32_t hasher, const uint64_t* h_leaves, size_t num_leaves, size_t leaf_len, uint32_t cap_height, gl_merkle** out) try {
     GL_REQUIRE(c && h_leaves && out && num_leaves >= 1 && leaf_len >= 1, GL_ERR_ARG, "gl_merkle_new: bad argument");
     GL_REQUIRE_HASHER(hasher, "gl_merkle_new_h");
     uint32_t lg = 0;
@@ -418,12 +399,12 @@ extern "C" int gl_merkle_new_h(gl_ctx* c, uint32_t hasher, const uint64_t* h_lea
     GL_TRY(gl_merkle_build(c, cols.p, offs.data(), (uint32_t)leaf_len, lg, cap_height, &t->tree, hasher));
     *out = t.release();
     return GL_OK;
-}
-extern "C" int gl_merkle_cap(const gl_merkle* t, uint64_t* h_out) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_merkle_cap(const gl_merkle* t, uint64_t* h_out) try {
     GL_REQUIRE(t && h_out, GL_ERR_ARG, "null argument");
     const GlMerkle& m = t->tree;
     return gl_copy_d2h(t->ctx, h_out, m.level_ptr(m.num_levels() - 1), (size_t(4) << m.cap_height) * sizeof(gl_t));
-}
+} catch (...) { return gl_caught(); }
 
 __global__ void k_gather_siblings(const gl_t* digests, const uint64_t* level_off, uint32_t levels, uint32_t leaf_index, gl_t* out) {
     const uint32_t l = threadIdx.x >> 2, k = threadIdx.x & 3;
@@ -445,11 +426,11 @@ int gl_merkle_prove_impl(gl_ctx* c, const GlMerkle& m, size_t leaf_index, uint64
     GL_CHECK_HIP(hipGetLastError());
     return gl_copy_d2h(c, h_out, d_out, nsib * 4 * sizeof(gl_t));
 }
-extern "C" int gl_merkle_prove(const gl_merkle* t, size_t leaf_index, uint64_t* h_out, uint32_t* n_siblings) {
+extern "C" int gl_merkle_prove(const gl_merkle* t, size_t leaf_index, uint64_t* h_out, uint32_t* n_siblings) try {
     GL_REQUIRE(t && h_out, GL_ERR_ARG, "null argument");
     return gl_merkle_prove_impl(t->ctx, t->tree, leaf_index, h_out, n_siblings);
-}
-extern "C" void gl_merkle_free(gl_merkle* t) {
+} catch (...) { return gl_caught(); }
+extern "C" void gl_merkle_free(gl_merkle* t) noexcept {
     if (!t) return;
     (void)hipSetDevice(t->ctx->device);
     (void)gl_stream_wait(t->ctx->stream);

@@ -1,4 +1,4 @@
-// NTT launchers, context management and the NTT / field entry points of the C ABI.
+// NTT launchers, the twiddle / power tables of a context and the NTT / field entry points of the C ABI.
 #include "context.hpp"
 #include <atomic>
 #include <memory>
@@ -21,8 +21,10 @@ int gl_ctx::get_pow_table(gl_t base, gl_t scale, uint32_t hi_len, GlPowTable* ou
     hipLaunchKernelGGL(ntt_power_table, dim3((m + 255) / 256), dim3(256), 0, stream, base, scale, t.lo, t.hi, hi_len);
     GL_CHECK_HIP(hipGetLastError());
     // an older, shorter table for the same key may still be in flight: it is parked until the context dies
-    if (it != pow_tables.end()) retired_tables.push_back(it->second.lo);
-    pow_tables[key] = t;
+    try {
+        if (it != pow_tables.end()) retired_tables.push_back(it->second.lo);
+        pow_tables[key] = t;
+    } catch (...) { (void)hipFree(t.lo); throw; }      // (only one of the two lines allocates: the old table is never parked AND kept)
     *out = t;
     return GL_OK;
 }
@@ -36,24 +38,14 @@ int gl_ctx::get_pass_table(gl_t w, gl_t scale, uint32_t lgN1, uint32_t lgN2, con
     GL_CHECK_HIP(hipMalloc((void**)&t, N * sizeof(gl_t)));
     hipLaunchKernelGGL(ntt_pass_table, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, w, scale, t, lgN1, lgN2);
     GL_CHECK_HIP(hipGetLastError());
-    pass_tables[key] = t;
+    try { pass_tables[key] = t; }
+    catch (...) { (void)hipFree(t); throw; }
     *out = t;
     return GL_OK;
 }
 
-extern "C" int gl_ctx_create(int device, void* stream, gl_ctx** out) {
-    GL_REQUIRE(out != nullptr, GL_ERR_ARG, "gl_ctx_create: out is null");
-    int count = 0;
-    hipError_t e = hipGetDeviceCount(&count);
-    if (e != hipSuccess || count == 0) return gl_fail(GL_ERR_HIP, "no HIP device available (this library has no CPU fallback)", __FILE__, __LINE__);
-    GL_REQUIRE(device >= 0 && device < count, GL_ERR_ARG, "gl_ctx_create: bad device index");
-    GL_CHECK_HIP(hipSetDevice(device));
-    std::unique_ptr<gl_ctx, void (*)(gl_ctx*)> holder(new gl_ctx(), gl_ctx_release);      // nothing leaks on an error path
-    gl_ctx* c = holder.get();
-    c->device = device;
-    if (const char* e = getenv("GL_NTT_SCRATCH_LOG")) { const int lg = atoi(e); if (lg >= 16 && lg <= 32) c->scratch_target = size_t(1) << lg; }      // tuning knob
-    if (stream) { c->stream = (hipStream_t)stream; c->own_stream = false; }
-    else { GL_CHECK_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
+// the two local twiddle tables of a new context (gl_ctx_create, context.hip)
+int gl_ntt_local_tables(gl_ctx* c) {
     const uint32_t len = 1u << NTT_LOCAL_MAX_LOG;
     for (int dir = 0; dir < 2; dir++) {
         GL_CHECK_HIP(hipMalloc((void**)&c->tw_local[dir], len * sizeof(gl_t)));
@@ -62,7 +54,6 @@ extern "C" int gl_ctx_create(int device, void* stream, gl_ctx** out) {
         hipLaunchKernelGGL(ntt_root_table, dim3(len / 256), dim3(256), 0, c->stream, w, c->tw_local[dir], len);
     }
     GL_CHECK_HIP(hipGetLastError());
-    *out = holder.release();
     return GL_OK;
 }
 // ---------------------------------------------------------------------------------------- launchers
@@ -252,39 +243,39 @@ int gl_ntt_run(gl_ctx* c, const gl_t* src, uint64_t src_stride, uint32_t n_in, g
 }
 
 // ------------------------------------------------------------------------------------- C ABI: NTTs
-extern "C" int gl_ntt_forward(gl_ctx* c, uint64_t* d, uint32_t log_n, uint32_t batch) {
+extern "C" int gl_ntt_forward(gl_ctx* c, uint64_t* d, uint32_t log_n, uint32_t batch) try {
     return gl_ntt_run(c, d, uint64_t(1) << log_n, 1u << log_n, d, uint64_t(1) << log_n, log_n, batch, false, 0, 0, 1);
-}
-extern "C" int gl_ntt_inverse(gl_ctx* c, uint64_t* d, uint32_t log_n, uint32_t batch) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_ntt_inverse(gl_ctx* c, uint64_t* d, uint32_t log_n, uint32_t batch) try {
     return gl_ntt_run(c, d, uint64_t(1) << log_n, 1u << log_n, d, uint64_t(1) << log_n, log_n, batch, true, 0, 0,
                       gl_host_inverse_2exp(log_n));
-}
-extern "C" int gl_ntt_coset_forward(gl_ctx* c, uint64_t* d, uint32_t log_n, uint32_t batch, uint64_t shift) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_ntt_coset_forward(gl_ctx* c, uint64_t* d, uint32_t log_n, uint32_t batch, uint64_t shift) try {
     GL_REQUIRE(gl_canon(shift) != 0, GL_ERR_ARG, "coset shift must be non-zero");
     return gl_ntt_run(c, d, uint64_t(1) << log_n, 1u << log_n, d, uint64_t(1) << log_n, log_n, batch, false, shift, 0, 1);
-}
-extern "C" int gl_ntt_coset_inverse(gl_ctx* c, uint64_t* d, uint32_t log_n, uint32_t batch, uint64_t shift) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_ntt_coset_inverse(gl_ctx* c, uint64_t* d, uint32_t log_n, uint32_t batch, uint64_t shift) try {
     GL_REQUIRE(gl_canon(shift) != 0, GL_ERR_ARG, "coset shift must be non-zero");
     return gl_ntt_run(c, d, uint64_t(1) << log_n, 1u << log_n, d, uint64_t(1) << log_n, log_n, batch, true, 0,
                       gl_canon(gl_inv(shift)), gl_host_inverse_2exp(log_n));
-}
-extern "C" int gl_ntt_coset_lde(gl_ctx* c, const uint64_t* d_coeffs, uint32_t log_n, uint32_t rate_bits, uint32_t batch, uint64_t* d_out) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_ntt_coset_lde(gl_ctx* c, const uint64_t* d_coeffs, uint32_t log_n, uint32_t rate_bits, uint32_t batch, uint64_t* d_out) try {
     GL_REQUIRE(log_n + rate_bits <= 2 * NTT_LOCAL_MAX_LOG, GL_ERR_ARG, "LDE too large");
     return gl_ntt_run(c, d_coeffs, uint64_t(1) << log_n, 1u << log_n, d_out, uint64_t(1) << (log_n + rate_bits),
                       log_n + rate_bits, batch, false, GL_MULT_GENERATOR, 0, 1);
-}
-extern "C" int gl_fft_host(gl_ctx* c, uint64_t* h_data, uint32_t log_n, uint32_t batch, int inverse) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_fft_host(gl_ctx* c, uint64_t* h_data, uint32_t log_n, uint32_t batch, int inverse) try {
     GL_REQUIRE(c && h_data, GL_ERR_ARG, "null argument");
     GL_TRY(c->activate());
     size_t bytes = ((size_t)batch << log_n) * sizeof(gl_t);
-    gl_t* d = nullptr;
-    GL_CHECK_HIP(hipMalloc((void**)&d, bytes ? bytes : 8));
+    struct Dev { gl_t* p = nullptr; ~Dev() { if (p) (void)hipFree(p); } } dev;
+    GL_CHECK_HIP(hipMalloc((void**)&dev.p, bytes ? bytes : 8));
+    gl_t* d = dev.p;
     int st = gl_copy_h2d(c, d, h_data, bytes);
     if (st == GL_OK) st = inverse ? gl_ntt_inverse(c, d, log_n, batch) : gl_ntt_forward(c, d, log_n, batch);
     if (st == GL_OK) st = gl_copy_d2h(c, h_data, d, bytes);
-    (void)hipFree(d);
     return st;
-}
+} catch (...) { return gl_caught(); }
 
 // ----------------------------------------------------------------------------- C ABI: field kernels
 __global__ void k_field_op(int op, const gl_t* a, const gl_t* b, const gl_t* cc, gl_t* out, size_t n) {
@@ -317,7 +308,7 @@ __global__ void k_ext_op(int op, const gl_t* a, const gl_t* b, gl_t* out, size_t
     r = gl2_canon(r);
     out[2 * i] = r.a; out[2 * i + 1] = r.b;
 }
-extern "C" int gl_field_op(gl_ctx* c, int op, const uint64_t* a, const uint64_t* b, const uint64_t* cc, uint64_t* out, size_t n) {
+extern "C" int gl_field_op(gl_ctx* c, int op, const uint64_t* a, const uint64_t* b, const uint64_t* cc, uint64_t* out, size_t n) try {
     GL_REQUIRE(c && a && out && op >= 0 && op <= 7, GL_ERR_ARG, "gl_field_op: bad argument");
     GL_REQUIRE((op == 3 || op == 4 || op == 5) || b, GL_ERR_ARG, "gl_field_op: b is null");
     GL_REQUIRE(op != 6 || cc, GL_ERR_ARG, "gl_field_op: c is null");
@@ -326,8 +317,8 @@ extern "C" int gl_field_op(gl_ctx* c, int op, const uint64_t* a, const uint64_t*
     hipLaunchKernelGGL(k_field_op, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, op, a, b, cc, out, n);
     GL_CHECK_HIP(hipGetLastError());
     return GL_OK;
-}
-extern "C" int gl_ext_op(gl_ctx* c, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_ext_op(gl_ctx* c, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) try {
     GL_REQUIRE(c && a && out && op >= 0 && op <= 3, GL_ERR_ARG, "gl_ext_op: bad argument");
     GL_REQUIRE(op == 3 || b, GL_ERR_ARG, "gl_ext_op: b is null");
     if (!n) return GL_OK;
@@ -335,4 +326,4 @@ extern "C" int gl_ext_op(gl_ctx* c, int op, const uint64_t* a, const uint64_t* b
     hipLaunchKernelGGL(k_ext_op, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, op, a, b, out, n);
     GL_CHECK_HIP(hipGetLastError());
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }

@@ -5,6 +5,7 @@
 #include "context.hpp"
 #include "host_circuit.hpp"
 #include "prover_kernels.cuh"
+#include "proof.hpp"
 #include <cstring>
 #include <memory>
 
@@ -29,90 +30,6 @@ struct gl_circuit {
     gl_t circuit_digest[4];
 };
 
-struct gl_proof {
-    std::vector<uint8_t> bytes;
-    std::vector<gl_t> challenges;     // betas gammas alphas zeta fri_alpha pow pi_hash fri_betas...
-    std::vector<gl_t> caps;           // 3 x 16 x 4
-    std::vector<gl_t> zs_pp;          // [20][n]
-    std::vector<gl_t> quotient;       // [16][n]
-    std::vector<uint64_t> query_indices;
-};
-
-// C handle of the Challenger for callers of the phase API that have no transcript of their own (C / C++ / Python)
-struct gl_challenger { HostChallenger ch; };
-extern "C" gl_challenger* gl_challenger_new(void) { return new gl_challenger(); }
-// Challenger::<F, H>::new (iop/challenger.rs:31-37) for H = Poseidon (0) or Keccak (1, KeccakPermutation: hash/keccak.rs:64-95)
-extern "C" gl_challenger* gl_challenger_new_h(uint32_t hasher) {
-    if (hasher > GL_HASHER_KECCAK) { (void)gl_fail(GL_ERR_ARG, "gl_challenger_new_h: hasher is 0 (Poseidon) or 1 (Keccak)", __FILE__, __LINE__); return nullptr; }
-    gl_challenger* c = new gl_challenger();
-    c->ch.hasher = hasher;
-    return c;
-}
-// observe_hash::<OH> / observe_cap::<OH> (iop/challenger.rs:72-80; BytesHash::to_vec hash_types.rs:181-191)
-extern "C" int gl_challenger_observe_hashes(gl_challenger* c, uint32_t oh, const uint64_t* h_hashes, size_t count) {
-    GL_REQUIRE(c && (h_hashes || !count) && oh <= GL_HASHER_KECCAK, GL_ERR_ARG, "gl_challenger_observe_hashes: bad argument");
-    GL_REQUIRE(glhost::hashes_well_formed(oh, h_hashes, count), GL_ERR_ARG, "a BytesHash<25> slot with non-zero padding bytes");
-    c->ch.observe_hashes(oh, h_hashes, count);
-    return GL_OK;
-}
-extern "C" void gl_challenger_free(gl_challenger* c) { delete c; }
-extern "C" int gl_challenger_observe(gl_challenger* c, const uint64_t* h_elements, size_t count) {
-    GL_REQUIRE(c && (h_elements || !count), GL_ERR_ARG, "gl_challenger_observe: null argument");
-    c->ch.observe_many(h_elements, count);
-    return GL_OK;
-}
-extern "C" int gl_challenger_get_challenges(gl_challenger* c, uint64_t* h_out, size_t count) {
-    GL_REQUIRE(c && (h_out || !count), GL_ERR_ARG, "gl_challenger_get_challenges: null argument");
-    for (size_t i = 0; i < count; i++) h_out[i] = c->ch.challenge();
-    return GL_OK;
-}
-// sponge state and pending inputs, as fri_proof_of_work reads them (fri/prover.rs:127-140): for gl_pow_grind
-extern "C" int gl_challenger_state(const gl_challenger* c, uint64_t h_sponge_state[12], uint64_t h_input_buffer[8], uint32_t* input_len) {
-    GL_REQUIRE(c && h_sponge_state && h_input_buffer && input_len, GL_ERR_ARG, "gl_challenger_state: null argument");
-    for (int i = 0; i < 12; i++) h_sponge_state[i] = c->ch.state[i];
-    for (int i = 0; i < c->ch.nin; i++) h_input_buffer[i] = c->ch.in[i];
-    *input_len = (uint32_t)c->ch.nin;
-    return GL_OK;
-}
-
-// ---- host circuit API ------------------------------------------------------------------------------------------------
-static int matmul_circuit_build(size_t m, bool zero_knowledge, gl_host_circuit** out, uint32_t hasher = GL_HASHER_POSEIDON) {
-    GL_REQUIRE(out, GL_ERR_ARG, "null out");
-    GL_REQUIRE(hasher <= GL_HASHER_KECCAK, GL_ERR_ARG, "hasher is 0 (Poseidon) or 1 (Keccak)");
-    std::unique_ptr<gl_host_circuit> h(new gl_host_circuit());
-    int st = glhost::build_matmul(m, &h->hc, zero_knowledge, hasher);
-    if (st != GL_OK) return gl_fail(st, "matmul dimension out of range (1..256)", __FILE__, __LINE__);
-    *out = h.release();
-    return GL_OK;
-}
-extern "C" int gl_matmul_circuit_build(size_t m, gl_host_circuit** out) { return matmul_circuit_build(m, false, out); }
-extern "C" int gl_matmul_circuit_build_zk(size_t m, gl_host_circuit** out) { return matmul_circuit_build(m, true, out); }
-// the demo's circuit under `type C = KeccakGoldilocksConfig` (plonky2/src/bin/matrix_mul.rs:21-23) or the Poseidon one, zk or not
-extern "C" int gl_matmul_circuit_build_h(size_t m, uint32_t zero_knowledge, uint32_t hasher, gl_host_circuit** out) {
-    GL_REQUIRE(zero_knowledge <= 1, GL_ERR_ARG, "zero_knowledge is 0 or 1");
-    return matmul_circuit_build(m, zero_knowledge != 0, out, hasher);
-}
-extern "C" int gl_host_circuit_desc(const gl_host_circuit* hc, gl_circuit_desc* out) {
-    GL_REQUIRE(hc && out, GL_ERR_ARG, "null argument");
-    *out = hc->hc.desc;
-    return GL_OK;
-}
-extern "C" int gl_host_circuit_row_gates(const gl_host_circuit* hc, uint8_t* h_out) {
-    GL_REQUIRE(hc && h_out, GL_ERR_ARG, "null argument");
-    memcpy(h_out, hc->hc.row_gate.data(), hc->hc.row_gate.size());
-    return GL_OK;
-}
-extern "C" int gl_host_circuit_constants_sigmas(const gl_host_circuit* hc, uint64_t* h_out) {
-    GL_REQUIRE(hc && h_out, GL_ERR_ARG, "null argument");
-    hc->hc.ensure_host_sigmas();
-    memcpy(h_out, hc->hc.constants_sigmas.data(), hc->hc.constants_sigmas.size() * sizeof(gl_t));
-    return GL_OK;
-}
-extern "C" int gl_matmul_witness(const gl_host_circuit* hc, const uint64_t* a, const uint64_t* b, uint64_t filler_seed, uint64_t* h_wires, uint64_t* h_pis) {
-    GL_REQUIRE(hc && a && b && h_wires && h_pis, GL_ERR_ARG, "null argument");
-    return glhost::matmul_witness(hc->hc, a, b, filler_seed, h_wires, h_pis);
-}
-extern "C" void gl_host_circuit_free(gl_host_circuit* hc) { delete hc; }
 
 // ---- device circuit -------------------------------------------------------------------------------------------------
 static int validate_desc(const gl_circuit_desc& d) {
@@ -145,7 +62,7 @@ static int validate_desc(const gl_circuit_desc& d) {
     return GL_OK;
 }
 
-extern "C" void gl_circuit_free(gl_circuit* c) {
+extern "C" void gl_circuit_free(gl_circuit* c) noexcept {
     if (!c) return;
     if (c->cs_batch) gl_batch_free(c->cs_batch);
     if (c->d_sigmas) c->ctx->pool_release(c->d_sigmas);
@@ -224,7 +141,7 @@ static int circuit_finish(gl_ctx* ctx, const gl_circuit_desc* desc, const gl_t* 
     *out = c.release();
     return GL_OK;
 }
-extern "C" int gl_circuit_create(gl_ctx* ctx, const gl_circuit_desc* desc, const uint64_t* h_cs, gl_circuit** out) {
+extern "C" int gl_circuit_create(gl_ctx* ctx, const gl_circuit_desc* desc, const uint64_t* h_cs, gl_circuit** out) try {
     GL_REQUIRE(ctx && desc && h_cs && out, GL_ERR_ARG, "null argument");
     GL_REQUIRE(desc->degree_bits >= 1 && desc->degree_bits <= 21 && desc->num_selectors <= 4, GL_ERR_ARG, "bad degree / selector count");
     gl_circuit_desc d = *desc;
@@ -235,9 +152,9 @@ extern "C" int gl_circuit_create(gl_ctx* ctx, const gl_circuit_desc* desc, const
     DevBuf d_cs(ctx); GL_TRY(d_cs.alloc(ncs * n * sizeof(gl_t)));
     GL_TRY(gl_copy_h2d(ctx, d_cs.p, h_cs, ncs * n * sizeof(gl_t)));
     return circuit_finish(ctx, &d, d_cs.as<gl_t>(), out);
-}
+} catch (...) { return gl_caught(); }
 // build() with the sigma polynomials computed on the device from the copy-constraint classes (sigma.hip)
-extern "C" int gl_circuit_create_from_classes(gl_ctx* ctx, const gl_circuit_desc* desc, const uint64_t* h_constants, const uint64_t* h_wire_classes, gl_circuit** out) {
+extern "C" int gl_circuit_create_from_classes(gl_ctx* ctx, const gl_circuit_desc* desc, const uint64_t* h_constants, const uint64_t* h_wire_classes, gl_circuit** out) try {
     GL_REQUIRE(ctx && desc && h_constants && h_wire_classes && out, GL_ERR_ARG, "null argument");
     GL_REQUIRE(desc->degree_bits >= 1 && desc->degree_bits <= 21 && desc->num_selectors <= 4, GL_ERR_ARG, "bad degree / selector count");
     gl_circuit_desc dd = *desc;
@@ -256,32 +173,27 @@ extern "C" int gl_circuit_create_from_classes(gl_ctx* ctx, const gl_circuit_desc
     ctx->timing_end();
     GL_TRY(st);
     return circuit_finish(ctx, desc, d_cs.as<gl_t>(), out);
-}
-extern "C" int gl_circuit_from_host(gl_ctx* ctx, const gl_host_circuit* hc, gl_circuit** out) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_circuit_from_host(gl_ctx* ctx, const gl_host_circuit* hc, gl_circuit** out) try {
     GL_REQUIRE(hc, GL_ERR_ARG, "null host circuit");
     // the constant columns are the first num_constants columns of the host matrix; the sigma columns come from the classes
     return gl_circuit_create_from_classes(ctx, &hc->hc.desc, hc->hc.constants_sigmas.data(), hc->hc.wire_class.data(), out);
-}
-extern "C" int gl_host_circuit_wire_classes(const gl_host_circuit* hc, uint64_t* h_out) {
-    GL_REQUIRE(hc && h_out, GL_ERR_ARG, "null argument");
-    memcpy(h_out, hc->hc.wire_class.data(), hc->hc.wire_class.size() * sizeof(uint64_t));
-    return GL_OK;
-}
-extern "C" int gl_circuit_description(const gl_circuit* c, gl_circuit_desc* out) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_circuit_description(const gl_circuit* c, gl_circuit_desc* out) try {
     GL_REQUIRE(c && out, GL_ERR_ARG, "null argument");
     *out = c->desc;
     return GL_OK;
-}
-extern "C" int gl_circuit_digest(const gl_circuit* c, uint64_t h_out[4]) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_circuit_digest(const gl_circuit* c, uint64_t h_out[4]) try {
     GL_REQUIRE(c && h_out, GL_ERR_ARG, "null argument");
     memcpy(h_out, c->circuit_digest, 32);
     return GL_OK;
-}
-extern "C" int gl_circuit_constants_sigmas_cap(const gl_circuit* c, uint64_t* h_out) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_circuit_constants_sigmas_cap(const gl_circuit* c, uint64_t* h_out) try {
     GL_REQUIRE(c && h_out, GL_ERR_ARG, "null argument");
     return gl_batch_cap(c->cs_batch, h_out);
-}
-extern "C" const gl_batch* gl_circuit_constants_sigmas_batch(const gl_circuit* c) { return c ? c->cs_batch : nullptr; }
+} catch (...) { return gl_caught(); }
+extern "C" const gl_batch* gl_circuit_constants_sigmas_batch(const gl_circuit* c) noexcept { return c ? c->cs_batch : nullptr; }
 
 // ---- helpers -------------------------------------------------------------------------------------------------------------
 static inline gl2_t h_ext(gl_t a, gl_t b) { return gl2_make(a, b); }
@@ -481,14 +393,14 @@ static int partial_products_phase(gl_ctx* ctx, const gl_circuit* cir, const uint
     GL_REQUIRE((cir->desc.num_lookup_polys != 0) == (deltas8 != nullptr), GL_ERR_ARG, "circuits with lookups take gl_partial_products_lookups (with the delta challenges), circuits without take gl_partial_products");
     return commit_zs(ctx, cir, d_wires, betas, gammas, deltas8, out, nullptr);
 }
-extern "C" int gl_partial_products(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* d_wires, const uint64_t betas[2], const uint64_t gammas[2], gl_batch** out) {
+extern "C" int gl_partial_products(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* d_wires, const uint64_t betas[2], const uint64_t gammas[2], gl_batch** out) try {
     return partial_products_phase(ctx, cir, d_wires, betas, gammas, nullptr, out);
-}
+} catch (...) { return gl_caught(); }
 extern "C" int gl_partial_products_lookups(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* d_wires, const uint64_t betas[2], const uint64_t gammas[2],
-                                           const uint64_t deltas[8], gl_batch** out) {
+                                           const uint64_t deltas[8], gl_batch** out) try {
     GL_REQUIRE(deltas, GL_ERR_ARG, "gl_partial_products_lookups: null deltas");
     return partial_products_phase(ctx, cir, d_wires, betas, gammas, deltas, out);
-}
+} catch (...) { return gl_caught(); }
 
 // ---- 9/10. compute_quotient_polys + split + commitment (plonk/prover.rs:229-271,574-744), for gl_quotient_polys[_lookups] and prove():
 //      d_q[2][8n] -> the 16 chunk COEFFICIENT columns -> committed batch.  `apow` is the host source of an asynchronous upload: the caller
@@ -562,20 +474,20 @@ static int quotient_phase(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* wi
     return rc;
 }
 extern "C" int gl_quotient_polys(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* wires, const gl_batch* zs_partial_products, const uint64_t pi_hash[4],
-                                 const uint64_t betas[2], const uint64_t gammas[2], const uint64_t alphas[2], gl_batch** out) {
+                                 const uint64_t betas[2], const uint64_t gammas[2], const uint64_t alphas[2], gl_batch** out) try {
     return quotient_phase(ctx, cir, wires, zs_partial_products, pi_hash, betas, gammas, alphas, nullptr, out);
-}
+} catch (...) { return gl_caught(); }
 extern "C" int gl_quotient_polys_lookups(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* wires, const gl_batch* zs_partial_products_lookups, const uint64_t pi_hash[4],
-                                         const uint64_t betas[2], const uint64_t gammas[2], const uint64_t alphas[2], const uint64_t deltas[8], gl_batch** out) {
+                                         const uint64_t betas[2], const uint64_t gammas[2], const uint64_t alphas[2], const uint64_t deltas[8], gl_batch** out) try {
     GL_REQUIRE(deltas, GL_ERR_ARG, "gl_quotient_polys_lookups: null deltas");
     return quotient_phase(ctx, cir, wires, zs_partial_products_lookups, pi_hash, betas, gammas, alphas, deltas, out);
-}
+} catch (...) { return gl_caught(); }
 
 // ---- 12. OpeningSet::new (plonk/proof.rs:306-344): polynomials `first .. first + count` of a batch at an extension point ----
 static void launch_open(gl_ctx* ctx, const gl_batch* b, size_t first, size_t count, gl2_t z, gl_t* d_out) {
     hipLaunchKernelGGL(k_eval_at_ext, dim3((unsigned)count), dim3(256), 0, ctx->stream, b->coeffs + first * b->n, (uint32_t)b->n, (uint64_t)b->n, z.a, z.b, d_out);
 }
-extern "C" int gl_open_at(gl_ctx* ctx, const gl_batch* b, const uint64_t z[2], size_t first_col, size_t num_cols, uint64_t* h_out) {
+extern "C" int gl_open_at(gl_ctx* ctx, const gl_batch* b, const uint64_t z[2], size_t first_col, size_t num_cols, uint64_t* h_out) try {
     GL_REQUIRE(ctx && b && z && h_out, GL_ERR_ARG, "gl_open_at: null argument");
     GL_REQUIRE(first_col <= b->ncols && num_cols <= b->ncols - first_col && num_cols <= DS_OPEN_MAX, GL_ERR_ARG, "gl_open_at: column range out of bounds");
     if (!num_cols) return GL_OK;
@@ -587,7 +499,7 @@ extern "C" int gl_open_at(gl_ctx* ctx, const gl_batch* b, const uint64_t z[2], s
     ctx->timing_end();
     GL_CHECK_HIP(hipGetLastError());
     return d2h(ctx, h_out, d_open, 2 * num_cols * sizeof(gl_t));
-}
+} catch (...) { return gl_caught(); }
 
 // fri_all_polys / fri_next_batch_polys (circuit_data.rs:564-597) in FriOpenings order (proof.rs:346-380) over the oracles constants||sigmas,
 // wires, Z||partial products(||lookups), quotient: at zeta the constants, sigmas, wires, zs, partial products, quotient chunks, lookup
@@ -634,7 +546,7 @@ struct gl_fri {
     // host sources of asynchronous uploads (alive until the object dies)
     std::vector<const gl_t*> h_cols; std::vector<gl_t> h_apow;
 };
-extern "C" void gl_fri_free(gl_fri* f) {
+extern "C" void gl_fri_free(gl_fri* f) noexcept {
     if (!f) return;
     gl_ctx* ctx = f->ctx;
     if (ctx) (void)gl_stream_wait(ctx->stream);
@@ -697,12 +609,12 @@ static int fri_combine(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* const
     *out = f.release();
     return GL_OK;
 }
-extern "C" int gl_fri_combine(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* const batches[4], const uint64_t zeta_in[2], const uint64_t alpha_in[2], gl_fri** out) {
+extern "C" int gl_fri_combine(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* const batches[4], const uint64_t zeta_in[2], const uint64_t alpha_in[2], gl_fri** out) try {
     GL_TRY(check_phase_api(ctx, cir));
     return fri_combine(ctx, cir, batches, zeta_in, alpha_in, out);
-}
+} catch (...) { return gl_caught(); }
 // fri_committed_trees, first half of one loop iteration (fri/prover.rs:76-92): Merkle tree of the current codeword
-extern "C" int gl_fri_commit_round(gl_fri* f, uint64_t* h_cap_out) {
+extern "C" int gl_fri_commit_round(gl_fri* f, uint64_t* h_cap_out) try {
     GL_REQUIRE(f && h_cap_out, GL_ERR_ARG, "gl_fri_commit_round: null argument");
     GL_REQUIRE(f->round < f->desc.num_fri_rounds && !f->committed, GL_ERR_ARG, "gl_fri_commit_round: no round left to commit (call gl_fri_fold first)");
     gl_ctx* ctx = f->ctx;
@@ -719,9 +631,9 @@ extern "C" int gl_fri_commit_round(gl_fri* f, uint64_t* h_cap_out) {
     f->trees.push_back(std::move(tree));
     f->committed = true;
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 // second half (fri/prover.rs:94-103): fold the coefficients by beta, next codeword on the coset shift^arity
-extern "C" int gl_fri_fold(gl_fri* f, const uint64_t beta_in[2]) {
+extern "C" int gl_fri_fold(gl_fri* f, const uint64_t beta_in[2]) try {
     GL_REQUIRE(f && beta_in, GL_ERR_ARG, "gl_fri_fold: null argument");
     GL_REQUIRE(f->committed, GL_ERR_ARG, "gl_fri_fold: commit the round first");
     gl_ctx* ctx = f->ctx;
@@ -737,19 +649,22 @@ extern "C" int gl_fri_fold(gl_fri* f, const uint64_t beta_in[2]) {
                        (uint32_t)next_n, arity, beta.a, beta.b, next->as<gl_t>(), next->as<gl_t>() + next_n);
     ctx->timing_end();
     GL_CHECK_HIP(hipGetLastError());
-    f->shift = gl_canon(gl_exp(f->shift, arity));
+    // the next round's state is built beside the handle and moved in at the end: a failure on the way leaves the round as it was
+    const gl_t next_shift = gl_canon(gl_exp(f->shift, arity));
+    const uint32_t next_lgN = f->cur_lgN - ab;
+    std::unique_ptr<DevBuf> next_vals(new DevBuf(ctx));
+    GL_TRY(next_vals->alloc(2 * (size_t(1) << next_lgN) * sizeof(gl_t)));
+    GL_TRY(gl_ntt_run(ctx, next->as<gl_t>(), next_n, (uint32_t)next_n, next_vals->as<gl_t>(), size_t(1) << next_lgN, next_lgN, 2, false, next_shift, 0, 1));
+    f->vals.reserve(f->vals.size() + 1); f->lg.reserve(f->lg.size() + 1);      // (at most 8 rounds) nothing below can fail
     f->vals.push_back(std::move(f->cur_vals)); f->lg.push_back(f->cur_lgN);
-    f->cur_lgN -= ab;
-    f->cur_vals.reset(new DevBuf(ctx));
-    GL_TRY(f->cur_vals->alloc(2 * (size_t(1) << f->cur_lgN) * sizeof(gl_t)));
-    GL_TRY(gl_ntt_run(ctx, next->as<gl_t>(), next_n, (uint32_t)next_n, f->cur_vals->as<gl_t>(), size_t(1) << f->cur_lgN, f->cur_lgN, 2, false, f->shift, 0, 1));
+    f->cur_vals = std::move(next_vals); f->cur_lgN = next_lgN; f->shift = next_shift;
     f->coef = std::move(next);
     f->cur_n = next_n;
     f->round++; f->committed = false;
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 // final polynomial: the remaining non-zero coefficients (coeffs.truncate(len >> rate_bits), fri/prover.rs:106-111), interleaved (a, b)
-extern "C" int gl_fri_final_poly(gl_fri* f, uint64_t* h_out, size_t cap_words, size_t* num_words) {
+extern "C" int gl_fri_final_poly(gl_fri* f, uint64_t* h_out, size_t cap_words, size_t* num_words) try {
     GL_REQUIRE(f && num_words, GL_ERR_ARG, "gl_fri_final_poly: null argument");
     GL_REQUIRE(f->round == f->desc.num_fri_rounds && !f->committed, GL_ERR_ARG, "gl_fri_final_poly: reduction rounds not finished");
     *num_words = 2 * f->cur_n;
@@ -760,16 +675,16 @@ extern "C" int gl_fri_final_poly(gl_fri* f, uint64_t* h_out, size_t cap_words, s
     GL_TRY(d2h(f->ctx, fin.data(), f->coef->p, 2 * f->cur_n * sizeof(gl_t)));
     for (size_t i = 0; i < f->cur_n; i++) { h_out[2 * i] = fin[i]; h_out[2 * i + 1] = fin[f->cur_n + i]; }
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 
 // ---- fri_proof_of_work (fri/prover.rs:115-160): smallest w such that permute(state with the pending inputs and w)[7] has
 //      enough leading zeros.  `sponge_state` is the Challenger's sponge, `input_buffer[0..input_len)` its pending inputs. ----
-extern "C" int gl_pow_grind(gl_ctx* ctx, const uint64_t sponge_state[12], const uint64_t* input_buffer, uint32_t input_len, uint32_t min_leading_zeros, uint64_t* witness) {
+extern "C" int gl_pow_grind(gl_ctx* ctx, const uint64_t sponge_state[12], const uint64_t* input_buffer, uint32_t input_len, uint32_t min_leading_zeros, uint64_t* witness) try {
     return gl_pow_grind_h(ctx, GL_HASHER_POSEIDON, sponge_state, input_buffer, input_len, min_leading_zeros, witness);
-}
+} catch (...) { return gl_caught(); }
 // fri_proof_of_work over Challenger<F, H>'s permutation, H = `hasher` (fri/prover.rs:115-160; KeccakPermutation hash/keccak.rs:64-95)
 extern "C" int gl_pow_grind_h(gl_ctx* ctx, uint32_t hasher, const uint64_t sponge_state[12], const uint64_t* input_buffer, uint32_t input_len, uint32_t min_leading_zeros,
-                              uint64_t* witness) {
+                              uint64_t* witness) try {
     GL_REQUIRE(hasher <= GL_HASHER_KECCAK, GL_ERR_ARG, "gl_pow_grind: hasher is 0 (Poseidon) or 1 (Keccak)");
     GL_REQUIRE(ctx && sponge_state && witness && (input_buffer || !input_len), GL_ERR_ARG, "gl_pow_grind: null argument");
     GL_REQUIRE(input_len < 8 && min_leading_zeros <= 40, GL_ERR_ARG, "gl_pow_grind: the witness must fit the rate (input_len < 8), at most 40 bits of work");
@@ -810,7 +725,7 @@ extern "C" int gl_pow_grind_h(gl_ctx* ctx, uint32_t hasher, const uint64_t spong
     GL_REQUIRE(res != ~0ull, GL_ERR_INTERNAL, "Proof of work failed. This is highly unlikely!");
     *witness = (uint64_t)res;
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 
 // ---- fri_prover_query_rounds (fri/prover.rs:162-216): the serialised FriQueryRound list
 //      (util/serialization/mod.rs:1477-1546: per query 4 x (leaf, u8 path length, siblings), then per reduction the
@@ -892,7 +807,7 @@ static int fri_query_blob(gl_fri* f, const uint32_t* x_index, uint32_t nq, std::
     }
     return GL_OK;
 }
-extern "C" int gl_fri_query(gl_fri* f, const uint32_t* x_index, uint32_t num_queries, uint8_t* h_blob, size_t cap_bytes, size_t* num_bytes) {
+extern "C" int gl_fri_query(gl_fri* f, const uint32_t* x_index, uint32_t num_queries, uint8_t* h_blob, size_t cap_bytes, size_t* num_bytes) try {
     GL_REQUIRE(f && x_index && num_bytes, GL_ERR_ARG, "gl_fri_query: null argument");
     GL_REQUIRE(num_queries >= 1 && num_queries <= 256, GL_ERR_ARG, "gl_fri_query: 1..256 queries");
     GL_TRY(f->ctx->activate());
@@ -903,7 +818,7 @@ extern "C" int gl_fri_query(gl_fri* f, const uint32_t* x_index, uint32_t num_que
     GL_REQUIRE(cap_bytes >= blob.size(), GL_ERR_ARG, "gl_fri_query: output too small");
     memcpy(h_blob, blob.data(), blob.size());
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 
 // ======================================================================================================================
 // prove(): the driver (plonk/prover.rs:102-329) -- the phases above plus the transcript
@@ -1082,24 +997,24 @@ static int prove_host_witness(gl_ctx* ctx, const gl_circuit* cir, const uint64_t
     ctx->timing_end();
     return prove_impl(ctx, cir, d_wit.as<gl_t>(), &d_wit, h_pis, npis, nullptr, out);
 }
-extern "C" int gl_prove(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* h_wires, const uint64_t* h_pis, size_t npis, gl_proof** out) {
+extern "C" int gl_prove(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* h_wires, const uint64_t* h_pis, size_t npis, gl_proof** out) try {
     GL_REQUIRE(ctx && cir && h_wires && out, GL_ERR_ARG, "gl_prove: null argument");
     return prove_host_witness(ctx, cir, nullptr, h_wires, h_pis, npis, out);
-}
+} catch (...) { return gl_caught(); }
 // the witness as the reference holds it: one host vector per wire (MatrixWitness.wire_values: Vec<Vec<F>>, iop/witness.rs:256-258)
-extern "C" int gl_prove_columns(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* const* h_wire_columns, const uint64_t* h_pis, size_t npis, gl_proof** out) {
+extern "C" int gl_prove_columns(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* const* h_wire_columns, const uint64_t* h_pis, size_t npis, gl_proof** out) try {
     GL_REQUIRE(ctx && cir && h_wire_columns && out, GL_ERR_ARG, "gl_prove_columns: null argument");
     for (size_t c = 0; c < 135; c++) GL_REQUIRE(h_wire_columns[c], GL_ERR_ARG, "gl_prove_columns: null column");
     return prove_host_witness(ctx, cir, h_wire_columns, nullptr, h_pis, npis, out);
-}
-extern "C" int gl_prove_device(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* d_wires, const uint64_t* h_pis, size_t npis, gl_proof** out) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_prove_device(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* d_wires, const uint64_t* h_pis, size_t npis, gl_proof** out) try {
     return prove_impl(ctx, cir, d_wires, nullptr, h_pis, npis, nullptr, out);
-}
+} catch (...) { return gl_caught(); }
 extern "C" int gl_prove_device_seeded(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* d_wires, const uint64_t* h_pis, size_t npis, const uint8_t seed[32],
-                                      gl_proof** out) {
+                                      gl_proof** out) try {
     return prove_impl(ctx, cir, d_wires, nullptr, h_pis, npis, nullptr, out, seed);
-}
-extern "C" int gl_witness_blind(gl_ctx* ctx, const gl_circuit* cir, uint64_t* d_wires, const uint8_t seed[32]) {
+} catch (...) { return gl_caught(); }
+extern "C" int gl_witness_blind(gl_ctx* ctx, const gl_circuit* cir, uint64_t* d_wires, const uint8_t seed[32]) try {
     GL_REQUIRE(ctx && cir && d_wires, GL_ERR_ARG, "gl_witness_blind: null argument");
     GL_REQUIRE(cir->ctx->device == ctx->device, GL_ERR_ARG, "gl_witness_blind: circuit lives on another device");
     const gl_circuit_desc& d = cir->desc;
@@ -1109,17 +1024,17 @@ extern "C" int gl_witness_blind(gl_ctx* ctx, const gl_circuit* cir, uint64_t* d_
     uint8_t os[32];
     if (!seed) { GL_TRY(gl_os_seed(os)); seed = os; }
     return gl_launch_witness_blind(ctx, seed, d_wires, (uint32_t)cir->n, d.num_gate_rows, b.regular, b.pairs);
-}
+} catch (...) { return gl_caught(); }
 extern "C" int gl_prove_device_hashed(gl_ctx* ctx, const gl_circuit* cir, const uint64_t* d_wires, const uint64_t* h_pis, size_t npis,
-                                      const uint64_t public_inputs_hash[4], gl_proof** out) {
+                                      const uint64_t public_inputs_hash[4], gl_proof** out) try {
     GL_REQUIRE(public_inputs_hash, GL_ERR_ARG, "gl_prove_device_hashed: null hash");
     return prove_impl(ctx, cir, d_wires, nullptr, h_pis, npis, public_inputs_hash, out);
-}
+} catch (...) { return gl_caught(); }
 // One pass of the proving pipeline over an all-zero witness, result thrown away: afterwards this context holds everything a proof of this
 // circuit needs besides its own data -- the code objects of every kernel on the path loaded, the twiddle / power tables of the circuit's
 // transform sizes built, the context's pool grown to the pipeline's working set.  (The reference precomputes its fft_root_table in build()
 // too, circuit_builder.rs:1016-1019.)  A zero witness does not satisfy the circuit; nothing on the path asserts that it does.
-extern "C" int gl_circuit_warm_up(gl_ctx* ctx, const gl_circuit* cir) {
+extern "C" int gl_circuit_warm_up(gl_ctx* ctx, const gl_circuit* cir) try {
     GL_REQUIRE(ctx && cir, GL_ERR_ARG, "gl_circuit_warm_up: null argument");
     GL_REQUIRE(cir->ctx->device == ctx->device, GL_ERR_ARG, "gl_circuit_warm_up: circuit lives on another device");
     GL_TRY(ctx->activate());
@@ -1131,44 +1046,10 @@ extern "C" int gl_circuit_warm_up(gl_ctx* ctx, const gl_circuit* cir) {
     const int st = prove_impl(ctx, cir, d_w.as<gl_t>(), nullptr, pis.data(), cir->desc.num_public_inputs, nullptr, &pr);
     if (pr) gl_proof_free(pr);
     return st == GL_ERR_ZETA_IN_SUBGROUP ? GL_OK : st;       // (probability 2^-49: still warmed up to the opening point)
-}
+} catch (...) { return gl_caught(); }
 
-extern "C" size_t gl_proof_num_bytes(const gl_proof* p) { return p ? p->bytes.size() : 0; }
-extern "C" int gl_proof_bytes(const gl_proof* p, uint8_t* h_out, size_t cap) {
-    GL_REQUIRE(p && h_out && cap >= p->bytes.size(), GL_ERR_ARG, "buffer too small");
-    memcpy(h_out, p->bytes.data(), p->bytes.size());
-    return GL_OK;
-}
-extern "C" size_t gl_proof_challenges(const gl_proof* p, uint64_t* h_out) {
-    if (!p || !h_out) return 0;
-    memcpy(h_out, p->challenges.data(), p->challenges.size() * sizeof(gl_t));
-    return p->challenges.size();
-}
-extern "C" int gl_proof_caps(const gl_proof* p, uint64_t* h_out) {
-    GL_REQUIRE(p && h_out, GL_ERR_ARG, "null argument");
-    memcpy(h_out, p->caps.data(), p->caps.size() * sizeof(gl_t));
-    return GL_OK;
-}
-extern "C" int gl_ctx_capture_intermediates(gl_ctx* ctx, int enable) {
+extern "C" int gl_ctx_capture_intermediates(gl_ctx* ctx, int enable) try {
     GL_REQUIRE(ctx, GL_ERR_ARG, "null context");
     ctx->capture_intermediates = enable != 0;
     return GL_OK;
-}
-extern "C" int gl_proof_zs_partial_products(const gl_proof* p, uint64_t* h_out) {
-    GL_REQUIRE(p && h_out, GL_ERR_ARG, "null argument");
-    GL_REQUIRE(!p->zs_pp.empty(), GL_ERR_ARG, "intermediates were not captured: call gl_ctx_capture_intermediates(ctx, 1) before proving");
-    memcpy(h_out, p->zs_pp.data(), p->zs_pp.size() * sizeof(gl_t));
-    return GL_OK;
-}
-extern "C" int gl_proof_quotient_chunks(const gl_proof* p, uint64_t* h_out) {
-    GL_REQUIRE(p && h_out, GL_ERR_ARG, "null argument");
-    GL_REQUIRE(!p->quotient.empty(), GL_ERR_ARG, "intermediates were not captured: call gl_ctx_capture_intermediates(ctx, 1) before proving");
-    memcpy(h_out, p->quotient.data(), p->quotient.size() * sizeof(gl_t));
-    return GL_OK;
-}
-extern "C" size_t gl_proof_query_indices(const gl_proof* p, uint64_t* h_out) {
-    if (!p || !h_out) return 0;
-    memcpy(h_out, p->query_indices.data(), p->query_indices.size() * sizeof(uint64_t));
-    return p->query_indices.size();
-}
-extern "C" void gl_proof_free(gl_proof* p) { delete p; }
+} catch (...) { return gl_caught(); }

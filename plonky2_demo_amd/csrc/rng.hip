@@ -46,18 +46,11 @@ int gl_fill_random(gl_ctx* c, const uint8_t seed[32], uint32_t stream0, uint32_t
     return GL_OK;
 }
 
-extern "C" int gl_random_elements(gl_ctx* c, const uint8_t seed[32], uint32_t stream, uint64_t first, uint64_t count, uint64_t* d_out) {
+extern "C" int gl_random_elements(gl_ctx* c, const uint8_t seed[32], uint32_t stream, uint64_t first, uint64_t count, uint64_t* d_out) try {
     GL_REQUIRE(c && seed && d_out, GL_ERR_ARG, "gl_random_elements: null argument");
     GL_TRY(c->activate());
     return gl_fill_random(c, seed, stream, 1, first, count, d_out, 0);
-}
-extern "C" int gl_random_elements_host(const uint8_t seed[32], uint32_t stream, uint64_t first, uint64_t count, uint64_t* h_out) {
-    GL_REQUIRE(seed && (h_out || !count), GL_ERR_ARG, "gl_random_elements_host: null argument");
-    GL_REQUIRE(first + count >= first && first + count <= (uint64_t(1) << 34), GL_ERR_ARG, "random elements: index beyond 2^34 (32-bit block counter)");
-    const gl_chacha_key key = gl_chacha_key_from_bytes(seed);
-    for (uint64_t i = 0; i < count; i++) h_out[i] = gl_random_element(key, stream, first + i);
-    return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 
 // RandomValueGenerator + CopyGenerator of blind() (circuit_builder.rs:777-818), then full_witness's zeros (iop/witness.rs:340-352):
 // rows g .. g + regular: all 135 wires random; then `pairs` row pairs whose first row's 80 routed wires are random and copied to the

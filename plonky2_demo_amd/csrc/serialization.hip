@@ -75,7 +75,7 @@ int read_fri_config(Reader& r, gl_circuit_desc& d) {
 }   // namespace
 
 // CommonCircuitData -> bytes.  *num_bytes receives the size; h_out may be null to query it.
-extern "C" int gl_common_data_to_bytes(const gl_circuit_desc* desc, uint8_t* h_out, size_t cap, size_t* num_bytes) {
+extern "C" int gl_common_data_to_bytes(const gl_circuit_desc* desc, uint8_t* h_out, size_t cap, size_t* num_bytes) try {
     GL_REQUIRE(desc && num_bytes, GL_ERR_ARG, "gl_common_data_to_bytes: null argument");
     const gl_circuit_desc& d = *desc;
     GL_REQUIRE(d.num_gates >= 1 && d.num_gates <= GL_MAX_GATES && d.num_fri_rounds <= 8 && d.num_selectors >= 1 && d.num_selectors <= 4, GL_ERR_ARG, "bad circuit description");
@@ -132,10 +132,10 @@ extern "C" int gl_common_data_to_bytes(const gl_circuit_desc* desc, uint8_t* h_o
     GL_REQUIRE(cap >= w.b.size(), GL_ERR_ARG, "gl_common_data_to_bytes: output too small");
     memcpy(h_out, w.b.data(), w.b.size());
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 
 // bytes -> CommonCircuitData (read_common_circuit_data, mod.rs:739-800).  *consumed receives the bytes read.
-extern "C" int gl_common_data_from_bytes(const uint8_t* h_bytes, size_t num_bytes, gl_circuit_desc* out, size_t* consumed) {
+extern "C" int gl_common_data_from_bytes(const uint8_t* h_bytes, size_t num_bytes, gl_circuit_desc* out, size_t* consumed) try {
     GL_REQUIRE(h_bytes && out, GL_ERR_ARG, "gl_common_data_from_bytes: null argument");
     Reader r(h_bytes, num_bytes);
     gl_circuit_desc d;
@@ -271,16 +271,16 @@ extern "C" int gl_common_data_from_bytes(const uint8_t* h_bytes, size_t num_byte
     *out = d;
     if (consumed) *consumed = r.pos;
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 
 // VerifierOnlyCircuitData (mod.rs:1889-1906): usize cap height, the cap's 2^height digests, the circuit digest
 extern "C" int gl_verifier_only_to_bytes(uint32_t cap_height, const uint64_t* constants_sigmas_cap, const uint64_t circuit_digest[4], uint8_t* h_out, size_t cap,
-                                         size_t* num_bytes) {
+                                         size_t* num_bytes) try {
     return gl_verifier_only_to_bytes_h(GL_HASHER_POSEIDON, cap_height, constants_sigmas_cap, circuit_digest, h_out, cap, num_bytes);
-}
+} catch (...) { return gl_caught(); }
 // write_verifier_only_circuit_data for C::Hasher = `hasher` (mod.rs:1889-1906; write_hash :248-256: a BytesHash<25> is its 25 bytes)
 extern "C" int gl_verifier_only_to_bytes_h(uint32_t hasher, uint32_t cap_height, const uint64_t* constants_sigmas_cap, const uint64_t circuit_digest[4], uint8_t* h_out,
-                                           size_t cap, size_t* num_bytes) {
+                                           size_t cap, size_t* num_bytes) try {
     GL_REQUIRE(constants_sigmas_cap && circuit_digest && num_bytes && cap_height <= 16 && hasher <= GL_HASHER_KECCAK, GL_ERR_ARG, "gl_verifier_only_to_bytes: bad argument");
     GL_REQUIRE(glhost::hashes_well_formed(hasher, constants_sigmas_cap, size_t(1) << cap_height) && glhost::hashes_well_formed(hasher, circuit_digest, 1), GL_ERR_ARG,
                "a BytesHash<25> slot with non-zero padding bytes");
@@ -297,14 +297,14 @@ extern "C" int gl_verifier_only_to_bytes_h(uint32_t hasher, uint32_t cap_height,
     GL_REQUIRE(cap >= w.b.size(), GL_ERR_ARG, "gl_verifier_only_to_bytes: output too small");
     memcpy(h_out, w.b.data(), w.b.size());
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 extern "C" int gl_verifier_only_from_bytes(const uint8_t* h_bytes, size_t num_bytes, uint32_t* cap_height, uint64_t* h_cap, size_t cap_words, uint64_t circuit_digest[4],
-                                           size_t* consumed) {
+                                           size_t* consumed) try {
     return gl_verifier_only_from_bytes_h(GL_HASHER_POSEIDON, h_bytes, num_bytes, cap_height, h_cap, cap_words, circuit_digest, consumed);
-}
+} catch (...) { return gl_caught(); }
 // read_verifier_only_circuit_data for C::Hasher = `hasher` (mod.rs:909-930; read_hash :1332-1338)
 extern "C" int gl_verifier_only_from_bytes_h(uint32_t hasher, const uint8_t* h_bytes, size_t num_bytes, uint32_t* cap_height, uint64_t* h_cap, size_t cap_words,
-                                             uint64_t circuit_digest[4], size_t* consumed) {
+                                             uint64_t circuit_digest[4], size_t* consumed) try {
     GL_REQUIRE(h_bytes && cap_height && circuit_digest && hasher <= GL_HASHER_KECCAK, GL_ERR_ARG, "gl_verifier_only_from_bytes: bad argument");
     Reader r(h_bytes, num_bytes);
     const uint64_t h = r.u64();
@@ -319,15 +319,15 @@ extern "C" int gl_verifier_only_from_bytes_h(uint32_t hasher, const uint8_t* h_b
     GL_REQUIRE(r.ok, GL_ERR_ARG, "truncated VerifierOnlyCircuitData");
     if (consumed) *consumed = r.pos;
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 
 // VerifierCircuitData::from_bytes(..).verify(proof) (circuit_data.rs:208-238; the bytes are verifier_only || common,
 // mod.rs:1908-1919)
-extern "C" int gl_verify_bytes(const uint8_t* h_verifier_data, size_t num_data_bytes, const uint8_t* proof_bytes, size_t num_proof_bytes) {
+extern "C" int gl_verify_bytes(const uint8_t* h_verifier_data, size_t num_data_bytes, const uint8_t* proof_bytes, size_t num_proof_bytes) try {
     return gl_verify_bytes_h(GL_HASHER_POSEIDON, h_verifier_data, num_data_bytes, proof_bytes, num_proof_bytes);
-}
+} catch (...) { return gl_caught(); }
 // VerifierCircuitData::<F, C, D>::from_bytes(..).verify(proof) with C::Hasher = `hasher` (circuit_data.rs:208-238)
-extern "C" int gl_verify_bytes_h(uint32_t hasher, const uint8_t* h_verifier_data, size_t num_data_bytes, const uint8_t* proof_bytes, size_t num_proof_bytes) {
+extern "C" int gl_verify_bytes_h(uint32_t hasher, const uint8_t* h_verifier_data, size_t num_data_bytes, const uint8_t* proof_bytes, size_t num_proof_bytes) try {
     GL_REQUIRE(h_verifier_data && proof_bytes && hasher <= GL_HASHER_KECCAK, GL_ERR_ARG, "gl_verify_bytes: bad argument");
     uint32_t cap_height = 0; uint64_t digest[4]; size_t used = 0, used2 = 0;
     std::vector<uint64_t> cap(size_t(4) << 16);
@@ -338,4 +338,4 @@ extern "C" int gl_verify_bytes_h(uint32_t hasher, const uint8_t* h_verifier_data
     GL_REQUIRE(cap_height == d.cap_height, GL_ERR_ARG, "cap height of the verifier data differs from the FRI configuration");
     d.hasher = hasher;
     return gl_verify(&d, cap.data(), digest, proof_bytes, num_proof_bytes);
-}
+} catch (...) { return gl_caught(); }

@@ -218,7 +218,7 @@ int reject(const char* why) { return gl_fail(GL_ERR_VERIFY, why, __FILE__, __LIN
 }  // namespace
 
 extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_sigmas_cap, const uint64_t circuit_digest[4],
-                         const uint8_t* proof_bytes, size_t num_bytes) {
+                         const uint8_t* proof_bytes, size_t num_bytes) try {
     GL_REQUIRE(desc && constants_sigmas_cap && circuit_digest && proof_bytes, GL_ERR_ARG, "gl_verify: null argument");
     const gl_circuit_desc& d = *desc;
     GL_REQUIRE(d.num_wires == 135 && d.num_routed_wires == 80 && d.num_challenges == 2 && d.quotient_degree_factor == 8 && d.rate_bits == 3,
@@ -489,11 +489,11 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
         if (!e_eq(fin, eval)) return reject("final polynomial evaluation is invalid");
     }
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 
 // convenience for callers that hold the host circuit: CircuitData::verify (plonk/circuit_data.rs:153-155)
 extern "C" int gl_host_circuit_verify(const gl_host_circuit* hc, const uint64_t* constants_sigmas_cap, const uint64_t circuit_digest[4],
-                                      const uint8_t* proof_bytes, size_t num_bytes) {
+                                      const uint8_t* proof_bytes, size_t num_bytes) try {
     GL_REQUIRE(hc, GL_ERR_ARG, "gl_host_circuit_verify: null circuit");
     return gl_verify(&hc->hc.desc, constants_sigmas_cap, circuit_digest, proof_bytes, num_bytes);
-}
+} catch (...) { return gl_caught(); }

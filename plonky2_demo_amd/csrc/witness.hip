@@ -56,7 +56,7 @@ __global__ void k_matmul_arith_rows(const gl_t* __restrict__ a, const gl_t* __re
     }
 }
 
-extern "C" void gl_matmul_witgen_free(gl_matmul_witgen* g) {
+extern "C" void gl_matmul_witgen_free(gl_matmul_witgen* g) noexcept {
     if (!g) return;
     if (g->ctx) {
         (void)g->ctx->activate();
@@ -71,7 +71,7 @@ extern "C" void gl_matmul_witgen_free(gl_matmul_witgen* g) {
     delete g;
 }
 
-extern "C" int gl_matmul_witgen_create(gl_ctx* ctx, const gl_host_circuit* hc, gl_matmul_witgen** out) {
+extern "C" int gl_matmul_witgen_create(gl_ctx* ctx, const gl_host_circuit* hc, gl_matmul_witgen** out) try {
     GL_REQUIRE(ctx && hc && out, GL_ERR_ARG, "gl_matmul_witgen_create: null argument");
     GL_TRY(ctx->activate());
     const glhost::HostCircuit& h = hc->hc;
@@ -90,10 +90,10 @@ extern "C" int gl_matmul_witgen_create(gl_ctx* ctx, const gl_host_circuit* hc, g
     g->cvals.resize(mm);
     *out = g.release();
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 
 extern "C" int gl_matmul_witgen_run(gl_matmul_witgen* g, const uint64_t* a, const uint64_t* b, uint64_t filler_seed, uint64_t* d_wires, uint64_t* h_pis,
-                                    uint64_t* h_pi_hash) {
+                                    uint64_t* h_pi_hash) try {
     GL_REQUIRE(g && a && b && d_wires && h_pis, GL_ERR_ARG, "gl_matmul_witgen_run: null argument");
     gl_ctx* ctx = g->ctx;
     GL_TRY(ctx->activate());
@@ -147,7 +147,7 @@ extern "C" int gl_matmul_witgen_run(gl_matmul_witgen* g, const uint64_t* a, cons
     ctx->timing_end();
     GL_CHECK_HIP(gl_stream_wait(st));                // the pinned staging buffers are reused by the next call
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 
 // ======================================================================================================================
 // Prover pool: many independent proofs in flight on one GPU from ONE call -- the C++ counterpart of the reference fanning a
@@ -155,8 +155,7 @@ extern "C" int gl_matmul_witgen_run(gl_matmul_witgen* g, const uint64_t* a, cons
 // witness generator each); gl_prover_pool_prove_matmul hands item i to lane i % lanes on `lanes` host threads, so that the
 // transcript round trips and the host-side hash sponge of one proof hide behind the kernels of the others.
 // ======================================================================================================================
-#include <thread>
-#include <atomic>
+#include "lanes.hpp"
 
 struct gl_prover_pool {
     int device = 0;
@@ -167,7 +166,7 @@ struct gl_prover_pool {
     std::vector<uint64_t*> d_wires;                      // one witness matrix per lane
 };
 
-extern "C" void gl_prover_pool_free(gl_prover_pool* p) {
+extern "C" void gl_prover_pool_free(gl_prover_pool* p) noexcept {
     if (!p) return;
     for (size_t k = 0; k < p->ctxs.size(); k++) {
         if (k < p->gens.size() && p->gens[k]) gl_matmul_witgen_free(p->gens[k]);
@@ -180,10 +179,11 @@ extern "C" void gl_prover_pool_free(gl_prover_pool* p) {
 
 // The same pool for ANY circuit the library proves (a description + the constants || sigmas value columns, as gl_circuit_create takes
 // them): no witness generators, the witnesses come from the host (gl_prover_pool_prove_columns).  Every lane is warmed up.
-extern "C" int gl_prover_pool_create_generic(int device, const gl_circuit_desc* desc, const uint64_t* h_constants_sigmas, uint32_t lanes, gl_prover_pool** out) {
-    GL_REQUIRE(desc && h_constants_sigmas && out && lanes >= 1 && lanes <= 64, GL_ERR_ARG, "gl_prover_pool_create_generic: bad argument (1..64 lanes)");
+extern "C" int gl_prover_pool_create_generic(int device, const gl_circuit_desc* desc, const uint64_t* h_constants_sigmas, uint32_t lanes, gl_prover_pool** out) try {
+    GL_REQUIRE(desc && h_constants_sigmas && out && lanes >= 1 && lanes <= GL_MAX_LANES, GL_ERR_ARG, "gl_prover_pool_create_generic: bad argument (1..64 lanes)");
     std::unique_ptr<gl_prover_pool, void (*)(gl_prover_pool*)> p(new gl_prover_pool(), gl_prover_pool_free);
     p->device = device;
+    p->ctxs.reserve(lanes);                              // (a context is never held outside the pool)
     for (uint32_t k = 0; k < lanes; k++) {
         gl_ctx* c = nullptr;
         GL_TRY(gl_ctx_create(device, nullptr, &c));
@@ -193,45 +193,32 @@ extern "C" int gl_prover_pool_create_generic(int device, const gl_circuit_desc* 
     for (uint32_t k = 0; k < lanes; k++) GL_TRY(gl_circuit_warm_up(p->ctxs[k], p->circuit));
     *out = p.release();
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 
 // count proofs from HOST witnesses: columns[i][j] = wire column j (n values) of witness i, as MatrixWitness.wire_values holds them
 // (iop/witness.rs:256-258); public_inputs[i] = its num_public_inputs values.  Item i is proved on lane i % lanes through gl_prove_columns
 // (the lane's pinned H2D ring).  out_proofs[i] receives a gl_proof; returns the first error of any lane (the other proofs stay valid).
 extern "C" int gl_prover_pool_prove_columns(gl_prover_pool* p, size_t count, const uint64_t* const* const* columns, const uint64_t* const* public_inputs,
-                                            gl_proof** out_proofs) {
+                                            gl_proof** out_proofs) try {
     GL_REQUIRE(p && p->circuit && (count == 0 || (columns && public_inputs && out_proofs)), GL_ERR_ARG, "gl_prover_pool_prove_columns: null argument");
     for (size_t i = 0; i < count; i++) out_proofs[i] = nullptr;
     gl_circuit_desc d;
     GL_TRY(gl_circuit_description(p->circuit, &d));
     const size_t lanes = p->ctxs.size(), npis = d.num_public_inputs;
-    std::atomic<int> first_error{GL_OK};
-    std::vector<std::string> messages(lanes);
     const uint64_t none = 0;
-    auto work = [&](size_t lane) {
-        for (size_t i = lane; i < count && first_error.load() == GL_OK; i += lanes) {
-            int st = (columns[i] && (public_inputs[i] || npis == 0)) ? GL_OK : GL_ERR_ARG;
-            if (st == GL_OK) st = gl_prove_columns(p->ctxs[lane], p->circuit, columns[i], npis ? public_inputs[i] : &none, npis, &out_proofs[i]);
-            if (st != GL_OK) { int expected = GL_OK; messages[lane] = st == GL_ERR_ARG && !columns[i] ? "gl_prover_pool_prove_columns: null witness" : gl_last_error(); first_error.compare_exchange_strong(expected, st); }
-        }
-    };
-    std::vector<std::thread> threads;
-    for (size_t k = 1; k < lanes && k < count; k++) threads.emplace_back(work, k);
-    work(0);
-    for (auto& t : threads) t.join();
-    const int st = first_error.load();
-    if (st != GL_OK) {
-        for (auto& m : messages) if (!m.empty()) return gl_fail(st, m.c_str(), __FILE__, __LINE__);
-        return gl_fail(st, "gl_prover_pool_prove_columns: a lane failed", __FILE__, __LINE__);
-    }
-    return GL_OK;
-}
+    return gl_run_lanes(lanes, count, "gl_prover_pool_prove_columns", [&](size_t lane, size_t i) {
+        GL_REQUIRE(columns[i], GL_ERR_ARG, "gl_prover_pool_prove_columns: null witness");
+        GL_REQUIRE(public_inputs[i] || npis == 0, GL_ERR_ARG, "gl_prover_pool_prove_columns: null public inputs");
+        return gl_prove_columns(p->ctxs[lane], p->circuit, columns[i], npis ? public_inputs[i] : &none, npis, &out_proofs[i]);
+    });
+} catch (...) { return gl_caught(); }
 
-extern "C" int gl_prover_pool_create(int device, const gl_host_circuit* hc, uint32_t lanes, gl_prover_pool** out) {
-    GL_REQUIRE(hc && out && lanes >= 1 && lanes <= 64, GL_ERR_ARG, "gl_prover_pool_create: bad argument (1..64 lanes)");
+extern "C" int gl_prover_pool_create(int device, const gl_host_circuit* hc, uint32_t lanes, gl_prover_pool** out) try {
+    GL_REQUIRE(hc && out && lanes >= 1 && lanes <= GL_MAX_LANES, GL_ERR_ARG, "gl_prover_pool_create: bad argument (1..64 lanes)");
     std::unique_ptr<gl_prover_pool, void (*)(gl_prover_pool*)> p(new gl_prover_pool(), gl_prover_pool_free);
     p->device = device; p->hc = hc;
     const size_t n = hc->hc.n;
+    p->ctxs.reserve(lanes);                              // (a context is never held outside the pool)
     for (uint32_t k = 0; k < lanes; k++) {
         gl_ctx* c = nullptr;
         GL_TRY(gl_ctx_create(device, nullptr, &c));
@@ -247,42 +234,28 @@ extern "C" int gl_prover_pool_create(int device, const gl_host_circuit* hc, uint
     }
     *out = p.release();
     return GL_OK;
-}
+} catch (...) { return gl_caught(); }
 
-extern "C" uint32_t gl_prover_pool_lanes(const gl_prover_pool* p) { return p ? (uint32_t)p->ctxs.size() : 0; }
-extern "C" const gl_circuit* gl_prover_pool_circuit(const gl_prover_pool* p) { return p ? p->circuit : nullptr; }
+extern "C" uint32_t gl_prover_pool_lanes(const gl_prover_pool* p) noexcept { return p ? (uint32_t)p->ctxs.size() : 0; }
+extern "C" const gl_circuit* gl_prover_pool_circuit(const gl_prover_pool* p) noexcept { return p ? p->circuit : nullptr; }
 
 // count proofs of A_i * B_i = C_i: a[i], b[i] row-major m x m operands on the host, filler_seeds[i] as gl_matmul_witness.
 // out_proofs[i] receives a gl_proof (gl_proof_free each); the public inputs are inside the proof bytes.  Returns the first
 // error of any lane (proofs already produced stay valid, the others are null).
 extern "C" int gl_prover_pool_prove_matmul(gl_prover_pool* p, size_t count, const uint64_t* const* a, const uint64_t* const* b,
-                                           const uint64_t* filler_seeds, gl_proof** out_proofs) {
+                                           const uint64_t* filler_seeds, gl_proof** out_proofs) try {
     GL_REQUIRE(p && (count == 0 || (a && b && out_proofs)), GL_ERR_ARG, "gl_prover_pool_prove_matmul: null argument");
     GL_REQUIRE(p->hc, GL_ERR_ARG, "gl_prover_pool_prove_matmul: this pool was created for a generic circuit (gl_prover_pool_prove_columns)");
     for (size_t i = 0; i < count; i++) out_proofs[i] = nullptr;
     const size_t lanes = p->ctxs.size(), npis = 3 * p->hc->hc.m * p->hc->hc.m;
     const bool zero_knowledge = p->hc->hc.desc.zero_knowledge != 0;      // the salts: OS entropy inside gl_prove_device_hashed
-    std::atomic<int> first_error{GL_OK};
-    std::vector<std::string> messages(lanes);
-    auto work = [&](size_t lane) {
-        std::vector<uint64_t> pis(npis);
+    std::vector<uint64_t> pis(lanes * npis);                             // each lane's public inputs
+    return gl_run_lanes(lanes, count, "gl_prover_pool_prove_matmul", [&](size_t lane, size_t i) {
+        GL_REQUIRE(a[i] && b[i], GL_ERR_ARG, "gl_prover_pool_prove_matmul: null operand");
+        uint64_t* lane_pis = pis.data() + lane * npis;
         uint64_t pi_hash[4];
-        for (size_t i = lane; i < count && first_error.load() == GL_OK; i += lanes) {
-            int st = (a[i] && b[i]) ? GL_OK : GL_ERR_ARG;
-            if (st == GL_OK) st = gl_matmul_witgen_run(p->gens[lane], a[i], b[i], filler_seeds ? filler_seeds[i] : (uint64_t)i, p->d_wires[lane], pis.data(), pi_hash);
-            if (st == GL_OK && zero_knowledge) st = gl_witness_blind(p->ctxs[lane], p->circuit, p->d_wires[lane], nullptr);     // a fresh OS seed per item
-            if (st == GL_OK) st = gl_prove_device_hashed(p->ctxs[lane], p->circuit, p->d_wires[lane], pis.data(), npis, pi_hash, &out_proofs[i]);
-            if (st != GL_OK) { int expected = GL_OK; messages[lane] = gl_last_error(); first_error.compare_exchange_strong(expected, st); }
-        }
-    };
-    std::vector<std::thread> threads;
-    for (size_t k = 1; k < lanes && k < count; k++) threads.emplace_back(work, k);
-    work(0);
-    for (auto& t : threads) t.join();
-    const int st = first_error.load();
-    if (st != GL_OK) {
-        for (auto& m : messages) if (!m.empty()) return gl_fail(st, m.c_str(), __FILE__, __LINE__);
-        return gl_fail(st, "gl_prover_pool_prove_matmul: a lane failed", __FILE__, __LINE__);
-    }
-    return GL_OK;
-}
+        GL_TRY(gl_matmul_witgen_run(p->gens[lane], a[i], b[i], filler_seeds ? filler_seeds[i] : (uint64_t)i, p->d_wires[lane], lane_pis, pi_hash));
+        if (zero_knowledge) GL_TRY(gl_witness_blind(p->ctxs[lane], p->circuit, p->d_wires[lane], nullptr));     // a fresh OS seed per item
+        return gl_prove_device_hashed(p->ctxs[lane], p->circuit, p->d_wires[lane], lane_pis, npis, pi_hash, &out_proofs[i]);
+    });
+} catch (...) { return gl_caught(); }

@@ -24,6 +24,45 @@ def test_library_exports_every_declared_symbol():
     assert set(_lib.SIGNATURES) <= set(names), "binding table has symbols the header does not declare"
 
 
+def _extern_c_definitions(text):
+    """(name, what stands between the parameter list and the body, what follows the body on its line) of every extern "C" definition."""
+    text = re.sub(r"//[^\n]*|/\*.*?\*/", "", text, flags=re.S)
+    for mo in re.finditer(r'^extern "C"[^(;{]*?(\w+)\s*\(', text, re.M):
+        depth, i = 1, mo.end()
+        while depth:                                     # the matching parenthesis of the parameter list
+            depth += {"(": 1, ")": -1}.get(text[i], 0)
+            i += 1
+        tail = re.match(r"\s*([^;{]*)([;{])", text[i:])
+        if tail.group(2) == "{":
+            depth, j = 1, i + tail.end()
+            while depth:                                 # the matching brace of the body (string literals here hold braces in pairs)
+                depth += {"{": 1, "}": -1}.get(text[j], 0)
+                j += 1
+            yield mo.group(1), tail.group(1).strip(), text[j:text.index("\n", j)]
+
+
+def test_every_entry_point_is_guarded_or_noexcept():
+    """The header promises that no entry point unwinds: every extern "C" definition is a function-try-block that ends in the one
+    handler of context.hpp (gl_caught), or is declared noexcept; and the last error is a fixed buffer, never a std::string."""
+    csrc = os.path.join(ROOT, "plonky2_demo_amd", "csrc")
+    seen = 0
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".hpp", ".cuh", ".h", ".inc")):
+            continue
+        src = open(os.path.join(csrc, f)).read()
+        # no std::string that holds a last error, under any name, and nothing assigned or appended to one
+        assert not re.search(r"std::string[^;(]*last_error|last_error\w*\s*(=[^=]|\+=|\.(assign|append)\b)", src), "%s assigns to a std::string last error" % f
+        if not f.endswith(".hip"):
+            continue
+        for name, between, rest in _extern_c_definitions(src):
+            seen += 1
+            assert between in ("try", "noexcept"), "%s: %s is neither guarded nor noexcept" % (f, name)
+            if between == "try":                          # the handler that closes the function-try-block
+                assert re.fullmatch(r" catch \(\.\.\.\) \{ (return gl_caught\(\);|\(void\)gl_caught\(\); return nullptr;) }", rest), "%s: %s: %s" % (f, name, rest)
+    assert seen >= 120
+    assert len(re.findall(r"\bGL_NOEXCEPT;", open(os.path.join(ROOT, "include", "plonky2_mi355x.h")).read())) >= 20
+
+
 def test_product_never_touches_the_oracle():
     """The shipped path must not import, link, include or dlopen anything under oracle/."""
     pkg = os.path.join(ROOT, "plonky2_demo_amd")

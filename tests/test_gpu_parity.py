@@ -728,6 +728,45 @@ def test_generic_prover_pool_proves_a_batch_of_host_witnesses(gpu, orc):
     pool2.close()
 
 
+def test_prover_pool_returns_the_first_error_and_keeps_the_proofs_already_made(gpu, orc):
+    # the contract of the pools' lane runner (csrc/lanes.hpp), through gl_prover_pool_prove_columns itself: 3 lanes, 5 items of which
+    # item 3 has no witness -> the status and text of that item, every proof that was produced is the oracle's, item 3 stays null,
+    # and the pool proves a good batch afterwards
+    import ctypes
+    from plonky2_demo_amd._lib import lib, GL_OK, ERRORS
+    p, ctx = gpu
+    m = 2
+    hc, oc = p.MatmulCircuit(m), orc.circuit(m, threads=4)
+    pool = p.api.GenericProverPool(hc.desc, hc.constants_sigmas(), lanes=3)
+    cols, pis, want = [], [], []
+    for k in range(5):
+        a, b = rand_field(300 + k, m * m) % (2**32 - 1), rand_field(400 + k, m * m) % (2**32 - 1)
+        w = oc.witness(a, b, filler_seed=k)
+        wires = w.wires()
+        cols.append([np.ascontiguousarray(wires[j]) for j in range(135)])
+        pis.append(np.ascontiguousarray(w.public_inputs()))
+        want.append(w.prove(threads=4).to_bytes())
+    col_arrays = [(ctypes.c_void_p * 135)(*[c.ctypes.data for c in item]) for item in cols]
+
+    def prove(null_item):
+        col_ptrs = (ctypes.c_void_p * 5)(*[None if i == null_item else ctypes.addressof(col_arrays[i]) for i in range(5)])
+        pi_ptrs = (ctypes.c_void_p * 5)(*[v.ctypes.data for v in pis])
+        out = (ctypes.c_void_p * 5)()
+        st = lib.gl_prover_pool_prove_columns(pool.handle, 5, col_ptrs, pi_ptrs, out)
+        text = (lib.gl_last_error() or b"").decode()
+        return st, text, [p.api.Proof(out[i], hc.desc).to_bytes() if out[i] else None for i in range(5)]
+
+    st, text, got = prove(3)
+    assert ERRORS.get(st) == "GL_ERR_ARG" and "null witness" in text, (st, text)
+    assert got[3] is None
+    for i in range(5):
+        assert got[i] is None or got[i] == want[i], i
+    st, text, got = prove(None)
+    assert st == GL_OK, text
+    assert got == want
+    pool.close()
+
+
 def test_host_witness_entry_on_eight_lanes_equals_prove_device(gpu):
     # the drop-in entry (plonk/prover.rs:145 -> gl_prove_columns): 64 proofs of the m = 64 circuit from HOST
     # witness matrices -- 135 separate pageable vectors each, as MatrixWitness.wire_values holds them (iop/witness.rs:256-258) -- on 8

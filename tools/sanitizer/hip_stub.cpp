@@ -1,8 +1,10 @@
 // A stand-in for the HIP runtime on the CPU, for ThreadSanitizer runs of the library's HOST-side context code (context.hip):
 // device and pinned memory are malloc'ed, every stream is a worker thread that executes its copies in order and ASYNCHRONOUSLY
 // (so a staging buffer shared by two callers really is overwritten while the first still reads it), queries and events follow
-// the stream's progress.  Only what context.hip references is provided.  Never linked into the product.
-#include <hip/hip_runtime.h>
+// the stream's progress.  Only what context.hip references is provided.  Never linked into the product.  Like the runtime it stands
+// in for, it is a C interface: running out of host memory inside it is hipErrorOutOfMemory, not an exception (abi_unwind.cpp makes
+// its allocations fail).
+#include "../../plonky2_demo_amd/csrc/context.hpp"
 #include <atomic>
 #include <condition_variable>
 #include <cstdlib>
@@ -53,25 +55,25 @@ hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n ? n : 8); return *p ? h
 hipError_t hipFree(void* p) { free(p); return hipSuccess; }
 hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = malloc(n ? n : 8); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
-hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (hipStream_t) new StubStream(); return hipSuccess; }
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) try { *s = (hipStream_t) new StubStream(); return hipSuccess; } catch (...) { return hipErrorOutOfMemory; }
 hipError_t hipStreamDestroy(hipStream_t s) { delete (StubStream*)s; return hipSuccess; }
-hipError_t hipStreamQuery(hipStream_t s) { return ((StubStream*)s)->idle() ? hipSuccess : hipErrorNotReady; }
-hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind, hipStream_t s) {
+hipError_t hipStreamQuery(hipStream_t s) { return (!s || ((StubStream*)s)->idle()) ? hipSuccess : hipErrorNotReady; }      // (null: the default stream, idle -- a context whose creation failed before it had a stream is torn down through it)
+hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind, hipStream_t s) try {
     ((StubStream*)s)->push([dst, src, n] { memcpy(dst, src, n); });
     return hipSuccess;
-}
+} catch (...) { return hipErrorOutOfMemory; }
 hipError_t hipDeviceSynchronize(void) { return hipSuccess; }
 hipError_t hipGetLastError(void) { return hipSuccess; }
 const char* hipGetErrorString(hipError_t) { return "stub HIP error"; }
-hipError_t hipEventCreate(hipEvent_t* e) { *e = (hipEvent_t) new StubEvent(); return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t* e) try { *e = (hipEvent_t) new StubEvent(); return hipSuccess; } catch (...) { return hipErrorOutOfMemory; }
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
 hipError_t hipEventDestroy(hipEvent_t e) { delete (StubEvent*)e; return hipSuccess; }
-hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) try {
     StubEvent* ev = (StubEvent*)e; StubStream* st = (StubStream*)s;
     const uint64_t t = st->push([] {});
     std::lock_guard<std::mutex> lk(ev->mu); ev->s = st; ev->ticket = t;
     return hipSuccess;
-}
+} catch (...) { return hipErrorOutOfMemory; }
 hipError_t hipEventQuery(hipEvent_t e) {
     StubEvent* ev = (StubEvent*)e;
     std::lock_guard<std::mutex> lk(ev->mu);
@@ -80,3 +82,6 @@ hipError_t hipEventQuery(hipEvent_t e) {
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.f; return hipSuccess; }
 hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const void*) { memset(a, 0, sizeof *a); a->device = 0; return hipSuccess; }
 }
+
+// the one step of gl_ctx_create that launches kernels (ntt.hip): a context over this runtime has no twiddle tables
+int gl_ntt_local_tables(gl_ctx*) { return GL_OK; }
