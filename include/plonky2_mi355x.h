@@ -493,6 +493,43 @@ int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_sigmas_cap,
 int gl_host_circuit_verify(const gl_host_circuit* hc, const uint64_t* constants_sigmas_cap, const uint64_t circuit_digest[4],
                            const uint8_t* proof_bytes, size_t num_bytes);
 
+/* ---- verify(), many proofs at once -------------------------------------------------------------------*/
+/* The rejecting site of gl_verify as a number: one code per check, in the order gl_verify makes them.  gl_verify_check_message
+ * gives the text gl_verify leaves in gl_last_error() for that site ("" for GL_CHECK_ACCEPTED).  Host code. */
+#define GL_CHECK_ACCEPTED 0
+#define GL_CHECK_VERIFIER_DATA 1          /* malformed verifier data: a 25-byte hash with non-zero padding bytes */
+#define GL_CHECK_STEP_PATH_LENGTH 2       /* malformed proof: FRI step Merkle path has the wrong length */
+#define GL_CHECK_INITIAL_PATH_LENGTH 3    /* malformed proof: initial Merkle path has the wrong length */
+#define GL_CHECK_TRUNCATED 4              /* malformed proof: truncated */
+#define GL_CHECK_PUBLIC_INPUT_COUNT 5     /* malformed proof: wrong number of public inputs */
+#define GL_CHECK_LENGTH 6                 /* malformed proof: length mismatch */
+#define GL_CHECK_VANISHING 7              /* vanishing polynomial identity fails at zeta (plonk/verifier.rs:64-101) */
+#define GL_CHECK_POW 8                    /* invalid proof of work witness (fri/verifier.rs:49-60) */
+#define GL_CHECK_INITIAL_MERKLE 9         /* initial Merkle proof fails (fri/verifier.rs:104-122, hash/merkle_proofs.rs:54-75) */
+#define GL_CHECK_FRI_CONSISTENCY 10       /* FRI consistency check fails (fri/verifier.rs:206-209) */
+#define GL_CHECK_STEP_MERKLE 11           /* FRI step Merkle proof fails (fri/verifier.rs:219-225) */
+#define GL_CHECK_FINAL_POLY 12            /* final polynomial evaluation is invalid (fri/verifier.rs:231-239) */
+#define GL_CHECK_DESCRIPTION 13           /* not a rejection: gl_verify answers GL_ERR_ARG, the proof is too short for the description's counts */
+const char* gl_verify_check_message(uint32_t check) GL_NOEXCEPT;
+/* VerifierCircuitData::verify for `count` proofs of one circuit.  Per proof the decode, the transcript, the vanishing identity at
+ * zeta and the proof of work run on the host (on up to host_threads threads; 0 means 1, at most 64); the Merkle paths
+ * (hash/merkle_proofs.rs:54-75) and the FRI queries (fri/verifier.rs:124-241) of all proofs that pass them run on the device in two
+ * launches per chunk of max_batch (1..4096) proofs, on the context's stream.
+ * gl_batch_verifier_new accepts the descriptions gl_verify accepts, with its checks, order and codes; in addition a
+ * fri_arity_bits[r] > 4 is GL_ERR_UNSUPPORTED (no builder here produces one), and a description whose proofs exceed 2^24 words
+ * is GL_ERR_ARG.  It uploads the cap and allocates device and pinned staging for max_batch proofs once.
+ * gl_batch_verifier_verify returns GL_OK when every proof was judged, whatever the verdicts, and another code only for a failure
+ * of the machinery (HIP, memory, null argument).  verdicts[i] is what gl_verify returns for proofs[i] alone (GL_OK or
+ * GL_ERR_VERIFY; GL_ERR_ARG with GL_CHECK_DESCRIPTION for a proof shorter than the description's counts), checks[i] (may be null)
+ * the GL_CHECK_* code of the check gl_verify would have reported first.  count may exceed max_batch and may be 0.  Calls on one
+ * verifier are serialised; verifiers on different contexts run side by side. */
+typedef struct gl_batch_verifier gl_batch_verifier;
+int gl_batch_verifier_new(gl_ctx* ctx, const gl_circuit_desc* desc, const uint64_t* constants_sigmas_cap, const uint64_t circuit_digest[4],
+                          uint32_t max_batch, uint32_t host_threads, gl_batch_verifier** out);
+int gl_batch_verifier_verify(gl_batch_verifier* v, const uint8_t* const* proofs, const size_t* num_bytes, size_t count,
+                             int32_t* verdicts /* [count] */, uint32_t* checks /* [count], may be null */);
+void gl_batch_verifier_free(gl_batch_verifier* v) GL_NOEXCEPT;
+
 /* ---- circuit data as bytes --------------------------------------------------------------------------*/
 /* The reference's serialised forms (plonky2/src/plonk/circuit_data.rs:125-142,208-238; util/serialization/mod.rs:739-800,
  * 1736-1790 CommonCircuitData, :909-930,1889-1906 VerifierOnlyCircuitData, :1908-1919 VerifierCircuitData = verifier_only ||

@@ -13,6 +13,10 @@ LIB_PATH = os.environ.get("PLONKY2_MI355X_LIB") or os.path.join(_HERE, "libplonk
 
 GL_OK = 0
 GL_ERR_VERIFY = 6
+# gl_batch_verifier_verify's per-proof codes (include/plonky2_mi355x.h GL_CHECK_*): the check of gl_verify that rejected the proof
+(GL_CHECK_ACCEPTED, GL_CHECK_VERIFIER_DATA, GL_CHECK_STEP_PATH_LENGTH, GL_CHECK_INITIAL_PATH_LENGTH, GL_CHECK_TRUNCATED, GL_CHECK_PUBLIC_INPUT_COUNT,
+ GL_CHECK_LENGTH, GL_CHECK_VANISHING, GL_CHECK_POW, GL_CHECK_INITIAL_MERKLE, GL_CHECK_FRI_CONSISTENCY, GL_CHECK_STEP_MERKLE, GL_CHECK_FINAL_POLY,
+ GL_CHECK_DESCRIPTION) = range(14)
 ERRORS = {1: "GL_ERR_ARG", 2: "GL_ERR_HIP", 3: "GL_ERR_UNSUPPORTED", 4: "GL_ERR_ZETA_IN_SUBGROUP", 5: "GL_ERR_INTERNAL", 6: "GL_ERR_VERIFY"}
 
 
@@ -170,6 +174,11 @@ SIGNATURES = {
     "gl_verifier_only_to_bytes_h": (c_int, [c_u32, c_u32, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "gl_verifier_only_from_bytes_h": (c_int, [c_u32, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_vp]),
     "gl_verify_bytes_h": (c_int, [c_u32, c_vp, c_sz, c_vp, c_sz]),
+    # batch verification (device Merkle paths and FRI queries)
+    "gl_verify_check_message": (ctypes.c_char_p, [c_u32]),
+    "gl_batch_verifier_new": (c_int, [c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, ctypes.POINTER(c_vp)]),
+    "gl_batch_verifier_verify": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "gl_batch_verifier_free": (None, [c_vp]),
 }
 
 HASHERS = {"poseidon": 0, "keccak": 1}

@@ -598,6 +598,10 @@ class _CircuitApi(_Owned):
         buf = np.frombuffer(bytes(by), dtype=np.uint8)
         return _verdict(lib.gl_verify(ctypes.byref(self.desc), _p(self.constants_sigmas_cap), _p(self.circuit_digest), _p(buf), buf.size))
 
+    def batch_verifier(self, max_batch=64, host_threads=1):
+        """A BatchVerifier for this circuit on its context: many proofs per call, Merkle paths and FRI queries on the device."""
+        return BatchVerifier(self.desc, self.constants_sigmas_cap, self.circuit_digest, ctx=self.ctx, max_batch=max_batch, host_threads=host_threads)
+
     def _prove(self, entry, wires_ptr, public_inputs, *hash_arg):
         pis = _u64(public_inputs)
         keep = pis if pis.size else np.zeros(1, dtype=np.uint64)          # a valid pointer even for zero public inputs
@@ -723,6 +727,45 @@ class CircuitView(_CircuitApi):
     def __init__(self, circuit_data, ctx):
         super().__init__(circuit_data.handle, ctx, circuit_data.desc)
         self.cd = circuit_data          # the owner of the handle outlives the view
+
+
+def verify_check_message(check):
+    """The text gl_verify leaves in gl_last_error for the rejecting site `check` (a GL_CHECK_* code); "" for an accepted proof."""
+    return (lib.gl_verify_check_message(int(check)) or b"").decode()
+
+
+class BatchVerifier(_Owned):
+    """VerifierCircuitData::verify for many proofs of one circuit per call (gl_batch_verifier): per proof the decode, the transcript, the
+    vanishing identity and the proof of work on `host_threads` host threads, the Merkle paths (hash/merkle_proofs.rs:54-75) and the FRI
+    queries (fri/verifier.rs:124-241) of all of them in two launches per `max_batch` proofs on the context's stream.  Takes what
+    gl_verify takes: the description, the constants/sigmas cap and the circuit digest."""
+    _free = "gl_batch_verifier_free"
+
+    def __init__(self, desc, constants_sigmas_cap, circuit_digest, ctx=None, max_batch=64, host_threads=1):
+        ctx = _ctx(ctx)
+        cap, dig = _u64(constants_sigmas_cap), _u64(circuit_digest)
+        if cap.size != 4 << desc.cap_height or dig.size != 4:
+            raise ValueError("cap must be [2^cap_height][4], digest [4]")
+        h = ctypes.c_void_p()
+        check(lib.gl_batch_verifier_new(ctx.handle, ctypes.byref(desc), _p(cap), _p(dig), int(max_batch), int(host_threads), ctypes.byref(h)))
+        self.handle, self.ctx, self.desc, self.checks = h.value, ctx, desc, []
+
+    def verify(self, proofs):
+        """[(accepted, reason)] for `proofs` (Proof objects or their bytes), the pair CircuitData.verify gives for each alone; `checks`
+        then holds the GL_CHECK_* codes.  A proof too short for the description's counts raises, as it does there."""
+        bufs = [bytes(p.to_bytes() if hasattr(p, "to_bytes") else p) for p in proofs]
+        n = len(bufs)
+        ptrs = (ctypes.c_char_p * max(n, 1))(*bufs)
+        sizes = (ctypes.c_size_t * max(n, 1))(*[len(b) for b in bufs])
+        verdicts, checks = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.uint32)
+        check(lib.gl_batch_verifier_verify(self.handle, ptrs, sizes, n, _p(verdicts), _p(checks)))
+        self.checks = [int(c) for c in checks[:n]]
+        out = []
+        for st, c in zip(verdicts[:n], self.checks):
+            if st not in (_lib.GL_OK, _lib.GL_ERR_VERIFY):
+                raise _lib.Plonky2Mi355xError(int(st), verify_check_message(c))
+            out.append((st == _lib.GL_OK, verify_check_message(c)))
+        return out
 
 
 # ------------------------------------------------------------------------------- circuit data as bytes (host code)

@@ -110,6 +110,27 @@ GL_HD void kck_digest25(const kck_state& s, uint64_t out[4]) {
     out[0] = kck_word(s, 0); out[1] = kck_word(s, 1); out[2] = kck_word(s, 2); out[3] = s.lo[3] & 0xFFu;
 }
 
+#if defined(__HIPCC__)
+// Absorbs the leaf whose element e is load(e) (absorbed as its canonical little-endian u64): whole 17-word blocks with compile-time
+// state indices, then the tail block with the padding; `len` > 3.
+template <class Load>
+__device__ __forceinline__ void kck_absorb_leaf(kck_state& s, uint32_t len, Load load) {
+    kck_clear(s);
+    uint32_t e0 = 0;
+    for (; len - e0 >= KCK_RATE_WORDS; e0 += KCK_RATE_WORDS) {
+#pragma unroll
+        for (int i = 0; i < KCK_RATE_WORDS; i++) kck_xor_word(s, i, gl_canon(load(e0 + i)));
+        kck_f1600(s);
+    }
+    const uint32_t rem = len - e0;                       // 0..16 words in the closing block
+#pragma unroll
+    for (int i = 0; i < KCK_RATE_WORDS - 1; i++)
+        if ((uint32_t)i < rem) kck_xor_word(s, i, gl_canon(load(e0 + i)));
+    kck_pad_words(s, rem);
+    kck_f1600(s);
+}
+#endif
+
 // KeccakHash<25>::two_to_one (hash/keccak.rs:119-126): Keccak-256 of the 50 bytes left || right, one permutation.  The right digest
 // starts at byte 25, so its words enter shifted by one byte.
 GL_HD void kck_two_to_one(const uint64_t l[4], const uint64_t r[4], uint64_t out[4]) {

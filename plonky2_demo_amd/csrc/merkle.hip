@@ -163,24 +163,6 @@ __global__ __launch_bounds__(64, 5) void k_hash_rows(const gl_t* rows, size_t co
 // ---------------------------------------------------------------------------- Keccak-256 trees (KeccakGoldilocksConfig, keccak.cuh)
 // One state per lane everywhere: a Keccak permutation is a third of a Poseidon one and absorbs twice the words, and the state's 50
 // registers leave no room for a cooperative form; launches too small to fill the chip are latency bound.
-// Absorbs the leaf whose element e is load(e) (absorbed as its canonical little-endian u64): whole 17-word blocks with compile-time
-// state indices, then the tail block with the padding; `len` > 3.
-template <class Load>
-__device__ __forceinline__ void kck_absorb_leaf(kck_state& s, uint32_t len, Load load) {
-    kck_clear(s);
-    uint32_t e0 = 0;
-    for (; len - e0 >= KCK_RATE_WORDS; e0 += KCK_RATE_WORDS) {
-#pragma unroll
-        for (int i = 0; i < KCK_RATE_WORDS; i++) kck_xor_word(s, i, gl_canon(load(e0 + i)));
-        kck_f1600(s);
-    }
-    const uint32_t rem = len - e0;                       // 0..16 words in the closing block
-#pragma unroll
-    for (int i = 0; i < KCK_RATE_WORDS - 1; i++)
-        if ((uint32_t)i < rem) kck_xor_word(s, i, gl_canon(load(e0 + i)));
-    kck_pad_words(s, rem);
-    kck_f1600(s);
-}
 // hash_or_noop (plonk/config.rs:55-66, HASH_SIZE 25): digest of natural row r -> digests[bitrev(r)], as k_merkle_leaves.
 // (No waves-per-SIMD bound: left alone the allocator takes 84 VGPRs = 5 waves per SIMD without scratch, and bounds of 3, 4 and 5 compile
 // to the same code; a bound of 6 spills 32 bytes per lane.  DESIGN.md section 13.)

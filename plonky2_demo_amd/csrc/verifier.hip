@@ -5,9 +5,11 @@
 // Input is exactly what the reference's `VerifierCircuitData::verify` sees: CommonCircuitData (here the gl_circuit_desc),
 // VerifierOnlyCircuitData (constants_sigmas_cap, circuit_digest) and ProofWithPublicInputs::to_bytes().  The proof is
 // checked in place: one pass turns the byte string into a flat table of canonical words plus offsets, and every later
-// step indexes that table.  No GPU is involved (verification is milliseconds of sequential hashing).
+// step indexes that table.  No GPU is involved.  The checks of the description and the per-proof stage up to the proof of work are
+// functions of their own (verify_stage.hpp): the batch verifier (batch_verify.hip) runs the same ones and gives the queries to the device.
 #include "context.hpp"
 #include "host_circuit.hpp"
+#include "verify_stage.hpp"
 
 namespace {
 
@@ -213,14 +215,39 @@ struct Cursor {                                        // little-endian reader o
     unsigned u8() { if (pos >= len) { ok = false; return 0; } return p[pos++]; }
 };
 
-int reject(const char* why) { return gl_fail(GL_ERR_VERIFY, why, __FILE__, __LINE__); }
+// every rejection goes through here: the code names the site, the table below holds its text
+int reject(uint32_t check, uint32_t* out = nullptr) {
+    if (out) *out = check;
+    return gl_fail(GL_ERR_VERIFY, glverify::check_message(check), __FILE__, __LINE__);
+}
+
+// a + b and a * b of sizes, SIZE_MAX once anything overflowed (a caller-filled description may hold any count)
+inline size_t sat_add(size_t a, size_t b) { size_t r; return a == SIZE_MAX || b == SIZE_MAX || __builtin_add_overflow(a, b, &r) ? SIZE_MAX : r; }
+inline size_t sat_mul(size_t a, size_t b) { size_t r; return a == SIZE_MAX || b == SIZE_MAX || __builtin_mul_overflow(a, b, &r) ? SIZE_MAX : r; }
 
 }  // namespace
 
-extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_sigmas_cap, const uint64_t circuit_digest[4],
-                         const uint8_t* proof_bytes, size_t num_bytes) try {
-    GL_REQUIRE(desc && constants_sigmas_cap && circuit_digest && proof_bytes, GL_ERR_ARG, "gl_verify: null argument");
-    const gl_circuit_desc& d = *desc;
+const char* glverify::check_message(uint32_t check) noexcept {
+    switch (check) {
+        case GL_CHECK_ACCEPTED: return "";
+        case GL_CHECK_VERIFIER_DATA: return "malformed verifier data: a 25-byte hash with non-zero padding bytes";
+        case GL_CHECK_STEP_PATH_LENGTH: return "malformed proof: FRI step Merkle path has the wrong length";
+        case GL_CHECK_INITIAL_PATH_LENGTH: return "malformed proof: initial Merkle path has the wrong length";
+        case GL_CHECK_TRUNCATED: return "malformed proof: truncated";
+        case GL_CHECK_PUBLIC_INPUT_COUNT: return "malformed proof: wrong number of public inputs";
+        case GL_CHECK_LENGTH: return "malformed proof: length mismatch";
+        case GL_CHECK_VANISHING: return "vanishing polynomial identity fails at zeta";
+        case GL_CHECK_POW: return "invalid proof of work witness";
+        case GL_CHECK_INITIAL_MERKLE: return "initial Merkle proof fails";
+        case GL_CHECK_FRI_CONSISTENCY: return "FRI consistency check fails";
+        case GL_CHECK_STEP_MERKLE: return "FRI step Merkle proof fails";
+        case GL_CHECK_FINAL_POLY: return "final polynomial evaluation is invalid";
+        case GL_CHECK_DESCRIPTION: return "gl_verify: a count of the description exceeds what the proof bytes can hold";
+    }
+    return "unknown check";
+}
+
+int glverify::shape_of(const gl_circuit_desc& d, size_t num_bytes, Shape& s) {
     GL_REQUIRE(d.num_wires == 135 && d.num_routed_wires == 80 && d.num_challenges == 2 && d.quotient_degree_factor == 8 && d.rate_bits == 3,
                GL_ERR_UNSUPPORTED, "gl_verify: only standard_recursion_config circuits are supported");
     GL_REQUIRE(d.num_gates >= 1 && d.num_gates <= GL_MAX_GATES, GL_ERR_ARG, "gl_verify: bad gate count");
@@ -233,26 +260,71 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
     // every count that sizes an allocation below is bounded by what a proof of num_bytes can hold (a description is caller-filled, but a
     // wrong one must be refused, not turned into a 2^40-byte allocation: tools/sanitizer/data_fuzz.cpp)
     GL_REQUIRE(d.num_selectors <= GL_MAX_GATES && d.cap_height <= 16 && d.num_query_rounds <= num_bytes / 8 && d.num_public_inputs <= num_bytes / 8,
-               GL_ERR_ARG, "gl_verify: a count of the description exceeds what the proof bytes can hold");
+               GL_ERR_ARG, check_message(GL_CHECK_DESCRIPTION));
     GL_REQUIRE(!glhost::gate_list_fault(d), GL_ERR_ARG, "gl_verify: bad gate / selector description");
     const size_t nch = 2, R = 80, W = 135, QF = 8, NPP = 9;            // partial products per challenge: ceil(80 / 8) - 1
-    const size_t ncap = size_t(1) << d.cap_height, ncs = d.num_constants + R;
-    const unsigned lgn = d.degree_bits, lgN = lgn + d.rate_bits;
-    const size_t n = size_t(1) << lgn, N = size_t(1) << lgN;
+    s = Shape();
+    s.hasher = d.hasher; s.num_queries = d.num_query_rounds; s.num_rounds = d.num_fri_rounds; s.cap_height = d.cap_height;
+    s.lgn = d.degree_bits; s.lgN = s.lgn + d.rate_bits;
+    s.ncap = size_t(1) << d.cap_height; s.num_constants = d.num_constants; s.num_public_inputs = d.num_public_inputs;
     unsigned total_arity = 0;
-    for (unsigned r = 0; r < d.num_fri_rounds; r++) { GL_REQUIRE(d.fri_arity_bits[r] >= 1 && d.fri_arity_bits[r] <= 8, GL_ERR_ARG, "gl_verify: bad FRI arity"); total_arity += d.fri_arity_bits[r]; }
-    GL_REQUIRE(total_arity <= lgn, GL_ERR_ARG, "gl_verify: FRI reduces below the final polynomial");
-    const size_t final_len = size_t(1) << (lgn - total_arity);
-    const size_t NLP = d.num_lookup_polys;                              // lookup polynomials per challenge, behind Z and the partial products
-    const size_t nzp = nch * (1 + NPP);
-    const size_t widths[4] = {ncs, W, nzp + nch * NLP, nch * QF};
+    for (unsigned r = 0; r < d.num_fri_rounds; r++) {
+        GL_REQUIRE(d.fri_arity_bits[r] >= 1 && d.fri_arity_bits[r] <= 8, GL_ERR_ARG, "gl_verify: bad FRI arity");
+        total_arity += d.fri_arity_bits[r]; s.arity_bits[r] = d.fri_arity_bits[r];
+    }
+    GL_REQUIRE(total_arity <= s.lgn, GL_ERR_ARG, "gl_verify: FRI reduces below the final polynomial");
+    s.final_len = size_t(1) << (s.lgn - total_arity);
+    s.nlp = d.num_lookup_polys;                                         // lookup polynomials per challenge, behind Z and the partial products
+    s.nzp = nch * (1 + NPP);
+    const size_t ncs = (size_t)d.num_constants + R;
+    const size_t widths[4] = {ncs, W, s.nzp + nch * s.nlp, nch * QF};
     // hiding: the leaves of the wires, Z / partial-products and quotient trees end in SALT_SIZE = 4 salt elements (mod.rs:431-456)
-    const size_t salt = d.zero_knowledge ? 4 : 0, leaf_lens[4] = {ncs, W + salt, widths[2] + salt, widths[3] + salt};
+    const size_t salt = d.zero_knowledge ? 4 : 0;
+    for (int o = 0; o < 4; o++) { s.widths[o] = widths[o]; s.leaf_lens[o] = widths[o] + (o ? salt : 0); }
+    // the table in wire order (util/serialization/mod.rs:1939-1981; OpeningSet mod.rs:1409-1423: the lookup vectors sit between zs_next
+    // and the partial products)
+    size_t at = 0;
+    auto take = [&](size_t k) { const size_t here = at; at = sat_add(at, k); return here; };
+    s.o_caps = take(3 * 4 * s.ncap);
+    s.o_const = take(2 * s.num_constants); s.o_sig = take(2 * R); s.o_wires = take(2 * W); s.o_zs = take(2 * nch); s.o_zsn = take(2 * nch);
+    s.o_lk = take(2 * nch * s.nlp); s.o_lkn = take(2 * nch * s.nlp); s.o_pp = take(2 * nch * NPP); s.o_quot = take(2 * nch * QF);
+    s.o_fcaps = take((size_t)d.num_fri_rounds * 4 * s.ncap);
+    s.o_query0 = at;
+    size_t in_query = 0;
+    for (uint32_t o = 0; o < NUM_INITIAL_TREES; o++) {
+        s.slot_leaf[o] = in_query; s.slot_leaf_len[o] = s.leaf_lens[o]; s.slot_nsib[o] = s.lgN - d.cap_height;
+        s.slot_sib[o] = in_query + s.leaf_lens[o];
+        in_query = s.slot_sib[o] + 4 * s.slot_nsib[o];
+    }
+    unsigned lg_cur = s.lgN;
+    for (unsigned r = 0; r < d.num_fri_rounds; r++) {
+        const uint32_t slot = NUM_INITIAL_TREES + r;
+        lg_cur -= d.fri_arity_bits[r];
+        if (lg_cur < d.cap_height) { s.paths_fit = false; break; }
+        s.slot_leaf[slot] = in_query; s.slot_leaf_len[slot] = size_t(2) << d.fri_arity_bits[r]; s.slot_nsib[slot] = lg_cur - d.cap_height;
+        s.slot_sib[slot] = in_query + s.slot_leaf_len[slot];
+        in_query = s.slot_sib[slot] + 4 * s.slot_nsib[slot];
+    }
+    s.query_stride = in_query;
+    (void)take(sat_mul(in_query, d.num_query_rounds));
+    s.o_final = take(2 * s.final_len);
+    s.o_pis = take(d.num_public_inputs);
+    s.t_words = at;
+    return GL_OK;
+}
+
+int glverify::host_stage(const gl_circuit_desc& d, const Shape& s, const uint64_t* constants_sigmas_cap, const uint64_t circuit_digest[4],
+                         const uint8_t* proof_bytes, size_t num_bytes, std::vector<gl_t>& T, Challenges& ch, uint32_t* check) {
+    const size_t nch = 2, R = 80, W = 135, QF = 8, NPP = 9;
+    const size_t ncap = s.ncap, NLP = s.nlp, final_len = s.final_len;
+    const unsigned lgn = s.lgn, lgN = s.lgN;
+    const size_t n = size_t(1) << lgn, N = size_t(1) << lgN;
+    *check = GL_CHECK_ACCEPTED;
 
     // ---- decode (util/serialization/mod.rs:1939-1981 read side, plonk/validate_shape.rs, fri/validate_shape.rs) ----
     // like the reference's read_field (from_canonical_u64 without a range check in release builds) a word >= p is taken mod p
     Cursor in(proof_bytes, num_bytes);
-    std::vector<gl_t> T;                               // all words of the proof in wire order, canonical
+    T.clear();                                         // all words of the proof in wire order, canonical
     T.reserve(num_bytes / 8 + 8);
     auto words = [&](size_t k) { size_t at = T.size(); for (size_t i = 0; i < k && in.ok; i++) T.push_back(gl_canon(in.u64())); return at; };
     // read_hash (util/serialization/mod.rs:1332-1338): k hashes into four-word slots -- a HashOut's four elements, or the 25 bytes of a
@@ -266,38 +338,42 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
     };
     // the verifier data's own hashes arrive in four-word slots
     if (!glhost::hashes_well_formed(hasher, constants_sigmas_cap, ncap) || !glhost::hashes_well_formed(hasher, circuit_digest, 1))
-        return reject("malformed verifier data: a 25-byte hash with non-zero padding bytes");
-    struct PathRef { size_t leaf, leaf_len, sib, nsib; };
+        return reject(GL_CHECK_VERIFIER_DATA, check);
     const size_t o_caps = hashes(3 * ncap);
     // OpeningSet in wire order (mod.rs:1409-1423): the lookup vectors sit between zs_next and the partial products
     const size_t o_const = words(2 * d.num_constants), o_sig = words(2 * R), o_wires = words(2 * W), o_zs = words(2 * nch), o_zsn = words(2 * nch),
                  o_lk = words(2 * nch * NLP), o_lkn = words(2 * nch * NLP), o_pp = words(2 * nch * NPP), o_quot = words(2 * nch * QF);
     const size_t o_fcaps = hashes((size_t)d.num_fri_rounds * ncap);
-    std::vector<PathRef> init_paths((size_t)d.num_query_rounds * 4), step_paths((size_t)d.num_query_rounds * d.num_fri_rounds);
+    size_t o_query0 = T.size();
     for (unsigned q = 0; q < d.num_query_rounds && in.ok; q++) {
+        unsigned init_nsib[4];
+        if (q == 0) o_query0 = T.size();
         for (int o = 0; o < 4; o++) {
-            PathRef& pr = init_paths[q * 4 + o];
-            pr.leaf = words(leaf_lens[o]); pr.leaf_len = leaf_lens[o];
-            pr.nsib = in.u8(); pr.sib = hashes(pr.nsib);
+            (void)words(s.leaf_lens[o]);
+            init_nsib[o] = in.u8(); (void)hashes(init_nsib[o]);
         }
         unsigned lg_cur = lgN;
         for (unsigned r = 0; r < d.num_fri_rounds; r++) {
-            PathRef& pr = step_paths[q * d.num_fri_rounds + r];
-            pr.leaf_len = size_t(2) << d.fri_arity_bits[r]; pr.leaf = words(pr.leaf_len);
-            pr.nsib = in.u8(); pr.sib = hashes(pr.nsib);
+            (void)words(size_t(2) << d.fri_arity_bits[r]);
+            const unsigned nsib = in.u8(); (void)hashes(nsib);
             lg_cur -= d.fri_arity_bits[r];
-            if (in.ok && pr.nsib + d.cap_height != lg_cur) return reject("malformed proof: FRI step Merkle path has the wrong length");
+            if (in.ok && nsib + d.cap_height != lg_cur) return reject(GL_CHECK_STEP_PATH_LENGTH, check);
         }
         for (int o = 0; o < 4 && in.ok; o++)
-            if (init_paths[q * 4 + o].nsib + d.cap_height != lgN) return reject("malformed proof: initial Merkle path has the wrong length");
+            if (init_nsib[o] + d.cap_height != lgN) return reject(GL_CHECK_INITIAL_PATH_LENGTH, check);
     }
     const size_t o_final = words(2 * final_len);
     const gl_t pow_witness = gl_canon(in.u64());
     const uint64_t npis = in.u64();
-    if (!in.ok) return reject("malformed proof: truncated");
-    if (npis != d.num_public_inputs) return reject("malformed proof: wrong number of public inputs");
+    if (!in.ok) return reject(GL_CHECK_TRUNCATED, check);
+    if (npis != d.num_public_inputs) return reject(GL_CHECK_PUBLIC_INPUT_COUNT, check);
     const size_t o_pis = words(npis);
-    if (!in.ok || in.pos != num_bytes) return reject("malformed proof: length mismatch");
+    if (!in.ok || in.pos != num_bytes) return reject(GL_CHECK_LENGTH, check);
+    // every path has the length the description gives it, so the table lies where the shape says (what the queries index by)
+    GL_REQUIRE(s.paths_fit && T.size() == s.t_words && o_caps == s.o_caps && o_const == s.o_const && o_sig == s.o_sig && o_wires == s.o_wires &&
+               o_zs == s.o_zs && o_zsn == s.o_zsn && o_lk == s.o_lk && o_lkn == s.o_lkn && o_pp == s.o_pp && o_quot == s.o_quot &&
+               o_fcaps == s.o_fcaps && o_query0 == s.o_query0 && o_final == s.o_final && o_pis == s.o_pis,
+               GL_ERR_INTERNAL, "gl_verify: the decoded proof does not lie where its description puts it");
     auto ext_at = [&](size_t off, size_t i) { return gl2_make(T[off + 2 * i], T[off + 2 * i + 1]); };
 
     // ---- challenges (plonk/get_challenges.rs:26-87, fri/challenges.rs:24-64) ----
@@ -320,13 +396,13 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
     tr.observe_many(&T[o_pp], 2 * nch * NPP); tr.observe_many(&T[o_quot], 2 * nch * QF); tr.observe_many(&T[o_lk], 2 * nch * NLP);
     tr.observe_many(&T[o_zsn], 2 * nch); tr.observe_many(&T[o_lkn], 2 * nch * NLP);
     const E fri_alpha = tr.challenge_ext();
-    E fri_betas[8];
-    for (unsigned r = 0; r < d.num_fri_rounds; r++) { tr.observe_hashes(hasher, &T[o_fcaps + (size_t)r * 4 * ncap], ncap); fri_betas[r] = tr.challenge_ext(); }
+    for (unsigned r = 0; r < d.num_fri_rounds; r++) { tr.observe_hashes(hasher, &T[o_fcaps + (size_t)r * 4 * ncap], ncap); ch.fri_betas[r] = tr.challenge_ext(); }
+    for (unsigned r = d.num_fri_rounds; r < MAX_FRI_ROUNDS; r++) ch.fri_betas[r] = e_of(0);
     tr.observe_many(&T[o_final], 2 * final_len);
     tr.observe(pow_witness);
     const gl_t pow_response = tr.challenge();
-    std::vector<size_t> x_index(d.num_query_rounds);
-    for (auto& x : x_index) x = (size_t)(tr.challenge() % (uint64_t)N);
+    ch.x_index.resize(d.num_query_rounds);
+    for (auto& x : ch.x_index) x = tr.challenge() % (uint64_t)N;
 
     // ---- vanishing(zeta) == Z_H(zeta) * t(zeta) per challenge (plonk/verifier.rs:64-101, vanishing_poly.rs:54-160) ----
     {
@@ -413,56 +489,72 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
             for (size_t t = terms.size(); t-- > 0;) acc = e_add(terms[t], e_scale(acc, alphas[c]));
             E tz = e_of(0);
             for (size_t k = QF; k-- > 0;) tz = e_add(e_mul(tz, zeta_n), ext_at(o_quot, c * QF + k));
-            if (!e_eq(acc, e_mul(z_h, tz))) return reject("vanishing polynomial identity fails at zeta");
+            if (!e_eq(acc, e_mul(z_h, tz))) return reject(GL_CHECK_VANISHING, check);
         }
     }
 
-    // ---- FRI (fri/verifier.rs:62-260) ----
-    if (pow_response != 0 && (unsigned)__builtin_clzll(pow_response) < d.proof_of_work_bits) return reject("invalid proof of work witness");
-    const E gzeta = e_scale(zeta, glhost::root_of_unity(lgn));
-    auto horner = [&](const std::vector<E>& v) { E acc = e_of(0); for (size_t i = v.size(); i-- > 0;) acc = e_add(e_mul(acc, fri_alpha), v[i]); return acc; };
-    // PrecomputedReducedOpenings (fri/verifier.rs:243-260)
-    std::vector<E> open0, open1;
-    for (size_t i = 0; i < d.num_constants; i++) open0.push_back(ext_at(o_const, i));
-    for (size_t i = 0; i < R; i++) open0.push_back(ext_at(o_sig, i));
-    for (size_t i = 0; i < W; i++) open0.push_back(ext_at(o_wires, i));
-    for (size_t i = 0; i < nch; i++) open0.push_back(ext_at(o_zs, i));
-    for (size_t i = 0; i < nch * NPP; i++) open0.push_back(ext_at(o_pp, i));
-    for (size_t i = 0; i < nch * QF; i++) open0.push_back(ext_at(o_quot, i));
-    for (size_t i = 0; i < nch * NLP; i++) open0.push_back(ext_at(o_lk, i));          // lookup polynomials come last in both batches (circuit_data.rs:564-597)
-    for (size_t i = 0; i < nch; i++) open1.push_back(ext_at(o_zsn, i));
-    for (size_t i = 0; i < nch * NLP; i++) open1.push_back(ext_at(o_lkn, i));
-    const E red0 = horner(open0), red1 = horner(open1);
-    E alpha_shift = e_of(1);
-    for (size_t i = 0; i < open1.size(); i++) alpha_shift = e_mul(alpha_shift, fri_alpha);
-    const gl_t* caps[4] = {constants_sigmas_cap, &T[o_caps], &T[o_caps + 4 * ncap], &T[o_caps + 8 * ncap]};
+    // ---- FRI (fri/verifier.rs:62-260): the proof of work, and what every query needs ----
+    if (pow_response != 0 && (unsigned)__builtin_clzll(pow_response) < d.proof_of_work_bits) return reject(GL_CHECK_POW, check);
+    ch.zeta = zeta; ch.fri_alpha = fri_alpha;
+    ch.gzeta = e_scale(zeta, glhost::root_of_unity(lgn));
+    // PrecomputedReducedOpenings (fri/verifier.rs:243-260): Horner in fri_alpha over batch 0 = constants, sigmas, wires, zs, partial products,
+    // quotient, then the lookup polynomials (last in both batches: circuit_data.rs:564-597), and batch 1 = zs_next, lookups_next
+    E red0 = e_of(0), red1 = e_of(0);
+    auto horner = [&](E& acc, size_t off, size_t count) { for (size_t i = count; i-- > 0;) acc = e_add(e_mul(acc, fri_alpha), ext_at(off, i)); };
+    horner(red0, o_lk, nch * NLP); horner(red0, o_quot, nch * QF); horner(red0, o_pp, nch * NPP); horner(red0, o_zs, nch);
+    horner(red0, o_wires, W); horner(red0, o_sig, R); horner(red0, o_const, d.num_constants);
+    horner(red1, o_lkn, nch * NLP); horner(red1, o_zsn, nch);
+    ch.red0 = red0; ch.red1 = red1;
+    ch.alpha_shift = e_of(1);
+    for (size_t i = 0; i < nch + nch * NLP; i++) ch.alpha_shift = e_mul(ch.alpha_shift, fri_alpha);
+    return GL_OK;
+}
+
+extern "C" const char* gl_verify_check_message(uint32_t check) noexcept { return glverify::check_message(check); }
+
+extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_sigmas_cap, const uint64_t circuit_digest[4],
+                         const uint8_t* proof_bytes, size_t num_bytes) try {
+    GL_REQUIRE(desc && constants_sigmas_cap && circuit_digest && proof_bytes, GL_ERR_ARG, "gl_verify: null argument");
+    const gl_circuit_desc& d = *desc;
+    glverify::Shape s;
+    GL_TRY(glverify::shape_of(d, num_bytes, s));
+    std::vector<gl_t> T;
+    glverify::Challenges ch;
+    uint32_t check;
+    GL_TRY(glverify::host_stage(d, s, constants_sigmas_cap, circuit_digest, proof_bytes, num_bytes, T, ch, &check));
+    auto ext_at = [&](size_t off, size_t i) { return gl2_make(T[off + 2 * i], T[off + 2 * i + 1]); };
+    const size_t ncap = s.ncap, nch = 2;
+    const unsigned lgN = s.lgN;
+    const E zeta = ch.zeta, gzeta = ch.gzeta, fri_alpha = ch.fri_alpha;
+
+    // ---- the queries (fri/verifier.rs:167-241); k_verify_merkle_paths and k_verify_fri_queries are this loop on the device ----
+    const gl_t* caps[4] = {constants_sigmas_cap, &T[s.o_caps], &T[s.o_caps + 4 * ncap], &T[s.o_caps + 8 * ncap]};
     const gl_t wN = glhost::root_of_unity(lgN);
-    std::vector<E> ev0, ev1;
     for (unsigned q = 0; q < d.num_query_rounds; q++) {
-        size_t x = x_index[q];
-        for (int o = 0; o < 4; o++) {
-            const PathRef& pr = init_paths[q * 4 + o];
-            if (!path_opens_to_cap(hasher, &T[pr.leaf], pr.leaf_len, x, &T[pr.sib], pr.nsib, caps[o], ncap)) return reject("initial Merkle proof fails");
-        }
+        size_t x = ch.x_index[q];
+        for (uint32_t o = 0; o < 4; o++)
+            if (!path_opens_to_cap(d.hasher, &T[s.leaf_at(q, o)], s.slot_leaf_len[o], x, &T[s.sib_at(q, o)], s.slot_nsib[o], caps[o], ncap)) return reject(GL_CHECK_INITIAL_MERKLE);
         // subgroup_x = g * w_N^{reverse_bits(x_index)} (fri/verifier.rs:183-186)
         size_t rev = 0;
         for (unsigned i = 0; i < lgN; i++) rev |= ((x >> i) & 1) << (lgN - 1 - i);
         gl_t subgroup_x = gl_canon(gl_mul(GL_MULT_GENERATOR, gl_exp(wN, rev)));
         // fri_combine_initial (fri/verifier.rs:124-165): batch 0 = every polynomial at zeta, batch 1 = the Z polynomials at g zeta; the
-        // unsalted prefix of each leaf only (unsalted_eval)
-        ev0.clear(); ev1.clear();
-        for (int o = 0; o < 4; o++) { const PathRef& pr = init_paths[q * 4 + o]; for (size_t i = 0; i < (o == 2 ? nzp : widths[o]); i++) ev0.push_back(e_of(T[pr.leaf + i])); }
-        for (size_t i = nzp; i < widths[2]; i++) ev0.push_back(e_of(T[init_paths[q * 4 + 2].leaf + i]));
-        for (size_t i = 0; i < nch; i++) ev1.push_back(e_of(T[init_paths[q * 4 + 2].leaf + i]));
-        for (size_t i = nzp; i < widths[2]; i++) ev1.push_back(e_of(T[init_paths[q * 4 + 2].leaf + i]));
+        // unsalted prefix of each leaf only (unsalted_eval); Horner in fri_alpha from the last polynomial of a batch to its first, the
+        // lookup polynomials last in both
+        const size_t leaf2 = s.leaf_at(q, 2);
+        E h0 = e_of(0), h1 = e_of(0);
+        auto horner = [&](E& acc, size_t off, size_t first, size_t last) { for (size_t i = last; i-- > first;) acc = e_add(e_mul(acc, fri_alpha), e_of(T[off + i])); };
+        horner(h0, leaf2, s.nzp, s.widths[2]);
+        for (uint32_t o = 4; o-- > 0;) horner(h0, s.leaf_at(q, o), 0, o == 2 ? s.nzp : s.widths[o]);
+        horner(h1, leaf2, s.nzp, s.widths[2]); horner(h1, leaf2, 0, nch);
         const E sx = e_of(subgroup_x);
-        E eval = e_mul(e_sub(horner(ev0), red0), gl2_inv(e_sub(sx, zeta)));
-        eval = e_add(e_mul(eval, alpha_shift), e_mul(e_sub(horner(ev1), red1), gl2_inv(e_sub(sx, gzeta))));
+        E eval = e_mul(e_sub(h0, ch.red0), gl2_inv(e_sub(sx, zeta)));
+        eval = e_add(e_mul(eval, ch.alpha_shift), e_mul(e_sub(h1, ch.red1), gl2_inv(e_sub(sx, gzeta))));
         for (unsigned r = 0; r < d.num_fri_rounds; r++) {
             const unsigned ab = d.fri_arity_bits[r];
-            const size_t arity = size_t(1) << ab, coset = x >> ab, within = x & (arity - 1);
-            const PathRef& pr = step_paths[q * d.num_fri_rounds + r];
-            if (!e_eq(ext_at(pr.leaf, within), eval)) return reject("FRI consistency check fails");
+            const uint32_t slot = glverify::NUM_INITIAL_TREES + r;
+            const size_t arity = size_t(1) << ab, coset = x >> ab, within = x & (arity - 1), leaf = s.leaf_at(q, slot);
+            if (!e_eq(ext_at(leaf, within), eval)) return reject(GL_CHECK_FRI_CONSISTENCY);
             // compute_evaluation (fri/verifier.rs:21-47): the degree < arity interpolant through the coset, at beta
             const gl_t g = glhost::root_of_unity(ab);
             size_t wrev = 0;
@@ -475,18 +567,18 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
                 size_t arev = 0;
                 for (unsigned i = 0; i < ab; i++) arev |= ((a >> i) & 1) << (ab - 1 - i);      // evals are stored in bit-reversed order
                 E numer = e_of(1); gl_t denom = 1;
-                for (size_t b = 0; b < arity; b++) if (b != a) { numer = e_mul(numer, e_sub(fri_betas[r], e_of(pts[b]))); denom = gl_mul(denom, gl_sub(pts[a], pts[b])); }
-                acc = e_add(acc, e_mul(ext_at(pr.leaf, arev), e_scale(numer, gl_inv(denom))));
+                for (size_t b = 0; b < arity; b++) if (b != a) { numer = e_mul(numer, e_sub(ch.fri_betas[r], e_of(pts[b]))); denom = gl_mul(denom, gl_sub(pts[a], pts[b])); }
+                acc = e_add(acc, e_mul(ext_at(leaf, arev), e_scale(numer, gl_inv(denom))));
             }
             eval = acc;
-            if (!path_opens_to_cap(hasher, &T[pr.leaf], pr.leaf_len, coset, &T[pr.sib], pr.nsib, &T[o_fcaps + (size_t)r * 4 * ncap], ncap)) return reject("FRI step Merkle proof fails");
+            if (!path_opens_to_cap(d.hasher, &T[leaf], s.slot_leaf_len[slot], coset, &T[s.sib_at(q, slot)], s.slot_nsib[slot], &T[s.o_fcaps + (size_t)r * 4 * ncap], ncap)) return reject(GL_CHECK_STEP_MERKLE);
             for (unsigned i = 0; i < ab; i++) subgroup_x = gl_sqr(subgroup_x);
             x = coset;
         }
         E fin = e_of(0);
         const E sxf = e_of(gl_canon(subgroup_x));
-        for (size_t i = final_len; i-- > 0;) fin = e_add(e_mul(fin, sxf), ext_at(o_final, i));
-        if (!e_eq(fin, eval)) return reject("final polynomial evaluation is invalid");
+        for (size_t i = s.final_len; i-- > 0;) fin = e_add(e_mul(fin, sxf), ext_at(s.o_final, i));
+        if (!e_eq(fin, eval)) return reject(GL_CHECK_FINAL_POLY);
     }
     return GL_OK;
 } catch (...) { return gl_caught(); }
