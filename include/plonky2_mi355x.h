@@ -424,6 +424,60 @@ int gl_challenger_get_challenges(gl_challenger* c, uint64_t* h_out, size_t count
 int gl_challenger_state(const gl_challenger* c, uint64_t h_sponge_state[12], uint64_t h_input_buffer[8], uint32_t* input_len);
 void gl_challenger_free(gl_challenger* c) GL_NOEXCEPT;
 
+/* ---- FRI openings of any instance ------------------------------------------------------------------
+ * PolynomialBatch::prove_openings (fri/oracle.rs:162-219) and verify_fri_proof (fri/verifier.rs:62-241) for an arbitrary
+ * FriInstanceInfo (fri/structure.rs): any number of oracles, any (point, polynomials) batches, any rate_bits / cap_height, salted
+ * oracles, either hasher.  This is the call through which provers other than plonk::prover (starky/src/prover.rs) reach the seam.
+ * gl_fri_combine / gl_prove* / gl_verify above keep their own Plonk-shaped path. */
+#define GL_MAX_FRI_ORACLES 8
+#define GL_MAX_FRI_BATCHES 4
+typedef struct gl_fri_params {          /* FriParams (fri/mod.rs) + C::Hasher */
+    uint32_t degree_bits, rate_bits, cap_height, proof_of_work_bits, num_query_rounds;
+    uint32_t num_fri_rounds, fri_arity_bits[8];
+    uint32_t hiding, hasher;
+} gl_fri_params;
+typedef struct gl_fri_instance {        /* FriInstanceInfo (fri/structure.rs) */
+    uint32_t num_oracles, oracle_num_polys[GL_MAX_FRI_ORACLES], oracle_blinding[GL_MAX_FRI_ORACLES];
+    uint32_t num_batches;               /* 1..GL_MAX_FRI_BATCHES */
+    uint64_t points[GL_MAX_FRI_BATCHES][2];
+    uint32_t batch_len[GL_MAX_FRI_BATCHES];      /* >= 1 each */
+    const uint32_t* polys;              /* sum(batch_len) pairs (oracle_index, polynomial_index), batch after batch */
+} gl_fri_instance;
+/* Validation, the same in the three calls below: GL_ERR_ARG for a count out of range (1..8 oracles of >= 1 polynomials, 1..4 batches,
+ * at most 65536 listed polynomials, 1..256 query rounds, at most 8 reductions of arity bits 1..8, at most 40 bits of work), an empty
+ * batch, polys == NULL, an oracle / polynomial index out of range, degree_bits < 1 or degree_bits + rate_bits > 24, a total reduction
+ * above degree_bits or above degree_bits + rate_bits - cap_height (circuit_builder.rs:977-980), an opening point on the LDE coset
+ * 7 H_N (the reference panics dividing by zero there), and a batch handle whose n, rate_bits, cap_height, hasher, column count or
+ * salt (oracle_blinding && hiding) differs from params / instance.  The two prover calls answer GL_ERR_UNSUPPORTED for a reduction
+ * of arity other than 16, as for circuits; the verifier takes arity bits 1..8.  Points and alpha may be non-canonical.  One
+ * polynomial may stand in several batches and several times in one. */
+/* prove_openings up to the call of fri_proof (fri/oracle.rs:183-204): per batch F_i = sum_j alpha^j f_ij and (F_i - F_i(z_i)) / (X - z_i)
+ * with the zero pushed back on, final = sum_i quotient_i alpha^(sum_{j > i} len_j) (reduce_polys_base and shift_poly on their shared
+ * counter, util/reducing.rs:83-106), LDE by rate_bits onto the coset.  batches[num_oracles] in the instance's oracle order; they must
+ * outlive the gl_fri, which gl_fri_commit_round / gl_fri_fold / gl_fri_final_poly / gl_fri_query drive as for a circuit; gl_fri_query
+ * writes the initial-tree proofs of all num_oracles oracles in order. */
+int gl_fri_combine_instance(gl_ctx* ctx, const gl_fri_params* params, const gl_fri_instance* instance, const gl_batch* const* batches,
+                            const uint64_t alpha[2], gl_fri** out);
+/* Diagnostic: the same result by the sequence gl_fri_combine runs, one batch after the other (four launches per batch, a column read
+ * once per batch that lists it), for measuring the one-pass kernels against it (tools/openings_rate.py) and testing them against it. */
+int gl_fri_combine_instance_per_batch(gl_ctx* ctx, const gl_fri_params* params, const gl_fri_instance* instance,
+                                      const gl_batch* const* batches, const uint64_t alpha[2], gl_fri** out);
+/* The whole of prove_openings (fri/oracle.rs:162-219, fri/prover.rs:20-216) on the caller's Challenger, from the draw of alpha on (the
+ * caller has observed the openings): commit caps and betas, final polynomial, proof of work, query indices.  Writes the FriProof in
+ * write_fri_proof order (util/serialization/mod.rs:1568-1582): commit-phase caps, query rounds, final polynomial, PoW witness.
+ * *num_bytes = its size, which the params and the instance fix; with h_out null only the size is answered: nothing runs and the
+ * challenger stays where it is.  A call that fails later leaves the challenger advanced. */
+int gl_prove_openings(gl_ctx* ctx, const gl_fri_params* params, const gl_fri_instance* instance, const gl_batch* const* batches,
+                      gl_challenger* challenger, uint8_t* h_out, size_t cap_bytes, size_t* num_bytes);
+/* verify_fri_proof (fri/verifier.rs:62-241) with the challenges of fri/challenges.rs:24-64 drawn from `challenger`, which is in the
+ * state gl_prove_openings expects.  Host code, no GPU.  caps[num_oracles][2^cap_height][4]; openings: the batches' values, batch
+ * after batch, two words each (FriOpenings).  GL_OK, or GL_ERR_VERIFY with gl_last_error() and *check (may be null) = the GL_CHECK_*
+ * code below of the first failing check, in the order: TRUNCATED / LENGTH / *_PATH_LENGTH from the decode; POW; then per query,
+ * ascending: INITIAL_MERKLE (oracles in order), per reduction FRI_CONSISTENCY before STEP_MERKLE, FINAL_POLY.  Only the unsalted prefix
+ * of a leaf enters fri_combine_initial (salt_size(oracle.blinding && params.hiding), fri/proof.rs unsalted_eval). */
+int gl_verify_openings(const gl_fri_params* params, const gl_fri_instance* instance, const uint64_t* caps, const uint64_t* openings,
+                       gl_challenger* challenger, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check);
+
 /* ---- prove() ---------------------------------------------------------------------------------------*/
 /* plonk::prover::prove (plonky2/src/plonk/prover.rs:102-329) from step 4 on, i.e. given the FULL witness matrix
  * `MatrixWitness.wire_values` (iop/witness.rs:256-258) h_wires[num_wires][n] and the public inputs.  Every

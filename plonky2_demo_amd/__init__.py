@@ -5,10 +5,10 @@ Host-side mirror (Python, over the C ABI of libplonky2_mi355x.so) of the referen
 ``MerkleTree`` (plonky2/src/hash/merkle_tree.rs:39-207), ``poseidon`` (plonky2/src/hash/poseidon.rs:598-609).
 Names and argument meaning follow the reference so that the parity tests read like its own tests.
 """
-from ._lib import LIB_PATH, Plonky2Mi355xError  # noqa: F401
+from ._lib import LIB_PATH, FriInstance, FriParams, Plonky2Mi355xError  # noqa: F401
 from . import api  # noqa: F401
 from .api import (  # noqa: F401
     BatchVerifier, Challenger, CircuitData, Context, FriProver, GenericCircuitData, MatmulCircuit, MerkleTree, PolynomialBatch, Proof, ProverPool, coset_fft, coset_ifft, default_context, fft, hash_or_noop, ifft,
     lde_onto_coset, poseidon, pow_grind, random_elements, GOLDILOCKS_ORDER, COSET_SHIFT,
-    hash_from_bytes, hash_or_noop_host, hash_to_bytes, hash_to_elements, two_to_one_host,
+    hash_from_bytes, hash_or_noop_host, hash_to_bytes, hash_to_elements, two_to_one_host, verify_fri_proof,
 )

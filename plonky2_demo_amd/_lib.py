@@ -179,7 +179,13 @@ SIGNATURES = {
     "gl_batch_verifier_new": (c_int, [c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, ctypes.POINTER(c_vp)]),
     "gl_batch_verifier_verify": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_vp]),
     "gl_batch_verifier_free": (None, [c_vp]),
+    # FRI openings of any instance (gl_fri_params*, gl_fri_instance*, ...)
+    "gl_fri_combine_instance": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp)]),
+    "gl_fri_combine_instance_per_batch": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp)]),
+    "gl_prove_openings": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp, c_sz, ctypes.POINTER(c_sz)]),
+    "gl_verify_openings": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(c_u32)]),
 }
+GL_MAX_FRI_ORACLES, GL_MAX_FRI_BATCHES = 8, 4
 
 HASHERS = {"poseidon": 0, "keccak": 1}
 
@@ -218,6 +224,60 @@ class CircuitDesc(ctypes.Structure):
         """Table t as a list of (input, output) pairs: `lut` holds the tables one after the other."""
         off = sum(self.lut_len[i] for i in range(t))
         return [(self.lut[2 * (off + k)], self.lut[2 * (off + k) + 1]) for k in range(self.lut_len[t])]
+
+
+class FriParams(ctypes.Structure):
+    """gl_fri_params: FriParams (fri/mod.rs) + C::Hasher."""
+    _fields_ = [("degree_bits", c_u32), ("rate_bits", c_u32), ("cap_height", c_u32), ("proof_of_work_bits", c_u32), ("num_query_rounds", c_u32),
+                ("num_fri_rounds", c_u32), ("fri_arity_bits", c_u32 * 8), ("hiding", c_u32), ("hasher", c_u32)]
+
+    def __init__(self, degree_bits, rate_bits, cap_height, proof_of_work_bits, num_query_rounds, reduction_arity_bits=(), hiding=False, hasher="poseidon"):
+        arity = [int(a) for a in reduction_arity_bits]
+        if len(arity) > 8:
+            raise ValueError("at most 8 FRI reductions")
+        super().__init__(degree_bits, rate_bits, cap_height, proof_of_work_bits, num_query_rounds, len(arity), (c_u32 * 8)(*arity), 1 if hiding else 0,
+                         hasher_id(hasher))
+
+    @classmethod
+    def of_circuit(cls, d):
+        """The FriParams of a gl_circuit_desc."""
+        return cls(d.degree_bits, d.rate_bits, d.cap_height, d.proof_of_work_bits, d.num_query_rounds, list(d.fri_arity_bits[:d.num_fri_rounds]),
+                   bool(d.zero_knowledge), d.hasher)
+
+    @property
+    def reduction_arity_bits(self):
+        return list(self.fri_arity_bits[:self.num_fri_rounds])
+
+
+class FriInstance(ctypes.Structure):
+    """gl_fri_instance: FriInstanceInfo (fri/structure.rs).  oracles: [(num_polys, blinding), ...]; batches: [(point (2 words), [(oracle_index,
+    polynomial_index), ...]), ...].  Counts beyond the C arrays are a ValueError; everything else is the library's to refuse."""
+    _fields_ = [("num_oracles", c_u32), ("oracle_num_polys", c_u32 * GL_MAX_FRI_ORACLES), ("oracle_blinding", c_u32 * GL_MAX_FRI_ORACLES),
+                ("num_batches", c_u32), ("points", (c_u64 * 2) * GL_MAX_FRI_BATCHES), ("batch_len", c_u32 * GL_MAX_FRI_BATCHES),
+                ("polys", ctypes.POINTER(c_u32))]
+
+    def __init__(self, oracles, batches):
+        super().__init__()
+        oracles, batches = list(oracles), [(tuple(int(w) for w in pt), [(int(o), int(c)) for o, c in polys]) for pt, polys in batches]
+        if len(oracles) > GL_MAX_FRI_ORACLES or len(batches) > GL_MAX_FRI_BATCHES:
+            raise ValueError("at most %d oracles and %d batches" % (GL_MAX_FRI_ORACLES, GL_MAX_FRI_BATCHES))
+        self.num_oracles, self.num_batches = len(oracles), len(batches)
+        for i, (k, blinding) in enumerate(oracles):
+            self.oracle_num_polys[i], self.oracle_blinding[i] = int(k), 1 if blinding else 0
+        flat = []
+        for i, (pt, polys) in enumerate(batches):
+            self.points[i][0], self.points[i][1] = pt
+            self.batch_len[i] = len(polys)
+            for o, c in polys:
+                flat += [o, c]
+        self._polys = (c_u32 * max(len(flat), 1))(*flat)      # kept alive with the structure
+        self.polys = ctypes.cast(self._polys, ctypes.POINTER(c_u32))
+        self.oracles, self.batches = oracles, batches
+
+    @property
+    def num_opened(self):
+        return sum(len(polys) for _, polys in self.batches)
+
 
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)   # AttributeError here = the .so does not export a declared symbol

@@ -443,6 +443,19 @@ class PolynomialBatch(_Owned):
         check(lib.gl_open_at((ctx or self.ctx).handle, self.handle, _p(_u64(z)), first_col, num_cols, _p(out)))
         return out
 
+    @staticmethod
+    def prove_openings(instance, oracles, challenger, fri_params, ctx=None):
+        """PolynomialBatch::prove_openings (fri/oracle.rs:162-219) for any FriInstance: the FriProof bytes in write_fri_proof order.  The
+        challenger has observed the openings; it is left behind the last query index."""
+        oracles = list(oracles)
+        ctx = ctx or oracles[0].ctx
+        arr = (ctypes.c_void_p * max(len(oracles), 1))(*[b.handle for b in oracles])
+        k = ctypes.c_size_t()
+        check(lib.gl_prove_openings(ctx.handle, ctypes.byref(fri_params), ctypes.byref(instance), arr, challenger.handle, None, 0, ctypes.byref(k)))
+        out = np.empty(k.value, dtype=np.uint8)
+        check(lib.gl_prove_openings(ctx.handle, ctypes.byref(fri_params), ctypes.byref(instance), arr, challenger.handle, _p(out), out.size, ctypes.byref(k)))
+        return out.tobytes()
+
     free = _Owned.close     # a batch borrowed from a circuit (handle_owned False) is only forgotten
 
 
@@ -897,13 +910,27 @@ class FriProver(_Owned):
 
     def __init__(self, cd, batches, zeta, alpha, ctx):
         self.ctx, self.cd, self.batches = ctx, cd, list(batches)     # the batches must outlive the FRI state
+        self.params = _lib.FriParams.of_circuit(cd.desc)
         arr = (ctypes.c_void_p * 4)(*[b.handle for b in self.batches])
         h = ctypes.c_void_p()
         check(lib.gl_fri_combine(ctx.handle, cd.handle, arr, _p(_u64(zeta)), _p(_u64(alpha)), ctypes.byref(h)))
         self.handle = h.value
 
+    @classmethod
+    def from_instance(cls, instance, oracles, alpha, fri_params, ctx=None, per_batch=False):
+        """prove_openings up to fri_proof (fri/oracle.rs:183-204) for any FriInstance (gl_fri_combine_instance).  per_batch: the diagnostic
+        form that reduces and divides one batch after the other."""
+        self = cls.__new__(cls)
+        self.batches = list(oracles)
+        self.ctx, self.cd, self.params, self.instance = ctx or self.batches[0].ctx, None, fri_params, instance
+        arr = (ctypes.c_void_p * max(len(self.batches), 1))(*[b.handle for b in self.batches])
+        h = ctypes.c_void_p()
+        check((lib.gl_fri_combine_instance_per_batch if per_batch else lib.gl_fri_combine_instance)(self.ctx.handle, ctypes.byref(fri_params), ctypes.byref(instance), arr, _p(_u64(alpha)), ctypes.byref(h)))
+        self.handle = h.value
+        return self
+
     def commit_round(self):
-        cap = np.empty((1 << self.cd.desc.cap_height, 4), dtype=np.uint64)
+        cap = np.empty((1 << self.params.cap_height, 4), dtype=np.uint64)
         check(lib.gl_fri_commit_round(self.handle, _p(cap)))
         return cap
 
@@ -953,6 +980,23 @@ class Challenger(_Owned):
         st, buf, k = np.empty(12, dtype=np.uint64), np.empty(8, dtype=np.uint64), ctypes.c_uint32()
         check(lib.gl_challenger_state(self.handle, _p(st), _p(buf), ctypes.byref(k)))
         return st, buf[: k.value].copy()
+
+
+def verify_fri_proof(instance, caps, openings, challenger, proof, fri_params):
+    """verify_fri_proof (fri/verifier.rs:62-241) with the challenges drawn from `challenger` (in the state prove_openings expects): host
+    code.  caps [num_oracles][2^cap_height][4], openings: every batch's values in order, [.][2] -> (accepted, message, GL_CHECK_* code)."""
+    caps, openings = _u64(caps).reshape(-1), _u64(openings).reshape(-1)
+    # counts the C arrays cannot hold are the library's to refuse (before it reads anything); within them the arrays must be long enough
+    if instance.num_oracles <= _lib.GL_MAX_FRI_ORACLES and instance.num_batches <= _lib.GL_MAX_FRI_BATCHES and fri_params.cap_height <= min(24, fri_params.degree_bits + fri_params.rate_bits):
+        listed = sum(instance.batch_len[b] for b in range(instance.num_batches))
+        if caps.size < instance.num_oracles * (4 << fri_params.cap_height) or openings.size < 2 * listed:
+            raise ValueError("caps are [num_oracles][2^cap_height][4], openings one extension value per listed polynomial")
+    buf = np.frombuffer(bytes(proof), dtype=np.uint8)
+    code = ctypes.c_uint32()
+    st = lib.gl_verify_openings(ctypes.byref(fri_params), ctypes.byref(instance), _p(caps), _p(openings), challenger.handle,
+                                _p(buf) if buf.size else None, buf.size, ctypes.byref(code))
+    ok, why = _verdict(st)
+    return ok, why, code.value
 
 
 def pow_grind(sponge_state, input_buffer, min_leading_zeros, ctx=None, hasher="poseidon"):

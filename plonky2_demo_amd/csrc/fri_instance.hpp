@@ -1,0 +1,65 @@
+// What gl_fri_combine_instance, gl_prove_openings (prove.hip) and gl_verify_openings (verifier.hip) share: the Challenger's C handle and
+// the validation of a FriParams / FriInstanceInfo pair (fri/mod.rs, fri/structure.rs).  Host code.
+#pragma once
+#include "context.hpp"
+#include "host_circuit.hpp"
+
+// C handle of the Challenger for callers of the phase API that have no transcript of their own (C / C++ / Python)
+struct gl_challenger { glhost::HostChallenger ch; };
+
+namespace glfri {
+
+enum { MAX_LISTED_POLYS = 65536, SALT_SIZE = 4 };
+
+inline size_t total_polys(const gl_fri_instance& in) { size_t t = 0; for (uint32_t b = 0; b < in.num_batches; b++) t += in.batch_len[b]; return t; }
+inline uint32_t salt_of(const gl_fri_params& p, const gl_fri_instance& in, uint32_t o) { return p.hiding && in.oracle_blinding[o] ? SALT_SIZE : 0; }
+inline gl2_t point_of(const gl_fri_instance& in, uint32_t b) { return gl2_make(gl_canon(in.points[b][0]), gl_canon(in.points[b][1])); }
+
+// the checks of include/plonky2_mi355x.h ("Validation"); `prover`: the two calls that fold by 16 only
+inline int check(const gl_fri_params* params, const gl_fri_instance* instance, bool prover) {
+    GL_REQUIRE(params && instance, GL_ERR_ARG, "FRI openings: null params / instance");
+    const gl_fri_params& p = *params; const gl_fri_instance& in = *instance;
+    GL_REQUIRE(p.hasher <= GL_HASHER_KECCAK, GL_ERR_ARG, "FRI openings: hasher is 0 (Poseidon) or 1 (Keccak)");
+    GL_REQUIRE(p.hiding <= 1, GL_ERR_ARG, "FRI openings: hiding is 0 or 1");
+    GL_REQUIRE(p.degree_bits >= 1 && p.rate_bits <= 24 && p.degree_bits <= 24 && p.degree_bits + p.rate_bits <= 24, GL_ERR_ARG,
+               "FRI openings: degree_bits >= 1 and an LDE of at most 2^24");
+    GL_REQUIRE(p.cap_height <= p.degree_bits + p.rate_bits, GL_ERR_ARG, "FRI openings: cap_height above the LDE's height");
+    GL_REQUIRE(p.num_query_rounds >= 1 && p.num_query_rounds <= 256 && p.proof_of_work_bits <= 40 && p.num_fri_rounds <= 8, GL_ERR_ARG,
+               "FRI openings: 1..256 query rounds, at most 40 bits of work, at most 8 reductions");
+    unsigned total = 0;
+    for (unsigned r = 0; r < p.num_fri_rounds; r++) {
+        GL_REQUIRE(p.fri_arity_bits[r] >= 1 && p.fri_arity_bits[r] <= 8, GL_ERR_ARG, "FRI openings: arity bits are 1..8");
+        total += p.fri_arity_bits[r];
+    }
+    GL_REQUIRE(total <= p.degree_bits && total + p.cap_height <= p.degree_bits + p.rate_bits, GL_ERR_ARG,
+               "FRI total reduction arity is too large");      // circuit_builder.rs:977-980
+    GL_REQUIRE(in.num_oracles >= 1 && in.num_oracles <= GL_MAX_FRI_ORACLES, GL_ERR_ARG, "FRI openings: 1..8 oracles");
+    GL_REQUIRE(in.num_batches >= 1 && in.num_batches <= GL_MAX_FRI_BATCHES, GL_ERR_ARG, "FRI openings: 1..4 batches");
+    for (uint32_t o = 0; o < in.num_oracles; o++)
+        GL_REQUIRE(in.oracle_num_polys[o] >= 1 && in.oracle_num_polys[o] <= MAX_LISTED_POLYS && in.oracle_blinding[o] <= 1, GL_ERR_ARG,
+                   "FRI openings: an oracle has 1..65536 polynomials, blinding is 0 or 1");
+    GL_REQUIRE(in.polys, GL_ERR_ARG, "FRI openings: null polynomial list");
+    size_t listed = 0;
+    for (uint32_t b = 0; b < in.num_batches; b++) {
+        GL_REQUIRE(in.batch_len[b] >= 1 && in.batch_len[b] <= MAX_LISTED_POLYS, GL_ERR_ARG, "FRI openings: an empty batch (or one above 65536 polynomials)");
+        listed += in.batch_len[b];
+    }
+    GL_REQUIRE(listed <= MAX_LISTED_POLYS, GL_ERR_ARG, "FRI openings: more than 65536 listed polynomials");
+    for (size_t k = 0; k < listed; k++)
+        GL_REQUIRE(in.polys[2 * k] < in.num_oracles && in.polys[2 * k + 1] < in.oracle_num_polys[in.polys[2 * k]], GL_ERR_ARG,
+                   "FRI openings: oracle / polynomial index out of range");
+    // a point 7 w with w^N = 1 is an LDE point: the quotient by (X - point) has a pole there (the reference panics dividing by zero)
+    const gl_t inv7 = gl_inv(GL_MULT_GENERATOR);
+    for (uint32_t b = 0; b < in.num_batches; b++) {
+        const gl2_t z = point_of(in, b);
+        if (z.b != 0) continue;
+        gl_t w = gl_mul(z.a, inv7);
+        for (uint32_t i = 0; i < p.degree_bits + p.rate_bits; i++) w = gl_sqr(w);
+        GL_REQUIRE(gl_canon(w) != 1, GL_ERR_ARG, "FRI openings: an opening point lies on the LDE coset");
+    }
+    if (prover)
+        for (unsigned r = 0; r < p.num_fri_rounds; r++) GL_REQUIRE(p.fri_arity_bits[r] == 4, GL_ERR_UNSUPPORTED, "FRI arity must be 16");
+    return GL_OK;
+}
+
+}  // namespace glfri

@@ -4,6 +4,7 @@
 // of a .hip file that holds a kernel cannot be linked that way.
 #include "context.hpp"
 #include "host_circuit.hpp"
+#include "fri_instance.hpp"
 #include "proof.hpp"
 #include "rng.cuh"
 #include <cstring>
@@ -11,8 +12,7 @@
 
 using glhost::HostChallenger;
 
-// C handle of the Challenger for callers of the phase API that have no transcript of their own (C / C++ / Python)
-struct gl_challenger { HostChallenger ch; };
+// the Challenger handle (struct gl_challenger: fri_instance.hpp, gl_prove_openings and gl_verify_openings take it)
 extern "C" gl_challenger* gl_challenger_new(void) try { return new gl_challenger(); } catch (...) { (void)gl_caught(); return nullptr; }
 // Challenger::<F, H>::new (iop/challenger.rs:31-37) for H = Poseidon (0) or Keccak (1, KeccakPermutation: hash/keccak.rs:64-95)
 extern "C" gl_challenger* gl_challenger_new_h(uint32_t hasher) try {

@@ -4,6 +4,7 @@
 // phase's challenge is a Poseidon transcript of it (iop/challenger.rs:81-148).
 #include "context.hpp"
 #include "host_circuit.hpp"
+#include "fri_instance.hpp"
 #include "prover_kernels.cuh"
 #include "proof.hpp"
 #include <cstring>
@@ -530,8 +531,8 @@ static FriOpenings fri_openings(const gl_batch* const oracles[4]) {
 //          transcript dependency ----
 struct gl_fri {
     gl_ctx* ctx = nullptr;
-    gl_circuit_desc desc;
-    const gl_batch* oracles[4] = {nullptr, nullptr, nullptr, nullptr};
+    gl_fri_params params;                    // FriParams + C::Hasher: all the rounds and the queries read (no circuit behind it)
+    std::vector<const gl_batch*> oracles;    // the initial trees, in the instance's oracle order
     size_t n = 0;
     uint32_t lgN = 0;
     // commit phase state
@@ -545,6 +546,7 @@ struct gl_fri {
     std::vector<uint32_t> lg;
     // host sources of asynchronous uploads (alive until the object dies)
     std::vector<const gl_t*> h_cols; std::vector<gl_t> h_apow;
+    std::vector<const gl_t*> h_listed_cols; std::vector<gl_t> h_listed_apow;
 };
 extern "C" void gl_fri_free(gl_fri* f) noexcept {
     if (!f) return;
@@ -552,6 +554,14 @@ extern "C" void gl_fri_free(gl_fri* f) noexcept {
     if (ctx) (void)gl_stream_wait(ctx->stream);
     delete f;                                  // its trees and buffers go back to the context's pool first
     gl_ctx_release(ctx);
+}
+static gl_fri_params fri_params_of(const gl_circuit_desc& d) {
+    gl_fri_params p;
+    p.degree_bits = d.degree_bits; p.rate_bits = d.rate_bits; p.cap_height = d.cap_height; p.proof_of_work_bits = d.proof_of_work_bits;
+    p.num_query_rounds = d.num_query_rounds; p.num_fri_rounds = d.num_fri_rounds;
+    for (int r = 0; r < 8; r++) p.fri_arity_bits[r] = d.fri_arity_bits[r];
+    p.hiding = d.zero_knowledge; p.hasher = d.hasher;
+    return p;
 }
 static int fri_combine(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* const batches[4], const uint64_t zeta_in[2], const uint64_t alpha_in[2], gl_fri** out) {
     GL_TRY(check_phase_args(ctx, cir));
@@ -564,8 +574,8 @@ static int fri_combine(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* const
     const size_t nopen = op.nopen, nnext = op.nnext;
     hipStream_t st = ctx->stream;
     std::unique_ptr<gl_fri, void (*)(gl_fri*)> f(new gl_fri(), gl_fri_free);
-    f->ctx = ctx; ctx->retain(); f->desc = d; f->n = n; f->lgN = d.degree_bits + d.rate_bits;
-    for (int o = 0; o < 4; o++) f->oracles[o] = batches[o];
+    f->ctx = ctx; ctx->retain(); f->params = fri_params_of(d); f->n = n; f->lgN = d.degree_bits + d.rate_bits;
+    f->oracles.assign(batches, batches + 4);
     const gl2_t zeta = gl2_make(gl_canon(zeta_in[0]), gl_canon(zeta_in[1])), fri_alpha = gl2_make(gl_canon(alpha_in[0]), gl_canon(alpha_in[1]));
     const gl2_t gzeta = gl2_canon(gl2_scalar(zeta, gl_host_root_of_unity(d.degree_bits)));
     f->coef.reset(new DevBuf(ctx)); GL_TRY(f->coef->alloc(2 * n * sizeof(gl_t)));            // planes a, b of alpha^2 Q0 + Q1
@@ -616,18 +626,18 @@ extern "C" int gl_fri_combine(gl_ctx* ctx, const gl_circuit* cir, const gl_batch
 // fri_committed_trees, first half of one loop iteration (fri/prover.rs:76-92): Merkle tree of the current codeword
 extern "C" int gl_fri_commit_round(gl_fri* f, uint64_t* h_cap_out) try {
     GL_REQUIRE(f && h_cap_out, GL_ERR_ARG, "gl_fri_commit_round: null argument");
-    GL_REQUIRE(f->round < f->desc.num_fri_rounds && !f->committed, GL_ERR_ARG, "gl_fri_commit_round: no round left to commit (call gl_fri_fold first)");
+    GL_REQUIRE(f->round < f->params.num_fri_rounds && !f->committed, GL_ERR_ARG, "gl_fri_commit_round: no round left to commit (call gl_fri_fold first)");
     gl_ctx* ctx = f->ctx;
     GL_TRY(ctx->activate());
-    const uint32_t ab = f->desc.fri_arity_bits[f->round], arity = 1u << ab;
+    const uint32_t ab = f->params.fri_arity_bits[f->round], arity = 1u << ab;
     const size_t curN = size_t(1) << f->cur_lgN;
     // leaves: `arity` consecutive entries of the bit-reversed value array, flattened (fri/prover.rs:80-89)
     std::vector<uint64_t> offs(2 * arity);
     for (uint32_t k = 0; k < arity; k++)
         for (uint32_t cpt = 0; cpt < 2; cpt++) offs[2 * k + cpt] = (uint64_t)cpt * curN + (uint64_t)host_bitrev32(k, ab) * (curN >> ab);
     std::unique_ptr<MerkleHolder> tree(new MerkleHolder(ctx));
-    GL_TRY(gl_merkle_build(ctx, f->cur_vals->as<gl_t>(), offs.data(), 2 * arity, f->cur_lgN - ab, f->desc.cap_height, &tree->m, f->desc.hasher));
-    GL_TRY(d2h(ctx, h_cap_out, tree->m.level_ptr(tree->m.num_levels() - 1), (size_t(4) << f->desc.cap_height) * sizeof(gl_t)));
+    GL_TRY(gl_merkle_build(ctx, f->cur_vals->as<gl_t>(), offs.data(), 2 * arity, f->cur_lgN - ab, f->params.cap_height, &tree->m, f->params.hasher));
+    GL_TRY(d2h(ctx, h_cap_out, tree->m.level_ptr(tree->m.num_levels() - 1), (size_t(4) << f->params.cap_height) * sizeof(gl_t)));
     f->trees.push_back(std::move(tree));
     f->committed = true;
     return GL_OK;
@@ -638,7 +648,7 @@ extern "C" int gl_fri_fold(gl_fri* f, const uint64_t beta_in[2]) try {
     GL_REQUIRE(f->committed, GL_ERR_ARG, "gl_fri_fold: commit the round first");
     gl_ctx* ctx = f->ctx;
     GL_TRY(ctx->activate());
-    const uint32_t ab = f->desc.fri_arity_bits[f->round], arity = 1u << ab;
+    const uint32_t ab = f->params.fri_arity_bits[f->round], arity = 1u << ab;
     const gl2_t beta = gl2_make(gl_canon(beta_in[0]), gl_canon(beta_in[1]));
     const size_t next_n = f->cur_n >> ab;
     GL_REQUIRE(next_n >= 1, GL_ERR_INTERNAL, "FRI fold below one coefficient");
@@ -666,7 +676,7 @@ extern "C" int gl_fri_fold(gl_fri* f, const uint64_t beta_in[2]) try {
 // final polynomial: the remaining non-zero coefficients (coeffs.truncate(len >> rate_bits), fri/prover.rs:106-111), interleaved (a, b)
 extern "C" int gl_fri_final_poly(gl_fri* f, uint64_t* h_out, size_t cap_words, size_t* num_words) try {
     GL_REQUIRE(f && num_words, GL_ERR_ARG, "gl_fri_final_poly: null argument");
-    GL_REQUIRE(f->round == f->desc.num_fri_rounds && !f->committed, GL_ERR_ARG, "gl_fri_final_poly: reduction rounds not finished");
+    GL_REQUIRE(f->round == f->params.num_fri_rounds && !f->committed, GL_ERR_ARG, "gl_fri_final_poly: reduction rounds not finished");
     *num_words = 2 * f->cur_n;
     if (!h_out) return GL_OK;
     GL_REQUIRE(cap_words >= 2 * f->cur_n, GL_ERR_ARG, "gl_fri_final_poly: output too small");
@@ -732,7 +742,8 @@ extern "C" int gl_pow_grind_h(gl_ctx* ctx, uint32_t hasher, const uint64_t spong
 //      `arity` extension evaluations and the path) ----
 static int fri_query_blob(gl_fri* f, const uint32_t* x_index, uint32_t nq, std::vector<uint8_t>& o) {
     gl_ctx* ctx = f->ctx;
-    const gl_circuit_desc& d = f->desc;
+    const gl_fri_params& d = f->params;
+    const size_t no = f->oracles.size();
     hipStream_t st = ctx->stream;
     const uint32_t lgN = f->lgN;
     const size_t N = size_t(1) << lgN;
@@ -740,10 +751,10 @@ static int fri_query_blob(gl_fri* f, const uint32_t* x_index, uint32_t nq, std::
     for (uint32_t q = 0; q < nq; q++) GL_REQUIRE(x_index[q] < N, GL_ERR_ARG, "gl_fri_query: query index out of range");
     // staging layout (u64 words): per oracle: rows [nq][ncols], paths [nq][levels][4]; per FRI round: leaves [nq][arity][2], paths
     struct Piece { size_t off, words; };
-    std::vector<Piece> row_piece(4), path_piece(4), fleaf_piece(d.num_fri_rounds), fpath_piece(d.num_fri_rounds);
+    std::vector<Piece> row_piece(no), path_piece(no), fleaf_piece(d.num_fri_rounds), fpath_piece(d.num_fri_rounds);
     size_t total = 0;
     const uint32_t init_levels = lgN - d.cap_height;
-    for (int o2 = 0; o2 < 4; o2++) {
+    for (size_t o2 = 0; o2 < no; o2++) {
         row_piece[o2] = {total, nq * f->oracles[o2]->leaf_len()}; total += row_piece[o2].words;
         path_piece[o2] = {total, (size_t)nq * init_levels * 4}; total += path_piece[o2].words;
     }
@@ -766,7 +777,7 @@ static int fri_query_blob(gl_fri* f, const uint32_t* x_index, uint32_t nq, std::
     const uint32_t* d_rows = d_leaf + nq;                     // natural LDE rows = bitrev(leaf)
     gl_t* stage = d_stage.as<gl_t>();
     ctx->timing_begin("FRI query gathers");
-    for (int o2 = 0; o2 < 4; o2++) {
+    for (size_t o2 = 0; o2 < no; o2++) {
         const gl_batch* b = f->oracles[o2];
         const uint64_t* d_lo = nullptr;
         GL_TRY(ctx->get_offsets_table(b->tree.level_off.data(), b->tree.level_off.size(), &d_lo));
@@ -792,7 +803,7 @@ static int fri_query_blob(gl_fri* f, const uint32_t* x_index, uint32_t nq, std::
     std::vector<gl_t> host_stage(total + 8);
     GL_TRY(d2h(ctx, host_stage.data(), stage, total * sizeof(gl_t)));      // also orders the idx_host upload before it dies
     for (uint32_t q = 0; q < nq; q++) {
-        for (int oi = 0; oi < 4; oi++) {
+        for (size_t oi = 0; oi < no; oi++) {
             const size_t nc = f->oracles[oi]->leaf_len();
             put_words(o, host_stage.data() + row_piece[oi].off + (size_t)q * nc, nc);
             o.push_back((uint8_t)init_levels);
@@ -817,6 +828,188 @@ extern "C" int gl_fri_query(gl_fri* f, const uint32_t* x_index, uint32_t num_que
     if (!h_blob) return GL_OK;
     GL_REQUIRE(cap_bytes >= blob.size(), GL_ERR_ARG, "gl_fri_query: output too small");
     memcpy(h_blob, blob.data(), blob.size());
+    return GL_OK;
+} catch (...) { return gl_caught(); }
+
+// ---- PolynomialBatch::prove_openings for any FriInstanceInfo (fri/oracle.rs:162-219, fri/structure.rs) ----
+static_assert(GLF_MAX_POINTS == GL_MAX_FRI_BATCHES, "the kernels' point table holds one entry per batch");
+static int check_instance_batches(gl_ctx* ctx, const gl_fri_params& p, const gl_fri_instance& in, const gl_batch* const* batches) {
+    GL_REQUIRE(batches, GL_ERR_ARG, "FRI openings: null batch list");
+    for (uint32_t o = 0; o < in.num_oracles; o++) {
+        const gl_batch* b = batches[o];
+        GL_REQUIRE(b && b->ctx && b->ctx->device == ctx->device, GL_ERR_ARG, "FRI openings: a null batch, or one on another device");
+        GL_REQUIRE(b->n == (size_t(1) << p.degree_bits) && b->rate_bits == p.rate_bits && b->cap_height == p.cap_height && b->ncols == in.oracle_num_polys[o],
+                   GL_ERR_ARG, "FRI openings: a batch whose degree, rate_bits, cap_height or column count differs from params / instance");
+        GL_REQUIRE(b->hasher == p.hasher, GL_ERR_ARG, "a batch committed under another hasher than the params'");
+        GL_REQUIRE(b->salt == glfri::salt_of(p, in, o), GL_ERR_ARG, "FRI openings: a batch is salted where the instance is not blinded (or the reverse)");
+    }
+    return GL_OK;
+}
+// `per_batch`: the sequence gl_fri_combine runs, one batch after the other (k_fri_combine + the three division launches, every listed
+// column read where it is listed) -- what tools/openings_rate.py measures the one-pass kernels against
+static int fri_combine_instance(gl_ctx* ctx, const gl_fri_params* params, const gl_fri_instance* instance, const gl_batch* const* batches, const uint64_t alpha_in[2], gl_fri** out,
+                                bool per_batch = false) {
+    GL_REQUIRE(ctx && alpha_in && out, GL_ERR_ARG, "gl_fri_combine_instance: null argument");
+    GL_TRY(glfri::check(params, instance, true));
+    const gl_fri_params& p = *params; const gl_fri_instance& in = *instance;
+    GL_TRY(check_instance_batches(ctx, p, in, batches));
+    GL_TRY(ctx->activate());
+    const size_t n = size_t(1) << p.degree_bits, N = n << p.rate_bits;
+    const uint32_t B = in.num_batches;
+    hipStream_t st = ctx->stream;
+    std::unique_ptr<gl_fri, void (*)(gl_fri*)> f(new gl_fri(), gl_fri_free);
+    f->ctx = ctx; ctx->retain(); f->params = p; f->n = n; f->lgN = p.degree_bits + p.rate_bits;
+    f->oracles.assign(batches, batches + in.num_oracles);
+    const gl2_t alpha = gl2_make(gl_canon(alpha_in[0]), gl_canon(alpha_in[1]));
+    // the distinct columns in order of first appearance, and per column and batch the sum of the powers of alpha it takes there
+    // (reduce_polys_base, reducing.rs:83-95: polynomial j of a batch takes alpha^j)
+    size_t first_col[GL_MAX_FRI_ORACLES + 1] = {0};
+    for (uint32_t o = 0; o < in.num_oracles; o++) first_col[o + 1] = first_col[o] + in.oracle_num_polys[o];
+    std::vector<int32_t> slot(first_col[in.num_oracles], -1);
+    std::vector<const gl_t*>& cols = f->h_cols;
+    std::vector<gl_t>& wts = f->h_apow;
+    std::vector<const gl_t*>& listed_cols = f->h_listed_cols;      // per_batch: the columns as listed, and alpha^j of each
+    std::vector<gl_t>& listed_apow = f->h_listed_apow;
+    GlFriPoints pt;
+    gl2_t alpha_len[GL_MAX_FRI_BATCHES];                    // alpha^(len of batch b)
+    for (uint32_t b = 0, k = 0; b < B; b++) {
+        gl2_t x = gl2_make(1, 0);
+        for (uint32_t j = 0; j < in.batch_len[b]; j++, k++) {
+            const uint32_t o = in.polys[2 * k], c = in.polys[2 * k + 1];
+            int32_t& sl = slot[first_col[o] + c];
+            if (sl < 0) { sl = (int32_t)cols.size(); cols.push_back(batches[o]->coeffs + (size_t)c * n); wts.resize(wts.size() + 2 * B, 0); }
+            gl_t* w = &wts[(size_t)sl * 2 * B + 2 * b];
+            w[0] = gl_canon(gl_add(w[0], x.a)); w[1] = gl_canon(gl_add(w[1], x.b));
+            if (per_batch) { listed_cols.push_back(batches[o]->coeffs + (size_t)c * n); listed_apow.push_back(x.a); listed_apow.push_back(x.b); }
+            x = gl2_canon(gl2_mul(x, alpha));
+        }
+        alpha_len[b] = x;
+    }
+    {   // shift_poly (reducing.rs:103-106): quotient b is multiplied by alpha^len of every later batch
+        gl2_t s = gl2_make(1, 0);
+        for (uint32_t b = GL_MAX_FRI_BATCHES; b-- > 0;) {
+            const gl2_t z = b < B ? glfri::point_of(in, b) : gl2_make(0, 0);
+            pt.z[b][0] = z.a; pt.z[b][1] = z.b;
+            pt.scale[b][0] = b < B ? s.a : 0; pt.scale[b][1] = b < B ? s.b : 0;
+            if (b < B) s = gl2_canon(gl2_mul(s, alpha_len[b]));
+        }
+    }
+    const size_t ncols = cols.size();
+    f->coef.reset(new DevBuf(ctx)); GL_TRY(f->coef->alloc(2 * n * sizeof(gl_t)));
+    {
+        DevBuf d_F(ctx), d_heads(ctx), d_cols(ctx), d_wts(ctx);
+        const uint32_t seg_len = (uint32_t)(n / 1024 > 32 ? n / 1024 : (n >= 32 ? 32 : n));      // at most 1024 segments
+        const uint32_t nseg = (uint32_t)((n + seg_len - 1) / seg_len);
+        GL_TRY(d_F.alloc(2 * (size_t)B * n * sizeof(gl_t)));
+        GL_TRY(d_heads.alloc(2 * (size_t)B * nseg * sizeof(gl_t)));
+        GL_TRY(d_cols.alloc(ncols * sizeof(gl_t*)));
+        GL_TRY(d_wts.alloc(wts.size() * sizeof(gl_t)));
+        GL_TRY(h2d_async(ctx, d_cols.p, cols.data(), ncols * sizeof(gl_t*)));
+        GL_TRY(h2d_async(ctx, d_wts.p, wts.data(), wts.size() * sizeof(gl_t)));
+        gl_t* F = d_F.as<gl_t>();
+        gl_t* Qa = f->coef->as<gl_t>(); gl_t* Qb = Qa + n;
+        const unsigned gb = (unsigned)((n + 63) / 64), sb = (nseg + 63) / 64;
+        if (per_batch) {
+            DevBuf d_lcols(ctx), d_lapow(ctx);
+            GL_TRY(d_lcols.alloc(listed_cols.size() * sizeof(gl_t*)));
+            GL_TRY(d_lapow.alloc(listed_apow.size() * sizeof(gl_t)));
+            GL_TRY(h2d_async(ctx, d_lcols.p, listed_cols.data(), listed_cols.size() * sizeof(gl_t*)));
+            GL_TRY(h2d_async(ctx, d_lapow.p, listed_apow.data(), listed_apow.size() * sizeof(gl_t)));
+            gl_t* Fa = F; gl_t* Fb = F + n;
+            ctx->timing_begin("reduce batch + divide by linear, batch after batch");
+            for (uint32_t b = 0, k = 0; b < B; k += in.batch_len[b], b++) {
+                hipLaunchKernelGGL(k_fri_combine, dim3(gb), dim3(256), 0, st, d_lcols.as<const gl_t*>() + k, d_lapow.as<gl_t>() + 2 * k, in.batch_len[b], (uint32_t)n, Fa, Fb);
+                hipLaunchKernelGGL(k_div_linear_heads, dim3(sb), dim3(64), 0, st, Fa, Fb, (uint32_t)n, seg_len, pt.z[b][0], pt.z[b][1], d_heads.as<gl_t>());
+                hipLaunchKernelGGL(k_div_linear_carries, dim3(1), dim3(1024), 0, st, d_heads.as<gl_t>(), (uint32_t)n, seg_len, pt.z[b][0], pt.z[b][1]);
+                hipLaunchKernelGGL(k_div_linear_apply, dim3(sb), dim3(64), 0, st, Fa, Fb, (uint32_t)n, seg_len, pt.z[b][0], pt.z[b][1], d_heads.as<gl_t>(), pt.scale[b][0],
+                                   pt.scale[b][1], Qa, Qb, b ? 1 : 0);
+            }
+            ctx->timing_end();
+            GL_CHECK_HIP(hipGetLastError());
+        } else {
+        ctx->timing_begin("reduce batches + divide by linear");
+#define GLF_LAUNCH(NB)                                                                                                                               \
+    case NB:                                                                                                                                         \
+        hipLaunchKernelGGL(k_fri_combine_points<NB>, dim3(gb), dim3(256), 0, st, d_cols.as<const gl_t*>(), d_wts.as<gl_t>(), (uint32_t)ncols, (uint32_t)n, F); \
+        hipLaunchKernelGGL(k_div_points_heads, dim3(sb, NB), dim3(64), 0, st, F, (uint32_t)n, seg_len, pt, d_heads.as<gl_t>());                      \
+        hipLaunchKernelGGL(k_div_points_carries, dim3(1, NB), dim3(1024), 0, st, d_heads.as<gl_t>(), (uint32_t)n, seg_len, pt);                      \
+        hipLaunchKernelGGL(k_div_points_apply<NB>, dim3(sb), dim3(64), 0, st, F, (uint32_t)n, seg_len, pt, d_heads.as<gl_t>(), Qa, Qb);               \
+        break;
+        switch (B) { GLF_LAUNCH(1) GLF_LAUNCH(2) GLF_LAUNCH(3) GLF_LAUNCH(4) }
+#undef GLF_LAUNCH
+        ctx->timing_end();
+        GL_CHECK_HIP(hipGetLastError());
+        }
+    }
+    // final_poly.lde(rate_bits).coset_fft(7) on both planes (fri/oracle.rs:199-204)
+    f->cur_vals.reset(new DevBuf(ctx)); GL_TRY(f->cur_vals->alloc(2 * N * sizeof(gl_t)));
+    GL_TRY(gl_ntt_run(ctx, f->coef->as<gl_t>(), n, (uint32_t)n, f->cur_vals->as<gl_t>(), N, f->lgN, 2, false, GL_MULT_GENERATOR, 0, 1));
+    f->cur_n = n; f->cur_lgN = f->lgN;
+    *out = f.release();
+    return GL_OK;
+}
+extern "C" int gl_fri_combine_instance(gl_ctx* ctx, const gl_fri_params* params, const gl_fri_instance* instance, const gl_batch* const* batches,
+                                       const uint64_t alpha[2], gl_fri** out) try {
+    return fri_combine_instance(ctx, params, instance, batches, alpha, out);
+} catch (...) { return gl_caught(); }
+extern "C" int gl_fri_combine_instance_per_batch(gl_ctx* ctx, const gl_fri_params* params, const gl_fri_instance* instance, const gl_batch* const* batches,
+                                                 const uint64_t alpha[2], gl_fri** out) try {
+    return fri_combine_instance(ctx, params, instance, batches, alpha, out, true);
+} catch (...) { return gl_caught(); }
+// fri_proof (fri/prover.rs:20-66) behind it, on the caller's Challenger; the FriProof in write_fri_proof order (util/serialization/mod.rs:1568-1582)
+extern "C" int gl_prove_openings(gl_ctx* ctx, const gl_fri_params* params, const gl_fri_instance* instance, const gl_batch* const* batches,
+                                 gl_challenger* challenger, uint8_t* h_out, size_t cap_bytes, size_t* num_bytes) try {
+    GL_REQUIRE(ctx && challenger && num_bytes, GL_ERR_ARG, "gl_prove_openings: null argument");
+    GL_TRY(glfri::check(params, instance, true));
+    const gl_fri_params& p = *params; const gl_fri_instance& in = *instance;
+    GL_TRY(check_instance_batches(ctx, p, in, batches));
+    GL_REQUIRE(challenger->ch.hasher == p.hasher, GL_ERR_ARG, "gl_prove_openings: the challenger runs under another hasher than the params'");
+    const uint32_t lgN = p.degree_bits + p.rate_bits, ncap = 4u << p.cap_height;
+    const size_t N = size_t(1) << lgN, hash_bytes = p.hasher == GL_HASHER_KECCAK ? 25 : 32;
+    size_t per_query = 0, final_len = size_t(1) << p.degree_bits;
+    for (uint32_t o = 0; o < in.num_oracles; o++) per_query += 8 * (size_t)(in.oracle_num_polys[o] + glfri::salt_of(p, in, o)) + 1 + (lgN - p.cap_height) * hash_bytes;
+    for (uint32_t r = 0, lg = lgN; r < p.num_fri_rounds; r++) {
+        lg -= p.fri_arity_bits[r]; final_len >>= p.fri_arity_bits[r];
+        per_query += 8 * (size_t(2) << p.fri_arity_bits[r]) + 1 + (lg - p.cap_height) * hash_bytes;
+    }
+    const size_t size = (size_t)p.num_fri_rounds * (ncap / 4) * hash_bytes + per_query * p.num_query_rounds + 16 * final_len + 8;
+    *num_bytes = size;
+    if (!h_out) return GL_OK;                          // the size alone: nothing ran, the challenger is where it was
+    GL_REQUIRE(cap_bytes >= size, GL_ERR_ARG, "gl_prove_openings: output too small");
+    HostChallenger& ch = challenger->ch;
+    const gl2_t alpha = ch.challenge_ext();
+    const gl_t alpha_w[2] = {alpha.a, alpha.b};
+    gl_fri* fri_raw = nullptr;
+    GL_TRY(fri_combine_instance(ctx, params, instance, batches, alpha_w, &fri_raw));
+    std::unique_ptr<gl_fri, void (*)(gl_fri*)> fri(fri_raw, gl_fri_free);
+    std::vector<uint8_t> o;
+    o.reserve(size);
+    std::vector<gl_t> cap(ncap);
+    for (unsigned r = 0; r < p.num_fri_rounds; r++) {
+        GL_TRY(gl_fri_commit_round(fri.get(), cap.data()));
+        put_hashes(o, p.hasher, cap.data(), ncap / 4);
+        ch.observe_hashes(p.hasher, cap.data(), ncap / 4);
+        const gl2_t beta = ch.challenge_ext();
+        const gl_t beta_w[2] = {beta.a, beta.b};
+        GL_TRY(gl_fri_fold(fri.get(), beta_w));
+    }
+    size_t fin_words = 0;
+    GL_TRY(gl_fri_final_poly(fri.get(), nullptr, 0, &fin_words));
+    std::vector<gl_t> fin_il(fin_words);
+    GL_TRY(gl_fri_final_poly(fri.get(), fin_il.data(), fin_il.size(), &fin_words));
+    ch.observe_many(fin_il.data(), fin_il.size());
+    gl_t pow_witness = 0;
+    GL_TRY(gl_pow_grind_h(ctx, p.hasher, ch.state, ch.in, (uint32_t)ch.nin, p.proof_of_work_bits, &pow_witness));
+    ch.observe(pow_witness);
+    const gl_t pow_response = ch.challenge();
+    GL_REQUIRE(pow_response == 0 || (uint32_t)__builtin_clzll(pow_response) >= p.proof_of_work_bits, GL_ERR_INTERNAL, "PoW response mismatch");
+    std::vector<uint32_t> x_index(p.num_query_rounds);
+    for (auto& x : x_index) x = (uint32_t)(ch.challenge() % (uint64_t)N);
+    GL_TRY(fri_query_blob(fri.get(), x_index.data(), p.num_query_rounds, o));
+    put_words(o, fin_il.data(), fin_il.size());
+    put_u64(o, pow_witness);
+    GL_REQUIRE(o.size() == size, GL_ERR_INTERNAL, "gl_prove_openings: the proof is not as long as its parameters say");
+    memcpy(h_out, o.data(), size);
     return GL_OK;
 } catch (...) { return gl_caught(); }
 

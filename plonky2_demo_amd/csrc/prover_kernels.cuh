@@ -903,6 +903,119 @@ __global__ void k_div_linear_apply(const gl_t* ca, const gl_t* cb, uint32_t n, u
     }
 }
 
+// ---- the same two steps for any FriInstanceInfo (fri/structure.rs): every opening point in one pass ---------------------
+// A column opened at several points is read once.  cols: the DISTINCT columns of the instance; wts [ncols][B][2]: per column and
+// batch the sum of the powers of alpha the column takes in that batch (zero: the column is not in the batch; the table is indexed by
+// the wave's column only, so the loads and the branch are scalar).  B accumulator pairs per coefficient; otherwise k_fri_combine's
+// shape: 64 consecutive coefficients per workgroup, each of the four waves a quarter of the columns, the quarters added through LDS.
+// out: canonical planes [B][2][n].
+#define GLF_MAX_POINTS 4
+struct GlFriPoints { gl_t z[GLF_MAX_POINTS][2]; gl_t scale[GLF_MAX_POINTS][2]; };      // per batch: the point, and the power of alpha its quotient takes
+template <int B>
+__global__ __launch_bounds__(256) void k_fri_combine_points(const gl_t* const* __restrict__ cols, const gl_t* __restrict__ wts, uint32_t ncols, uint32_t n,
+                                                            gl_t* __restrict__ out) {
+    __shared__ gl_t sa[4][B][64], sb[4][B][64];
+    const uint32_t ii = threadIdx.x & 63, g = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t i = blockIdx.x * 64 + ii;
+    gl_t a[B], b[B];
+#pragma unroll
+    for (int t = 0; t < B; t++) a[t] = b[t] = 0;
+    if (i < n) {
+        const uint32_t per = (ncols + 3) / 4, j0 = g * per, j1 = (j0 + per < ncols) ? j0 + per : ncols;
+        for (uint32_t j = j0; j < j1; j++) {
+            const gl_t c = cols[j][i];
+            const gl_t* w = wts + (size_t)j * (2 * B);
+#pragma unroll
+            for (int t = 0; t < B; t++) {
+                const gl_t wa = w[2 * t], wb = w[2 * t + 1];
+                if (wa | wb) { a[t] = gl_mul_add(a[t], c, wa); b[t] = gl_mul_add(b[t], c, wb); }
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < B; t++) { sa[g][t][ii] = a[t]; sb[g][t][ii] = b[t]; }
+    __syncthreads();
+    if (g == 0 && i < n) {
+#pragma unroll
+        for (int t = 0; t < B; t++) {
+            out[(size_t)(2 * t) * n + i] = gl_canon(gl_add(gl_add(sa[0][t][ii], sa[1][t][ii]), gl_add(sa[2][t][ii], sa[3][t][ii])));
+            out[(size_t)(2 * t + 1) * n + i] = gl_canon(gl_add(gl_add(sb[0][t][ii], sb[1][t][ii]), gl_add(sb[2][t][ii], sb[3][t][ii])));
+        }
+    }
+}
+// the point of batch blockIdx.y out of the kernel argument: selects over constant indices (an index computed at run time would put the
+// table into private memory)
+__device__ __forceinline__ gl2_t glf_point(const GlFriPoints& pt, uint32_t bt) {
+    gl_t za = pt.z[0][0], zb = pt.z[0][1];
+#pragma unroll
+    for (int t = 1; t < GLF_MAX_POINTS; t++) if (bt == (uint32_t)t) { za = pt.z[t][0]; zb = pt.z[t][1]; }
+    return gl2_make(za, zb);
+}
+// k_div_linear_heads / _carries with a batch dimension: blockIdx.y = batch; F planes [B][2][n], heads [B][nseg][2]
+__global__ void k_div_points_heads(const gl_t* F, uint32_t n, uint32_t seg, GlFriPoints pt, gl_t* heads) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x, nseg = (n + seg - 1) / seg, bt = blockIdx.y;
+    if (s >= nseg) return;
+    const gl2_t z = glf_point(pt, bt);
+    const gl_t* ca = F + (size_t)(2 * bt) * n;
+    const gl_t* cb = ca + n;
+    const uint32_t lo = s * seg, hi = (lo + seg < n) ? lo + seg : n;
+    gl2_t acc = gl2_make(0, 0);
+    for (uint32_t k = hi; k > lo; k--) acc = gl2_add(gl2_mul(acc, z), gl2_make(ca[k - 1], cb[k - 1]));
+    heads[2 * ((size_t)bt * nseg + s)] = acc.a; heads[2 * ((size_t)bt * nseg + s) + 1] = acc.b;
+}
+__global__ __launch_bounds__(1024) void k_div_points_carries(gl_t* heads, uint32_t n, uint32_t seg, GlFriPoints pt) {
+    __shared__ gl_t La[1024], Lb[1024], Za[1024], Zb[1024];
+    const uint32_t s = threadIdx.x, nseg = (n + seg - 1) / seg, bt = blockIdx.y;
+    const gl2_t z = glf_point(pt, bt);
+    heads += 2 * (size_t)bt * nseg;
+    gl2_t L = gl2_make(0, 0), Z = gl2_make(1, 0);
+    if (s < nseg) {
+        const uint32_t lo = s * seg, len = (lo + seg < n) ? seg : n - lo;
+        L = gl2_make(heads[2 * s], heads[2 * s + 1]);
+        Z = gl2_exp(z, len);
+    }
+    La[s] = L.a; Lb[s] = L.b; Za[s] = Z.a; Zb[s] = Z.b;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {
+        gl2_t L2 = gl2_make(0, 0), Z2 = gl2_make(1, 0);
+        const bool has = s + d < 1024;
+        if (has) { L2 = gl2_make(La[s + d], Lb[s + d]); Z2 = gl2_make(Za[s + d], Zb[s + d]); }
+        __syncthreads();
+        if (has) {      // (L, Z) o (L2, Z2) = (L + Z L2, Z Z2)
+            L = gl2_add(L, gl2_mul(Z, L2));
+            Z = gl2_mul(Z, Z2);
+            La[s] = L.a; Lb[s] = L.b; Za[s] = Z.a; Zb[s] = Z.b;
+        }
+        __syncthreads();
+    }
+    if (s < nseg) {
+        gl_t ca = 0, cb = 0;
+        if (s + 1 < nseg) { ca = La[s + 1]; cb = Lb[s + 1]; }
+        heads[2 * s] = gl_canon(ca); heads[2 * s + 1] = gl_canon(cb);
+    }
+}
+// k_div_linear_apply for all batches at once: one thread runs the B recurrences of its segment side by side and writes
+// sum_b scale_b quotient_b, each coefficient once and summed in batch order inside the thread -- no launch adds into another's output,
+// so the result does not depend on any order of execution
+template <int B>
+__global__ void k_div_points_apply(const gl_t* F, uint32_t n, uint32_t seg, GlFriPoints pt, const gl_t* carries, gl_t* qa, gl_t* qb) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x, nseg = (n + seg - 1) / seg;
+    if (s >= nseg) return;
+    const uint32_t lo = s * seg, hi = (lo + seg < n) ? lo + seg : n;
+    gl2_t b[B];
+#pragma unroll
+    for (int t = 0; t < B; t++) b[t] = gl2_make(carries[2 * ((size_t)t * nseg + s)], carries[2 * ((size_t)t * nseg + s) + 1]);
+    for (uint32_t k = hi; k > lo; k--) {
+        gl2_t q = gl2_make(0, 0);
+#pragma unroll
+        for (int t = 0; t < B; t++) {
+            q = gl2_add(q, gl2_mul(b[t], gl2_make(pt.scale[t][0], pt.scale[t][1])));      // quotient_t[k-1] = b_k of batch t
+            b[t] = gl2_add(gl2_mul(b[t], gl2_make(pt.z[t][0], pt.z[t][1])), gl2_make(F[(size_t)(2 * t) * n + k - 1], F[(size_t)(2 * t + 1) * n + k - 1]));
+        }
+        qa[k - 1] = gl_canon(q.a); qb[k - 1] = gl_canon(q.b);
+    }
+}
+
 // ---- FRI fold: out[k] = sum_{i < arity} beta^i in[arity k + i]   (fri/prover.rs:94-103, plonk_common.rs:116-128) ------
 __global__ __launch_bounds__(256) void k_fri_fold(const gl_t* ia, const gl_t* ib, uint32_t n_out, uint32_t arity, gl_t ba, gl_t bb, gl_t* oa, gl_t* ob) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;

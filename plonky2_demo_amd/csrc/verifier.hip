@@ -9,6 +9,7 @@
 // functions of their own (verify_stage.hpp): the batch verifier (batch_verify.hip) runs the same ones and gives the queries to the device.
 #include "context.hpp"
 #include "host_circuit.hpp"
+#include "fri_instance.hpp"
 #include "verify_stage.hpp"
 
 namespace {
@@ -38,6 +39,27 @@ bool path_opens_to_cap(uint32_t hasher, const gl_t* leaf, size_t leaf_len, size_
     if (index >= cap_len) return false;
     for (int k = 0; k < 4; k++) if (cur[k] != (hasher == GL_HASHER_KECCAK ? cap[4 * index + k] : gl_canon(cap[4 * index + k]))) return false;
     return true;
+}
+
+// compute_evaluation (fri/verifier.rs:21-47): the degree < arity interpolant through the coset of `subgroup_x`, at beta; `evals`: the
+// step's 2^ab extension values (a, b) in bit-reversed order, `within` = x_index_within_coset
+gl2_t compute_evaluation(gl_t subgroup_x, size_t within, unsigned ab, const gl_t* evals, gl2_t beta) {
+    const size_t arity = size_t(1) << ab;
+    const gl_t g = glhost::root_of_unity(ab);
+    size_t wrev = 0;
+    for (unsigned i = 0; i < ab; i++) wrev |= ((within >> i) & 1) << (ab - 1 - i);
+    const gl_t start = gl_canon(gl_mul(subgroup_x, gl_exp(g, arity - wrev)));      // coset_start = x * g^{-rev(within)}
+    std::vector<gl_t> pts(arity);
+    { gl_t y = 1; for (size_t k = 0; k < arity; k++) { pts[k] = gl_canon(gl_mul(start, y)); y = gl_mul(y, g); } }
+    E acc = e_of(0);
+    for (size_t a = 0; a < arity; a++) {
+        size_t arev = 0;
+        for (unsigned i = 0; i < ab; i++) arev |= ((a >> i) & 1) << (ab - 1 - i);      // evals are stored in bit-reversed order
+        E numer = e_of(1); gl_t denom = 1;
+        for (size_t b = 0; b < arity; b++) if (b != a) { numer = e_mul(numer, e_sub(beta, e_of(pts[b]))); denom = gl_mul(denom, gl_sub(pts[a], pts[b])); }
+        acc = e_add(acc, e_mul(gl2_make(evals[2 * arev], evals[2 * arev + 1]), e_scale(numer, gl_inv(denom))));
+    }
+    return acc;
 }
 
 // ---- the demo's gates over the extension field ----
@@ -555,22 +577,7 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
             const uint32_t slot = glverify::NUM_INITIAL_TREES + r;
             const size_t arity = size_t(1) << ab, coset = x >> ab, within = x & (arity - 1), leaf = s.leaf_at(q, slot);
             if (!e_eq(ext_at(leaf, within), eval)) return reject(GL_CHECK_FRI_CONSISTENCY);
-            // compute_evaluation (fri/verifier.rs:21-47): the degree < arity interpolant through the coset, at beta
-            const gl_t g = glhost::root_of_unity(ab);
-            size_t wrev = 0;
-            for (unsigned i = 0; i < ab; i++) wrev |= ((within >> i) & 1) << (ab - 1 - i);
-            const gl_t start = gl_canon(gl_mul(subgroup_x, gl_exp(g, arity - wrev)));      // coset_start = x * g^{-rev(within)}
-            std::vector<gl_t> pts(arity);
-            { gl_t y = 1; for (size_t k = 0; k < arity; k++) { pts[k] = gl_canon(gl_mul(start, y)); y = gl_mul(y, g); } }
-            E acc = e_of(0);
-            for (size_t a = 0; a < arity; a++) {
-                size_t arev = 0;
-                for (unsigned i = 0; i < ab; i++) arev |= ((a >> i) & 1) << (ab - 1 - i);      // evals are stored in bit-reversed order
-                E numer = e_of(1); gl_t denom = 1;
-                for (size_t b = 0; b < arity; b++) if (b != a) { numer = e_mul(numer, e_sub(ch.fri_betas[r], e_of(pts[b]))); denom = gl_mul(denom, gl_sub(pts[a], pts[b])); }
-                acc = e_add(acc, e_mul(ext_at(leaf, arev), e_scale(numer, gl_inv(denom))));
-            }
-            eval = acc;
+            eval = compute_evaluation(subgroup_x, within, ab, &T[leaf], ch.fri_betas[r]);
             if (!path_opens_to_cap(d.hasher, &T[leaf], s.slot_leaf_len[slot], coset, &T[s.sib_at(q, slot)], s.slot_nsib[slot], &T[s.o_fcaps + (size_t)r * 4 * ncap], ncap)) return reject(GL_CHECK_STEP_MERKLE);
             for (unsigned i = 0; i < ab; i++) subgroup_x = gl_sqr(subgroup_x);
             x = coset;
@@ -588,4 +595,125 @@ extern "C" int gl_host_circuit_verify(const gl_host_circuit* hc, const uint64_t*
                                       const uint8_t* proof_bytes, size_t num_bytes) try {
     GL_REQUIRE(hc, GL_ERR_ARG, "gl_host_circuit_verify: null circuit");
     return gl_verify(&hc->hc.desc, constants_sigmas_cap, circuit_digest, proof_bytes, num_bytes);
+} catch (...) { return gl_caught(); }
+
+// ---- verify_fri_proof for any FriInstanceInfo (fri/verifier.rs:62-241, fri/challenges.rs:24-64, fri/validate_shape.rs) ----
+// The FriProof alone, in write_fri_proof order (util/serialization/mod.rs:1568-1582), on the caller's Challenger.  gl_verify above keeps
+// its own query loop over the Plonk layout; the two share path_opens_to_cap, compute_evaluation, the Cursor and the rejection table.
+extern "C" int gl_verify_openings(const gl_fri_params* params, const gl_fri_instance* instance, const uint64_t* caps, const uint64_t* openings,
+                                  gl_challenger* challenger, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check) try {
+    if (check) *check = GL_CHECK_ACCEPTED;
+    GL_TRY(glfri::check(params, instance, false));
+    GL_REQUIRE(caps && openings && challenger && proof_bytes, GL_ERR_ARG, "gl_verify_openings: null argument");
+    const gl_fri_params& p = *params; const gl_fri_instance& in = *instance;
+    GL_REQUIRE(challenger->ch.hasher == p.hasher, GL_ERR_ARG, "gl_verify_openings: the challenger runs under another hasher than the params'");
+    const uint32_t hasher = p.hasher, no = in.num_oracles, B = in.num_batches, nq = p.num_query_rounds;
+    const unsigned lgN = p.degree_bits + p.rate_bits;
+    const size_t N = size_t(1) << lgN, ncap = size_t(1) << p.cap_height;
+    size_t final_len = size_t(1) << p.degree_bits;
+    for (unsigned r = 0; r < p.num_fri_rounds; r++) final_len >>= p.fri_arity_bits[r];
+    if (!glhost::hashes_well_formed(hasher, caps, no * ncap)) return reject(GL_CHECK_VERIFIER_DATA, check);
+
+    // ---- decode: words canonical (read_field takes a word >= p mod p), 25-byte hashes in four-word slots ----
+    Cursor cur(proof_bytes, num_bytes);
+    std::vector<gl_t> T;
+    T.reserve(num_bytes / 8 + 8);
+    auto words = [&](size_t k) { size_t at = T.size(); for (size_t i = 0; i < k && cur.ok; i++) T.push_back(gl_canon(cur.u64())); return at; };
+    auto hashes = [&](size_t k) {
+        if (hasher != GL_HASHER_KECCAK) return words(4 * k);
+        size_t at = T.size();
+        for (size_t i = 0; i < k && cur.ok; i++) { for (int w = 0; w < 3; w++) T.push_back(cur.u64()); T.push_back(cur.u8()); }
+        return at;
+    };
+    struct Query { size_t leaf[GL_MAX_FRI_ORACLES], sib[GL_MAX_FRI_ORACLES], step_leaf[8], step_sib[8]; };
+    std::vector<Query> queries(nq);
+    size_t leaf_len[GL_MAX_FRI_ORACLES];
+    for (uint32_t o = 0; o < no; o++) leaf_len[o] = (size_t)in.oracle_num_polys[o] + glfri::salt_of(p, in, o);
+    const size_t o_fcaps = hashes((size_t)p.num_fri_rounds * ncap);
+    for (uint32_t q = 0; q < nq && cur.ok; q++) {
+        Query& Q = queries[q];
+        unsigned init_nsib[GL_MAX_FRI_ORACLES];
+        for (uint32_t o = 0; o < no; o++) {
+            Q.leaf[o] = words(leaf_len[o]);
+            init_nsib[o] = cur.u8(); Q.sib[o] = hashes(init_nsib[o]);
+        }
+        unsigned lg_cur = lgN;
+        for (unsigned r = 0; r < p.num_fri_rounds; r++) {
+            Q.step_leaf[r] = words(size_t(2) << p.fri_arity_bits[r]);
+            const unsigned nsib = cur.u8(); Q.step_sib[r] = hashes(nsib);
+            lg_cur -= p.fri_arity_bits[r];
+            if (cur.ok && nsib + p.cap_height != lg_cur) return reject(GL_CHECK_STEP_PATH_LENGTH, check);
+        }
+        for (uint32_t o = 0; o < no && cur.ok; o++)
+            if (init_nsib[o] + p.cap_height != lgN) return reject(GL_CHECK_INITIAL_PATH_LENGTH, check);
+    }
+    const size_t o_final = words(2 * final_len);
+    const gl_t pow_witness = gl_canon(cur.u64());
+    if (!cur.ok) return reject(GL_CHECK_TRUNCATED, check);
+    if (cur.pos != num_bytes) return reject(GL_CHECK_LENGTH, check);
+    auto ext_at = [&](size_t off, size_t i) { return gl2_make(T[off + 2 * i], T[off + 2 * i + 1]); };
+
+    // ---- challenges (fri/challenges.rs:24-64) ----
+    glhost::HostChallenger& tr = challenger->ch;
+    const E alpha = tr.challenge_ext();
+    E betas[8];
+    for (unsigned r = 0; r < p.num_fri_rounds; r++) { tr.observe_hashes(hasher, &T[o_fcaps + (size_t)r * 4 * ncap], ncap); betas[r] = tr.challenge_ext(); }
+    tr.observe_many(&T[o_final], 2 * final_len);
+    tr.observe(pow_witness);
+    const gl_t pow_response = tr.challenge();
+    std::vector<size_t> x_index(nq);
+    for (auto& x : x_index) x = tr.challenge() % (uint64_t)N;
+    if (pow_response != 0 && (unsigned)__builtin_clzll(pow_response) < p.proof_of_work_bits) return reject(GL_CHECK_POW, check);
+
+    // PrecomputedReducedOpenings (fri/verifier.rs:243-260): per batch Horner in alpha over its opened values; alpha^len of each batch
+    E red[GL_MAX_FRI_BATCHES], alpha_len[GL_MAX_FRI_BATCHES], point[GL_MAX_FRI_BATCHES];
+    size_t first[GL_MAX_FRI_BATCHES + 1] = {0};
+    for (uint32_t b = 0; b < B; b++) {
+        first[b + 1] = first[b] + in.batch_len[b];
+        E acc = e_of(0), pw = e_of(1);
+        for (size_t j = first[b + 1]; j-- > first[b];) {
+            acc = e_add(e_mul(acc, alpha), gl2_make(gl_canon(openings[2 * j]), gl_canon(openings[2 * j + 1])));
+            pw = e_mul(pw, alpha);
+        }
+        red[b] = acc; alpha_len[b] = pw; point[b] = glfri::point_of(in, b);
+    }
+
+    // ---- the queries (fri/verifier.rs:163-241) ----
+    const gl_t wN = glhost::root_of_unity(lgN);
+    for (uint32_t q = 0; q < nq; q++) {
+        const Query& Q = queries[q];
+        size_t x = x_index[q];
+        for (uint32_t o = 0; o < no; o++)
+            if (!path_opens_to_cap(hasher, &T[Q.leaf[o]], leaf_len[o], x, &T[Q.sib[o]], lgN - p.cap_height, caps + (size_t)o * 4 * ncap, ncap))
+                return reject(GL_CHECK_INITIAL_MERKLE, check);
+        size_t rev = 0;
+        for (unsigned i = 0; i < lgN; i++) rev |= ((x >> i) & 1) << (lgN - 1 - i);
+        gl_t subgroup_x = gl_canon(gl_mul(GL_MULT_GENERATOR, gl_exp(wN, rev)));
+        // fri_combine_initial (fri/verifier.rs:122-161): a polynomial's index is below its oracle's column count, so only the unsalted
+        // prefix of a leaf is read (unsalted_eval)
+        const E sx = e_of(subgroup_x);
+        E eval = e_of(0);
+        for (uint32_t b = 0; b < B; b++) {
+            E h = e_of(0);
+            for (size_t j = first[b + 1]; j-- > first[b];) h = e_add(e_mul(h, alpha), e_of(T[Q.leaf[in.polys[2 * j]] + in.polys[2 * j + 1]]));
+            eval = e_add(e_mul(eval, alpha_len[b]), e_mul(e_sub(h, red[b]), gl2_inv(e_sub(sx, point[b]))));
+        }
+        unsigned lg_cur = lgN;
+        for (unsigned r = 0; r < p.num_fri_rounds; r++) {
+            const unsigned ab = p.fri_arity_bits[r];
+            const size_t arity = size_t(1) << ab, coset = x >> ab, within = x & (arity - 1), leaf = Q.step_leaf[r];
+            lg_cur -= ab;
+            if (!e_eq(ext_at(leaf, within), eval)) return reject(GL_CHECK_FRI_CONSISTENCY, check);
+            eval = compute_evaluation(subgroup_x, within, ab, &T[leaf], betas[r]);
+            if (!path_opens_to_cap(hasher, &T[leaf], 2 * arity, coset, &T[Q.step_sib[r]], lg_cur - p.cap_height, &T[o_fcaps + (size_t)r * 4 * ncap], ncap))
+                return reject(GL_CHECK_STEP_MERKLE, check);
+            for (unsigned i = 0; i < ab; i++) subgroup_x = gl_sqr(subgroup_x);
+            x = coset;
+        }
+        E fin = e_of(0);
+        const E sxf = e_of(gl_canon(subgroup_x));
+        for (size_t i = final_len; i-- > 0;) fin = e_add(e_mul(fin, sxf), ext_at(o_final, i));
+        if (!e_eq(fin, eval)) return reject(GL_CHECK_FINAL_POLY, check);
+    }
+    return GL_OK;
 } catch (...) { return gl_caught(); }

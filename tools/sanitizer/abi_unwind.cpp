@@ -191,6 +191,36 @@ int main(int argc, char** argv) {
           [&] { return gl_verifier_only_from_bytes_h(0, only.data(), only.size(), &cap_height, cap_back.data(), cap_back.size(), dig_back, &used); }, yes,
           [&] { return fnv(cap_back.data(), cap_back.size() * 8, fnv(dig_back, 32, cap_height)); }, nothing);
     sweep("gl_verify_bytes", nothing, [&] { return gl_verify_bytes(vd.data(), vd.size(), pr.data(), pr.size()); }, yes, [] { return uint64_t(1); }, nothing);
+    {   // gl_verify_openings on a FriProof assembled here: one oracle holding the constant polynomial c (n = 8, rate_bits 1, cap_height 1),
+        // opened at one point.  Its quotient is zero, so the codeword, the one reduction (arity 8) and the final polynomial are zero; every
+        // leaf of the initial tree is [c], every node of a level the same hash.
+        gl_fri_params fp = {};
+        fp.degree_bits = 3; fp.rate_bits = 1; fp.cap_height = 1; fp.num_query_rounds = 2; fp.num_fri_rounds = 1; fp.fri_arity_bits[0] = 3;
+        const uint32_t polys[2] = {0, 0};
+        gl_fri_instance fi = {};
+        fi.num_oracles = 1; fi.oracle_num_polys[0] = 1; fi.num_batches = 1; fi.points[0][0] = 5; fi.batch_len[0] = 1; fi.polys = polys;
+        const uint64_t c = 0x1234567, leaf[1] = {c}, opening[2] = {c, 0}, zeros[16] = {0};
+        uint64_t level[4][4], step_leaf[4];
+        if (gl_hash_or_noop_host(0, leaf, 1, 1, level[0]) != GL_OK || gl_hash_or_noop_host(0, zeros, 1, 16, step_leaf) != GL_OK) abort();
+        for (int l = 0; l < 3; l++) if (gl_two_to_one_host(0, level[l], level[l], 1, level[l + 1]) != GL_OK) abort();
+        uint64_t caps[8];
+        for (int i = 0; i < 8; i++) caps[i] = level[3][i % 4];
+        std::vector<uint8_t> fproof;
+        auto word = [&](uint64_t v) { for (int i = 0; i < 8; i++) fproof.push_back((uint8_t)(v >> (8 * i))); };
+        for (int i = 0; i < 8; i++) word(step_leaf[i % 4]);                       // the commit cap: both leaves of the zero codeword's tree
+        for (int q = 0; q < 2; q++) {
+            word(c); fproof.push_back(3);
+            for (int l = 0; l < 3; l++) for (int k = 0; k < 4; k++) word(level[l][k]);
+            for (int i = 0; i < 16; i++) word(0);
+            fproof.push_back(0);
+        }
+        word(0); word(0); word(0);                                                // the final polynomial (one coefficient) and the PoW witness
+        gl_challenger* ch = nullptr;
+        uint32_t code = 99;
+        sweep("gl_verify_openings", [&] { ch = gl_challenger_new_h(0); if (!ch) abort(); code = 99; },
+              [&] { return gl_verify_openings(&fp, &fi, caps, opening, ch, fproof.data(), fproof.size(), &code); }, yes, [&] { return uint64_t(code); },
+              [&] { gl_challenger_free(ch); ch = nullptr; });
+    }
 
     // ---- the context's entry points over the stub runtime (the stub's own allocations on the calling thread fail in turn too) ----
     gl_ctx* ctx = nullptr;
