@@ -5,8 +5,13 @@
 // SIMD each; the 32-bit add / sub / carry / select / logic instructions take ~2.4 -- but only in runs of their own kind -- and
 // a VALU instruction that reads a carry or mask another VALU instruction wrote needs two instructions in between (else s_nop).
 // One product is 4 multiply-adds for the 128-bit result, 3 carry adds, 1 multiply-add for lo + hl * EPS (the multiply by
-// EPS = 2^32 - 1, the 64-bit add and its carry in one instruction), 2 borrow subtractions for - hh and one two-sided fix-up
-// built from the two carry masks on the scalar unit: 15 instructions instead of the compiler's 24 -- and with THREE
+// EPS = 2^32 - 1, the 64-bit add and its carry in one instruction), 2 borrow subtractions for - hh and a fix-up from the two
+// carry masks, combined on the scalar unit.  CANON = false (the S-boxes): a select and a multiply-add (+ EPS where the fold
+// carried and - hh did not borrow), 12 instructions instead of the compiler's 24; the other side of the fix-up (- EPS where
+// - hh borrowed and the fold did not carry: one product in ~2^32) sits behind a wave-uniform scalar branch, where the two-sided
+// tail (2 selects, a subtraction, a 64-bit add) runs for the whole wave.  CANON = true (the butterflies' twiddle products) runs
+// that two-sided tail on every product, 15 instructions with its compare: with the branch in the NTT kernels the 2^21
+// transforms came out wrong now and then inside the whole GPU suite, cause not found (profiles/README.md).  With THREE
 // independent products interleaved the carry chains need no wait states and the cheap instructions form runs.
 //
 // Same function as gl_mul (field/src/goldilocks_field.rs:355-369 reduce128): any u64 representatives in, a u64
@@ -99,11 +104,13 @@ __device__ __forceinline__ void glx_mul3(gl_t aA, gl_t bA, gl_t aB, gl_t bB, gl_
           [w3A] "v"(w3A), [cmA] "s"(cmA), [w3B] "v"(w3B), [cmB] "s"(cmB), [w3C] "v"(w3C), [cmC] "s"(cmC)
         : "vcc");
     const gl_t yA = glx_mk64(y0A, y1A), yB = glx_mk64(y0B, y1B), yC = glx_mk64(y0C, y1C);
-    u32 f0A, f1A, f0B, f1B, f0C, f1C;
-    uint64_t tA, tB, tC;
     // N = b & ~c: subtract EPS.  P = c & ~b: add EPS.  CANON: y >= p and nothing subtracted: add EPS as well (= y - p mod 2^64).
-    // (f1:f0) = +EPS, -EPS (mod 2^64) or 0; the scalar unit combines the masks while the vector unit is busy elsewhere.  The sum
-    // y + f is one 64-bit add (v_lshl_add_u64), left to the compiler.
+    // The scalar unit combines the masks while the vector unit is busy elsewhere.
+    if constexpr (CANON) {
+        // the two-sided tail on every product: (f1:f0) = +EPS, -EPS (mod 2^64) or 0, and the sum y + f is one 64-bit add
+        // (v_lshl_add_u64), left to the compiler
+        u32 f0A, f1A, f0B, f1B, f0C, f1C;
+        uint64_t tA, tB, tC;
 #define GLX_MUL3_TAIL                                                     \
         "v_cndmask_b32_e64 %[f1A], 0, -1, %[tA]\n\t"                      \
         "v_cndmask_b32_e64 %[f1B], 0, -1, %[tB]\n\t"                      \
@@ -114,7 +121,6 @@ __device__ __forceinline__ void glx_mul3(gl_t aA, gl_t bA, gl_t aB, gl_t bB, gl_
         "v_sub_u32 %[f0A], %[f0A], %[f1A]\n\t"                            \
         "v_sub_u32 %[f0B], %[f0B], %[f1B]\n\t"                            \
         "v_sub_u32 %[f0C], %[f0C], %[f1C]"
-    if constexpr (CANON) {
         uint64_t gA, gB, gC;
         asm("v_cmp_gt_u64_e64 %[gA], %[yA], %[pm1]\n\t"
             "v_cmp_gt_u64_e64 %[gB], %[yB], %[pm1]\n\t"
@@ -139,21 +145,47 @@ __device__ __forceinline__ void glx_mul3(gl_t aA, gl_t bA, gl_t aB, gl_t bB, gl_
               [bwA] "+s"(bwA), [bwB] "+s"(bwB), [bwC] "+s"(bwC)
             : [cA] "s"(cA), [cB] "s"(cB), [cC] "s"(cC)
             : "scc");
-    } else {
-        asm("s_andn2_b64 %[tA], %[bwA], %[cA]\n\t"
-            "s_andn2_b64 %[tB], %[bwB], %[cB]\n\t"
-            "s_andn2_b64 %[tC], %[bwC], %[cC]\n\t"
-            "s_andn2_b64 %[bwA], %[cA], %[bwA]\n\t"
-            "s_andn2_b64 %[bwB], %[cB], %[bwB]\n\t"
-            "s_andn2_b64 %[bwC], %[cC], %[bwC]\n\t"
-            GLX_MUL3_TAIL
-            : [f0A] "=&v"(f0A), [f1A] "=&v"(f1A), [f0B] "=&v"(f0B), [f1B] "=&v"(f1B), [f0C] "=&v"(f0C), [f1C] "=&v"(f1C),
-              [tA] "=&s"(tA), [tB] "=&s"(tB), [tC] "=&s"(tC), [bwA] "+s"(bwA), [bwB] "+s"(bwB), [bwC] "+s"(bwC)
-            : [cA] "s"(cA), [cB] "s"(cB), [cC] "s"(cC)
-            : "scc");
-    }
 #undef GLX_MUL3_TAIL
-    rA = yA + glx_mk64(f0A, f1A); rB = yB + glx_mk64(f0B, f1B); rC = yC + glx_mk64(f0C, f1C);
+        rA = yA + glx_mk64(f0A, f1A); rB = yB + glx_mk64(f0B, f1B); rC = yC + glx_mk64(f0C, f1C);
+    } else {
+        // N needs z < hh < 2^32: for the S-boxes about one product in 2^32 (the reference puts this borrow behind a branch_hint(),
+        // goldilocks_field.rs:355-369).  So the wave tests the three N masks (scalar, wave-uniform): none set -> r = y + EPS * P, one
+        // select and one multiply-add per product; any set -> the two-sided tail, a cold block.  With N = 0 that tail adds (0:EPS)
+        // under P as well: the same 64-bit word either way.
+        uint64_t nA, nB, nC, pA, pB, pC;
+        asm("s_andn2_b64 %[nA], %[bwA], %[cA]\n\t"
+            "s_andn2_b64 %[nB], %[bwB], %[cB]\n\t"
+            "s_andn2_b64 %[nC], %[bwC], %[cC]\n\t"
+            "s_andn2_b64 %[pA], %[cA], %[bwA]\n\t"
+            "s_andn2_b64 %[pB], %[cB], %[bwB]\n\t"
+            "s_andn2_b64 %[pC], %[cC], %[bwC]"
+            : [nA] "=&s"(nA), [nB] "=&s"(nB), [nC] "=&s"(nC), [pA] "=&s"(pA), [pB] "=&s"(pB), [pC] "=&s"(pC)
+            : [bwA] "s"(bwA), [bwB] "s"(bwB), [bwC] "s"(bwC), [cA] "s"(cA), [cB] "s"(cB), [cC] "s"(cC)
+            : "scc");
+        u32 eA, eB, eC;
+        asm("v_cndmask_b32_e64 %[eA], 0, 1, %[pA]\n\t"
+            "v_cndmask_b32_e64 %[eB], 0, 1, %[pB]\n\t"
+            "v_cndmask_b32_e64 %[eC], 0, 1, %[pC]"
+            : [eA] "=&v"(eA), [eB] "=&v"(eB), [eC] "=&v"(eC)
+            : [pA] "s"(pA), [pB] "s"(pB), [pC] "s"(pC));
+        rA = glx_add_eps_if(yA, eA); rB = glx_add_eps_if(yB, eB); rC = glx_add_eps_if(yC, eC);
+        // (an if without an else: the fast tail above is not worth a branch around it, and the wave falls through the test)
+        if (__builtin_expect((nA | nB | nC) != 0, 0)) {
+            u32 f0A, f1A, f0B, f1B, f0C, f1C;
+            asm("v_cndmask_b32_e64 %[f1A], 0, -1, %[nA]\n\t"
+                "v_cndmask_b32_e64 %[f1B], 0, -1, %[nB]\n\t"
+                "v_cndmask_b32_e64 %[f1C], 0, -1, %[nC]\n\t"
+                "v_cndmask_b32_e64 %[f0A], 0, -1, %[pA]\n\t"
+                "v_cndmask_b32_e64 %[f0B], 0, -1, %[pB]\n\t"
+                "v_cndmask_b32_e64 %[f0C], 0, -1, %[pC]\n\t"
+                "v_sub_u32 %[f0A], %[f0A], %[f1A]\n\t"
+                "v_sub_u32 %[f0B], %[f0B], %[f1B]\n\t"
+                "v_sub_u32 %[f0C], %[f0C], %[f1C]"
+                : [f0A] "=&v"(f0A), [f1A] "=&v"(f1A), [f0B] "=&v"(f0B), [f1B] "=&v"(f1B), [f0C] "=&v"(f0C), [f1C] "=&v"(f1C)
+                : [nA] "s"(nA), [nB] "s"(nB), [nC] "s"(nC), [pA] "s"(pA), [pB] "s"(pB), [pC] "s"(pC));
+            rA = yA + glx_mk64(f0A, f1A); rB = yB + glx_mk64(f0B, f1B); rC = yC + glx_mk64(f0C, f1C);
+        }
+    }
 }
 
 // One product (the same arithmetic, with the wait states the lone carry chains need): for counts that are not multiples of three
@@ -188,6 +220,7 @@ __device__ __forceinline__ gl_t glx_mul(gl_t a, gl_t b) {
         "s_nop 1\n\t"
         "v_subbrev_co_u32_e64 %[y1], %[bw], 0, %[y1], vcc"
         : [y0] "+v"(y0), [y1] "+v"(y1), [bw] "=&s"(bw) : [w3] "v"(w3), [cm] "s"(cm) : "vcc");
+    // t = b & ~c (subtract EPS), bw = c & ~b (add EPS; CANON: or y >= p where nothing is subtracted)
     if constexpr (CANON) {
         const gl_t y = glx_mk64(y0, y1);
         asm("v_cmp_gt_u64_e64 %0, %1, %2" : "=s"(g) : "v"(y), "s"(GL_P - 1));
@@ -202,6 +235,22 @@ __device__ __forceinline__ gl_t glx_mul(gl_t a, gl_t b) {
             "s_andn2_b64 %[t], %[bw], %[c]\n\t"
             "s_andn2_b64 %[bw], %[c], %[bw]"
             : [t] "=&s"(t), [bw] "+s"(bw) : [c] "s"(c) : "scc");
+        // the rare t behind a wave-uniform branch, as in glx_mul3: the fast tail is computed first and overwritten in the cold block
+        asm("v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(f0) : "s"(bw));
+        gl_t r = glx_add_eps_if(glx_mk64(y0, y1), f0);
+        if (__builtin_expect(t != 0, 0)) {
+            asm("v_cndmask_b32_e64 %[f1], 0, -1, %[t]\n\t"
+                "v_cndmask_b32_e64 %[f0], 0, -1, %[bw]\n\t"
+                "v_sub_u32 %[f0], %[f0], %[f1]\n\t"
+                "v_add_co_u32 %[y0], vcc, %[y0], %[f0]\n\t"
+                "s_nop 1\n\t"
+                "v_addc_co_u32 %[y1], vcc, %[y1], %[f1], vcc"
+                : [f0] "=&v"(f0), [f1] "=&v"(f1), [y0] "+v"(y0), [y1] "+v"(y1)
+                : [t] "s"(t), [bw] "s"(bw)
+                : "vcc");
+            r = glx_mk64(y0, y1);
+        }
+        return r;
     }
     asm("v_cndmask_b32_e64 %[f1], 0, -1, %[t]\n\t"
         "v_cndmask_b32_e64 %[f0], 0, -1, %[bw]\n\t"

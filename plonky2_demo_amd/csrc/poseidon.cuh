@@ -285,7 +285,8 @@ GL_HD constexpr uint32_t psd_mds_entry(int r, int c) {
 GL_HD void psd_sbox_all(gl_t (&s)[12]) {
 #if defined(__HIP_DEVICE_COMPILE__)
     // x^7 = (x * x^2) * x^4, three words at a time: glx_mul3 interleaves three independent products so that its carry chains
-    // need no wait states
+    // need no wait states (12 instructions per product; each call tests its three borrow masks on the scalar unit and leaves
+    // the rare subtracting side of the fix-up to a cold block: 16 wave-uniform branches per layer, none taken on ordinary data)
 #pragma unroll
     for (int k = 0; k < 12; k += 3) {
         gl_t a2, b2, c2, a4, b4, c4, a3, b3, c3;
@@ -302,8 +303,8 @@ GL_HD void psd_sbox_all(gl_t (&s)[12]) {
 // Three partial rounds at once (tools/gen_poseidon_constants.py derive_groups): with d_j = sbox(x_j) - a_j the change of lane
 // 0 in round j of the group (a_j = lane 0 entering its S-box), everything else is linear, so lane 0 of the next two rounds
 // needs only row 0 of M and of M^2 applied to the group's input state, and the state after the group is M^3 (entries
-// < 2^25: still one multiply-add per 32-bit half) applied to it plus three rank-one corrections: ~910 instead of 3 x 500
-// instructions.  `s` enters and leaves with the round constants of its next round already added.
+// < 2^25: still one multiply-add per 32-bit half) applied to it plus three rank-one corrections: ~870 instead of 3 x 500
+// instructions (~910 before the lone products' fix-up became a select and a multiply-add, gl64_gfx950.cuh glx_mul).  `s` enters and leaves with the round constants of its next round already added.
 // SUBST = false: x_j = a_j (the permutation).  SUBST = true: x_j = in[j], the PoseidonGate's S-box input wires, and a[j]
 // returns the computed a_j for the constraint a_j - in[j] (gates/poseidon.rs:165-189).
 template <bool SUBST>
