@@ -241,6 +241,24 @@ def test_ntt_chunked_batches(gpu, orc):
         ctx.set_scratch_elems(1 << 24)
 
 
+def test_ntt_table_cache_in_a_fresh_context_in_a_fixed_order_of_use(gpu, orc):
+    # gl_ntt_run keeps its power tables per context (gl_ctx::get_pow_table): a table is created at the length of its first use, regrown
+    # when a longer one is asked for (the short one is parked, it may be in flight) and reused when it is long enough.  One fixed order
+    # of use in a context that has no table yet, every result against the oracle.
+    p, _ = gpu
+    ctx = p.Context(0)
+    small, big, mid = rand_field(4100, (3, 1 << 10)), rand_field(4101, (2, 1 << 16)), rand_field(4102, (3, 1 << 12))
+    lde_want = orc.lde(small, 3, threads=4)
+    assert (p.lde_onto_coset(small, 3, ctx=ctx) == lde_want).all()                   # creates the short table of the shift 7
+    assert (p.coset_fft(big, ctx=ctx) == orc.coset_fft(big)).all()                   # regrows it, parks the short one
+    assert (p.lde_onto_coset(small, 3, ctx=ctx) == lde_want).all()                   # the longer table serves the short use
+    assert (p.coset_fft(mid, ctx=ctx) == orc.coset_fft(mid)).all()
+    for batch in (4, 5):                                                             # the pass table that carries the 1/N scale, made once
+        v = rand_field(4103 + batch, (batch, 1 << 13))
+        assert (p.ifft(v, ctx=ctx) == orc.ifft(v)).all()
+    ctx.synchronize()
+
+
 # --------------------------------------------------------------------------------------- Poseidon/Merkle
 def test_poseidon_known_answers(gpu, orc, golden):
     p, ctx = gpu
@@ -613,10 +631,13 @@ def test_hand_scheduled_primitives_against_int128(gpu):
 
 
 def test_goldilocks_primitives_edge_grid_against_int128(gpu):
-    # tools/ubench/gl_prims.hip: glx_mul / glx_mul3 (both canonicalisations), add_cc / sub_cc, the accumulator folds and EVERY branch of
-    # glx_shl_c (12, 24, 32, 36, 48, 60, 72, 84) on an edge grid that holds the boundary forms of each branch (2^k for all k, p - 2^k,
-    # h 2^(96-E), low bits zero) x itself plus random words, against unsigned __int128 on the host.  (this program
-    # was outside pytest, and profiles/r02_gl_primitives.txt held FAIL rows of a development build of the 32 < E < 64 branch.)
+    # tools/ubench/gl_prims.hip, the cost bench of the primitives, checks each CANDIDATE it times first.  From gl64_gfx950.cuh those are
+    # glx_mul3<false / true> and glx_shl_c<12, 24, 32, 36, 48, 60, 72, 84> (one exponent or more per branch); the single product, add_cc /
+    # sub_cc, the accumulator folds and the canonical fix-up it checks are its own look-alikes (m_mul_t, m_add_cc, m_sub_cc, m_accred,
+    # m_reduce96, m_fix_canon), not the header's functions -- those are checked by tools/ubench/glx_check.hip (test_glx_primitives.py).
+    # Inputs: an edge grid that holds the boundary forms of each branch (2^k for all k, p - 2^k, h 2^(96-E), low bits zero) x itself plus
+    # random words, against unsigned __int128 on the host.  (this program was outside pytest, and
+    # profiles/r02_gl_primitives.txt held FAIL rows of a development build of the 32 < E < 64 branch.)
     import os, subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = os.path.join(root, "tools", "ubench", "bin", "gl_prims")

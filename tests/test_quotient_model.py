@@ -18,6 +18,9 @@ pytestmark = pytest.mark.gpu
 P = vm.P
 EDGES = [0, 1, 2, P - 1, P - 2, 2**32 - 1, 2**32, 2**32 + 1, 2**63 - 1, 2**63, P - 2**32]
 RESIDUES = [0, 5]
+# S-box inputs whose 7th power takes the cold block of the Goldilocks product (gl64_gfx950.cuh glx_mul<false> / glx_mul3<false>: subtract EPS
+# without a carry, tests/test_sbox_cold_paths.py): x x for 2^48, x^2 x^2 for 2^24, x^3 x^4 for 2^14
+SBOX_COLD = [2**48, 2**24, 2**14]
 
 
 def bit_wires(desc):
@@ -74,9 +77,11 @@ def challenge_set(name, rng):
     return CHALLENGES[name]
 
 
-def run_case(gpu, orc, desc, k, seed, kept_constants=None):
+def run_case(gpu, orc, desc, k, seed, kept_constants=None, sbox_cold=False):
     """steps 1-9 of one case: `desc` with every column free except `kept_constants` (the circuit's own constant columns, where the loader
-    checks them); residue k"""
+    checks them); residue k.  sbox_cold (a circuit with the PoseidonGate): every S-box of the gate also meets the SBOX_COLD values -- in
+    k_quotient<true> every S-box input but the first round's is a wire value, so the S-box input wire columns draw half of their targets
+    from them; the first round reads inputs + deltas + RC[0], so rows 3, 4, 5 hold value - RC[0][i] in the inputs, swap 0 and deltas 0."""
     p, ctx = gpu
     rng = np.random.Generator(np.random.PCG64(seed))
     lg_n = desc.degree_bits
@@ -89,7 +94,16 @@ def run_case(gpu, orc, desc, k, seed, kept_constants=None):
     selector_values = list(range(desc.num_gates)) + [vm.UNUSED_SELECTOR]
     t_cs = edge_targets(rng, nc + 80, n, {c: selector_values for c in range(desc.num_selectors)})
     bits = bit_wires(desc)
-    t_w = edge_targets(rng, 135, n, {c: [0, 1] for c in bits})
+    special = {c: [0, 1] for c in bits}
+    if sbox_cold:
+        assert vm.POSEIDON in set(desc.gate_types[g] for g in range(desc.num_gates)) and n >= 6
+        special.update({c: SBOX_COLD for c in vm.PSD_FULL_SBOX_WIRES + vm.PSD_PARTIAL_SBOX_WIRES})
+    t_w = edge_targets(rng, 135, n, special)
+    if sbox_cold:
+        rc0 = vm._poseidon_tables()[0][0]
+        for row, value in zip((3, 4, 5), SBOX_COLD):
+            t_w[0:12, row] = [(value - rc0[i]) % P for i in range(12)]
+            t_w[vm.PSD_WIRE_SWAP:vm.PSD_WIRE_DELTA + 4, row] = 0
     t_z = edge_targets(rng, 20 + 2 * nlp, n)
     # 3. interpolate and evaluate on H_n
     cs_values = through_points(orc, t_cs, lg_n, k)
@@ -103,13 +117,23 @@ def run_case(gpu, orc, desc, k, seed, kept_constants=None):
     # 5. the construction: one point in eight carries its intended edge value in every free column
     first_free = nc if kept_constants is not None else 0
     assert (cs[first_free:, edge_points] == t_cs[first_free:]).all() and (wires[:, edge_points] == t_w).all() and (zs[:, edge_points] == t_z).all()
+    first_round = [(value - c) % P for value in SBOX_COLD for c in vm._poseidon_tables()[0][0]] if sbox_cold else []
     for arr in (cs[first_free:], wires, zs):
-        assert np.isin(arr[:, edge_points], np.array(EDGES + selector_values, dtype=np.uint64)).all()
+        allowed = EDGES + selector_values + (SBOX_COLD + first_round if arr is wires else [])
+        assert np.isin(arr[:, edge_points], np.array(allowed, dtype=np.uint64)).all()
         assert (arr[:, edge_points[0]] == 0).all() and (arr[:, edge_points[1]] == 1).all() and (arr[:, edge_points[2]] == P - 1).all()
         others = np.delete(arr, edge_points, axis=1)
         assert np.isin(others, np.array(EDGES, dtype=np.uint64)).mean() < 0.01          # the other seven in eight are the random part
     for c in bits:
         assert {0, 1} <= set(int(v) for v in wires[c, edge_points])
+    if sbox_cold:
+        # each value sits at an edge point of a full-round and of a partial-round S-box input wire, and in front of the first round
+        rc0 = vm._poseidon_tables()[0][0]
+        for row, value in zip((3, 4, 5), SBOX_COLD):
+            assert (wires[vm.PSD_FULL_SBOX_WIRES][:, edge_points] == value).any() and (wires[vm.PSD_PARTIAL_SBOX_WIRES][:, edge_points] == value).any()
+            at = edge_points[row]
+            assert all((int(wires[i, at]) + int(wires[vm.PSD_WIRE_DELTA + i, at]) * (1 if i < 4 else 0) + rc0[i]) % P == value for i in range(12))
+            assert not wires[vm.PSD_WIRE_SWAP:vm.PSD_WIRE_DELTA + 4, at].any()
 
     def launch(ch):
         q_b = cd.quotient_polys(wires_b, zs_b, ch["pi_hash"], ch["betas"], ch["gammas"], ch["alphas"], deltas=ch["deltas"] if nlp else None)
@@ -150,12 +174,13 @@ def test_main_and_extension_gate_launches_on_the_chained_circuit(gpu, orc, lg_n,
 def test_main_poseidon_and_lookup_launches_on_the_circuit_with_every_oracle_gate(gpu, orc, k):
     # oracle kind 15 at its smallest (bits = 1): k_quotient<false> (BaseSum, Exponentiation, Arithmetic, ...), k_quotient<true> and
     # k_quotient_lookup with two tables; three selector groups.  The constants are the circuit's own (the loader reads the lookup rows from
-    # the lookup selector columns); sigmas, wires, Z, partial products and lookup polynomials free.
+    # the lookup selector columns); sigmas, wires, Z, partial products and lookup polynomials free.  The circuit with the PoseidonGate: its
+    # S-box input wires also carry the values whose 7th power takes the cold block of the Goldilocks product (run_case sbox_cold).
     oc = orc.circuit_of_kind(15, 1, threads=4)
     desc = oc.product_desc()
     types = set(desc.gate_types[g] for g in range(desc.num_gates))
     assert {vm.POSEIDON, vm.BASE_SUM, vm.EXPONENTIATION, vm.LOOKUP, vm.LOOKUP_TABLE} <= types and desc.num_luts == 2 and desc.num_lookup_polys == 7
-    run_case(gpu, orc, desc, k, seed=1500 + k, kept_constants=oc.constants_sigmas()[:desc.num_constants])
+    run_case(gpu, orc, desc, k, seed=1500 + k, kept_constants=oc.constants_sigmas()[:desc.num_constants], sbox_cold=True)
 
 
 @pytest.mark.parametrize("k", RESIDUES)

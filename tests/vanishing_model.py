@@ -80,35 +80,43 @@ def _arithmetic_gate(c, w, pi):
     return [(w[4 * i + 3] - (w[4 * i] * w[4 * i + 1] * c[0] + w[4 * i + 2] * c[1])) % P for i in range(20)]
 
 
+# PoseidonGate wire columns (gates/poseidon.rs:36-95): inputs 0..11, outputs 12..23, the swap bit, the four deltas, then the S-box INPUTS of
+# the first full rounds 1..3 (round 0 reads the inputs), of the 22 partial rounds (word 0) and of the four last full rounds
+PSD_WIRE_SWAP, PSD_WIRE_DELTA = 24, 25
+PSD_WIRE_FULL0_SBOX, PSD_WIRE_PARTIAL_SBOX, PSD_WIRE_FULL1_SBOX = 29, 65, 87
+PSD_FULL_SBOX_WIRES = list(range(PSD_WIRE_FULL0_SBOX, PSD_WIRE_FULL0_SBOX + 36)) + list(range(PSD_WIRE_FULL1_SBOX, PSD_WIRE_FULL1_SBOX + 48))
+PSD_PARTIAL_SBOX_WIRES = list(range(PSD_WIRE_PARTIAL_SBOX, PSD_WIRE_PARTIAL_SBOX + 22))
+
+
 def _poseidon_gate(c, w, pi):
     """PoseidonGate (gates/poseidon.rs:36-95 the wires, :193-272 the constraints).  The reference evaluates the partial rounds in their
     factorised form (partial_first_constant_layer, mds_partial_layer_init / _fast); the factorisation is linear algebra on the round
     constants and the MDS matrix that treats every S-box OUTPUT as a free variable and keeps state[0] at every S-box input, so the
     textbook rounds below give the same constraints whatever the S-box input wires hold."""
     rc, M = _poseidon_tables()
-    swap = w[24]
+    swap = w[PSD_WIRE_SWAP]
     out = [swap * (swap - 1) % P]
     s = list(w[0:12])
     for i in range(4):
-        delta = w[25 + i]
+        delta = w[PSD_WIRE_DELTA + i]
         out.append((swap * (w[i + 4] - w[i]) - delta) % P)
         s[i], s[i + 4] = (w[i] + delta) % P, (w[i + 4] - delta) % P
     r = 0
     for k in range(4):                                  # first full rounds; the S-box inputs of round 0 are not wires
         s = [(a + b) % P for a, b in zip(s, rc[r])]
         if k:
-            sbox_in = w[29 + 12 * (k - 1):29 + 12 * k]
+            sbox_in = w[PSD_WIRE_FULL0_SBOX + 12 * (k - 1):PSD_WIRE_FULL0_SBOX + 12 * k]
             out += [(a - b) % P for a, b in zip(s, sbox_in)]
             s = list(sbox_in)
         s = _mds(M, [pow(a, 7, P) for a in s]); r += 1
     for k in range(22):                                 # partial rounds
         s = [(a + b) % P for a, b in zip(s, rc[r])]
-        out.append((s[0] - w[65 + k]) % P)
-        s[0] = pow(w[65 + k], 7, P)
+        out.append((s[0] - w[PSD_WIRE_PARTIAL_SBOX + k]) % P)
+        s[0] = pow(w[PSD_WIRE_PARTIAL_SBOX + k], 7, P)
         s = _mds(M, s); r += 1
     for k in range(4):                                  # second full rounds
         s = [(a + b) % P for a, b in zip(s, rc[r])]
-        sbox_in = w[87 + 12 * k:87 + 12 * (k + 1)]
+        sbox_in = w[PSD_WIRE_FULL1_SBOX + 12 * k:PSD_WIRE_FULL1_SBOX + 12 * (k + 1)]
         out += [(a - b) % P for a, b in zip(s, sbox_in)]
         s = _mds(M, [pow(a, 7, P) for a in sbox_in]); r += 1
     return out + [(s[i] - w[12 + i]) % P for i in range(12)]

@@ -125,6 +125,44 @@ def perm_naive(state, rc, M):
     return s
 
 
+SBOX_INV_EXP = pow(7, -1, P - 1)           # x -> x^7 is a bijection of the field (7 does not divide p - 1): the 7th root is a power
+
+
+def sbox_inv(x):
+    return pow(x, SBOX_INV_EXP, P)
+
+
+def sbox_inputs(state, rc, M):
+    """perm_naive with its trace: (the 30 states right after the round constants -- what the S-boxes of each round read: all twelve
+    words in a full round, word 0 in a partial one -- and the output)"""
+    s = [x % P for x in state]
+    trace = []
+    for r in range(N_ROUNDS):
+        s = [(a + c) % P for a, c in zip(s, rc[r])]
+        trace.append(s[:])
+        full = r < HALF_FULL or r >= HALF_FULL + N_PARTIAL
+        s = mat_vec(M, [sbox(a) for a in s] if full else [sbox(s[0])] + s[1:])
+    return trace, s
+
+
+def perm_naive_to_input(after_constants, round_, rc, Minv):
+    """The input of perm_naive whose state right after the constants of round `round_` is `after_constants`."""
+    s = [(a - c) % P for a, c in zip(after_constants, rc[round_])]
+    for r in range(round_ - 1, -1, -1):
+        s = mat_vec(Minv, s)
+        full = r < HALF_FULL or r >= HALF_FULL + N_PARTIAL
+        s = [sbox_inv(a) for a in s] if full else [sbox_inv(s[0])] + s[1:]
+        s = [(a - c) % P for a, c in zip(s, rc[r])]
+    return s
+
+
+def perm_naive_inverse(out, rc, M):
+    """The inverse of perm_naive: the MDS inverse over the field and the 7th root, round by round from the last."""
+    Minv = mat_inv(M)
+    last = [sbox_inv(a) for a in mat_vec(Minv, [x % P for x in out])]       # the state after the constants of round 29
+    return perm_naive_to_input(last, N_ROUNDS - 1, rc, Minv)
+
+
 def perm_fast(state, rc, T):
     M = T["M"]
     s = [x % P for x in state]
