@@ -478,6 +478,114 @@ int gl_prove_openings(gl_ctx* ctx, const gl_fri_params* params, const gl_fri_ins
 int gl_verify_openings(const gl_fri_params* params, const gl_fri_instance* instance, const uint64_t* caps, const uint64_t* openings,
                        gl_challenger* challenger, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check);
 
+/* ---- STARK: an AIR as data, and the two prover phases it needs ---------------------------------------
+ * starky's `Stark` states its constraints as code (eval_packed_generic, starky/src/stark.rs:26-62); over a C ABI they are data: one
+ * term list per constraint, in the order the Stark yields them.  Constraint c is  sum_t coeff_t * prod_f operand_{t,f}  with every
+ * operand a trace column on the local row, the same on the next row, or a public input; its filter names the ConstraintConsumer
+ * method it goes through (constraint_consumer.rs:53-76).  The FRI side of StarkConfig (starky/src/config.rs) is a gl_fri_params;
+ * num_challenges stands here.  Derived as stark.rs:79-221 does: quotient_degree_factor q = max(1, constraint_degree - 1),
+ * quotient_degree_bits = ceil(log2 q), permutation batch size q, ceil(pairs * num_challenges / q) Z polynomials, and the
+ * FriInstanceInfo of stark.rs:88-137 (oracles trace, Z if there are pairs, quotient; batches at zeta and g zeta).
+ * What is here: the description and its validation, and the two phases between the commitments -- the permutation argument's Z
+ * polynomials and the quotient -- as phase entries shaped like gl_partial_products / gl_quotient_polys, every polynomial
+ * device-resident; gl_stark_prove, which is those phases in the order of starky/src/prover.rs:32-194 on the library's own challenger;
+ * and gl_stark_verify (verifier.rs:21-145), host code.  Public inputs are NOT observed by the transcript: this version of the
+ * reference does not observe them (get_challenges.rs:21-73).
+ * Proof bytes -- PARITY UNPINNED: the reference has no writer for StarkProofWithPublicInputs and no Rust-written STARK proof exists
+ * here, so the layout is this project's, in the circuit proof's conventions (little-endian words, no length prefixes, every count
+ * fixed by the description and the params; a hash is 32 bytes under Poseidon, 25 under Keccak):
+ *   trace_cap | permutation_zs_cap (with pairs) | quotient_polys_cap            2^cap_height hashes each
+ *   local_values[num_columns] | next_values[num_columns]                       two words each (StarkOpeningSet, proof.rs:129-135)
+ *   permutation_zs[nz] | permutation_zs_next[nz] (with pairs) | quotient_polys[num_challenges q]
+ *   the FriProof exactly as gl_prove_openings writes it
+ *   public_inputs[num_public_inputs]                                            one word each */
+#define GL_STARK_ALL 0u          /* ConstraintConsumer::constraint            */
+#define GL_STARK_TRANSITION 1u   /* ::constraint_transition  (times x - g^-1) */
+#define GL_STARK_FIRST_ROW 2u    /* ::constraint_first_row   (times L_first)  */
+#define GL_STARK_LAST_ROW 3u     /* ::constraint_last_row    (times L_last)   */
+#define GL_STARK_LOCAL 0u        /* operand kinds, bits 31..30 of a factor word; bits 29..0 = column / public-input index */
+#define GL_STARK_NEXT 1u
+#define GL_STARK_PUBLIC 2u
+#define GL_STARK_MAX_COLUMNS 1024u
+#define GL_STARK_MAX_PUBLIC_INPUTS 256u
+#define GL_STARK_MAX_DEGREE 9u          /* q <= 8, quotient_degree_bits <= 3 */
+#define GL_STARK_MAX_CHALLENGES 4u
+#define GL_STARK_MAX_CONSTRAINTS 4096u
+#define GL_STARK_MAX_TERMS 65536u       /* over all constraints */
+#define GL_STARK_MAX_FACTORS 64u        /* per term, public inputs included */
+#define GL_STARK_MAX_PAIRS 64u
+#define GL_STARK_MAX_PAIR_LEN 64u
+typedef struct gl_stark_desc {
+    uint32_t num_columns, num_public_inputs;   /* S::COLUMNS, S::PUBLIC_INPUTS */
+    uint32_t constraint_degree;                /* Stark::constraint_degree()   */
+    uint32_t num_challenges;                   /* StarkConfig::num_challenges  */
+    uint32_t num_constraints;
+    const uint32_t* constraint_filter;         /* [num_constraints] GL_STARK_ALL .. LAST_ROW, in the order the Stark yields them */
+    const uint32_t* constraint_num_terms;      /* [num_constraints] */
+    const uint64_t* term_coeff;                /* [sum of terms]  may be non-canonical */
+    const uint32_t* term_num_factors;          /* [sum of terms]  0 = a constant term  */
+    const uint32_t* factors;                   /* [sum of factors] kind << 30 | index  */
+    uint32_t num_permutation_pairs;            /* Stark::permutation_pairs()           */
+    const uint32_t* pair_len;                  /* [num_permutation_pairs] column_pairs.len() >= 1 */
+    const uint32_t* pair_columns;              /* [sum pair_len][2] (lhs, rhs)         */
+} gl_stark_desc;
+typedef struct gl_stark gl_stark;      /* a checked description + params with its tables in HBM */
+/* Validation, the same in every entry below; host code, no GPU.  GL_ERR_ARG for: a null table, a count outside the GL_STARK_MAX_* caps
+ * above (at least 1 column, 1 constraint, 1 challenge, degree 1), an unknown filter or operand kind, a column / public-input index out
+ * of range, a pair without column pairs, and a term with more LOCAL / NEXT factors than the quotient can hold: more than q + 1, or
+ * more than q under GL_STARK_FIRST_ROW / GL_STARK_LAST_ROW (the quotient's degree must stay below q n; DESIGN.md section 15 derives it).
+ * GL_ERR_UNSUPPORTED for params.hiding != 0 (StarkConfig::fri_params passes false) and for quotient_degree_bits > rate_bits (the
+ * reference asserts "not supported yet", prover.rs:222-225).  The gl_fri_params rules, arity 16 only among them, are gl_prove_openings'
+ * own, applied to the STARK's instance. */
+int gl_stark_check(const gl_stark_desc* desc, const gl_fri_params* params);
+/* Copies the description, uploads the term program and the pair tables once and precomputes what depends on degree_bits only: g^-1,
+ * 1/n, Z_H and 1/Z_H on the quotient coset, and L_first / L_last on it.  The handle holds a reference to the context, and every entry
+ * below that takes it takes THAT context (GL_ERR_ARG for another: the tables are blocks of its stream-ordered pool); threads that
+ * prove concurrently create one gl_stark per context. */
+int gl_stark_create(gl_ctx* ctx, const gl_stark_desc* desc, const gl_fri_params* params, gl_stark** out);
+void gl_stark_free(gl_stark* s) GL_NOEXCEPT;
+/* compute_permutation_z_polys (starky/src/permutation.rs:66-117) followed by the commitment of prover.rs:89-100: d_trace_values
+ * [num_columns][n] trace VALUES on the device, challenges[q][num_challenges][2] = (beta, gamma) of challenge set j, challenge c at
+ * [j][c] (get_n_permutation_challenge_sets(challenger, num_challenges, q) in the order drawn) -> PolynomialBatch of the Z polynomials.
+ * Instance j of a batch takes challenge_sets[j].challenges[chal], (pair, chal) running over pairs x 0..num_challenges in chunks of q
+ * (get_permutation_batches, permutation.rs:228-249).  GL_ERR_ARG for a description without pairs, and -- where the reference panics
+ * inverting zero -- GL_ERR_ARG "a permutation denominator is zero" (probability about n / p: draw other challenges). */
+int gl_stark_permutation_zs(gl_ctx* ctx, const gl_stark* s, const uint64_t* d_trace_values, const uint64_t* challenges, gl_batch** zs);
+/* compute_quotient_polys up to its coset_ifft (prover.rs:198-311): the values of (sum_i alpha^i C_i) / Z_H at the points 7 w^i of the
+ * quotient coset of size n << quotient_degree_bits, natural order, h_out[num_challenges][n << quotient_degree_bits]; the Stark's
+ * constraints first, then the permutation checks of permutation.rs:282-320.  No degree check: inputs that do not satisfy the
+ * constraints are answered by value.  zs and challenges are null exactly for a description without pairs; alphas[num_challenges],
+ * public_inputs[num_public_inputs]; the batches must match the description and params (GL_ERR_ARG). */
+int gl_stark_quotient_values(gl_ctx* ctx, const gl_stark* s, const gl_batch* trace, const gl_batch* zs, const uint64_t* challenges,
+                             const uint64_t* alphas, const uint64_t* public_inputs, uint64_t* h_out);
+/* The same, then coset_ifft, trim_to_len(q n) -- a non-zero coefficient from index q n on is GL_ERR_ARG "the trace does not satisfy the
+ * constraints", the reference's expect("Quotient has failed...") (prover.rs:123-128) -- the split into chunks of n and from_coeffs
+ * (prover.rs:129-144): PolynomialBatch of the num_challenges x q chunk polynomials, challenge after challenge. */
+int gl_stark_quotient_polys(gl_ctx* ctx, const gl_stark* s, const gl_batch* trace, const gl_batch* zs, const uint64_t* challenges,
+                            const uint64_t* alphas, const uint64_t* public_inputs, gl_batch** quotient);
+/* The size of every proof of this description under these params. */
+size_t gl_stark_proof_size(const gl_stark* s) GL_NOEXCEPT;
+/* starky::prover::prove (prover.rs:32-194) given the trace: h_trace_cols[num_columns] -> n values each (may be non-canonical),
+ * h_public_inputs[num_public_inputs].  In order: trace commitment, its cap observed; with pairs the challenge sets
+ * (get_n_permutation_challenge_sets(challenger, num_challenges, q)), the Z polynomials, their cap observed; alphas; the quotient chunks,
+ * their cap observed; zeta, and GL_ERR_ZETA_IN_SUBGROUP for zeta^n = 1 (prover.rs:150-157); the openings at zeta and g zeta, observed in
+ * FriOpenings order (proof.rs:161-182); gl_prove_openings' path on the STARK's instance.  *num_bytes = gl_stark_proof_size(s) always;
+ * cap_bytes below it is GL_ERR_ARG.  A trace that does not satisfy the constraints is GL_ERR_ARG as in gl_stark_quotient_polys where the
+ * trim can see it (q no power of two); otherwise it yields a proof the verifier rejects.  A zero permutation denominator is GL_ERR_ARG
+ * as in gl_stark_permutation_zs.  Two calls on the same input give the same bytes (the PoW witness is the smallest). */
+int gl_stark_prove(gl_ctx* ctx, const gl_stark* s, const uint64_t* const* h_trace_cols, const uint64_t* h_public_inputs, uint8_t* h_out,
+                   size_t cap_bytes, size_t* num_bytes);
+/* the same with the trace already in HBM, d_cols[num_columns][n] (left untouched) */
+int gl_stark_prove_device(gl_ctx* ctx, const gl_stark* s, const uint64_t* d_cols, const uint64_t* h_public_inputs, uint8_t* h_out,
+                          size_t cap_bytes, size_t* num_bytes);
+/* verify_stark_proof (starky/src/verifier.rs:21-145).  Host code, no GPU; degree_bits comes from params and the proof's path lengths
+ * are checked against it.  GL_OK, or GL_ERR_VERIFY with gl_last_error() and *check (may be null) = the GL_CHECK_* code of the first
+ * failing check, in the order: TRUNCATED / LENGTH (the size the description and the params fix); the challenges of
+ * get_challenges.rs:21-73; eval_vanishing_poly at zeta over the extension field, by a host interpreter of the same term list with
+ * eval_l_0_and_l_last and zeta - g^-1, and per challenge vanishing == Z_H(zeta) reduce_with_powers(chunk, zeta^n): VANISHING; then
+ * gl_verify_openings' checks in its order.  The verifier takes FRI arity bits 1..8, as gl_verify_openings does. */
+int gl_stark_verify(const gl_stark_desc* desc, const gl_fri_params* params, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check);
+
 /* ---- prove() ---------------------------------------------------------------------------------------*/
 /* plonk::prover::prove (plonky2/src/plonk/prover.rs:102-329) from step 4 on, i.e. given the FULL witness matrix
  * `MatrixWitness.wire_values` (iop/witness.rs:256-258) h_wires[num_wires][n] and the public inputs.  Every

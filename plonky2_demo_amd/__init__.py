@@ -6,9 +6,13 @@ Host-side mirror (Python, over the C ABI of libplonky2_mi355x.so) of the referen
 Names and argument meaning follow the reference so that the parity tests read like its own tests.
 """
 from ._lib import LIB_PATH, FriInstance, FriParams, Plonky2Mi355xError  # noqa: F401
+from ._lib import (  # noqa: F401  (gl_stark_desc filters and operand kinds)
+    GL_STARK_ALL, GL_STARK_TRANSITION, GL_STARK_FIRST_ROW, GL_STARK_LAST_ROW, GL_STARK_LOCAL, GL_STARK_NEXT, GL_STARK_PUBLIC,
+)
 from . import api  # noqa: F401
 from .api import (  # noqa: F401
     BatchVerifier, Challenger, CircuitData, Context, FriProver, GenericCircuitData, MatmulCircuit, MerkleTree, PolynomialBatch, Proof, ProverPool, coset_fft, coset_ifft, default_context, fft, hash_or_noop, ifft,
     lde_onto_coset, poseidon, pow_grind, random_elements, GOLDILOCKS_ORDER, COSET_SHIFT,
     hash_from_bytes, hash_or_noop_host, hash_to_bytes, hash_to_elements, two_to_one_host, verify_fri_proof,
+    Stark, StarkConfig, StarkDesc, fibonacci_stark, stark_verify,
 )

@@ -184,6 +184,17 @@ SIGNATURES = {
     "gl_fri_combine_instance_per_batch": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp)]),
     "gl_prove_openings": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp, c_sz, ctypes.POINTER(c_sz)]),
     "gl_verify_openings": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(c_u32)]),
+    # STARK: an AIR as data (gl_stark_desc*, gl_fri_params*, ...)
+    "gl_stark_check": (c_int, [c_vp, c_vp]),
+    "gl_stark_create": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)]),
+    "gl_stark_free": (None, [c_vp]),
+    "gl_stark_permutation_zs": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)]),
+    "gl_stark_quotient_values": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "gl_stark_quotient_polys": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)]),
+    "gl_stark_proof_size": (c_sz, [c_vp]),
+    "gl_stark_prove": (c_int, [c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp, c_sz, ctypes.POINTER(c_sz)]),
+    "gl_stark_prove_device": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(c_sz)]),
+    "gl_stark_verify": (c_int, [c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(c_u32)]),
 }
 GL_MAX_FRI_ORACLES, GL_MAX_FRI_BATCHES = 8, 4
 
@@ -277,6 +288,44 @@ class FriInstance(ctypes.Structure):
     @property
     def num_opened(self):
         return sum(len(polys) for _, polys in self.batches)
+
+
+(GL_STARK_ALL, GL_STARK_TRANSITION, GL_STARK_FIRST_ROW, GL_STARK_LAST_ROW) = range(4)      # constraint filters
+(GL_STARK_LOCAL, GL_STARK_NEXT, GL_STARK_PUBLIC) = range(3)                                # operand kinds
+
+
+class StarkDescStruct(ctypes.Structure):
+    """gl_stark_desc.  constraints: [(filter, [(coeff, [(kind, index), ...]), ...]), ...] in the order the Stark yields them; pairs:
+    [[(lhs, rhs), ...], ...] (Stark::permutation_pairs).  Nothing is checked here: refusing is gl_stark_check's."""
+    _fields_ = [("num_columns", c_u32), ("num_public_inputs", c_u32), ("constraint_degree", c_u32), ("num_challenges", c_u32),
+                ("num_constraints", c_u32), ("constraint_filter", ctypes.POINTER(c_u32)), ("constraint_num_terms", ctypes.POINTER(c_u32)),
+                ("term_coeff", ctypes.POINTER(c_u64)), ("term_num_factors", ctypes.POINTER(c_u32)), ("factors", ctypes.POINTER(c_u32)),
+                ("num_permutation_pairs", c_u32), ("pair_len", ctypes.POINTER(c_u32)), ("pair_columns", ctypes.POINTER(c_u32))]
+
+    def __init__(self, num_columns, num_public_inputs, constraint_degree, num_challenges, constraints, pairs=()):
+        super().__init__()
+        filters, num_terms, coeffs, num_factors, factors = [], [], [], [], []
+        for filt, terms in constraints:
+            filters.append(int(filt))
+            num_terms.append(len(terms))
+            for coeff, ops in terms:
+                coeffs.append(int(coeff))
+                num_factors.append(len(ops))
+                factors += [(int(kind) << 30 | int(index)) & 0xFFFFFFFF for kind, index in ops]
+        pair_len = [len(p) for p in pairs]
+        pair_columns = [int(c) for p in pairs for lr in p for c in lr]
+        self.num_columns, self.num_public_inputs = num_columns, num_public_inputs
+        self.constraint_degree, self.num_challenges = constraint_degree, num_challenges
+        self.num_constraints, self.num_permutation_pairs = len(filters), len(pair_len)
+        self._keep = []                                       # the tables live as long as the structure
+
+        def table(ctype, values):
+            arr = (ctype * max(len(values), 1))(*values)
+            self._keep.append(arr)
+            return ctypes.cast(arr, ctypes.POINTER(ctype))
+        self.constraint_filter, self.constraint_num_terms = table(c_u32, filters), table(c_u32, num_terms)
+        self.term_coeff, self.term_num_factors, self.factors = table(c_u64, coeffs), table(c_u32, num_factors), table(c_u32, factors)
+        self.pair_len, self.pair_columns = table(c_u32, pair_len), table(c_u32, pair_columns)
 
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -999,6 +999,187 @@ def verify_fri_proof(instance, caps, openings, challenger, proof, fri_params):
     return ok, why, code.value
 
 
+# ------------------------------------------------------------------------------------- STARK: an AIR as data
+class StarkConfig:
+    """starky::config::StarkConfig (starky/src/config.rs): num_challenges and the FriConfig."""
+
+    def __init__(self, num_challenges, rate_bits, cap_height, proof_of_work_bits, num_query_rounds, arity_bits=4, final_poly_bits=5):
+        self.num_challenges, self.rate_bits, self.cap_height = num_challenges, rate_bits, cap_height
+        self.proof_of_work_bits, self.num_query_rounds = proof_of_work_bits, num_query_rounds
+        self.arity_bits, self.final_poly_bits = arity_bits, final_poly_bits
+
+    @classmethod
+    def standard_fast_config(cls):
+        """config.rs:17-29: rate 2, 84 queries, 16 bits of work, ConstantArityBits(4, 5)."""
+        return cls(2, 1, 4, 16, 84, 4, 5)
+
+    def fri_params(self, degree_bits, hasher="poseidon"):
+        """StarkConfig::fri_params (config.rs:31-33; hiding = false) with FriReductionStrategy::ConstantArityBits
+        (fri/reduction_strategies.rs:39-50)."""
+        arities, d = [], degree_bits
+        while d > self.final_poly_bits and d + self.rate_bits - self.arity_bits >= self.cap_height:
+            arities.append(self.arity_bits)
+            d -= self.arity_bits
+        return _lib.FriParams(degree_bits, self.rate_bits, self.cap_height, self.proof_of_work_bits, self.num_query_rounds, arities, False, hasher)
+
+
+class StarkDesc:
+    """A Stark (starky/src/stark.rs) as data: constraints = [(filter, [(coeff, [(kind, index), ...]), ...]), ...] in the order
+    eval_packed_generic yields them, filter one of GL_STARK_ALL / TRANSITION / FIRST_ROW / LAST_ROW, kind one of GL_STARK_LOCAL / NEXT /
+    PUBLIC; pairs = Stark::permutation_pairs() as [[(lhs, rhs), ...], ...]."""
+
+    def __init__(self, num_columns, num_public_inputs, constraint_degree, constraints, pairs=()):
+        self.num_columns, self.num_public_inputs, self.constraint_degree = num_columns, num_public_inputs, constraint_degree
+        self.constraints = [(f, [(c, list(ops)) for c, ops in terms]) for f, terms in constraints]
+        self.pairs = [list(p) for p in pairs]
+
+    @property
+    def quotient_degree_factor(self):
+        return max(1, self.constraint_degree - 1)                     # stark.rs:79-81
+
+    @property
+    def quotient_degree_bits(self):
+        return (self.quotient_degree_factor - 1).bit_length()         # log2_ceil
+
+    def num_permutation_batches(self, num_challenges):
+        return -(-len(self.pairs) * num_challenges // self.quotient_degree_factor)      # stark.rs:216-221
+
+    def struct(self, num_challenges):
+        return _lib.StarkDescStruct(self.num_columns, self.num_public_inputs, self.constraint_degree, num_challenges, self.constraints, self.pairs)
+
+    def check(self, config, degree_bits, hasher="poseidon"):
+        """gl_stark_check: raises Plonky2Mi355xError with the refusal; needs no GPU."""
+        params = config.fri_params(degree_bits, hasher)
+        check(lib.gl_stark_check(ctypes.byref(self.struct(config.num_challenges)), ctypes.byref(params)))
+
+
+class Stark(_Owned):
+    """A checked description with its tables in HBM (gl_stark): starky's prove() and verify, and the two STARK-only prover phases on their
+    own, every polynomial device-resident."""
+    _free = "gl_stark_free"
+
+    def __init__(self, desc, config, degree_bits, hasher="poseidon", ctx=None):
+        self.ctx, self.desc, self.config, self.degree_bits = _ctx(ctx), desc, config, degree_bits
+        self.params = config.fri_params(degree_bits, hasher)
+        h = ctypes.c_void_p()
+        check(lib.gl_stark_create(self.ctx.handle, ctypes.byref(desc.struct(config.num_challenges)), ctypes.byref(self.params), ctypes.byref(h)))
+        self.handle = h.value
+
+    def commit_trace(self, trace):
+        """PolynomialBatch::from_values of the trace columns (prover.rs:52-65)."""
+        return PolynomialBatch.from_values(trace, self.params.rate_bits, False, self.params.cap_height, ctx=self.ctx, hasher=self.params.hasher)
+
+    def _challenges(self, challenge_sets):
+        if challenge_sets is None:
+            return None
+        ch = _u64(challenge_sets)
+        if ch.size != self.desc.quotient_degree_factor * self.config.num_challenges * 2:
+            raise ValueError("challenge sets are [quotient_degree_factor][num_challenges][2] (beta, gamma)")
+        return ch
+
+    def permutation_zs(self, trace, challenge_sets):
+        """compute_permutation_z_polys + commitment (permutation.rs:66-117, prover.rs:89-100).  trace: [num_columns][n] values."""
+        t = _u64(trace)
+        if t.shape != (self.desc.num_columns, 1 << self.degree_bits):
+            raise ValueError("the trace is [num_columns][n]")
+        if challenge_sets is None:
+            raise ValueError("the Z polynomials need the challenge sets")
+        d = DeviceBuffer(self.ctx, t.nbytes).upload(t)
+        try:
+            h = ctypes.c_void_p()
+            check(lib.gl_stark_permutation_zs(self.ctx.handle, self.handle, d.ptr, _p(self._challenges(challenge_sets)), ctypes.byref(h)))
+        finally:
+            d.free()
+        return PolynomialBatch(h.value, self.ctx, self.params.rate_bits, self.params.cap_height)
+
+    def _quotient_args(self, trace_batch, zs_batch, challenge_sets, alphas, public_inputs):
+        ch, al, pi = self._challenges(challenge_sets), _u64(alphas), _u64(public_inputs)
+        if al.size != self.config.num_challenges or pi.size != self.desc.num_public_inputs:
+            raise ValueError("alphas are [num_challenges], public inputs [num_public_inputs]")
+        return (self.ctx.handle, self.handle, trace_batch.handle, zs_batch.handle if zs_batch is not None else None,
+                _p(ch) if ch is not None else None, _p(al), _p(pi) if pi.size else None), (ch, al, pi)
+
+    def quotient_values(self, trace_batch, zs_batch, challenge_sets, alphas, public_inputs):
+        """(sum alpha^i C_i) / Z_H on the quotient coset (prover.rs:198-311), [num_challenges][n << quotient_degree_bits]; no degree check."""
+        args, keep = self._quotient_args(trace_batch, zs_batch, challenge_sets, alphas, public_inputs)
+        out = np.empty((self.config.num_challenges, (1 << self.degree_bits) << self.desc.quotient_degree_bits), dtype=np.uint64)
+        check(lib.gl_stark_quotient_values(*args, _p(out)))
+        return out
+
+    def quotient_polys(self, trace_batch, zs_batch, challenge_sets, alphas, public_inputs):
+        """The same, then coset_ifft, the trim_to_len check, the chunks of n and from_coeffs (prover.rs:114-144)."""
+        args, keep = self._quotient_args(trace_batch, zs_batch, challenge_sets, alphas, public_inputs)
+        h = ctypes.c_void_p()
+        check(lib.gl_stark_quotient_polys(*args, ctypes.byref(h)))
+        return PolynomialBatch(h.value, self.ctx, self.params.rate_bits, self.params.cap_height)
+
+
+    @property
+    def proof_size(self):
+        return lib.gl_stark_proof_size(self.handle)
+
+    def _public_inputs(self, public_inputs):
+        pi = _u64(public_inputs)
+        if pi.size != self.desc.num_public_inputs:
+            raise ValueError("the Stark has %d public inputs" % self.desc.num_public_inputs)
+        return pi
+
+    def prove(self, trace, public_inputs):
+        """starky::prover::prove (prover.rs:32-194): trace [num_columns][n] values -> the proof's bytes (layout: include/plonky2_mi355x.h)."""
+        cols = [_u64(c) for c in trace]
+        if len(cols) != self.desc.num_columns or any(c.size != 1 << self.degree_bits for c in cols):
+            raise ValueError("the trace is [num_columns][n]")
+        pi = self._public_inputs(public_inputs)
+        ptrs = (ctypes.c_void_p * len(cols))(*[c.ctypes.data for c in cols])
+        out, k = np.empty(self.proof_size, dtype=np.uint8), ctypes.c_size_t()
+        check(lib.gl_stark_prove(self.ctx.handle, self.handle, ptrs, _p(pi) if pi.size else None, _p(out), out.size, ctypes.byref(k)))
+        return out[:k.value].tobytes()
+
+    def prove_device(self, d_cols_ptr, public_inputs):
+        """The same with the trace in HBM, d_cols[num_columns][n]."""
+        pi = self._public_inputs(public_inputs)
+        out, k = np.empty(self.proof_size, dtype=np.uint8), ctypes.c_size_t()
+        check(lib.gl_stark_prove_device(self.ctx.handle, self.handle, d_cols_ptr, _p(pi) if pi.size else None, _p(out), out.size, ctypes.byref(k)))
+        return out[:k.value].tobytes()
+
+    def verify(self, proof):
+        """verify_stark_proof (verifier.rs:21-145), host code -> (accepted, message, GL_CHECK_* code)."""
+        return stark_verify(self.desc, self.config, self.degree_bits, proof, hasher=self.params.hasher)
+
+
+def stark_verify(desc, config, degree_bits, proof, hasher="poseidon"):
+    """gl_stark_verify: needs no GPU and no Stark handle -> (accepted, message, GL_CHECK_* code)."""
+    params = config.fri_params(degree_bits, hasher)
+    buf = np.frombuffer(bytes(proof), dtype=np.uint8)
+    code = ctypes.c_uint32()
+    st = lib.gl_stark_verify(ctypes.byref(desc.struct(config.num_challenges)), ctypes.byref(params), _p(buf) if buf.size else None, buf.size, ctypes.byref(code))
+    ok, why = _verdict(st)
+    return ok, why, code.value
+
+
+def fibonacci_stark(num_rows):
+    """FibonacciStark (starky/src/fibonacci_stark.rs): (description, trace generator).  generate_trace(x0, x1) -> [4][num_rows] values
+    (fibonacci_stark.rs:44-57); the public inputs are x0, x1 and column 1 of the last row."""
+    L, N, PUB, p = _lib.GL_STARK_LOCAL, _lib.GL_STARK_NEXT, _lib.GL_STARK_PUBLIC, GOLDILOCKS_ORDER
+    m1 = p - 1
+    desc = StarkDesc(4, 3, 2, [
+        (_lib.GL_STARK_FIRST_ROW, [(1, [(L, 0)]), (m1, [(PUB, 0)])]),
+        (_lib.GL_STARK_FIRST_ROW, [(1, [(L, 1)]), (m1, [(PUB, 1)])]),
+        (_lib.GL_STARK_LAST_ROW, [(1, [(L, 1)]), (m1, [(PUB, 2)])]),
+        (_lib.GL_STARK_TRANSITION, [(1, [(N, 0)]), (m1, [(L, 1)])]),                       # x0' <- x1
+        (_lib.GL_STARK_TRANSITION, [(1, [(N, 1)]), (m1, [(L, 0)]), (m1, [(L, 1)])]),       # x1' <- x0 + x1
+    ], [[(2, 3)]])
+
+    def generate_trace(x0, x1):
+        rows, acc = [], [int(x0) % p, int(x1) % p, 0, 1]
+        for _ in range(num_rows):
+            rows.append(list(acc))
+            acc = [acc[1], (acc[0] + acc[1]) % p, (acc[2] + 1) % p, (acc[3] + 1) % p]
+        rows[num_rows - 1][3] = 0                      # so that columns 2 and 3 are permutations of one another
+        return np.array(rows, dtype=np.uint64).T.copy()
+    return desc, generate_trace
+
+
 def pow_grind(sponge_state, input_buffer, min_leading_zeros, ctx=None, hasher="poseidon"):
     """fri_proof_of_work (fri/prover.rs:115-160): the smallest valid witness."""
     ctx = _ctx(ctx)

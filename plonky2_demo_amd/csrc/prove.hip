@@ -198,19 +198,9 @@ extern "C" const gl_batch* gl_circuit_constants_sigmas_batch(const gl_circuit* c
 
 // ---- helpers -------------------------------------------------------------------------------------------------------------
 static inline gl2_t h_ext(gl_t a, gl_t b) { return gl2_make(a, b); }
-static void put_u64(std::vector<uint8_t>& o, uint64_t v) { for (int i = 0; i < 8; i++) o.push_back((uint8_t)(v >> (8 * i))); }
-static void put_words(std::vector<uint8_t>& o, const gl_t* v, size_t n) { for (size_t i = 0; i < n; i++) put_u64(o, gl_canon(v[i])); }
-// write_hash (util/serialization/mod.rs:248-256): a HashOut is four field elements, a BytesHash<25> its 25 bytes
-static void put_hashes(std::vector<uint8_t>& o, uint32_t hasher, const gl_t* h, size_t count) {
-    if (hasher != GL_HASHER_KECCAK) { put_words(o, h, 4 * count); return; }
-    for (size_t i = 0; i < count; i++) {
-        for (int k = 0; k < 3; k++) put_u64(o, h[4 * i + k]);
-        o.push_back((uint8_t)h[4 * i + 3]);
-    }
-}
+// put_u64 / put_words / put_hashes and BatchHolder: proof.hpp, shared with stark.hip
 static uint32_t host_bitrev32(uint32_t x, uint32_t bits) { uint32_t r = 0; for (uint32_t i = 0; i < bits; i++) r = (r << 1) | ((x >> i) & 1); return r; }
 
-struct BatchHolder { gl_batch* b = nullptr; ~BatchHolder() { if (b) gl_batch_free(b); } };
 struct MerkleHolder { gl_ctx* c; GlMerkle m; explicit MerkleHolder(gl_ctx* ctx) : c(ctx) {} ~MerkleHolder() { gl_merkle_release(c, &m); } };
 
 static int d2h(gl_ctx* c, void* dst, const void* src, size_t bytes) { return gl_copy_d2h(c, dst, src, bytes); }
