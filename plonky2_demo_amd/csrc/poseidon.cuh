@@ -303,8 +303,9 @@ GL_HD void psd_sbox_all(gl_t (&s)[12]) {
 // Three partial rounds at once (tools/gen_poseidon_constants.py derive_groups): with d_j = sbox(x_j) - a_j the change of lane
 // 0 in round j of the group (a_j = lane 0 entering its S-box), everything else is linear, so lane 0 of the next two rounds
 // needs only row 0 of M and of M^2 applied to the group's input state, and the state after the group is M^3 (entries
-// < 2^25: still one multiply-add per 32-bit half) applied to it plus three rank-one corrections: ~870 instead of 3 x 500
-// instructions (~910 before the lone products' fix-up became a select and a multiply-add, gl64_gfx950.cuh glx_mul).  `s` enters and leaves with the round constants of its next round already added.
+// < 2^21: still one multiply-add per 32-bit half) applied to it plus rank-one corrections.  The first correction is folded
+// into the state: the d_0 terms are d_0 times column 0 of M, M^2 and M^3, so word 0 is replaced by sbox(x_0) before the three
+// linear maps and only d_1 and d_2 remain.  `s` enters and leaves with the round constants of its next round already added.
 // SUBST = false: x_j = a_j (the permutation).  SUBST = true: x_j = in[j], the PoseidonGate's S-box input wires, and a[j]
 // returns the computed a_j for the constraint a_j - in[j] (gates/poseidon.rs:165-189).
 template <bool SUBST>
@@ -317,30 +318,27 @@ __device__ __forceinline__ void psd_partial_group(gl_t (&s)[12], int g, const gl
     asm volatile("" : "+s"(z));
 #endif
     const uint32_t* __restrict__ R2 = d_POSEIDON_G3_R2 + z;
-    const uint32_t* __restrict__ M3 = d_POSEIDON_G3_M3 + z;
     const uint32_t* __restrict__ V1 = d_POSEIDON_G3_V1 + z;
-    const uint32_t* __restrict__ V2 = d_POSEIDON_G3_V2 + z;
+    a[0] = s[0];
+    s[0] = psd_sbox(SUBST ? in[0] : s[0]);
     uint32_t lo[12], hi[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) { lo[i] = (uint32_t)s[i]; hi[i] = (uint32_t)(s[i] >> 32); }
-    a[0] = s[0];
-    const gl_t d0 = gl_sub(psd_sbox(SUBST ? in[0] : s[0]), s[0]);
-    const uint32_t d0l = (uint32_t)d0, d0h = (uint32_t)(d0 >> 32);
-    gl_t al = glx_mad_k(d0l, 25u, (uint64_t)(uint32_t)K[0]), ah = glx_mad_k(d0h, 25u, K[0] >> 32);      // M[0][0]
+    gl_t al = glx_mad_k(lo[0], psd_mds_entry(0, 0), (uint64_t)(uint32_t)K[0]), ah = glx_mad_k(hi[0], psd_mds_entry(0, 0), K[0] >> 32);
 #pragma unroll
-    for (int i = 0; i < 12; i++) { al = glx_mac_c(al, lo[i], psd_mds_entry(0, i)); ah = glx_mac_c(ah, hi[i], psd_mds_entry(0, i)); }
+    for (int i = 1; i < 12; i++) { al = glx_mac_c(al, lo[i], psd_mds_entry(0, i)); ah = glx_mac_c(ah, hi[i], psd_mds_entry(0, i)); }
     const gl_t a1 = psd_acc_reduce(al, ah);
     a[1] = a1;
     const gl_t d1 = gl_sub(psd_sbox(SUBST ? in[1] : a1), a1);
     const uint32_t d1l = (uint32_t)d1, d1h = (uint32_t)(d1 >> 32);
-    al = glx_mad_k(d1l, 25u, (uint64_t)(uint32_t)K[1]); ah = glx_mad_k(d1h, 25u, K[1] >> 32);      // (inline-constant coefficient first)
+    al = glx_mad_k(d1l, psd_mds_entry(0, 0), (uint64_t)(uint32_t)K[1]); ah = glx_mad_k(d1h, psd_mds_entry(0, 0), K[1] >> 32);   // (inline-constant coefficient first)
 #pragma unroll
     for (int i = 0; i < 12; i++) { const uint32_t c = R2[i]; al += (gl_t)lo[i] * c; ah += (gl_t)hi[i] * c; }
-    { const uint32_t c = V1[0]; al += (gl_t)d0l * c; ah += (gl_t)d0h * c; }
     const gl_t a2 = psd_acc_reduce(al, ah);
     a[2] = a2;
     const gl_t d2 = gl_sub(psd_sbox(SUBST ? in[2] : a2), a2);
     const uint32_t d2l = (uint32_t)d2, d2h = (uint32_t)(d2 >> 32);
+    const uint32_t* __restrict__ M3 = d_POSEIDON_G3_M3 + z;
 #pragma unroll
     for (int l0 = 0; l0 < 12; l0 += 3) {
         gl_t xl[3], xh[3];
@@ -353,7 +351,6 @@ __device__ __forceinline__ void psd_partial_group(gl_t (&s)[12], int g, const gl
             xl[k] = glx_mad_k(d2l, psd_mds_entry(l, 0), (uint64_t)(uint32_t)K[2 + l]); xh[k] = glx_mad_k(d2h, psd_mds_entry(l, 0), K[2 + l] >> 32);
 #pragma unroll
             for (int i = 0; i < 12; i++) { const uint32_t c = M3[12 * l + i]; xl[k] += (gl_t)lo[i] * c; xh[k] += (gl_t)hi[i] * c; }
-            { const uint32_t c = V2[l]; xl[k] += (gl_t)d0l * c; xh[k] += (gl_t)d0h * c; }
             { const uint32_t c = V1[l]; xl[k] += (gl_t)d1l * c; xh[k] += (gl_t)d1h * c; }
         }
         glx_acc_reduce3(xl[0], xh[0], xl[1], xh[1], xl[2], xh[2], s[l0], s[l0 + 1], s[l0 + 2]);

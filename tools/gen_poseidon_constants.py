@@ -195,12 +195,15 @@ def derive_groups(rc, M):
         a_2 = row0(M^2) T + d_0 (M m0)[0] + d_1 M[0][0]     + k2
         T'  = M^3 T + d_0 M^2 m0 + d_1 M m0 + d_2 m0        + K3          (m0 = column 0 of M)
     where k1, k2, K3 collect the round constants of rounds r+1..r+3 pushed through M.  The entries of M^2 and M^3 are
-    below 2^15 and 2^25, so every product is still ONE 32 x 32 multiply-add per 32-bit half on the GPU."""
+    below 2^13 and 2^21, so every product is still ONE 32 x 32 multiply-add per 32-bit half on the GPU.
+
+    The kernels fold d_0 into the state: V2, V1[0] and V0[0] are column 0 of M^3, M^2[0][0] and M[0][0], so with
+    T* = T except T*[0] = sbox(a_0) the three d_0 terms disappear (perm_grouped_folded)."""
     Mi = [[MDS_CIRC[(c - r) % W] + (MDS_DIAG[r] if r == c else 0) for c in range(W)] for r in range(W)]   # plain integers
     imul = lambda A, B: [[sum(A[i][t] * B[t][j] for t in range(W)) for j in range(W)] for i in range(W)]
     M2 = imul(Mi, Mi)
     M3 = imul(M2, Mi)
-    assert max(max(r) for r in M2) < 2**15 and max(max(r) for r in M3) < 2**25
+    assert max(max(r) for r in M2) < 2**13 and max(max(r) for r in M3) < 2**21
     col0 = lambda A: [A[i][0] for i in range(W)]
     G = dict(R1=Mi[0], R2=M2[0], M3=M3, V0=col0(Mi), V1=col0(M2), V2=col0(M3), K=[])
     for g in range(N_GROUPS):
@@ -273,6 +276,29 @@ def mds_mfma(s, A, K, n):
                 pair.append(tot % 2**64)
             acc.append(tuple(pair))
     return acc, [(al + (ah << 32)) % P for al, ah in acc]
+
+
+def perm_grouped_folded(state, rc, M, G):
+    """perm_grouped with d_0 folded into the state, as the kernels compute a group (poseidon.cuh psd_partial_group): word 0 becomes
+    sbox(a_0) before the three linear maps, and only the d_1 and d_2 corrections remain."""
+    dot = lambda row, v: sum(a * b for a, b in zip(row, v)) % P
+    mds = lambda s, n: [(a + c) % P for a, c in zip(mat_vec(M, s), rc[n] if n < N_ROUNDS else [0] * W)]
+    s = [(a + c) % P for a, c in zip(state, rc[0])]
+    r = 0
+    for _ in range(HALF_FULL):
+        s = mds([sbox(a) for a in s], r + 1); r += 1
+    for g in range(N_GROUPS):
+        k1, k2, K3 = G["K"][g][0], G["K"][g][1], G["K"][g][2:]
+        s = [sbox(s[0])] + s[1:]
+        a1 = (dot(G["R1"], s) + k1) % P; d1 = (sbox(a1) - a1) % P
+        a2 = (dot(G["R2"], s) + d1 * G["V0"][0] + k2) % P; d2 = (sbox(a2) - a2) % P
+        s = [(dot(G["M3"][l], s) + d1 * G["V1"][l] + d2 * G["V0"][l] + K3[l]) % P for l in range(W)]
+        r += GROUP
+    while r < HALF_FULL + N_PARTIAL:
+        s = mds([sbox(s[0])] + s[1:], r + 1); r += 1
+    for _ in range(HALF_FULL):
+        s = mds([sbox(a) for a in s], r + 1); r += 1
+    return s
 
 
 def perm_grouped(state, rc, M, G):
@@ -358,7 +384,8 @@ def emit(path, rc, T, G, F):
         "// per partial round: out[i] = s[i] + s0*COL[r][i-1]",
         arr("POSEIDON_PARTIAL_COL", flat(T["cols_w"])),
         "// GPU form of the partial rounds, three at a time (derive_groups): row 0 of M^2, M^3 row-major, column 0 of M^2 and",
-        "// of M^3 (plain integers < 2^25), and per group k1, k2, K3[12] (the round constants pushed through M)",
+        "// of M^3 (plain integers < 2^21; V2 serves the unfolded form of the model only: the kernels fold d_0 into the state), and",
+        "// per group k1, k2, K3[12] (the round constants pushed through M)",
         arr32("POSEIDON_G3_R2", G["R2"]),
         arr32("POSEIDON_G3_M3", flat(G["M3"])),
         arr32("POSEIDON_G3_V1", G["V1"]),
@@ -404,6 +431,7 @@ def main():
     for t in tests:
         assert perm_naive(t, rc, T["M"]) == perm_fast(t, rc, T), "fast != naive"
         assert perm_naive(t, rc, T["M"]) == perm_grouped(t, rc, T["M"], G), "grouped != naive"
+        assert perm_naive(t, rc, T["M"]) == perm_grouped_folded(t, rc, T["M"], G), "folded groups != naive"
     for inp, out in KATS:
         assert perm_fast(inp, rc, T) == out, "KAT mismatch"
     F = derive_mfma(rc)
@@ -419,7 +447,7 @@ def main():
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(
         HERE, "..", "plonky2_demo_amd", "csrc", "poseidon_constants.h")
     emit(out, rc, T, G, F)
-    print("ok: naive==fast==grouped on %d inputs, 4 KATs pass, MFMA layer == VALU layer; wrote %s" % (len(tests), os.path.normpath(out)))
+    print("ok: naive==fast==grouped==folded on %d inputs, 4 KATs pass, MFMA layer == VALU layer; wrote %s" % (len(tests), os.path.normpath(out)))
     return T
 
 
