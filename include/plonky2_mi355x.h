@@ -422,6 +422,9 @@ int gl_challenger_observe_hashes(gl_challenger* c, uint32_t oh, const uint64_t* 
 int gl_challenger_observe(gl_challenger* c, const uint64_t* h_elements, size_t count);
 int gl_challenger_get_challenges(gl_challenger* c, uint64_t* h_out, size_t count);
 int gl_challenger_state(const gl_challenger* c, uint64_t h_sponge_state[12], uint64_t h_input_buffer[8], uint32_t* input_len);
+/* Challenger::compact (iop/challenger.rs:146-152): absorb any pending input (one duplexing), then drop the buffered outputs, so that
+ * the next challenge comes from a fresh permutation.  evm's prove_single_table and its verifier begin every table with it. */
+int gl_challenger_compact(gl_challenger* c);
 void gl_challenger_free(gl_challenger* c) GL_NOEXCEPT;
 
 /* ---- FRI openings of any instance ------------------------------------------------------------------
@@ -586,6 +589,123 @@ int gl_stark_prove_device(gl_ctx* ctx, const gl_stark* s, const uint64_t* d_cols
  * gl_verify_openings' checks in its order.  The verifier takes FRI arity bits 1..8, as gl_verify_openings does. */
 int gl_stark_verify(const gl_stark_desc* desc, const gl_fri_params* params, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check);
 
+/* ---- STARK table sets: cross-table lookups as data ----------------------------------------------------
+ * evm/src/cross_table_lookup.rs for any number of tables: every table is a gl_stark_desc with its gl_fri_params (degree_bits may
+ * differ per table), and the lookups between them are data.  What is here: the description and its validation; the CTL running
+ * products Z -- `partial_products` (cross_table_lookup.rs:279-306) -- computed on the device and committed together with the table's
+ * permutation Zs (the from_values of evm/src/prover.rs:341-352); and the quotient with the CTL checks after the permutation checks, as
+ * phase entries per table.  With gl_challenger_compact, gl_open_at (the CTL Zs at g^-1) and gl_prove_openings on the three-batch
+ * instance a caller that keeps the transcript has every device phase of evm's prove_single_table; gl_stark_set_prove is all of them in
+ * one call on the library's challenger, gl_stark_set_verify the host verifier.  evm's own tables and trace generation, PublicValues,
+ * the recursive circuits, hiding and a lane pool for set proofs stay out of scope.
+ * Proof bytes -- PARITY UNPINNED, as for gl_stark_prove: the concatenation, in table order, of per-table proofs in that layout with
+ * two changes: the Z cap is always present, and ctl_zs_last[num_ctl_zs] (ONE word each: base-field evaluations at g^-1) stands between
+ * permutation_ctl_zs_next and quotient_polys:
+ *   trace_cap | permutation_ctl_zs_cap | quotient_polys_cap
+ *   local_values | next_values | permutation_ctl_zs[nz + nctl] | permutation_ctl_zs_next[nz + nctl] | ctl_zs_last[nctl] | quotient_polys
+ *   the FriProof of the three-batch instance | public_inputs
+ * The CTL challenges are not written: they are derived.  The size is fixed by the description.
+ * The flat encoding.  Three pools, each consumed in order:
+ *   Columns (cross_table_lookup.rs:24-116): Column k is  constant_k + sum_t coeff_t * trace[column_t]  over its column_num_terms[k]
+ *     terms (0 terms = a constant); coefficients and constants may be non-canonical; one trace column twice in a Column is refused
+ *     (the reference's debug_assert "Duplicate columns").
+ *   TableWithColumns: twc_table[i], and its twc_num_columns[i] (1..16) Columns are the next of the Column pool, followed by ONE more,
+ *     the filter Column, where twc_has_filter[i] = 1.
+ *   CrossTableLookups: lookup l takes the next lookup_num_looking[l] (1..8) TableWithColumns as its looking tables and the one after
+ *     them as its looked table; all of them have the same number of Columns (cross_table_lookup.rs:169-171).
+ * A table may stand in several lookups, be looking and looked, and stand twice in one lookup.
+ * Derived as the reference does: a table's CTL Zs are in the order of cross_table_lookup_data (cross_table_lookup.rs:220-277): lookup
+ * by lookup, challenge by challenge, the looking tables in order, then the looked one; num_ctl_zs is that of :178-185; a table's Z
+ * oracle holds its permutation Zs first, then its CTL Zs; the FriInstanceInfo is that of evm/src/stark.rs:83-142 (a third batch at
+ * g^-1 with the CTL Zs only; without a CTL Z there is no third batch). */
+#define GL_STARK_SET_MAX_TABLES 8u
+#define GL_CTL_MAX_TERMS 64u            /* per Column */
+#define GL_CTL_MAX_COLUMNS 16u          /* per TableWithColumns, the filter not counted */
+#define GL_CTL_MAX_LOOKING 8u           /* looking tables per lookup */
+#define GL_CTL_MAX_LOOKUPS 32u
+typedef struct gl_stark_set_desc {
+    uint32_t num_tables;                       /* 1..8 */
+    const gl_stark_desc* tables;               /* [num_tables] */
+    const gl_fri_params* params;               /* [num_tables] */
+    uint32_t num_ctl_columns;                  /* the Column pool */
+    const uint32_t* column_num_terms;          /* [num_ctl_columns] 0..64 */
+    const uint64_t* column_constant;           /* [num_ctl_columns] */
+    const uint32_t* term_column;               /* [sum of terms] trace column of the table the Column is used in */
+    const uint64_t* term_coeff;                /* [sum of terms] */
+    uint32_t num_twcs;                         /* the TableWithColumns pool */
+    const uint32_t* twc_table;                 /* [num_twcs] */
+    const uint32_t* twc_num_columns;           /* [num_twcs] 1..16 */
+    const uint32_t* twc_has_filter;            /* [num_twcs] 0 | 1 */
+    uint32_t num_lookups;                      /* 0..32 */
+    const uint32_t* lookup_num_looking;        /* [num_lookups] 1..8 */
+} gl_stark_set_desc;
+typedef struct gl_stark_set gl_stark_set;      /* a checked set with every table's tables and CTL programs in HBM */
+/* Validation, the same in every entry below; host code, no GPU.  Per table everything gl_stark_check refuses.  Across tables
+ * GL_ERR_ARG unless hasher, rate_bits, cap_height, num_query_rounds, proof_of_work_bits and num_challenges agree and every reduction
+ * of every table has the same arity bits (one reduction strategy).  GL_ERR_ARG for a count outside the caps above, a null table, a
+ * table index or a trace column out of range, a duplicate column in a Column, lookups whose TableWithColumns differ in their number
+ * of Columns, pools that the lookups do not consume exactly, a table with neither permutation pairs nor a CTL Z (the reference asserts
+ * "No CTL?", evm/src/prover.rs:339), and a filtered TableWithColumns on a table of constraint_degree < 3: with a filter f the
+ * transition check Z(g x) - Z(x) (f c + 1 - f) has three trace-degree factors and needs q >= 2; without one it has two and q >= 1
+ * suffices.  The gl_fri_params rules are applied to each table's three-batch instance. */
+int gl_stark_set_check(const gl_stark_set_desc* desc);
+/* The counts the description fixes for table `table`: permutation Zs (stark.rs:216-221) and CTL Zs (cross_table_lookup.rs:178-185).
+ * Host code; either out may be null. */
+int gl_stark_set_num_zs(const gl_stark_set_desc* desc, uint32_t table, uint32_t* num_permutation_zs, uint32_t* num_ctl_zs);
+/* gl_stark_create for every table and the CTL Column programs of every table uploaded once.  One context per handle, as for gl_stark. */
+int gl_stark_set_create(gl_ctx* ctx, const gl_stark_set_desc* desc, gl_stark_set** out);
+void gl_stark_set_free(gl_stark_set* s) GL_NOEXCEPT;
+/* Diagnostic: the CTL Zs of table `table` by value, h_out[num_ctl_zs][n].  d_trace_values [num_columns][n] trace VALUES on the device
+ * (may be non-canonical), ctl_challenges[num_challenges][2] = (beta, gamma) of get_grand_product_challenge_set, may be non-canonical.
+ * Z[i] = prod_{i' <= i} factor[i'] -- INCLUSIVE, unlike the permutation Zs -- with factor = combine(columns(row)) =
+ * reduce_with_powers(evals, beta) + gamma where filter(row) = 1 (or there is no filter) and 1 where filter(row) = 0; any other filter
+ * value is GL_ERR_ARG "non-binary CTL filter" (the reference asserts).  GL_ERR_ARG for a table without CTL Zs. */
+int gl_stark_set_ctl_z_values(gl_ctx* ctx, const gl_stark_set* s, uint32_t table, const uint64_t* d_trace_values, const uint64_t* ctl_challenges,
+                              uint64_t* h_out);
+/* The committed Z batch of table `table` (evm/src/prover.rs:341-352): its permutation Zs (gl_stark_permutation_zs' values under
+ * permutation_challenges[q][num_challenges][2]; null exactly for a table without pairs), then its CTL Zs. */
+int gl_stark_set_zs(gl_ctx* ctx, const gl_stark_set* s, uint32_t table, const uint64_t* d_trace_values, const uint64_t* permutation_challenges,
+                    const uint64_t* ctl_challenges, gl_batch** zs);
+/* gl_stark_quotient_values for table `table` of a set: after the Stark's constraints and the permutation checks,
+ * eval_cross_table_lookup_checks (cross_table_lookup.rs:374-414, the order of evm/src/vanishing_poly.rs): per CTL Z, in order,
+ * constraint_first_row(Z - select(f, combine(local))) and constraint_transition(Z_next - Z select(f_next, combine(next))) with
+ * select(f, x) = f x + 1 - f.  zs is the batch gl_stark_set_zs returns (permutation Zs, then CTL Zs; never null);
+ * permutation_challenges is null exactly for a table without pairs.  h_out[num_challenges][n << quotient_degree_bits]; no degree check. */
+int gl_stark_set_quotient_values(gl_ctx* ctx, const gl_stark_set* s, uint32_t table, const gl_batch* trace, const gl_batch* zs,
+                                 const uint64_t* permutation_challenges, const uint64_t* ctl_challenges, const uint64_t* alphas,
+                                 const uint64_t* public_inputs, uint64_t* h_out);
+/* The same, then what gl_stark_quotient_polys does with the values: coset_ifft, the trim_to_len(q n) check (GL_ERR_ARG where it sees a
+ * non-zero coefficient; with q a power of two it has nothing to look at), the chunks of n and from_coeffs. */
+int gl_stark_set_quotient_polys(gl_ctx* ctx, const gl_stark_set* s, uint32_t table, const gl_batch* trace, const gl_batch* zs,
+                                const uint64_t* permutation_challenges, const uint64_t* ctl_challenges, const uint64_t* alphas,
+                                const uint64_t* public_inputs, gl_batch** quotient);
+/* The size of every proof of this set. */
+size_t gl_stark_set_proof_size(const gl_stark_set* s) GL_NOEXCEPT;
+/* prove_with_traces + prove_with_commitments (evm/src/prover.rs:94-285).  h_trace_cols[num_tables] -> [num_columns of the table] -> n
+ * values (may be non-canonical); h_public_inputs[num_tables] -> [num_public_inputs of the table] (an entry may be null for a table
+ * without any).  In order: every trace committed; every trace cap observed in table order; the CTL challenge set
+ * (get_grand_product_challenge_set: beta, gamma per challenge); then per table in order, on the SAME challenger: compact; the
+ * permutation challenge sets if it has pairs; the Z batch (gl_stark_set_zs), its cap observed; alphas; the quotient, its cap observed;
+ * zeta, GL_ERR_ZETA_IN_SUBGROUP as for gl_stark_prove; StarkOpeningSet::new (evm/src/proof.rs:224-259); the openings observed in
+ * to_fri_openings order (three batches, ctl_zs_last lifted to the extension); gl_prove_openings' path on the three-batch instance.
+ * *num_bytes = gl_stark_set_proof_size(s) always.  A non-binary filter, a zero permutation denominator and a trace the trim check can see
+ * to be wrong are GL_ERR_ARG as in the phase entries; traces that are not consistent across tables yield a proof the verifier rejects. */
+int gl_stark_set_prove(gl_ctx* ctx, const gl_stark_set* s, const uint64_t* const* const* h_trace_cols, const uint64_t* const* h_public_inputs,
+                       uint8_t* h_out, size_t cap_bytes, size_t* num_bytes);
+/* the same with the traces already in HBM: d_cols[num_tables] -> [num_columns][n] (left untouched) */
+int gl_stark_set_prove_device(gl_ctx* ctx, const gl_stark_set* s, const uint64_t* const* d_cols, const uint64_t* const* h_public_inputs,
+                              uint8_t* h_out, size_t cap_bytes, size_t* num_bytes);
+/* verify_proof + verify_stark_proof_with_challenges + verify_cross_table_lookups (evm/src/verifier.rs:29-216, cross_table_lookup.rs:542-569).
+ * Host code, no GPU.  GL_OK, or GL_ERR_VERIFY with *check (may be null) = the GL_CHECK_* code of the first failing check and *table (may
+ * be null) = the table it failed in (num_tables for a check that belongs to no single table: the total length, GL_CHECK_CTL).  Order:
+ * TRUNCATED / LENGTH on the total size; the trace caps and the CTL challenges; then TABLE BY TABLE in order: its challenges
+ * (compact first), the vanishing identity at zeta over the extension field with the CTL checks on the Zs after the permutation ones
+ * (CtlCheckVars::from_proofs): VANISHING; gl_verify_openings' checks on its three-batch instance in their order; LAST, over all tables,
+ * per lookup and challenge prod looking ctl_zs_last == looked ctl_zs_last: GL_CHECK_CTL.  So a changed ctl_zs_last word is answered by the
+ * FRI checks of its table (the batch at g^-1 no longer matches the committed polynomial), not by GL_CHECK_CTL; GL_CHECK_CTL is what
+ * an honestly proven but inconsistent system gets. */
+int gl_stark_set_verify(const gl_stark_set_desc* desc, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check, uint32_t* table);
+
 /* ---- prove() ---------------------------------------------------------------------------------------*/
 /* plonk::prover::prove (plonky2/src/plonk/prover.rs:102-329) from step 4 on, i.e. given the FULL witness matrix
  * `MatrixWitness.wire_values` (iop/witness.rs:256-258) h_wires[num_wires][n] and the public inputs.  Every
@@ -672,6 +792,7 @@ int gl_host_circuit_verify(const gl_host_circuit* hc, const uint64_t* constants_
 #define GL_CHECK_STEP_MERKLE 11           /* FRI step Merkle proof fails (fri/verifier.rs:219-225) */
 #define GL_CHECK_FINAL_POLY 12            /* final polynomial evaluation is invalid (fri/verifier.rs:231-239) */
 #define GL_CHECK_DESCRIPTION 13           /* not a rejection: gl_verify answers GL_ERR_ARG, the proof is too short for the description's counts */
+#define GL_CHECK_CTL 14                   /* gl_stark_set_verify: a cross-table lookup's looking Z products differ from the looked Z (cross_table_lookup.rs:542-569) */
 const char* gl_verify_check_message(uint32_t check) GL_NOEXCEPT;
 /* VerifierCircuitData::verify for `count` proofs of one circuit.  Per proof the decode, the transcript, the vanishing identity at
  * zeta and the proof of work run on the host (on up to host_threads threads; 0 means 1, at most 64); the Merkle paths

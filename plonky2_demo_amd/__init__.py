@@ -15,4 +15,5 @@ from .api import (  # noqa: F401
     lde_onto_coset, poseidon, pow_grind, random_elements, GOLDILOCKS_ORDER, COSET_SHIFT,
     hash_from_bytes, hash_or_noop_host, hash_to_bytes, hash_to_elements, two_to_one_host, verify_fri_proof,
     Stark, StarkConfig, StarkDesc, fibonacci_stark, stark_verify,
+    CrossTableLookup, CtlColumn, StarkSet, StarkSetDesc, TableWithColumns, stark_set_verify,
 )

@@ -16,7 +16,7 @@ GL_ERR_VERIFY = 6
 # gl_batch_verifier_verify's per-proof codes (include/plonky2_mi355x.h GL_CHECK_*): the check of gl_verify that rejected the proof
 (GL_CHECK_ACCEPTED, GL_CHECK_VERIFIER_DATA, GL_CHECK_STEP_PATH_LENGTH, GL_CHECK_INITIAL_PATH_LENGTH, GL_CHECK_TRUNCATED, GL_CHECK_PUBLIC_INPUT_COUNT,
  GL_CHECK_LENGTH, GL_CHECK_VANISHING, GL_CHECK_POW, GL_CHECK_INITIAL_MERKLE, GL_CHECK_FRI_CONSISTENCY, GL_CHECK_STEP_MERKLE, GL_CHECK_FINAL_POLY,
- GL_CHECK_DESCRIPTION) = range(14)
+ GL_CHECK_DESCRIPTION, GL_CHECK_CTL) = range(15)
 ERRORS = {1: "GL_ERR_ARG", 2: "GL_ERR_HIP", 3: "GL_ERR_UNSUPPORTED", 4: "GL_ERR_ZETA_IN_SUBGROUP", 5: "GL_ERR_INTERNAL", 6: "GL_ERR_VERIFY"}
 
 
@@ -195,6 +195,20 @@ SIGNATURES = {
     "gl_stark_prove": (c_int, [c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp, c_sz, ctypes.POINTER(c_sz)]),
     "gl_stark_prove_device": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(c_sz)]),
     "gl_stark_verify": (c_int, [c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(c_u32)]),
+    # STARK table sets: cross-table lookups as data (gl_stark_set_desc*, ...)
+    "gl_challenger_compact": (c_int, [c_vp]),
+    "gl_stark_set_check": (c_int, [c_vp]),
+    "gl_stark_set_num_zs": (c_int, [c_vp, c_u32, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
+    "gl_stark_set_create": (c_int, [c_vp, c_vp, ctypes.POINTER(c_vp)]),
+    "gl_stark_set_free": (None, [c_vp]),
+    "gl_stark_set_ctl_z_values": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_vp]),
+    "gl_stark_set_zs": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)]),
+    "gl_stark_set_quotient_values": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "gl_stark_set_quotient_polys": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)]),
+    "gl_stark_set_proof_size": (c_sz, [c_vp]),
+    "gl_stark_set_prove": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(c_sz)]),
+    "gl_stark_set_prove_device": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(c_sz)]),
+    "gl_stark_set_verify": (c_int, [c_vp, c_vp, c_sz, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
 }
 GL_MAX_FRI_ORACLES, GL_MAX_FRI_BATCHES = 8, 4
 
@@ -326,6 +340,50 @@ class StarkDescStruct(ctypes.Structure):
         self.constraint_filter, self.constraint_num_terms = table(c_u32, filters), table(c_u32, num_terms)
         self.term_coeff, self.term_num_factors, self.factors = table(c_u64, coeffs), table(c_u32, num_factors), table(c_u32, factors)
         self.pair_len, self.pair_columns = table(c_u32, pair_len), table(c_u32, pair_columns)
+
+
+class StarkSetDescStruct(ctypes.Structure):
+    """gl_stark_set_desc.  tables: [(StarkDescStruct, FriParams), ...]; lookups: [([looking, ...], looked), ...] with every TableWithColumns
+    (table index, [Column, ...], filter Column or None) and every Column ([(trace column, coeff), ...], constant).  The three pools are
+    written in the order the lookups consume them.  Nothing is checked here: refusing is gl_stark_set_check's."""
+    _fields_ = [("num_tables", c_u32), ("tables", ctypes.POINTER(StarkDescStruct)), ("params", ctypes.POINTER(FriParams)),
+                ("num_ctl_columns", c_u32), ("column_num_terms", ctypes.POINTER(c_u32)), ("column_constant", ctypes.POINTER(c_u64)),
+                ("term_column", ctypes.POINTER(c_u32)), ("term_coeff", ctypes.POINTER(c_u64)),
+                ("num_twcs", c_u32), ("twc_table", ctypes.POINTER(c_u32)), ("twc_num_columns", ctypes.POINTER(c_u32)),
+                ("twc_has_filter", ctypes.POINTER(c_u32)), ("num_lookups", c_u32), ("lookup_num_looking", ctypes.POINTER(c_u32))]
+
+    def __init__(self, tables, lookups):
+        super().__init__()
+        tables = list(tables)
+        self._keep = [tables]                                  # the per-table structures own the tables the copies below point into
+        descs, params = (StarkDescStruct * max(len(tables), 1))(), (FriParams * max(len(tables), 1))()
+        for i, (desc, fri) in enumerate(tables):
+            ctypes.memmove(ctypes.byref(descs[i]), ctypes.byref(desc), ctypes.sizeof(StarkDescStruct))
+            ctypes.memmove(ctypes.byref(params[i]), ctypes.byref(fri), ctypes.sizeof(FriParams))
+        self._keep += [descs, params]
+        self.num_tables, self.tables, self.params = len(tables), descs, params
+        num_terms, constants, term_column, term_coeff, twc_table, twc_ncols, twc_filter, looking_counts = [], [], [], [], [], [], [], []
+        for looking, looked in lookups:
+            looking_counts.append(len(looking))
+            for table, columns, filter_column in list(looking) + [looked]:
+                twc_table.append(int(table))
+                twc_ncols.append(len(columns))
+                twc_filter.append(0 if filter_column is None else 1)
+                for terms, constant in list(columns) + ([] if filter_column is None else [filter_column]):
+                    num_terms.append(len(terms))
+                    constants.append(int(constant) & 0xFFFFFFFFFFFFFFFF)
+                    term_column += [int(c) & 0xFFFFFFFF for c, _ in terms]
+                    term_coeff += [int(f) & 0xFFFFFFFFFFFFFFFF for _, f in terms]
+
+        def table(ctype, values):
+            arr = (ctype * max(len(values), 1))(*values)
+            self._keep.append(arr)
+            return ctypes.cast(arr, ctypes.POINTER(ctype))
+        self.num_ctl_columns, self.num_twcs, self.num_lookups = len(num_terms), len(twc_table), len(looking_counts)
+        self.column_num_terms, self.column_constant = table(c_u32, num_terms), table(c_u64, constants)
+        self.term_column, self.term_coeff = table(c_u32, term_column), table(c_u64, term_coeff)
+        self.twc_table, self.twc_num_columns, self.twc_has_filter = table(c_u32, twc_table), table(c_u32, twc_ncols), table(c_u32, twc_filter)
+        self.lookup_num_looking = table(c_u32, looking_counts)
 
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -975,6 +975,10 @@ class Challenger(_Owned):
         check(lib.gl_challenger_get_challenges(self.handle, _p(out), n))
         return [int(x) for x in out]
 
+    def compact(self):
+        """Challenger::compact (challenger.rs:146-152): absorb pending input, drop the buffered outputs."""
+        check(lib.gl_challenger_compact(self.handle))
+
     def state(self):
         """(sponge_state[12], input_buffer) as fri_proof_of_work reads them."""
         st, buf, k = np.empty(12, dtype=np.uint64), np.empty(8, dtype=np.uint64), ctypes.c_uint32()
@@ -1155,6 +1159,203 @@ def stark_verify(desc, config, degree_bits, proof, hasher="poseidon"):
     st = lib.gl_stark_verify(ctypes.byref(desc.struct(config.num_challenges)), ctypes.byref(params), _p(buf) if buf.size else None, buf.size, ctypes.byref(code))
     ok, why = _verdict(st)
     return ok, why, code.value
+
+
+# ------------------------------------------------------------------------------------- STARK table sets: cross-table lookups
+class CtlColumn:
+    """evm's Column (cross_table_lookup.rs:24-116): a linear combination of trace columns plus a constant."""
+
+    def __init__(self, terms=(), constant=0):
+        self.terms, self.const = [(int(c), int(f)) for c, f in terms], int(constant)
+
+    @classmethod
+    def single(cls, c):
+        return cls([(c, 1)])
+
+    @classmethod
+    def singles(cls, cs):
+        return [cls.single(c) for c in cs]
+
+    @classmethod
+    def constant(cls, constant):
+        return cls([], constant)
+
+    @classmethod
+    def linear_combination(cls, terms, constant=0):
+        """linear_combination_with_constant: a duplicate column is the library's to refuse (gl_stark_set_check)."""
+        terms = list(terms)
+        if not terms:
+            raise ValueError("a linear combination has at least one term (CtlColumn.constant for none)")
+        return cls(terms, constant)
+
+    @classmethod
+    def le_bits(cls, cs):
+        return cls.linear_combination([(c, pow(2, k, GOLDILOCKS_ORDER)) for k, c in enumerate(cs)])
+
+    @classmethod
+    def sum(cls, cs):
+        return cls.linear_combination([(c, 1) for c in cs])
+
+    def flat(self):
+        return self.terms, self.const
+
+
+class TableWithColumns:
+    """cross_table_lookup.rs:141-156: a table index, its Columns and an optional filter Column."""
+
+    def __init__(self, table, columns, filter_column=None):
+        self.table, self.columns, self.filter_column = int(table), list(columns), filter_column
+
+    def flat(self):
+        return self.table, [c.flat() for c in self.columns], None if self.filter_column is None else self.filter_column.flat()
+
+
+class CrossTableLookup:
+    """cross_table_lookup.rs:158-186: the looking tables and the looked one."""
+
+    def __init__(self, looking_tables, looked_table):
+        self.looking_tables, self.looked_table = list(looking_tables), looked_table
+
+    def flat(self):
+        return [t.flat() for t in self.looking_tables], self.looked_table.flat()
+
+
+class StarkSetDesc:
+    """Tables [(StarkDesc, degree_bits), ...] under one StarkConfig, tied by cross-table lookups (gl_stark_set_desc)."""
+
+    def __init__(self, tables, lookups, config, hasher="poseidon"):
+        self.tables, self.lookups, self.config, self.hasher = [(d, int(lg)) for d, lg in tables], list(lookups), config, hasher
+
+    def fri_params(self, table):
+        return self.config.fri_params(self.tables[table][1], self.hasher)
+
+    def struct(self):
+        return _lib.StarkSetDescStruct([(d.struct(self.config.num_challenges), self.config.fri_params(lg, self.hasher)) for d, lg in self.tables],
+                                       [l.flat() for l in self.lookups])
+
+    def check(self):
+        """gl_stark_set_check: raises Plonky2Mi355xError with the refusal; needs no GPU."""
+        check(lib.gl_stark_set_check(ctypes.byref(self.struct())))
+
+    def num_zs(self, table):
+        """(permutation Zs, CTL Zs) of a table: stark.rs:216-221 and cross_table_lookup.rs:178-185."""
+        a, b = ctypes.c_uint32(), ctypes.c_uint32()
+        check(lib.gl_stark_set_num_zs(ctypes.byref(self.struct()), table, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+
+class StarkSet(_Owned):
+    """A checked table set with every table's tables and CTL programs in HBM (gl_stark_set)."""
+    _free = "gl_stark_set_free"
+
+    def __init__(self, desc, ctx=None):
+        self.ctx, self.desc = _ctx(ctx), desc
+        h = ctypes.c_void_p()
+        check(lib.gl_stark_set_create(self.ctx.handle, ctypes.byref(desc.struct()), ctypes.byref(h)))
+        self.handle = h.value
+        self.counts = [desc.num_zs(t) for t in range(len(desc.tables))]
+
+    def _trace(self, table, trace):
+        d, lg = self.desc.tables[table]
+        t = _u64(trace)
+        if t.shape != (d.num_columns, 1 << lg):
+            raise ValueError("the trace of table %d is [num_columns][n]" % table)
+        return t
+
+    def _ctl_challenges(self, ctl_challenges):
+        ch = _u64(ctl_challenges)
+        if ch.size != 2 * self.desc.config.num_challenges:
+            raise ValueError("the CTL challenges are [num_challenges][2] (beta, gamma)")
+        return ch
+
+    def _permutation_sets(self, table, permutation_challenge_sets):
+        if permutation_challenge_sets is None:
+            return None
+        sets = _u64(permutation_challenge_sets)
+        if sets.size != self.desc.tables[table][0].quotient_degree_factor * self.desc.config.num_challenges * 2:
+            raise ValueError("challenge sets are [quotient_degree_factor][num_challenges][2] (beta, gamma)")
+        return sets
+
+    @property
+    def proof_size(self):
+        return lib.gl_stark_set_proof_size(self.handle)
+
+    def prove(self, traces, public_inputs=None):
+        """prove_with_traces (evm/src/prover.rs:94-285): traces[table] = [num_columns][n] values -> the set proof's bytes."""
+        cols = [[_u64(c) for c in self._trace(t, trace)] for t, trace in enumerate(traces)]
+        if len(cols) != len(self.desc.tables):
+            raise ValueError("one trace per table")
+        pis = [_u64([] if public_inputs is None else public_inputs[t]) for t in range(len(cols))]
+        if any(pi.size != d.num_public_inputs for pi, (d, _) in zip(pis, self.desc.tables)):
+            raise ValueError("public inputs are [num_tables][num_public_inputs of the table]")
+        per_table = [(ctypes.c_void_p * len(cs))(*[c.ctypes.data for c in cs]) for cs in cols]
+        ptrs = (ctypes.c_void_p * len(cols))(*[ctypes.addressof(a) for a in per_table])
+        pi_ptrs = (ctypes.c_void_p * len(cols))(*[pi.ctypes.data if pi.size else None for pi in pis])
+        out, k = np.empty(self.proof_size, dtype=np.uint8), ctypes.c_size_t()
+        check(lib.gl_stark_set_prove(self.ctx.handle, self.handle, ptrs, pi_ptrs, _p(out), out.size, ctypes.byref(k)))
+        return out[:k.value].tobytes()
+
+    def verify(self, proof):
+        return stark_set_verify(self.desc, proof)
+
+    def ctl_z_values(self, table, trace, ctl_challenges):
+        """partial_products (cross_table_lookup.rs:279-306) of every CTL Z of a table, by value: [num_ctl_zs][n]."""
+        t, ch = self._trace(table, trace), self._ctl_challenges(ctl_challenges)
+        out = np.empty((self.counts[table][1], t.shape[1]), dtype=np.uint64)
+        d = DeviceBuffer(self.ctx, t.nbytes).upload(t)
+        try:
+            check(lib.gl_stark_set_ctl_z_values(self.ctx.handle, self.handle, table, d.ptr, _p(ch), _p(out) if out.size else None))
+        finally:
+            d.free()
+        return out
+
+    def zs(self, table, trace, permutation_challenge_sets, ctl_challenges):
+        """The committed Z batch of a table (evm/src/prover.rs:341-352): its permutation Zs, then its CTL Zs."""
+        t, ch = self._trace(table, trace), self._ctl_challenges(ctl_challenges)
+        sets = self._permutation_sets(table, permutation_challenge_sets)
+        d = DeviceBuffer(self.ctx, t.nbytes).upload(t)
+        try:
+            h = ctypes.c_void_p()
+            check(lib.gl_stark_set_zs(self.ctx.handle, self.handle, table, d.ptr, _p(sets) if sets is not None else None, _p(ch), ctypes.byref(h)))
+        finally:
+            d.free()
+        params = self.desc.fri_params(table)
+        return PolynomialBatch(h.value, self.ctx, params.rate_bits, params.cap_height)
+
+
+    def _quotient_args(self, table, trace_batch, zs_batch, permutation_challenge_sets, ctl_challenges, alphas, public_inputs):
+        d = self.desc.tables[table][0]
+        sets = self._permutation_sets(table, permutation_challenge_sets)
+        ch, al, pi = self._ctl_challenges(ctl_challenges), _u64(alphas), _u64(public_inputs)
+        if al.size != self.desc.config.num_challenges or pi.size != d.num_public_inputs:
+            raise ValueError("alphas are [num_challenges], public inputs [num_public_inputs]")
+        return (self.ctx.handle, self.handle, table, trace_batch.handle, zs_batch.handle, _p(sets) if sets is not None else None, _p(ch), _p(al),
+                _p(pi) if pi.size else None), (sets, ch, al, pi)
+
+    def quotient_values(self, table, trace_batch, zs_batch, permutation_challenge_sets, ctl_challenges, alphas, public_inputs):
+        """The quotient's values on the quotient coset with the CTL checks after the permutation checks, [num_challenges][n << qdb]."""
+        args, keep = self._quotient_args(table, trace_batch, zs_batch, permutation_challenge_sets, ctl_challenges, alphas, public_inputs)
+        d, lg = self.desc.tables[table]
+        out = np.empty((self.desc.config.num_challenges, (1 << lg) << d.quotient_degree_bits), dtype=np.uint64)
+        check(lib.gl_stark_set_quotient_values(*args, _p(out)))
+        return out
+
+    def quotient_polys(self, table, trace_batch, zs_batch, permutation_challenge_sets, ctl_challenges, alphas, public_inputs):
+        """The same, then coset_ifft, the trim_to_len check, the chunks of n and from_coeffs."""
+        args, keep = self._quotient_args(table, trace_batch, zs_batch, permutation_challenge_sets, ctl_challenges, alphas, public_inputs)
+        h = ctypes.c_void_p()
+        check(lib.gl_stark_set_quotient_polys(*args, ctypes.byref(h)))
+        params = self.desc.fri_params(table)
+        return PolynomialBatch(h.value, self.ctx, params.rate_bits, params.cap_height)
+
+
+def stark_set_verify(desc, proof):
+    """gl_stark_set_verify: needs no GPU and no handle -> (accepted, message, GL_CHECK_* code, table the check failed in)."""
+    buf = np.frombuffer(bytes(proof), dtype=np.uint8)
+    code, table = ctypes.c_uint32(), ctypes.c_uint32()
+    st = lib.gl_stark_set_verify(ctypes.byref(desc.struct()), _p(buf) if buf.size else None, buf.size, ctypes.byref(code), ctypes.byref(table))
+    ok, why = _verdict(st)
+    return ok, why, code.value, table.value
 
 
 def fibonacci_stark(num_rows):

@@ -39,6 +39,11 @@ extern "C" int gl_challenger_get_challenges(gl_challenger* c, uint64_t* h_out, s
     for (size_t i = 0; i < count; i++) h_out[i] = c->ch.challenge();
     return GL_OK;
 } catch (...) { return gl_caught(); }
+extern "C" int gl_challenger_compact(gl_challenger* c) try {
+    GL_REQUIRE(c, GL_ERR_ARG, "gl_challenger_compact: null argument");
+    c->ch.compact();
+    return GL_OK;
+} catch (...) { return gl_caught(); }
 // sponge state and pending inputs, as fri_proof_of_work reads them (fri/prover.rs:127-140): for gl_pow_grind
 extern "C" int gl_challenger_state(const gl_challenger* c, uint64_t h_sponge_state[12], uint64_t h_input_buffer[8], uint32_t* input_len) try {
     GL_REQUIRE(c && h_sponge_state && h_input_buffer && input_len, GL_ERR_ARG, "gl_challenger_state: null argument");

@@ -164,6 +164,8 @@ struct HostChallenger {
         for (size_t i = 0; i < count; i++) { gl_t e[4]; hash_to_elements(oh, h + 4 * i, e); observe_many(e, 4); }
     }
     gl_t challenge() { if (nin || !nout) duplexing(); return gl_canon(out[--nout]); }
+    // Challenger::compact (challenger.rs:146-152): pending input is absorbed, buffered outputs are dropped
+    void compact() { if (nin) duplexing(); nout = 0; }
     gl2_t challenge_ext() { gl2_t r; r.a = challenge(); r.b = challenge(); return r; }
 };
 

@@ -5,18 +5,17 @@
 #include "context.hpp"
 #include "fri_instance.hpp"
 #include "proof.hpp"
+#include "stark_internal.hpp"
 #include "stark_kernels.cuh"
 #include <algorithm>
 #include <cstring>
 #include <memory>
 #include <vector>
 
+using namespace glstark;
+
 namespace {
 
-struct StarkShape {             // what stark.rs:79-221 derives from the description
-    uint32_t q = 0, qdb = 0, num_instances = 0, nz = 0;
-    size_t terms = 0, factors = 0, column_pairs = 0;
-};
 
 // the FriInstanceInfo of stark.rs:88-137 at the points zeta, g zeta: oracles trace, (Z), quotient; batches [trace, Z, quotient] at zeta
 // and [trace, Z] at g zeta
@@ -44,7 +43,9 @@ struct StarkInstance {
     }
 };
 
-int stark_check(const gl_stark_desc* desc, const gl_fri_params* params, StarkShape* shape, bool prover = true) {
+}  // namespace
+
+int glstark::stark_check(const gl_stark_desc* desc, const gl_fri_params* params, StarkShape* shape, bool prover) {
     GL_REQUIRE(desc && params, GL_ERR_ARG, "gl_stark: null description / params");
     const gl_stark_desc& d = *desc;
     GL_REQUIRE(d.num_columns >= 1 && d.num_columns <= GL_STARK_MAX_COLUMNS, GL_ERR_ARG, "gl_stark: 1..1024 columns");
@@ -94,22 +95,6 @@ int stark_check(const gl_stark_desc* desc, const gl_fri_params* params, StarkSha
     return GL_OK;
 }
 
-}  // namespace
-
-struct gl_stark {
-    gl_ctx* ctx = nullptr;
-    gl_fri_params params;
-    StarkShape s;
-    uint32_t num_columns = 0, num_public_inputs = 0, nc = 0, num_constraints = 0;
-    size_t n = 0, size = 0;
-    void* d_tables = nullptr;   // one block: the term program, the pair tables, Z_H on the coset
-    const uint32_t* d_filter = nullptr; const uint32_t* d_num_terms = nullptr; const uint32_t* d_term_nf = nullptr; const uint32_t* d_factors = nullptr;
-    const uint32_t* d_pair_off = nullptr; const uint32_t* d_pair_cols = nullptr;
-    const gl_t* d_coeff = nullptr;
-    gl_t* d_lagrange = nullptr; // L_first | L_last on the quotient coset, [2][size]
-    gl_t zh_inv[8] = {0}, last = 0, n_inv = 0;
-    GlPowTable xt;              // 7 w_size^i
-};
 
 extern "C" int gl_stark_check(const gl_stark_desc* desc, const gl_fri_params* params) try {
     return stark_check(desc, params, nullptr);
@@ -191,22 +176,25 @@ int check_stark_args(gl_ctx* ctx, const gl_stark* s) {
     GL_REQUIRE(s->ctx == ctx, GL_ERR_ARG, "gl_stark: the stark was created on another context");
     return ctx->activate();
 }
-int check_stark_batch(const gl_stark* s, const gl_batch* b, size_t ncols, const char* what) {
+
+}  // namespace
+
+int glstark::check_stark_batch(const gl_stark* s, const gl_batch* b, size_t ncols, const char* what) {
     GL_REQUIRE(b && b->ncols == ncols && b->n == s->n && b->rate_bits == s->params.rate_bits && b->cap_height == s->params.cap_height && b->salt == 0, GL_ERR_ARG, what);
     GL_REQUIRE(b->hasher == s->params.hasher, GL_ERR_ARG, "gl_stark: a batch committed under another hasher than the params'");
     return GL_OK;
 }
 // the challenge sets [q][num_challenges][2], canonical, into a pool block (synchronises: the host source is the caller's)
-int upload_challenges(gl_ctx* ctx, const gl_stark* s, const uint64_t* challenges, DevBuf& d_ch) {
+int glstark::upload_challenges(gl_ctx* ctx, const gl_stark* s, const uint64_t* challenges, DevBuf& d_ch) {
     std::vector<gl_t> ch((size_t)s->s.q * s->nc * 2);
     for (size_t i = 0; i < ch.size(); i++) ch[i] = gl_canon(challenges[i]);
     GL_TRY(d_ch.alloc(ch.size() * sizeof(gl_t)));
     return gl_copy_h2d(ctx, d_ch.p, ch.data(), ch.size() * sizeof(gl_t));
 }
-int read_flag(gl_ctx* ctx, const uint32_t* d_flag, uint32_t* flag) { return gl_copy_d2h(ctx, flag, d_flag, sizeof *flag); }
+int glstark::read_flag(gl_ctx* ctx, const uint32_t* d_flag, uint32_t* flag) { return gl_copy_d2h(ctx, flag, d_flag, sizeof *flag); }
 
 // compute_permutation_z_polys (permutation.rs:66-117): d_trace VALUES [num_columns][n] -> d_z VALUES [nz][n]
-int permutation_z_values(gl_ctx* ctx, const gl_stark* s, const gl_t* d_trace, const gl_t* d_ch, gl_t* d_z) {
+int glstark::permutation_z_values(gl_ctx* ctx, const gl_stark* s, const gl_t* d_trace, const gl_t* d_ch, gl_t* d_z) {
     const uint32_t n = (uint32_t)s->n, nz = s->s.nz, nseg = (n + GLS_SEG - 1) / GLS_SEG;
     hipStream_t st = ctx->stream;
     DevBuf d_quot(ctx), d_seg(ctx), d_flag(ctx);
@@ -229,6 +217,8 @@ int permutation_z_values(gl_ctx* ctx, const gl_stark* s, const gl_t* d_trace, co
     GL_REQUIRE(!flag, GL_ERR_ARG, "gl_stark: a permutation denominator is zero under these challenges (probability about n / p)");
     return GL_OK;
 }
+
+namespace {
 
 // compute_quotient_polys up to the coset_ifft (prover.rs:198-311): d_out[num_challenges][size] values on the quotient coset
 int quotient_values(gl_ctx* ctx, const gl_stark* s, const gl_batch* trace, const gl_batch* zs, const gl_t* d_ch, const uint64_t* alphas, const gl_t* d_pub, gl_t* d_out) {
@@ -256,15 +246,17 @@ int quotient_values(gl_ctx* ctx, const gl_stark* s, const gl_batch* trace, const
     return GL_OK;
 }
 
+}  // namespace
+
 // what the two quotient entries share: argument checks, the uploads, the kernel; d_q[num_challenges][size]
-int quotient_phase(gl_ctx* ctx, const gl_stark* s, const gl_batch* trace, const gl_batch* zs, const uint64_t* challenges, const uint64_t* alphas,
-                   const uint64_t* public_inputs, DevBuf& d_q) {
+int glstark::quotient_phase(gl_ctx* ctx, const gl_stark* s, const gl_batch* trace, const gl_batch* zs, const uint64_t* challenges, const uint64_t* alphas,
+                   const uint64_t* public_inputs, DevBuf& d_q, uint32_t ctl_zs) {
     GL_TRY(check_stark_args(ctx, s));
     GL_REQUIRE(alphas && (public_inputs || !s->num_public_inputs), GL_ERR_ARG, "gl_stark quotient: null alphas / public inputs");
     GL_TRY(check_stark_batch(s, trace, s->num_columns, "gl_stark quotient: the trace batch does not match the description / params"));
     GL_REQUIRE((s->s.nz != 0) == (zs != nullptr) && (s->s.nz == 0 || challenges), GL_ERR_ARG,
                "gl_stark quotient: the Z batch and the challenge sets go with permutation pairs (null without)");
-    if (zs) GL_TRY(check_stark_batch(s, zs, s->s.nz, "gl_stark quotient: the Z batch does not match the description / params"));
+    if (zs) GL_TRY(check_stark_batch(s, zs, s->s.nz + ctl_zs, "gl_stark quotient: the Z batch does not match the description / params"));   // a set's: CTL Zs follow
     DevBuf d_ch(ctx), d_pub(ctx);
     if (zs) GL_TRY(upload_challenges(ctx, s, challenges, d_ch));
     std::vector<gl_t> pub(s->num_public_inputs + 1, 0);
@@ -274,8 +266,6 @@ int quotient_phase(gl_ctx* ctx, const gl_stark* s, const gl_batch* trace, const 
     GL_TRY(d_q.alloc((size_t)s->nc * s->size * sizeof(gl_t)));
     return quotient_values(ctx, s, trace, zs, d_ch.as<const gl_t>(), alphas, d_pub.as<const gl_t>(), d_q.as<gl_t>());
 }
-
-}  // namespace
 
 extern "C" int gl_stark_permutation_zs(gl_ctx* ctx, const gl_stark* s, const uint64_t* d_trace_values, const uint64_t* challenges, gl_batch** zs) try {
     GL_REQUIRE(zs, GL_ERR_ARG, "gl_stark_permutation_zs: null out");
@@ -298,12 +288,8 @@ extern "C" int gl_stark_quotient_values(gl_ctx* ctx, const gl_stark* s, const gl
     return gl_copy_d2h(ctx, h_out, d_q.p, (size_t)s->nc * s->size * sizeof(gl_t));
 } catch (...) { return gl_caught(); }
 
-extern "C" int gl_stark_quotient_polys(gl_ctx* ctx, const gl_stark* s, const gl_batch* trace, const gl_batch* zs, const uint64_t* challenges,
-                                       const uint64_t* alphas, const uint64_t* public_inputs, gl_batch** quotient) try {
-    GL_REQUIRE(quotient, GL_ERR_ARG, "gl_stark_quotient_polys: null out");
-    *quotient = nullptr;
-    DevBuf d_q(ctx);
-    GL_TRY(quotient_phase(ctx, s, trace, zs, challenges, alphas, public_inputs, d_q));
+// the quotient's values d_q[num_challenges][size] on the coset -> the committed chunk polynomials (prover.rs:114-144)
+int glstark::quotient_commit(gl_ctx* ctx, const gl_stark* s, DevBuf& d_q, gl_batch** quotient) {
     const uint32_t lgS = s->params.degree_bits + s->s.qdb, size = (uint32_t)s->size, keep = (uint32_t)(s->s.q * s->n);
     hipStream_t st = ctx->stream;
     // values.coset_ifft(F::coset_shift()) (prover.rs:313-317)
@@ -324,6 +310,15 @@ extern "C" int gl_stark_quotient_polys(gl_ctx* ctx, const gl_stark* s, const gl_
     for (uint32_t j = 0; j < s->nc; j++)
         GL_CHECK_HIP(hipMemcpyAsync(d_c.as<gl_t>() + (size_t)j * keep, d_q.as<gl_t>() + (size_t)j * size, (size_t)keep * sizeof(gl_t), hipMemcpyDeviceToDevice, st));
     return gl_batch_from_device_h(ctx, s->params.hasher, d_c.as<uint64_t>(), (size_t)s->nc * s->s.q, s->n, s->params.rate_bits, s->params.cap_height, 0, quotient);
+}
+
+extern "C" int gl_stark_quotient_polys(gl_ctx* ctx, const gl_stark* s, const gl_batch* trace, const gl_batch* zs, const uint64_t* challenges,
+                                       const uint64_t* alphas, const uint64_t* public_inputs, gl_batch** quotient) try {
+    GL_REQUIRE(quotient, GL_ERR_ARG, "gl_stark_quotient_polys: null out");
+    *quotient = nullptr;
+    DevBuf d_q(ctx);
+    GL_TRY(quotient_phase(ctx, s, trace, zs, challenges, alphas, public_inputs, d_q));
+    return quotient_commit(ctx, s, d_q, quotient);
 } catch (...) { return gl_caught(); }
 
 // ---- the whole prover and the verifier (starky/src/prover.rs:32-194, verifier.rs:21-145) -------------------------------------------
@@ -345,7 +340,9 @@ size_t stark_proof_bytes(const gl_fri_params& p, uint32_t num_columns, uint32_t 
     return (s.nz ? 3 : 2) * (hash_wire_bytes(p.hasher) << p.cap_height) + 16 * (2 * (size_t)num_columns + 2 * (size_t)s.nz + (size_t)s.q * nc) +
            fri_proof_bytes(p, num_columns, nc, s) + 8 * (size_t)num_public_inputs;
 }
-gl2_t ext_pow2(gl2_t x, unsigned k) { for (unsigned i = 0; i < k; i++) x = gl2_mul(x, x); return gl2_canon(x); }
+}  // namespace
+gl2_t glstark::ext_pow2(gl2_t x, unsigned k) { for (unsigned i = 0; i < k; i++) x = gl2_mul(x, x); return gl2_canon(x); }
+namespace {
 
 int stark_prove_device(gl_ctx* ctx, const gl_stark* s, const uint64_t* d_cols, const uint64_t* h_public_inputs, uint8_t* h_out, size_t cap_bytes, size_t* num_bytes) {
     GL_TRY(check_stark_args(ctx, s));
@@ -415,23 +412,15 @@ int stark_prove_device(gl_ctx* ctx, const gl_stark* s, const uint64_t* d_cols, c
     return GL_OK;
 }
 
-struct VCursor {                                       // little-endian reader over the proof bytes
-    const uint8_t* p; size_t len, pos = 0;
-    uint64_t u64() { uint64_t v = 0; for (int i = 0; i < 8; i++) v |= (uint64_t)p[pos + i] << (8 * i); pos += 8; return v; }
-    void words(gl_t* out, size_t k) { for (size_t i = 0; i < k; i++) out[i] = gl_canon(u64()); }       // read_field takes a word mod p
-    void hashes(uint32_t hasher, gl_t* out, size_t k) {
-        if (hasher != GL_HASHER_KECCAK) { words(out, 4 * k); return; }
-        for (size_t i = 0; i < k; i++) { for (int w = 0; w < 3; w++) out[4 * i + w] = u64(); out[4 * i + 3] = p[pos++]; }
-    }
-};
-int stark_reject(uint32_t code, uint32_t* check) {
+}  // namespace
+
+int glstark::stark_reject(uint32_t code, uint32_t* check) {
     if (check) *check = code;
     return gl_fail(GL_ERR_VERIFY, gl_verify_check_message(code), __FILE__, __LINE__);
 }
-inline gl2_t e_of(gl_t v) { return gl2_make(gl_canon(v), 0); }
 
 // eval_vanishing_poly at zeta over the extension field (vanishing_poly.rs, verifier.rs:81-106): the host interpreter of the term list
-void vanishing_at(const gl_stark_desc& d, const StarkShape& s, const gl2_t* local, const gl2_t* next, const gl_t* pub, const gl_t* alphas, gl2_t z_last,
+void glstark::vanishing_at(const gl_stark_desc& d, const StarkShape& s, const gl2_t* local, const gl2_t* next, const gl_t* pub, const gl_t* alphas, gl2_t z_last,
                   gl2_t l_first, gl2_t l_last, const gl2_t* zs, const gl2_t* zs_next, const gl_t* sets, gl2_t* accs) {
     const uint32_t nc = d.num_challenges;
     for (uint32_t j = 0; j < nc; j++) accs[j] = gl2_make(0, 0);
@@ -469,8 +458,6 @@ void vanishing_at(const gl_stark_desc& d, const StarkShape& s, const gl2_t* loca
         consume(gl2_sub(prd, pl));
     }
 }
-
-}  // namespace
 
 extern "C" size_t gl_stark_proof_size(const gl_stark* s) noexcept {
     return s ? stark_proof_bytes(s->params, s->num_columns, s->num_public_inputs, s->nc, s->s) : 0;
@@ -553,3 +540,11 @@ extern "C" int gl_stark_verify(const gl_stark_desc* desc, const gl_fri_params* p
     const StarkInstance si(ncols, nc, s, zeta, gl2_canon(gl2_scalar(zeta, g)));
     return gl_verify_openings(&p, &si.inst, caps.data(), openings.data(), &ch, fri, fri_len, check);
 } catch (...) { return gl_caught(); }
+
+// the launches of k_stark_seg_products and k_stark_seg_scan for the other running products (stark_set.hip): d_seg[nz][nseg] becomes the
+// exclusive prefix of the segment products of d_fac[nz][n]
+void glstark::seg_products_scan(hipStream_t st, const gl_t* d_fac, uint32_t n, uint32_t nz, gl_t* d_seg) {
+    const uint32_t nseg = (n + GLS_SEG - 1) / GLS_SEG;
+    hipLaunchKernelGGL(k_stark_seg_products, dim3(nseg, nz), dim3(256), 0, st, d_fac, n, d_seg);
+    hipLaunchKernelGGL(k_stark_seg_scan, dim3((nz + 63) / 64), dim3(64), 0, st, d_seg, nseg, nz);
+}

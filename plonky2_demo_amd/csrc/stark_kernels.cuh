@@ -9,10 +9,8 @@
 // loads are scalar and every branch on the program is uniform.  All values are exact field elements.
 #pragma once
 #include "gl64.cuh"
+#include "stark_segments.cuh"
 #include "../../include/plonky2_mi355x.h"
-
-#define GLS_SEG 2048            // rows per workgroup segment of the scan (256 threads x 8)
-#define GLS_ROWS 8              // rows per thread of k_stark_perm_quotients: one inversion for 8 denominators
 
 struct GlStarkPerm {
     const gl_t* trace;          // trace VALUES [num_columns][n]

@@ -265,6 +265,7 @@ const char* glverify::check_message(uint32_t check) noexcept {
         case GL_CHECK_STEP_MERKLE: return "FRI step Merkle proof fails";
         case GL_CHECK_FINAL_POLY: return "final polynomial evaluation is invalid";
         case GL_CHECK_DESCRIPTION: return "gl_verify: a count of the description exceeds what the proof bytes can hold";
+        case GL_CHECK_CTL: return "cross-table lookup verification failed: the looking tables' Z products differ from the looked table's";
     }
     return "unknown check";
 }
