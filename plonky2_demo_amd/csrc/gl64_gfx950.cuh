@@ -325,6 +325,58 @@ __device__ __forceinline__ void glx_acc_reduce3(gl_t alA, gl_t ahA, gl_t alB, gl
         : [tA] "v"(topA), [loA] "v"(loA), [tB] "v"(topB), [loB] "v"(loB), [tC] "v"(topC), [loC] "v"(loC));
     rA = glx_add_eps_if(zA, eA); rB = glx_add_eps_if(zB, eB); rC = glx_add_eps_if(zC, eC);
 }
+// acc + x * c (mod 2^64) for a wave-uniform c, with the carry-out the instruction writes anyway kept as a lane mask: the last term of
+// an accumulator that may wrap once (the M^4 step of psd_partial_group4)
+__device__ __forceinline__ gl_t glx_mac_co(gl_t acc, uint32_t x, uint32_t c, uint64_t& carry) {
+    asm("v_mad_u64_u32 %0, %1, %2, %3, %0" : "+v"(acc), "=s"(carry) : "v"(x), "s"(c));
+    return acc;
+}
+// glx_acc_reduce3 for accumulators that may have wrapped: the value of a pair is al + wl 2^64 + (ah + wh 2^64) 2^32 with al, ah any
+// 64-bit words and wl, wh the carry masks of glx_mac_co (an accumulator is a 64-bit word plus one 32 x 32 product: below 2^65 - 2^33).  2^64 = EPS and
+// 2^96 = -1 (mod p).  The hot path is glx_acc_reduce3's, instruction for instruction; the carry out of `top` (ah >= 2^64 - 2^32 and a
+// carry from the middle word: worth 2^96 as well, and never together with wh) is the mask the second add writes anyway.  The
+// scalar unit combines the nine masks; a wave with any of them set -- an accumulator is ~5.5 sigma below 2^64 on random data --
+// adds EPS and subtracts 1 in a cold block.
+__device__ __forceinline__ void glx_acc_reduce3w(gl_t alA, gl_t ahA, uint64_t wlA, uint64_t whA, gl_t alB, gl_t ahB, uint64_t wlB, uint64_t whB,
+                                                 gl_t alC, gl_t ahC, uint64_t wlC, uint64_t whC, gl_t& rA, gl_t& rB, gl_t& rC) {
+    typedef uint32_t u32;
+    u32 w1A = (u32)(alA >> 32), topA = (u32)(ahA >> 32), w1B = (u32)(alB >> 32), topB = (u32)(ahB >> 32), w1C = (u32)(alC >> 32), topC = (u32)(ahC >> 32);
+    uint64_t sA, sB, sC;
+    asm("v_add_co_u32_e64 %[w1A], %[sA], %[w1A], %[lA]\n\t"
+        "v_add_co_u32_e64 %[w1B], %[sB], %[w1B], %[lB]\n\t"
+        "v_add_co_u32_e64 %[w1C], %[sC], %[w1C], %[lC]\n\t"
+        "v_addc_co_u32_e64 %[tA], %[sA], 0, %[tA], %[sA]\n\t"
+        "v_addc_co_u32_e64 %[tB], %[sB], 0, %[tB], %[sB]\n\t"
+        "v_addc_co_u32_e64 %[tC], %[sC], 0, %[tC], %[sC]"
+        : [w1A] "+v"(w1A), [tA] "+v"(topA), [w1B] "+v"(w1B), [tB] "+v"(topB), [w1C] "+v"(w1C), [tC] "+v"(topC), [sA] "=&s"(sA), [sB] "=&s"(sB), [sC] "=&s"(sC)
+        : [lA] "v"((u32)ahA), [lB] "v"((u32)ahB), [lC] "v"((u32)ahC));
+    const gl_t loA = glx_mk64((u32)alA, w1A), loB = glx_mk64((u32)alB, w1B), loC = glx_mk64((u32)alC, w1C);
+    gl_t zA, zB, zC;
+    uint64_t cA, cB, cC;
+    u32 eA, eB, eC;
+    asm("v_mad_u64_u32 %[zA], %[cA], %[tA], -1, %[loA]\n\t"
+        "v_mad_u64_u32 %[zB], %[cB], %[tB], -1, %[loB]\n\t"
+        "v_mad_u64_u32 %[zC], %[cC], %[tC], -1, %[loC]\n\t"
+        "v_cndmask_b32_e64 %[eA], 0, 1, %[cA]\n\t"
+        "v_cndmask_b32_e64 %[eB], 0, 1, %[cB]\n\t"
+        "v_cndmask_b32_e64 %[eC], 0, 1, %[cC]"
+        : [zA] "=&v"(zA), [cA] "=&s"(cA), [zB] "=&v"(zB), [cB] "=&s"(cB), [zC] "=&v"(zC), [cC] "=&s"(cC), [eA] "=&v"(eA), [eB] "=&v"(eB), [eC] "=&v"(eC)
+        : [tA] "v"(topA), [loA] "v"(loA), [tB] "v"(topB), [loB] "v"(loB), [tC] "v"(topC), [loC] "v"(loC));
+    rA = glx_add_eps_if(zA, eA); rB = glx_add_eps_if(zB, eB); rC = glx_add_eps_if(zC, eC);
+    const uint64_t nA = whA | sA, nB = whB | sB, nC = whC | sC;          // worth -1 each
+    if (__builtin_expect((wlA | wlB | wlC | nA | nB | nC) != 0, 0)) {
+        u32 pA, pB, pC, mA, mB, mC;
+        asm("v_cndmask_b32_e64 %[pA], 0, -1, %[wlA]\n\t"
+            "v_cndmask_b32_e64 %[pB], 0, -1, %[wlB]\n\t"
+            "v_cndmask_b32_e64 %[pC], 0, -1, %[wlC]\n\t"
+            "v_cndmask_b32_e64 %[mA], 0, 1, %[nA]\n\t"
+            "v_cndmask_b32_e64 %[mB], 0, 1, %[nB]\n\t"
+            "v_cndmask_b32_e64 %[mC], 0, 1, %[nC]"
+            : [pA] "=&v"(pA), [pB] "=&v"(pB), [pC] "=&v"(pC), [mA] "=&v"(mA), [mB] "=&v"(mB), [mC] "=&v"(mC)
+            : [wlA] "s"(wlA), [wlB] "s"(wlB), [wlC] "s"(wlC), [nA] "s"(nA), [nB] "s"(nB), [nC] "s"(nC));
+        rA = gl_sub(gl_add(rA, (gl_t)pA), (gl_t)mA); rB = gl_sub(gl_add(rB, (gl_t)pB), (gl_t)mB); rC = gl_sub(gl_add(rC, (gl_t)pC), (gl_t)mC);
+    }
+}
 
 // ---- canonical arithmetic for the NTT butterflies: operands < p in, results < p out (one fix-up each instead of two) ----------
 __device__ __forceinline__ gl_t glx_canon(gl_t x) { return glx_add_eps_if(x, (x >= GL_P) ? 1u : 0u); }          // x - p mod 2^64
@@ -524,6 +576,9 @@ template <int E>
 __device__ gl_t glx_shl_c(gl_t x);
 __device__ gl_t glx_acc_reduce(gl_t al, gl_t ah);
 __device__ void glx_acc_reduce3(gl_t alA, gl_t ahA, gl_t alB, gl_t ahB, gl_t alC, gl_t ahC, gl_t& rA, gl_t& rB, gl_t& rC);
+__device__ gl_t glx_mac_co(gl_t acc, uint32_t x, uint32_t c, uint64_t& carry);
+__device__ void glx_acc_reduce3w(gl_t alA, gl_t ahA, uint64_t wlA, uint64_t whA, gl_t alB, gl_t ahB, uint64_t wlB, uint64_t whB,
+                                 gl_t alC, gl_t ahC, uint64_t wlC, uint64_t whC, gl_t& rA, gl_t& rB, gl_t& rC);
 struct GlxWideAcc2 {
     gl_t a0[2], a1[2], a2[2];
     uint32_t k0[2], k1[2], k2[2];

@@ -7,6 +7,9 @@
 // structure; the MDS layer exploits the 6-bit circulant entries: every state word is split into 32-bit halves and the two
 // 12-term dot products are accumulated in 64-bit registers without intermediate reduction (v_mad_u64_u32), followed by
 // one 96-bit reduction per output word -- the same lazy-reduction idea as poseidon.rs:176-198.
+// The linear layers between the S-box layer of full round 3 and full round 26 -- that round's MDS layer and the 22 partial rounds',
+// 23 maps with 22 one-word S-boxes between them -- run in groups of 4 + 4 + 4 + 4 + 4 + 3 (psd_partial_group4, psd_partial_group_k):
+// six dense maps (five M^4, one M^3) instead of one per round, the S-boxes of a group fed by single rows of M, M^2, M^3.
 // Host (Challenger, public_inputs_hash, witness rows, verifier): the factorised "fast" partial rounds of
 // poseidon.rs:311-366,399-427 with 128-bit lazy dot products; its tables are derived by tools/gen_poseidon_constants.py.
 #pragma once
@@ -212,6 +215,9 @@ GL_HD void psd_mds_then_constants(gl_t (&s)[12], const gl_t* __restrict__ rc) {
 #ifndef PSD_MDS_MFMA
 #define PSD_MDS_MFMA 1                  // default MDS layer of the hash kernels (-DPSD_MDS_MFMA=0: the VALU layer)
 #endif
+#ifndef PSD_GROUP4
+#define PSD_GROUP4 1                    // partial rounds of the permutation in groups of four maps (-DPSD_GROUP4=0: three rounds at a time)
+#endif
 enum { PSD_LAYER_VALU = 0, PSD_LAYER_MFMA = 1, PSD_LAYER_HASH = PSD_MDS_MFMA ? PSD_LAYER_MFMA : PSD_LAYER_VALU };
 #if defined(__HIPCC__)
 typedef int psd_i32x4 __attribute__((ext_vector_type(4)));
@@ -308,9 +314,10 @@ GL_HD void psd_sbox_all(gl_t (&s)[12]) {
 // linear maps and only d_1 and d_2 remain.  `s` enters and leaves with the round constants of its next round already added.
 // SUBST = false: x_j = a_j (the permutation).  SUBST = true: x_j = in[j], the PoseidonGate's S-box input wires, and a[j]
 // returns the computed a_j for the constraint a_j - in[j] (gates/poseidon.rs:165-189).
+// K: the group's k1, k2, K3[12] (psd_partial_group: group g of the three-round grouping; the permutation's last, three-map group
+// passes its own constants)
 template <bool SUBST>
-__device__ __forceinline__ void psd_partial_group(gl_t (&s)[12], int g, const gl_t* in, gl_t* a) {
-    const gl_t* __restrict__ K = d_POSEIDON_G3_K + 14 * g;
+__device__ __forceinline__ void psd_partial_group_k(gl_t (&s)[12], const gl_t* __restrict__ K, const gl_t* in, gl_t* a) {
     // the matrix constants are re-read (scalar loads) in every group: hoisted out of the loop they exceed the SGPR file
     // and get parked in VGPR lanes (250 v_readlane per group)
     uint32_t z = 0;
@@ -356,6 +363,67 @@ __device__ __forceinline__ void psd_partial_group(gl_t (&s)[12], int g, const gl
         glx_acc_reduce3(xl[0], xh[0], xl[1], xh[1], xl[2], xh[2], s[l0], s[l0 + 1], s[l0 + 2]);
     }
 }
+template <bool SUBST>
+__device__ __forceinline__ void psd_partial_group(gl_t (&s)[12], int g, const gl_t* in, gl_t* a) {
+    psd_partial_group_k<SUBST>(s, d_POSEIDON_G3_K + 14 * g, in, a);
+}
+
+// Four linear maps at once (tools/gen_poseidon_constants.py derive_groups4, perm_grouped4), the permutation only.  Same folded
+// convention: `s` enters and leaves with the constants of its next round added and word 0 is S-boxed before the maps -- by this
+// function, except in the head group (fold = false), which starts right behind the S-box layer of full round 3 and takes that
+// round's MDS layer as its first map.  a_1, a_2, a_3 need row 0 of M, M^2, M^3; the state after the group is M^4 s plus d_1, d_2, d_3
+// times column 0 of M^3, M^2, M.  M^4 has 29-bit entries, still one multiply-add per 32-bit half, but its row sums are up to
+// 1.04 2^32: an accumulator of the last step can wrap, once (its true value is below 2^65).  The terms are ordered so that only the
+// last multiply-add can carry -- d_3 col0(M) + K first, columns 1..11, d_1, d_2, and column 0 of M^4, the largest entry of every
+// row, last (the generator asserts that everything before it is below 2^64) -- and glx_acc_reduce3w takes its carry-out.
+__device__ __forceinline__ void psd_partial_group4(gl_t (&s)[12], const gl_t* __restrict__ K, bool fold) {
+    uint32_t z = 0;
+    asm volatile("" : "+s"(z));            // the matrix constants are re-read in every group (psd_partial_group_k)
+    const uint32_t* __restrict__ R2 = d_POSEIDON_G3_R2 + z;
+    const uint32_t* __restrict__ R3 = d_POSEIDON_G3_M3 + z;        // row 0 of M^3
+    const uint32_t* __restrict__ V2 = d_POSEIDON_G3_V1 + z;        // column 0 of M^2
+    const uint32_t* __restrict__ V3 = d_POSEIDON_G3_V2 + z;        // column 0 of M^3
+    if (fold) s[0] = psd_sbox(s[0]);       // wave-uniform
+    uint32_t lo[12], hi[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) { lo[i] = (uint32_t)s[i]; hi[i] = (uint32_t)(s[i] >> 32); }
+    gl_t al = glx_mad_k(lo[0], psd_mds_entry(0, 0), (uint64_t)(uint32_t)K[0]), ah = glx_mad_k(hi[0], psd_mds_entry(0, 0), K[0] >> 32);
+#pragma unroll
+    for (int i = 1; i < 12; i++) { al = glx_mac_c(al, lo[i], psd_mds_entry(0, i)); ah = glx_mac_c(ah, hi[i], psd_mds_entry(0, i)); }
+    const gl_t a1 = psd_acc_reduce(al, ah);
+    const gl_t d1 = gl_sub(psd_sbox(a1), a1);
+    const uint32_t d1l = (uint32_t)d1, d1h = (uint32_t)(d1 >> 32);
+    al = glx_mad_k(d1l, psd_mds_entry(0, 0), (uint64_t)(uint32_t)K[1]); ah = glx_mad_k(d1h, psd_mds_entry(0, 0), K[1] >> 32);
+#pragma unroll
+    for (int i = 0; i < 12; i++) { const uint32_t c = R2[i]; al += (gl_t)lo[i] * c; ah += (gl_t)hi[i] * c; }
+    const gl_t a2 = psd_acc_reduce(al, ah);
+    const gl_t d2 = gl_sub(psd_sbox(a2), a2);
+    const uint32_t d2l = (uint32_t)d2, d2h = (uint32_t)(d2 >> 32);
+    al = glx_mad_k(d2l, psd_mds_entry(0, 0), (uint64_t)(uint32_t)K[2]); ah = glx_mad_k(d2h, psd_mds_entry(0, 0), K[2] >> 32);
+#pragma unroll
+    for (int i = 0; i < 12; i++) { const uint32_t c = R3[i]; al += (gl_t)lo[i] * c; ah += (gl_t)hi[i] * c; }
+    { const uint32_t c = V2[0]; al += (gl_t)d1l * c; ah += (gl_t)d1h * c; }           // below 2^63 in all: 21-bit entries
+    const gl_t a3 = psd_acc_reduce(al, ah);
+    const gl_t d3 = gl_sub(psd_sbox(a3), a3);
+    const uint32_t d3l = (uint32_t)d3, d3h = (uint32_t)(d3 >> 32);
+    const uint32_t* __restrict__ M4 = d_POSEIDON_G4_M4 + z;
+#pragma unroll
+    for (int l0 = 0; l0 < 12; l0 += 3) {
+        gl_t xl[3], xh[3];
+        uint64_t wl[3], wh[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const int l = l0 + k;
+            xl[k] = glx_mad_k(d3l, psd_mds_entry(l, 0), (uint64_t)(uint32_t)K[3 + l]); xh[k] = glx_mad_k(d3h, psd_mds_entry(l, 0), K[3 + l] >> 32);
+#pragma unroll
+            for (int i = 1; i < 12; i++) { const uint32_t c = M4[12 * l + i]; xl[k] += (gl_t)lo[i] * c; xh[k] += (gl_t)hi[i] * c; }
+            { const uint32_t c = V3[l]; xl[k] += (gl_t)d1l * c; xh[k] += (gl_t)d1h * c; }
+            { const uint32_t c = V2[l]; xl[k] += (gl_t)d2l * c; xh[k] += (gl_t)d2h * c; }
+            { const uint32_t c = M4[12 * l]; xl[k] = glx_mac_co(xl[k], lo[0], c, wl[k]); xh[k] = glx_mac_co(xh[k], hi[0], c, wh[k]); }
+        }
+        glx_acc_reduce3w(xl[0], xh[0], wl[0], wh[0], xl[1], xh[1], wl[1], wh[1], xl[2], xh[2], wl[2], wh[2], s[l0], s[l0 + 1], s[l0 + 2]);
+    }
+}
 #endif
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -373,12 +441,22 @@ __device__ __forceinline__ void psd_permute_layer(gl_t (&s)[12]) {
     if constexpr (LAYER == PSD_LAYER_MFMA) A = psd_mfma_a();
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = gl_add_c(s[i], rc[i]);
+#if PSD_GROUP4
+    // three full rounds and the S-box layer of the fourth; its MDS layer and those of the 22 partial rounds are 23 linear maps with
+    // 22 one-word S-boxes between them, run as 4 + 4 + 4 + 4 + 4 + 3 (six dense maps): five groups of four, one of three
+#pragma unroll 1
+    for (int r = 0; r < 4; r++) { psd_sbox_all(s); if (r < 3) psd_mds_layer<LAYER, true>(s, r + 1, A); }
+#pragma unroll 1
+    for (int g = 0; g < POSEIDON_G4_GROUPS; g++) psd_partial_group4(s, d_POSEIDON_G4_K + 15 * g, g != 0);
+    { gl_t a[3]; psd_partial_group_k<false>(s, d_POSEIDON_G4_K + 15 * POSEIDON_G4_GROUPS, nullptr, a); }
+#else
 #pragma unroll 1
     for (int r = 0; r < 4; r++) { psd_sbox_all(s); psd_mds_layer<LAYER, true>(s, r + 1, A); }
 #pragma unroll 1
     for (int g = 0; g < POSEIDON_PARTIAL_GROUPS; g++) { gl_t a[3]; psd_partial_group<false>(s, g, nullptr, a); }
 #pragma unroll 1
     for (int r = 4 + 3 * POSEIDON_PARTIAL_GROUPS; r < 4 + POSEIDON_PARTIAL_ROUNDS; r++) { s[0] = psd_sbox(s[0]); psd_mds_layer<LAYER, true>(s, r + 1, A); }
+#endif
 #pragma unroll 1
     for (int r = 4 + POSEIDON_PARTIAL_ROUNDS; r < 7 + POSEIDON_PARTIAL_ROUNDS; r++) { psd_sbox_all(s); psd_mds_layer<LAYER, true>(s, r + 1, A); }
     psd_sbox_all(s);

@@ -216,6 +216,109 @@ def derive_groups(rc, M):
     return G
 
 
+GROUP4_SPLIT = [4, 4, 4, 4, 4, 3]          # the 23 linear maps behind the S-box layer of full round 3: the MDS layer of that round and
+                                           # those of the 22 partial rounds, with the 22 one-word S-boxes between them
+assert sum(GROUP4_SPLIT) == N_PARTIAL + 1
+
+
+def derive_groups4(rc, M):
+    """GPU formulation of the partial rounds in groups of g linear maps, g = 4 and 3 (poseidon.cuh psd_partial_group4), folded
+    convention: the state s enters and leaves with the constants of its next round added, and word 0 is S-boxed before the maps
+    (the head group starts behind the S-box layer of full round 3, where it already is).  With d_0 = 0 by the fold,
+        a_j = row0(M^j) s + sum_{0<i<j} (M^(j-i))[0][0] d_i + k_j,   d_j = sbox(a_j) - a_j          (0 < j < g)
+        out = M^g s + sum_{0<i<g} col0(M^(g-i)) d_i + K
+    Map m of the 23 (m = 0: the MDS layer of full round 3) is followed by the constants of round m + 4; a group whose first map is
+    m has c_i = rc[m + i + 3], v_1 = c_1, v_i = M v_(i-1) + c_i, k_j = v_j[0], K = v_g.
+
+    M^4 has 29-bit entries: still one multiply-add per 32-bit half, but the row sums exceed 2^32 (by at most 4 %), so a 64-bit
+    accumulator of the last step can wrap -- once: its true value stays below 2^65.  The kernels add the terms in the order of
+    group4_last_step below: column 0 of M^4, the largest entry of every row, goes last, and everything before it stays below 2^64,
+    so only the carry-out of the final multiply-add has to be kept.  Asserted here for every row."""
+    Mi = [[MDS_CIRC[(c - r) % W] + (MDS_DIAG[r] if r == c else 0) for c in range(W)] for r in range(W)]   # plain integers
+    imul = lambda A, B: [[sum(A[i][t] * B[t][j] for t in range(W)) for j in range(W)] for i in range(W)]
+    M2 = imul(Mi, Mi)
+    M3 = imul(M2, Mi)
+    M4 = imul(M3, Mi)
+    col0 = lambda A: [A[i][0] for i in range(W)]
+    assert max(max(r) for r in M4).bit_length() == 29 and max(max(r) for r in M3).bit_length() == 21 and max(col0(M3)).bit_length() == 21
+    H = 2**32 - 1                                              # the largest 32-bit half
+    for l in range(W):
+        before_last = H + H * (Mi[l][0] + sum(M4[l][1:]) + M3[l][0] + M2[l][0])       # K half, d_3, columns 1..11, d_1, d_2
+        assert before_last < 2**64, "row %d: a partial sum before the last term can wrap" % l
+        assert before_last + H * M4[l][0] < 2**65, "row %d: an accumulator can wrap twice" % l
+        assert M4[l][0] == max(M4[l])
+    # a_1, a_2, a_3 and the last step of a three-map group cannot wrap at all
+    assert H + H * (sum(M3[0]) + M2[0][0] + Mi[0][0]) < 2**63 and H + H * (max(sum(r) for r in M3) + max(col0(M2)) + max(col0(Mi))) < 2**63
+    G = dict(split=GROUP4_SPLIT, M1=Mi, M2=M2, M3=M3, M4=M4, K=[], first_map=[])
+    m = 0
+    for g in GROUP4_SPLIT:
+        v = rc[m + 4][:]
+        ks = [v[0]]
+        for i in range(2, g + 1):
+            nxt = rc[m + i + 3] if m + i + 3 < N_ROUNDS else [0] * W
+            v = [(a + b) % P for a, b in zip(mat_vec(M, v), nxt)]
+            if i < g:
+                ks.append(v[0])
+        G["K"].append(ks + v)                                  # g - 1 scalars, then K[12]
+        G["first_map"].append(m)
+        m += g
+    return G
+
+
+def group4_last_step(G, g, s, d, K):
+    """The accumulators of the last step of a group of g maps, term by term in the kernels' order: for every output word the lo-half
+    and the hi-half sum as integers (not reduced mod 2^64) and whether each wrapped at 2^64.  s: the folded input state (u64 words),
+    d: [d_1 .. d_(g-1)].  The order: d_(g-1) col0(M) + K (the multiply-add that carries the constant), columns 1..11 of M^g,
+    the remaining d_i, and column 0 of M^g last."""
+    pw = {1: G["M1"], 2: G["M2"], 3: G["M3"], 4: G["M4"]}
+    Mg = pw[g]
+    out = []
+    for l in range(W):
+        acc = []
+        for h in range(2):
+            half = lambda x: (x >> (32 * h)) & 0xFFFFFFFF
+            a = half(K[l]) + half(d[g - 2]) * pw[1][l][0]
+            for i in range(1, W):
+                a += half(s[i]) * Mg[l][i]
+            for i in range(1, g - 1):
+                a += half(d[i - 1]) * pw[g - i][l][0]
+            assert a < 2**64, "a partial sum before the last term wrapped"
+            a += half(s[0]) * Mg[l][0]
+            assert a < 2**65
+            acc.append(a)
+        out.append((acc[0], acc[1], acc[0] >= 2**64, acc[1] >= 2**64))
+    return out
+
+
+def perm_grouped4(state, rc, M, G, trace=None):
+    """The whole permutation as the kernels run it (poseidon.cuh psd_permute_layer): three full rounds, the S-box layer of full round 3,
+    the groups of derive_groups4 (the head group takes that round's MDS layer as its first map), the last four full rounds.  State
+    words are canonical here.  trace, if a list, receives per group (g, folded input state, [d_i], group4_last_step's result)."""
+    mds = lambda s, n: [(a + c) % P for a, c in zip(mat_vec(M, s), rc[n] if n < N_ROUNDS else [0] * W)]
+    pw = {1: G["M1"], 2: G["M2"], 3: G["M3"], 4: G["M4"]}
+    dot = lambda row, v: sum(a * b for a, b in zip(row, v))
+    s = [(a + c) % P for a, c in zip(state, rc[0])]
+    for r in range(HALF_FULL - 1):
+        s = mds([sbox(a) for a in s], r + 1)
+    s = [sbox(a) for a in s]
+    for n, g in enumerate(G["split"]):
+        ks, K = G["K"][n][:g - 1], G["K"][n][g - 1:]
+        if n:
+            s = [sbox(s[0])] + s[1:]
+        d = []
+        for j in range(1, g):
+            a = (dot(pw[j][0], s) + sum(pw[j - i][0][0] * d[i - 1] for i in range(1, j)) + ks[j - 1]) % P
+            d.append((sbox(a) - a) % P)
+        acc = group4_last_step(G, g, s, d, K)
+        if trace is not None:
+            trace.append((g, s[:], d[:], acc))
+        s = [(al + (ah << 32)) % P for al, ah, _, _ in acc]
+    r = HALF_FULL + N_PARTIAL
+    for _ in range(HALF_FULL):
+        s = mds([sbox(a) for a in s], r + 1); r += 1
+    return s
+
+
 MFMA_BIAS = 0x80808080                     # each 32-bit half XOR 0x80808080: bytes b -> signed b - 128 (i8 operands)
 
 
@@ -347,7 +450,7 @@ KATS = [
 ]
 
 
-def emit(path, rc, T, G, F):
+def emit(path, rc, T, G, F, G4):
     """Writes <path> (host wrapper, guarded) and <path minus .h>.inc (raw tables behind POSEIDON_TABLE)."""
     def arr(name, vals, per_line=4):
         out = ["POSEIDON_TABLE(%s, %d) = {" % (name, len(vals))]
@@ -391,6 +494,11 @@ def emit(path, rc, T, G, F):
         arr32("POSEIDON_G3_V1", G["V1"]),
         arr32("POSEIDON_G3_V2", G["V2"]),
         arr("POSEIDON_G3_K", flat(G["K"])),
+        "// GPU form of the permutation's partial rounds (derive_groups4): the 23 linear maps behind the S-box layer of full round 3 in",
+        "// groups of %s.  M^4 row-major (29-bit entries; its rows and columns of lower powers are the G3 tables: row 0 of M^3 is the" % "+".join(map(str, G4["split"])),
+        "// first row of G3_M3, column 0 of M^3 is G3_V2); per four-map group k1, k2, k3, K[12], then the three-map group's k1, k2, K[12]",
+        arr32("POSEIDON_G4_M4", flat(G4["M4"])),
+        arr("POSEIDON_G4_K", flat(G4["K"])),
         "// GPU MDS layer on the i8 matrix cores (derive_mfma): A operand coefficients, word 4 d + q = input word q of a K block",
         "// for the output words o = 0..3 of a row block (byte o), d = (K block - row block) mod 3, d = 3: block (0, 0) with the",
         "// diagonal; and per round n (n = 30: no constants) the bias-corrected (k_lo, k_hi) of output word i at 24 n + 2 i",
@@ -410,6 +518,7 @@ def emit(path, rc, T, G, F):
         "#define POSEIDON_HALF_FULL_ROUNDS 4",
         "#define POSEIDON_PARTIAL_ROUNDS 22",
         "#define POSEIDON_PARTIAL_GROUPS %d" % N_GROUPS,
+        "#define POSEIDON_G4_GROUPS %d    /* four-map groups (the first one headed by the MDS layer of full round 3), then one three-map group */" % G4["split"].count(4),
         "#define POSEIDON_TABLE(name, n) static const uint64_t name[n]",
         "#define POSEIDON_TABLE32(name, n) static const uint32_t name[n]",
         '#include "%s"' % os.path.basename(inc_path),
@@ -428,10 +537,13 @@ def main():
     rnd = random.Random(1)
     tests = [k[0] for k in KATS] + [[rnd.randrange(P) for _ in range(W)] for _ in range(4)]
     G = derive_groups(rc, T["M"])
+    G4 = derive_groups4(rc, T["M"])
+    assert G4["split"] == [4] * 5 + [3]                      # what poseidon.cuh psd_permute_layer runs
     for t in tests:
         assert perm_naive(t, rc, T["M"]) == perm_fast(t, rc, T), "fast != naive"
         assert perm_naive(t, rc, T["M"]) == perm_grouped(t, rc, T["M"], G), "grouped != naive"
         assert perm_naive(t, rc, T["M"]) == perm_grouped_folded(t, rc, T["M"], G), "folded groups != naive"
+        assert perm_naive(t, rc, T["M"]) == perm_grouped4(t, rc, T["M"], G4), "groups of four != naive"
     for inp, out in KATS:
         assert perm_fast(inp, rc, T) == out, "KAT mismatch"
     F = derive_mfma(rc)
@@ -446,8 +558,8 @@ def main():
             assert out == [(a + c) % P for a, c in zip(mat_vec(M, t), cst)], "MFMA layer != M s + rc"
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(
         HERE, "..", "plonky2_demo_amd", "csrc", "poseidon_constants.h")
-    emit(out, rc, T, G, F)
-    print("ok: naive==fast==grouped==folded on %d inputs, 4 KATs pass, MFMA layer == VALU layer; wrote %s" % (len(tests), os.path.normpath(out)))
+    emit(out, rc, T, G, F, G4)
+    print("ok: naive==fast==grouped==folded==groups of four on %d inputs, 4 KATs pass, MFMA layer == VALU layer; wrote %s" % (len(tests), os.path.normpath(out)))
     return T
 
 

@@ -16,6 +16,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <string>
 #include <utility>
 #include <vector>
@@ -64,6 +65,20 @@ __global__ __launch_bounds__(256) void k_acc3(const u64* al, const u64* ah, u64*
     gl_t rA, rB, rC;
     glx_acc_reduce3(al[i], ah[i], al[n + i], ah[n + i], al[2 * n + i], ah[2 * n + i], rA, rB, rC);
     o[i] = rA; o[n + i] = rB; o[2 * n + i] = rC;
+}
+// slots 0..2 of a / b: the lo accumulators before their last term / that term as x | c << 32; slots 3..5: the hi accumulators
+__global__ __launch_bounds__(256) void k_acc3w(const u64* acc, const u64* term, u64* o, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    gl_t al[3], ah[3], r[3];
+    uint64_t wl[3], wh[3];
+    for (int k = 0; k < 3; k++) {
+        const u64 tl = term[k * n + i], th = term[(3 + k) * n + i];
+        al[k] = glx_mac_co(acc[k * n + i], (u32)tl, __builtin_amdgcn_readfirstlane((u32)(tl >> 32)), wl[k]);
+        ah[k] = glx_mac_co(acc[(3 + k) * n + i], (u32)th, __builtin_amdgcn_readfirstlane((u32)(th >> 32)), wh[k]);
+    }
+    glx_acc_reduce3w(al[0], ah[0], wl[0], wh[0], al[1], ah[1], wl[1], wh[1], al[2], ah[2], wl[2], wh[2], r[0], r[1], r[2]);
+    for (int k = 0; k < 3; k++) { o[k * n + i] = r[k]; o[(3 + k) * n + i] = 0; }
 }
 
 template <bool CANON> struct F_mul { __device__ __forceinline__ gl_t operator()(gl_t a, gl_t b) const { return glx_mul<CANON>(a, b); } };
@@ -442,6 +457,49 @@ int main() {
             t.cases++; t.count[cacc(l3[i], h3[i])]++;
             if (out[i] % P != racc(l3[i], h3[i])) t.mismatch(l3[i], h3[i], out[i], racc(l3[i], h3[i]), i < n ? "slot 0" : i < 2 * n ? "slot 1" : "slot 2");
         }
+        t.finish();
+    }
+
+    {   // glx_mac_co + glx_acc_reduce3w: any 64-bit accumulator plus one 32 x 32 product as the last term, the wrap handed over as a mask.
+        // The coefficient is wave-uniform (a scalar operand), so a wave of 64 elements shares one.
+        Tally t("glx_acc_reduce3w", {"lo wraps", "hi wraps", "top carries", "lo and hi wrap", "none"}, 0x1F);
+        const size_t m = ((std::min<size_t>(n, 164 * 164 + 12 + 16384) + 63) / 64 + 2) * 64;
+        std::vector<u64> acc(6 * m), term(6 * m), out;
+        const u32 coef[] = {0, 1, 0x1FFFFFFFu, 0xFFFFFFFFu, 0x16BD2D97u /* M^4[0][0] */};
+        u64 seed = 99;
+        for (int k = 0; k < 6; k++)
+            for (size_t i = 0; i < m; i++) {
+                const size_t wave = i / 64;
+                u32 c = wave % 7 < 5 ? coef[(wave + k) % 5] : (u32)(splitmix(seed) >> 35);
+                u64 a = k < 3 ? ha[(i + 5 * k) % n] : hb[(i + 17 * k) % n];
+                u32 x = (u32)splitmix(seed);
+                if (i % 5 == 0) x = 0xFFFFFFFFu;
+                if (wave == m / 64 - 1) {          // the carry out of the top word: ah = 2^64 - 1 unwrapped, al.hi + ah.lo >= 2^32
+                    x = 0; a = k < 3 ? ((u64)(1 + i % 3) << 32) + i : ~0ULL - (i % 2);
+                }
+                if (wave == m / 64 - 2) {          // and together with a wrapped lo accumulator
+                    if (k < 3) { a = ~0ULL - i; x = 0xFFFFFFFFu; c = 0xFFFFFFFFu; } else { a = ~0ULL; x = 0; }
+                }
+                acc[k * m + i] = a; term[k * m + i] = (u64)x | ((u64)c << 32);
+            }
+        // one coefficient per wave and slot: copy lane 0's
+        for (int k = 0; k < 6; k++) for (size_t i = 0; i < m; i++) term[k * m + i] = (term[k * m + i] & M32) | (term[k * m + (i & ~(size_t)63)] & ~M32);
+        run_slots([](const u64* a, const u64* b, const uint8_t*, u64* o, size_t mm) { hipLaunchKernelGGL(k_acc3w, dim3(blocks_for(mm)), dim3(256), 0, 0, a, b, o, mm); }, 6, m, acc, term, nullptr, out);
+        for (int k = 0; k < 3; k++)
+            for (size_t i = 0; i < m; i++) {
+                const u128 l = (u128)acc[k * m + i] + (u128)(term[k * m + i] & M32) * (term[k * m + i] >> 32);
+                const u128 h = (u128)acc[(3 + k) * m + i] + (u128)(term[(3 + k) * m + i] & M32) * (term[(3 + k) * m + i] >> 32);
+                const u64 want = h_mod(l + (h << 32));            // l, h < 2^65
+                const bool wl = l >> 64, wh = h >> 64;
+                const bool top = !wh && (u32)((u64)h >> 32) == 0xFFFFFFFFu && (((u64)l >> 32) + ((u64)h & M32)) >> 32;
+                t.cases++;
+                if (wl) t.count[0]++;
+                if (wh) t.count[1]++;
+                if (top) t.count[2]++;
+                if (wl && wh) t.count[3]++;
+                if (!wl && !wh && !top) t.count[4]++;
+                if (out[k * m + i] % P != want) t.mismatch(acc[k * m + i], acc[(3 + k) * m + i], out[k * m + i], want, wl ? (wh ? "lo, hi" : "lo") : wh ? "hi" : top ? "top" : "none");
+            }
         t.finish();
     }
 
