@@ -7,6 +7,8 @@
   lookup 0   ops and ops2 look [a, b, c] up in mul; the looking filter is the LINEAR COMBINATION s0 + s1, the looked filter is `used`
   lookup 1   no filter on either side; mul is the LOOKING table -- so it is both looking and looked -- with the columns
              [le_bits(b0..b3), 3 t + 7] (a Column with a constant), looked up in ops' [u, w]
+TABLES5 is the same system with a mul table of degree 5 (used^5 = used besides) under rate_bits 2: tables of q = 2 and of q = 4 in one
+set, the first on every second point of the LDE.
 An AIR has stark_airs' shape; a Column is (terms, constant), a TableWithColumns a namespace (table, columns, filter), a lookup a pair
 (looking list, looked): what stark_ctl_model takes.
 """
@@ -47,6 +49,11 @@ ops = _air("ops", 7, 0, 3, RATE_BITS, _OPS_CONSTRAINTS, [], None)
 ops2 = _air("ops2", 7, 0, 3, RATE_BITS, _OPS_CONSTRAINTS, [[(5, 6)]], None)
 mul = _air("mul", 9, 0, 3, RATE_BITS, _MUL_CONSTRAINTS, [], None)
 TABLES = [ops, ops2, mul]
+
+# the variant: one more constraint on mul, five trace factors on every row (q + 1 at q = 4); every table at the set's rate_bits 2
+RATE_BITS5 = 2
+mul5 = _air("mul5", 9, 0, 5, RATE_BITS5, _MUL_CONSTRAINTS + [(ALL, [(1, [L(3)] * 5), (M1, [L(3)])])], [], None)
+TABLES5 = [_air("ops", 7, 0, 3, RATE_BITS5, _OPS_CONSTRAINTS, [], None), _air("ops2", 7, 0, 3, RATE_BITS5, _OPS_CONSTRAINTS, [[(5, 6)]], None), mul5]
 
 FILTER_OPS = ([(3, 1), (4, 1)], 0)                  # s0 + s1
 LOOKUPS = [
@@ -117,7 +124,7 @@ def api_set(p, tables, lookups, lgs, config, hasher="poseidon"):
     return p.StarkSetDesc(descs, [p.CrossTableLookup([tw(t) for t in looking], tw(looked)) for looking, looked in lookups], config, hasher=hasher)
 
 
-def config(p, nc):
+def config(p, nc, rate_bits=RATE_BITS):
     c = p.StarkConfig.standard_fast_config()
-    c.num_challenges, c.rate_bits = nc, RATE_BITS
+    c.num_challenges, c.rate_bits = nc, rate_bits
     return c

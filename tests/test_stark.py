@@ -1,5 +1,6 @@
 """GPU tests of the STARK seam (csrc/stark.hip, csrc/stark_kernels.cuh) against the Python-integer model tests/stark_model.py, itself
-pinned by tests/test_stark_model.py, on the four AIRs of tests/stark_airs.py.
+pinned by tests/test_stark_model.py, on the AIRs of tests/stark_airs.py under num_challenges 1 to 4 (test_stark_model.py's matrix guard
+holds the shapes the cases below rely on).  A case without a count in its name runs the standard configuration's two.
 
 degree_bits 5: 32 rows, less than a wave and one partial segment of the scan, the reference test's size; 12: 4096 rows cross the
 2048-row segment of the scan, and the quotient kernel runs 16 to 64 blocks.
@@ -23,10 +24,16 @@ EDGE_CHALLENGES = [0, 1, P - 1, 2**32]
 NON_CANONICAL = [P + 3, 2**64 - 1]
 
 
-def config_of(p, air):
+def config_of(p, air, nc=NC):
     c = p.StarkConfig.standard_fast_config()
-    c.rate_bits = air.rate_bits
+    assert c.num_challenges == NC
+    c.num_challenges, c.rate_bits = nc, air.rate_bits
     return c
+
+
+def case(*args, nc=None):
+    """a parametrised case (..., nc); without a count, the standard configuration's two under the plain id"""
+    return pytest.param(*args, nc or NC, id="-".join(str(a) for a in args) + ("-nc%d" % nc if nc else ""))
 
 
 def desc_of(p, air):
@@ -41,9 +48,9 @@ def values_of(variant, rng, k):
     return [pool[(i + int(rng.integers(0, len(pool)))) % len(pool)] for i in range(k)]
 
 
-def sets_of(variant, rng, air):
-    flat = values_of(variant, rng, air.q * NC * 2)
-    return [[(flat[2 * (j * NC + c)], flat[2 * (j * NC + c) + 1]) for c in range(NC)] for j in range(air.q)]
+def sets_of(variant, rng, air, nc=NC):
+    flat = values_of(variant, rng, air.q * nc * 2)
+    return [[(flat[2 * (j * nc + c)], flat[2 * (j * nc + c) + 1]) for c in range(nc)] for j in range(air.q)]
 
 
 def flat_sets(sets):
@@ -51,31 +58,51 @@ def flat_sets(sets):
 
 
 # ------------------------------------------------------------------------------- permutation Z by value
-@pytest.mark.parametrize("lg_n", [5, 12])
-@pytest.mark.parametrize("name", ["cubic", "quartic"])
-def test_permutation_zs_equal_the_model_at_every_word(gpu, orc, name, lg_n):
-    p, ctx = gpu
-    air = stark_airs.AIRS[name]
+def edge_trace_for_the_zs(air, nc, lg_n):
+    """-> (the three variants' challenge sets, a trace of EDGES values under which none of them has a zero denominator); needs no GPU"""
     n = 1 << lg_n
     rng = np.random.Generator(np.random.PCG64(500 + lg_n))
-    all_sets = {v: sets_of(v, rng, air) for v in VARIANTS}
-    # columns drawn from the edge operands; a row under which some instance's denominator vanishes for one of the challenge sets is drawn again
-    trace = np.array(EDGES, dtype=U64)[rng.integers(0, len(EDGES), size=(air.num_columns, n))]
+    all_sets = {v: sets_of(v, rng, air, nc) for v in VARIANTS}
+    edges = np.array(EDGES, dtype=U64)
+    batches = sm.permutation_batches(air, nc)
+    # columns drawn from the edge operands; where some instance's denominator vanishes for one of the challenge sets, the cells it is made
+    # of -- that row of the right-hand columns of the batch's pairs -- are drawn again.  (Drawing the whole row again cannot converge on 33
+    # single-column pairs: every gamma of the edge pool is minus an edge operand, so a row is free of zeros with probability (9/11)^33.)
+    trace = edges[rng.integers(0, len(EDGES), size=(air.num_columns, n))]
     for _ in range(64):
         bad = np.zeros(n, dtype=bool)
         for sets in all_sets.values():
-            for _, den in sm.permutation_num_den(air, NC, trace, sets):
-                bad |= np.array([d == 0 for d in den])
+            for batch, (_, den) in zip(batches, sm.permutation_num_den(air, nc, trace, sets)):
+                zero = np.array([d == 0 for d in den])
+                if zero.any():
+                    bad |= zero
+                    cols = sorted({rhs for pair, _, _ in batch for _, rhs in air.pairs[pair]})
+                    trace[np.ix_(cols, np.flatnonzero(zero))] = edges[rng.integers(0, len(EDGES), size=(len(cols), int(zero.sum())))]
         if not bad.any():
             break
-        trace[:, bad] = np.array(EDGES, dtype=U64)[rng.integers(0, len(EDGES), size=(air.num_columns, int(bad.sum())))]
     assert not bad.any(), "could not arrange the edge rows so that no denominator is zero"
-    assert np.isin(trace, np.array(EDGES, dtype=U64)).all()
-    stark = p.Stark(desc_of(p, air), config_of(p, air), lg_n, ctx=ctx)
+    assert np.isin(trace, edges).all()
+    return all_sets, trace
+
+
+Z_CASES = [case("cubic", 5), case("quartic", 5), case("cubic", 12), case("quartic", 12),
+           case("pairs33", 5, nc=2), case("pairs33", 8, nc=2),     # 66 Zs: the second block of k_stark_seg_scan
+           case("pairs33", 5, nc=4),                               # 132 Zs: three blocks
+           case("longpair", 5, nc=3), case("longpair", 12, nc=3),  # beta^63; three instances in two Zs, the last batch partial; two segments
+           case("nonic", 5, nc=3), case("linear", 5, nc=1)]
+
+
+@pytest.mark.parametrize("name,lg_n,nc", Z_CASES)
+def test_permutation_zs_equal_the_model_at_every_word(gpu, orc, name, lg_n, nc):
+    p, ctx = gpu
+    air = stark_airs.AIRS[name]
+    n = 1 << lg_n
+    all_sets, trace = edge_trace_for_the_zs(air, nc, lg_n)
+    stark = p.Stark(desc_of(p, air), config_of(p, air, nc), lg_n, ctx=ctx)
     for variant, sets in all_sets.items():
         zs_b = stark.permutation_zs(trace, flat_sets(sets))
-        want, _ = sm.permutation_zs(air, NC, trace, sets)
-        assert zs_b.ncols == sm.num_zs(air, NC) and zs_b.degree == n
+        want, _ = sm.permutation_zs(air, nc, trace, sets)
+        assert zs_b.ncols == sm.num_zs(air, nc) and zs_b.degree == n
         got = orc.fft(zs_b.polynomials)                              # the committed polynomials back on H
         bad_words = np.argwhere(got != np.array(want, dtype=U64))
         assert not len(bad_words), "%s challenges: %d words differ, first (Z, row) %s" % (variant, len(bad_words), bad_words[:4].tolist())
@@ -108,17 +135,25 @@ def variant_of(air, variant, rng):
     return a
 
 
-@pytest.mark.parametrize("name,lg_n", [("fibonacci", 5), ("cubic", 5), ("quartic", 5), ("wide", 5), ("quartic", 12), ("wide", 12)])
-def test_quotient_values_equal_the_model_at_every_coset_point(gpu, orc, name, lg_n):
+@pytest.mark.parametrize("name,lg_n,nc", [
+    case("fibonacci", 5), case("cubic", 5), case("quartic", 5), case("wide", 5), case("quartic", 12), case("wide", 12),
+    case("fibonacci", 5, nc=1), case("quartic", 5, nc=3), case("quintic", 5, nc=4), case("sextic", 5, nc=3), case("nonic", 5, nc=4), case("nonic", 5, nc=1),
+    case("linear", 5, nc=2), case("longpair", 5, nc=3), case("manyfactors", 5, nc=2), case("nopublic", 5, nc=1),
+    case("nonic", 9, nc=3)])       # size 4096: both halves of the two-level power table, and `next` wraps at the last 8 points
+def test_quotient_values_equal_the_model_at_every_coset_point(gpu, orc, name, lg_n, nc):
     p, ctx = gpu
     base = stark_airs.AIRS[name]
     n, step = 1 << lg_n, 1 << (base.rate_bits - base.qdb)
-    size, nz = n << base.qdb, sm.num_zs(base, NC)
+    size, nz = n << base.qdb, sm.num_zs(base, nc)
+    if name == "quintic":
+        assert step == 2 and base.qdb == 2           # every second LDE point, four values of 1 / Z_H
+    if (name, lg_n) == ("nonic", 9):
+        assert size == 4096 and base.qdb == 3
     rng = np.random.Generator(np.random.PCG64(700 + lg_n))
     k = step * int(rng.integers(0, 1 << base.qdb))                   # a multiple of step: the quotient coset sees the edge rows
     edge_points = np.arange(k, n << base.rate_bits, 1 << base.rate_bits)
     t_trace = edge_targets(rng, base.num_columns, n)
-    config = config_of(p, base)
+    config = config_of(p, base, nc)
     trace_b = p.PolynomialBatch.from_values(list(through_points(orc, t_trace, lg_n, base.rate_bits, k)), base.rate_bits, False, config.cap_height, ctx=ctx)
     trace_lde = trace_b.lde_values()
     assert (trace_lde[:, edge_points] == t_trace).all()
@@ -129,49 +164,77 @@ def test_quotient_values_equal_the_model_at_every_coset_point(gpu, orc, name, lg
     for variant in VARIANTS:
         air = variant_of(base, variant, rng)
         stark = p.Stark(desc_of(p, air), config, lg_n, ctx=ctx)
-        sets = sets_of(variant, rng, air) if nz else None
-        alphas, pis = values_of(variant, rng, NC), values_of(variant, rng, air.num_public_inputs)
+        sets = sets_of(variant, rng, air, nc) if nz else None
+        alphas, pis = values_of(variant, rng, nc), values_of(variant, rng, air.num_public_inputs)
         got = stark.quotient_values(trace_b, zs_b, flat_sets(sets) if nz else None, alphas, pis)
-        assert got.shape == (NC, size)
-        want = np.array(sm.quotient_values(orc, air, NC, lg_n, trace_lde[:, ::step], zs_lde[:, ::step], sets, alphas, pis), dtype=U64)
+        assert got.shape == (nc, size)
+        want = np.array(sm.quotient_values(orc, air, nc, lg_n, trace_lde[:, ::step], zs_lde[:, ::step], sets, alphas, pis), dtype=U64)
         bad = np.argwhere(got != want)
-        assert not len(bad), "%s at 2^%d, %s variant: %d of %d words differ, first (challenge, point) %s" % (name, lg_n, variant, len(bad), NC * size, bad[:4].tolist())
+        assert not len(bad), "%s at 2^%d, %s variant: %d of %d words differ, first (challenge, point) %s" % (name, lg_n, variant, len(bad), nc * size, bad[:4].tolist())
         # the wrap-around of `next` at the last 2^qdb points is part of the comparison; it reads the first points' rows
         assert (1 << base.qdb) <= size
 
 
 # ------------------------------------------------------------------------------- quotient polynomials
-def model_prover(orc, air, lg_n, trace, pis, sets, alphas):
+def model_prover(orc, air, nc, lg_n, trace, pis, sets, alphas):
     """the model's Z values and quotient chunks of a trace (None where trim_to_len fails)"""
-    zs = sm.permutation_zs(air, NC, trace, sets)[0] if air.pairs else []
+    zs = sm.permutation_zs(air, nc, trace, sets)[0] if air.pairs else []
     trace_coeffs = orc.ifft(trace)
     zs_coeffs = orc.ifft(np.array(zs, dtype=U64)) if zs else np.zeros((0, 1 << lg_n), dtype=U64)
-    values = sm.quotient_values(orc, air, NC, lg_n, orc.lde(trace_coeffs, air.qdb), orc.lde(zs_coeffs, air.qdb) if zs else [], sets, alphas, pis)
-    return zs, trace_coeffs, zs_coeffs, sm.quotient_chunks(orc, air, NC, lg_n, values)
+    values = sm.quotient_values(orc, air, nc, lg_n, orc.lde(trace_coeffs, air.qdb), orc.lde(zs_coeffs, air.qdb) if zs else [], sets, alphas, pis)
+    return zs, trace_coeffs, zs_coeffs, sm.quotient_chunks(orc, air, nc, lg_n, values)
 
 
-def test_quotient_polys_equal_the_model_and_refuse_a_broken_trace(gpu, orc):
+def quotient_polys_and_a_changed_cell(gpu, orc, air, nc, lg_n=5):
+    """the chunks of a satisfying trace against the model's -> (the stark, the trace with one cell changed, its public inputs, the challenges)"""
     p, ctx = gpu
-    air, lg_n = stark_airs.quartic, 5
     rng = np.random.Generator(np.random.PCG64(900))
     trace, pis = air.trace(1 << lg_n, seed=4)
-    sets, alphas = sets_of("random", rng, air), values_of("random", rng, NC)
-    stark = p.Stark(desc_of(p, air), config_of(p, air), lg_n, ctx=ctx)
+    sets, alphas = sets_of("random", rng, air, nc), values_of("random", rng, nc)
+    stark = p.Stark(desc_of(p, air), config_of(p, air, nc), lg_n, ctx=ctx)
     trace_b = stark.commit_trace(list(trace))
     zs_b = stark.permutation_zs(trace, flat_sets(sets))
-    chunks = model_prover(orc, air, lg_n, trace, pis, sets, alphas)[3]
+    chunks = model_prover(orc, air, nc, lg_n, trace, pis, sets, alphas)[3]
     assert chunks is not None
     q_b = stark.quotient_polys(trace_b, zs_b, flat_sets(sets), alphas, pis)
-    assert q_b.ncols == NC * air.q == 6 and (q_b.polynomials == chunks).all()
-    # one cell changed: q = 3 is no power of two, so the trim sees the quotient's degree; the one-call prover refuses the same way
+    assert q_b.ncols == nc * air.q and (q_b.polynomials == chunks).all()
     bad = trace.copy()
     bad[0, 9] = (int(bad[0, 9]) + 1) % P
+    return stark, bad, pis, sets, alphas
+
+
+def refused_through_the_trim(p, stark, bad, pis, sets, alphas):
     with pytest.raises(p.Plonky2Mi355xError, match="does not satisfy the constraints") as e:
         stark.quotient_polys(stark.commit_trace(list(bad)), stark.permutation_zs(bad, flat_sets(sets)), flat_sets(sets), alphas, pis)
     assert e.value.code == 1
     with pytest.raises(p.Plonky2Mi355xError, match="does not satisfy the constraints") as e:
         stark.prove(bad, pis)
     assert e.value.code == 1
+
+
+def test_quotient_polys_equal_the_model_and_refuse_a_broken_trace(gpu, orc):
+    air = stark_airs.quartic
+    assert NC * air.q == 6
+    # one cell changed: q = 3 is no power of two, so the trim sees the quotient's degree; the one-call prover refuses the same way
+    refused_through_the_trim(gpu[0], *quotient_polys_and_a_changed_cell(gpu, orc, air, NC))
+
+
+def test_quotient_polys_of_five_chunks_equal_the_model_and_refuse_a_broken_trace(gpu, orc):
+    # q = 5 under qdb = 3: the trim checks 3 n coefficients per challenge and quotient_commit keeps 5 n of 8 n, three times
+    air = stark_airs.sextic
+    assert (air.q, air.qdb) == (5, 3)
+    refused_through_the_trim(gpu[0], *quotient_polys_and_a_changed_cell(gpu, orc, air, 3))
+
+
+def test_quotient_polys_of_eight_chunks_equal_the_model_and_the_verifier_rejects_a_broken_trace(gpu, orc):
+    # q = 8 fills the coset: nothing to trim, the prover cannot see the changed cell; the identity at zeta does (as for fibonacci below)
+    air = stark_airs.nonic
+    assert (air.q, air.qdb) == (8, 3)
+    stark, bad, pis, _, _ = quotient_polys_and_a_changed_cell(gpu, orc, air, 4)
+    trace, _ = air.trace(32, seed=4)
+    assert stark.verify(stark.prove(trace, pis)) == (True, "", 0)
+    ok, why, code = stark.verify(stark.prove(bad, pis))
+    assert (ok, code) == (False, sm.VANISHING) and "anishing" in why
 
 
 def test_a_broken_fibonacci_trace_yields_a_proof_the_verifier_rejects(gpu):
@@ -188,15 +251,16 @@ def test_a_broken_fibonacci_trace_yields_a_proof_the_verifier_rejects(gpu):
 
 
 # ------------------------------------------------------------------------------- whole proofs
-def check_whole_proof(p, orc, air, lg_n, hasher, stark, proof, trace, pis, max_queries=None):
+def check_whole_proof(p, orc, air, nc, lg_n, hasher, stark, proof, trace, pis, max_queries=None):
     from prover_phase_model import eval_ext
     from test_fri_openings import model_challenger, verify_path_of
     params = stark.params
     assert len(proof) == stark.proof_size
-    pp = sm.ParsedStarkProof(air, NC, params, proof)
+    pp = sm.ParsedStarkProof(air, nc, params, proof)
     assert pp.public_inputs == [int(v) % P for v in pis]
-    sets, alphas, zeta = sm.replay(air, NC, pp, model_challenger(orc, hasher))
-    zs, trace_coeffs, zs_coeffs, chunks = model_prover(orc, air, lg_n, trace, pis, sets, alphas)
+    sets, alphas, zeta = sm.replay(air, nc, pp, model_challenger(orc, hasher))
+    assert len(alphas) == nc and len(pp.quotient) == nc * air.q and len(pp.zs) == sm.num_zs(air, nc)
+    zs, trace_coeffs, zs_coeffs, chunks = model_prover(orc, air, nc, lg_n, trace, pis, sets, alphas)
     assert chunks is not None
     if hasher == "poseidon":
         cap = lambda cols, values: orc.batch(cols, params.rate_bits, params.cap_height, from_values=values).cap.tolist()       # noqa: E731
@@ -217,21 +281,24 @@ def check_whole_proof(p, orc, air, lg_n, hasher, stark, proof, trace, pis, max_q
     assert pp.zs == [eval_ext(c, zeta) for c in zs_coeffs] and pp.zs_next == [eval_ext(c, gzeta) for c in zs_coeffs]
     assert pp.quotient == [eval_ext(c, zeta) for c in chunks]
     seen = {}
-    assert sm.verify(air, NC, params, proof, model_challenger(orc, hasher), verify_path_of(orc, hasher), max_queries=max_queries, trace=seen) == sm.fom.ACCEPTED
+    assert sm.verify(air, nc, params, proof, model_challenger(orc, hasher), verify_path_of(orc, hasher), max_queries=max_queries, trace=seen) == sm.fom.ACCEPTED
     assert (seen["zeta"], seen["alphas"]) == (zeta, alphas)           # the model transcript's, which the openings above were checked at
     assert stark.verify(proof) == (True, "", 0)
 
 
-@pytest.mark.parametrize("name,lg_n,hasher", [("fibonacci", 5, "poseidon"), ("fibonacci", 7, "poseidon"), ("fibonacci", 12, "poseidon"), ("cubic", 7, "poseidon"),
-                                              ("quartic", 7, "poseidon"), ("wide", 5, "poseidon"), ("fibonacci", 7, "keccak")])
-def test_whole_proof(gpu, orc, name, lg_n, hasher):
+@pytest.mark.parametrize("name,lg_n,hasher,nc", [
+    case("fibonacci", 5, "poseidon"), case("fibonacci", 7, "poseidon"), case("fibonacci", 12, "poseidon"), case("cubic", 7, "poseidon"),
+    case("quartic", 7, "poseidon"), case("wide", 5, "poseidon"), case("fibonacci", 7, "keccak"),
+    case("fibonacci", 5, "poseidon", nc=1), case("quartic", 7, "poseidon", nc=3), case("nonic", 5, "poseidon", nc=4), case("sextic", 7, "poseidon", nc=3),
+    case("pairs33", 5, "poseidon", nc=2), case("longpair", 5, "poseidon", nc=3), case("nonic", 5, "keccak", nc=3)])
+def test_whole_proof(gpu, orc, name, lg_n, hasher, nc):
     p, ctx = gpu
     air = stark_airs.AIRS[name]
     trace, pis = air.trace(1 << lg_n, seed=6)
-    stark = p.Stark(desc_of(p, air), config_of(p, air), lg_n, hasher=hasher, ctx=ctx)
+    stark = p.Stark(desc_of(p, air), config_of(p, air, nc), lg_n, hasher=hasher, ctx=ctx)
     assert len(stark.params.reduction_arity_bits) == {5: 0, 7: 1, 12: 2}[lg_n]
     proof = stark.prove(trace, pis)
-    check_whole_proof(p, orc, air, lg_n, hasher, stark, proof, trace, pis, max_queries=8 if lg_n == 12 else None)
+    check_whole_proof(p, orc, air, nc, lg_n, hasher, stark, proof, trace, pis, max_queries=8 if lg_n == 12 else None)
     assert stark.prove(trace, pis) == proof, "two calls on the same input give different bytes"
     d = ctx.alloc(trace.nbytes).upload(trace)
     try:
@@ -280,24 +347,24 @@ def words_bytes(a):
     return np.ascontiguousarray(np.asarray(a, dtype=U64), dtype="<u8").tobytes()
 
 
-@pytest.mark.parametrize("name", ["fibonacci", "quartic", "wide"])
-def test_phase_entries_driven_by_the_python_challenger_reproduce_the_one_call_bytes(gpu, name):
+@pytest.mark.parametrize("name,nc", [case("fibonacci"), case("quartic"), case("wide"), case("nonic", nc=3)])
+def test_phase_entries_driven_by_the_python_challenger_reproduce_the_one_call_bytes(gpu, name, nc):
     p, ctx = gpu
     air, lg_n = stark_airs.AIRS[name], 7
     trace, pis = air.trace(1 << lg_n, seed=7)
-    stark = p.Stark(desc_of(p, air), config_of(p, air), lg_n, ctx=ctx)
-    params, nz = stark.params, sm.num_zs(air, NC)
+    stark = p.Stark(desc_of(p, air), config_of(p, air, nc), lg_n, ctx=ctx)
+    params, nz = stark.params, sm.num_zs(air, nc)
     ch = p.Challenger()
     trace_b = stark.commit_trace(list(trace))
     ch.observe_hashes(trace_b.cap)
     out = words_bytes(trace_b.cap)
     sets, zs_b = None, None
     if nz:
-        sets = np.array(ch.get_n_challenges(2 * air.q * NC), dtype=U64)
+        sets = np.array(ch.get_n_challenges(2 * air.q * nc), dtype=U64)
         zs_b = stark.permutation_zs(trace, sets)
         ch.observe_hashes(zs_b.cap)
         out += words_bytes(zs_b.cap)
-    alphas = ch.get_n_challenges(NC)
+    alphas = ch.get_n_challenges(nc)
     q_b = stark.quotient_polys(trace_b, zs_b, sets, alphas, pis)
     ch.observe_hashes(q_b.cap)
     out += words_bytes(q_b.cap)
@@ -311,7 +378,7 @@ def test_phase_entries_driven_by_the_python_challenger_reproduce_the_one_call_by
         out += words_bytes(part)
     for part in (local, zl, quot, nxt, zn):                            # FriOpenings order (proof.rs:161-182)
         ch.observe_elements(part)
-    model_instance = sm.fri_instance(air, NC, zeta, lg_n)
+    model_instance = sm.fri_instance(air, nc, zeta, lg_n)
     instance = p.FriInstance(model_instance.oracles, model_instance.batches)
     out += p.PolynomialBatch.prove_openings(instance, [trace_b] + ([zs_b] if nz else []) + [q_b], ch, params, ctx=ctx)
     out += words_bytes(pis)
@@ -351,6 +418,22 @@ def test_the_committed_fixture_is_current(gpu):
     proof = p.Stark(desc, p.StarkConfig.standard_fast_config(), 5, ctx=ctx).prove(trace, [0, 1, int(trace[1, 31])])
     with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "stark_fibonacci_n32.bin"), "rb") as f:
         assert f.read() == proof, "tests/golden/stark_fibonacci_n32.bin is stale: run tools/make_stark_fixture.py on the GPU"
+
+
+def test_the_committed_nonic_fixture_is_current(gpu):
+    import json
+    import os
+    p, ctx = gpu
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    with open(os.path.join(golden, "stark_nonic_n32_nc3.json")) as f:
+        meta = json.load(f)
+    air, nc = stark_airs.AIRS[meta["air"]], meta["num_challenges"]
+    assert (meta["air"], nc, meta["num_rows"], meta["params"]["rate_bits"]) == ("nonic", 3, 32, 3)
+    trace, pis = air.trace(meta["num_rows"], seed=meta["trace_seed"])
+    assert pis == meta["public_inputs"]
+    proof = p.Stark(desc_of(p, air), config_of(p, air, nc), 5, ctx=ctx).prove(trace, pis)
+    with open(os.path.join(golden, "stark_nonic_n32_nc3.bin"), "rb") as f:
+        assert f.read() == proof, "tests/golden/stark_nonic_n32_nc3.bin is stale: run tools/make_stark_fixture.py nonic on the GPU"
 
 
 # ------------------------------------------------------------------------------- refusals that need a context

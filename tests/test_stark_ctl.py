@@ -77,21 +77,30 @@ def model_ctl_zs(lookups, table, trace, challenges, num_tables=3):
 @pytest.mark.parametrize("filt", ["zero", "one", "alternating"])
 @pytest.mark.parametrize("lg_n", [5, 11, 12])
 def test_ctl_zs_equal_the_model_at_every_word(gpu, lg_n, filt):
+    ctl_zs_equal_the_model(gpu, lg_n, filt, NC)
+
+
+@pytest.mark.parametrize("nc", [3, 4])
+def test_ctl_zs_of_three_and_four_challenges_equal_the_model_at_every_word(gpu, nc):
+    ctl_zs_equal_the_model(gpu, 5, "alternating", nc)
+
+
+def ctl_zs_equal_the_model(gpu, lg_n, filt, nc):
     p, ctx = gpu
     n = 1 << lg_n
     rng = np.random.Generator(np.random.PCG64(900 + lg_n))
-    sset = p.StarkSet(airs.api_set(p, airs.TABLES, airs.LOOKUPS, [lg_n] * 3, airs.config(p, NC)), ctx=ctx)
+    sset = p.StarkSet(airs.api_set(p, airs.TABLES, airs.LOOKUPS, [lg_n] * 3, airs.config(p, nc)), ctx=ctx)
     i0 = n // 2 + 3                                          # in the second segment at 2^12
     first_twc = {airs.OPS: airs.LOOKUPS[0][0][0], airs.OPS2: airs.LOOKUPS[0][0][1], airs.MUL: airs.LOOKUPS[0][1]}
     for variant in VARIANTS:
-        chs = challenges_of(variant, rng)
+        chs = challenges_of(variant, rng, nc)
         for table, air in enumerate(airs.TABLES):
             trace = edge_trace(rng, air.num_columns, n)
             set_filter(trace, table, filt)
             twc = first_twc[table]                           # the table's first CTL Z: lookup 0 under challenge 0, zero from row i0 on
             zero_combine_row(trace, twc.columns, chs[0], i0)
             want = model_ctl_zs(airs.LOOKUPS, table, trace, chs)
-            assert len(want) == sset.counts[table][1] == cm.num_ctl_zs(airs.LOOKUPS, table, NC)
+            assert len(want) == sset.counts[table][1] == cm.num_ctl_zs(airs.LOOKUPS, table, nc)
             if filt == "zero":
                 assert all(v == 1 for v in want[0])           # Z = 1 identically
             elif cm.eval_table(twc.filter, trace, i0) == 1:
@@ -195,16 +204,28 @@ def flat_sets(sets):
 
 # the CTL checks alone (ops, mul) and after a permutation pair's (ops2); 2^12 crosses many blocks and the wrap-around of `next`
 @pytest.mark.parametrize("table,lg_n,nc,variants", [(airs.OPS, 5, 2, VARIANTS), (airs.OPS2, 5, 2, VARIANTS), (airs.MUL, 5, 1, VARIANTS),
-                                                    (airs.OPS2, 5, 1, VARIANTS), (airs.OPS2, 12, 2, ("edges",)), (airs.MUL, 12, 1, ("non-canonical",))])
+                                                    (airs.OPS2, 5, 1, VARIANTS), (airs.OPS2, 12, 2, ("edges",)), (airs.MUL, 12, 1, ("non-canonical",)),
+                                                    (airs.OPS2, 5, 3, VARIANTS), (airs.MUL, 5, 3, VARIANTS), (airs.OPS2, 5, 4, VARIANTS), (airs.MUL, 5, 4, VARIANTS)])
 def test_quotient_values_equal_the_model_at_every_coset_point(gpu, orc, table, lg_n, nc, variants):
+    quotient_values_equal_the_model(gpu, orc, airs.TABLES, table, lg_n, nc, variants)
+
+
+@pytest.mark.parametrize("table,nc", [(airs.MUL, 2), (airs.MUL, 3), (airs.OPS2, 4)])
+def test_quotient_values_beside_a_degree_5_table_equal_the_model_at_every_coset_point(gpu, orc, table, nc):
+    # mul at q = 4: four values of 1 / Z_H, alpha^(2 nctl) after a longer single-table part; ops2 at q = 2 on every second LDE point
+    assert [(a.q, 1 << (a.rate_bits - a.qdb)) for a in airs.TABLES5] == [(2, 2), (2, 2), (4, 1)]
+    quotient_values_equal_the_model(gpu, orc, airs.TABLES5, table, 5, nc, VARIANTS)
+
+
+def quotient_values_equal_the_model(gpu, orc, tables, table, lg_n, nc, variants):
     from test_quotient_model import edge_targets
     p, ctx = gpu
-    air = airs.TABLES[table]
+    air = tables[table]
     n, size = 1 << lg_n, (1 << lg_n) << air.qdb
     step = 1 << (air.rate_bits - air.qdb)
     rng = np.random.Generator(np.random.PCG64(1100 + 10 * lg_n + table))
-    config = airs.config(p, nc)
-    sset = p.StarkSet(airs.api_set(p, airs.TABLES, airs.LOOKUPS, [lg_n] * 3, config), ctx=ctx)
+    config = airs.config(p, nc, air.rate_bits)
+    sset = p.StarkSet(airs.api_set(p, tables, airs.LOOKUPS, [lg_n] * 3, config), ctx=ctx)
     nzs = sum(sset.counts[table])
     k = step * int(rng.integers(0, 1 << air.qdb))                    # a multiple of step: the quotient coset sees the edge rows
     edge_points = np.arange(k, n << air.rate_bits, 1 << air.rate_bits)
@@ -304,7 +325,8 @@ def check_set_proof(p, orc, tables, lookups, lgs, nc, hasher, sset, proof, trace
             assert pp.quotient_cap == cap(chunks, False) and pp.quotient == [eval_ext(c, zeta) for c in chunks]
 
 
-@pytest.mark.parametrize("lgs,nc,hasher", [([5, 6, 5], 2, "poseidon"), ([5, 6, 5], 1, "poseidon"), ([5, 6, 5], 2, "keccak"), ([12, 11, 12], 2, "poseidon")])
+@pytest.mark.parametrize("lgs,nc,hasher", [([5, 6, 5], 2, "poseidon"), ([5, 6, 5], 1, "poseidon"), ([5, 6, 5], 2, "keccak"), ([12, 11, 12], 2, "poseidon"),
+                                           ([5, 6, 5], 4, "poseidon")])
 def test_whole_set_proof(gpu, orc, lgs, nc, hasher):
     p, ctx = gpu
     sset = p.StarkSet(airs.api_set(p, airs.TABLES, airs.LOOKUPS, lgs, airs.config(p, nc), hasher=hasher), ctx=ctx)
@@ -335,6 +357,23 @@ def test_an_inconsistent_system_is_rejected_by_the_cross_table_check(gpu, orc):
     assert (ok, code, table) == (False, p._lib.GL_CHECK_CTL, 3) and "ross-table" in why
     params = [sset.desc.fri_params(t) for t in range(3)]
     assert cm.verify_set(airs.TABLES, airs.LOOKUPS, nc, params, proof, model_challenger(orc, "poseidon"), verify_path_of(orc, "poseidon")) == (cm.CTL, 3)
+
+
+def test_whole_set_proof_with_a_degree_5_table_and_its_inconsistent_system(gpu, orc):
+    # tables of q = 2 and q = 4 in one set under rate_bits 2
+    from test_fri_openings import verify_path_of
+    p, ctx = gpu
+    lgs, nc = [5, 6, 5], 3
+    sset = p.StarkSet(airs.api_set(p, airs.TABLES5, airs.LOOKUPS, lgs, airs.config(p, nc, airs.RATE_BITS5)), ctx=ctx)
+    assert [sset.desc.fri_params(t).rate_bits for t in range(3)] == [2, 2, 2]
+    traces = airs.traces(lgs, seed=7)
+    proof = sset.prove(traces)
+    check_set_proof(p, orc, airs.TABLES5, airs.LOOKUPS, lgs, nc, "poseidon", sset, proof, traces)
+    removed = sset.prove(airs.remove_one_looked_row(traces))
+    ok, why, code, table = sset.verify(removed)
+    assert (ok, code, table) == (False, p._lib.GL_CHECK_CTL, 3) and "ross-table" in why
+    params = [sset.desc.fri_params(t) for t in range(3)]
+    assert cm.verify_set(airs.TABLES5, airs.LOOKUPS, nc, params, removed, model_challenger(orc, "poseidon"), verify_path_of(orc, "poseidon")) == (cm.CTL, 3)
 
 
 def test_a_single_table_set_with_one_permutation_pair(gpu, orc):

@@ -110,6 +110,43 @@ def test_the_quotient_of_a_consistent_system_has_degree_below_q_n(orc, nc):
         assert orc.coset_ifft(np.array(bad, dtype=U64), 7)[:, air.q * n:].any()
 
 
+@pytest.mark.parametrize("nc", [1, 2, 3, 4])
+def test_the_quotient_of_the_system_with_a_degree_5_table_has_degree_below_q_n(orc, nc):
+    # TABLES5: the same traces satisfy it (used^5 = used); ops and ops2 keep q = 2, mul has q = 4.  Every table on a coset twice as large
+    # as its own, so that the trim has a tail to look at; mul's own constraint used^5 - used sits on the bound: degree 5 (n - 1) - n
+    rng = np.random.Generator(np.random.PCG64(40 + nc))
+    traces = airs.traces(LGS, seed=3)
+    chs = challenges(rng, nc)
+    data = cm.cross_table_lookup_data(traces, airs.LOOKUPS, chs)
+    assert [(a.q, a.qdb, a.rate_bits) for a in airs.TABLES5] == [(2, 1, 2), (2, 1, 2), (4, 2, 2)]
+    assert [len(d) for d in data] == [cm.num_ctl_zs(airs.LOOKUPS, t, nc) for t in range(3)] == [2 * nc, nc, 2 * nc]
+    for table, air in enumerate(airs.TABLES5):
+        lg_n = LGS[table]
+        n = 1 << lg_n
+        air = copy.copy(air)
+        air.qdb += 1
+        sets = [[tuple(int(v) for v in rng.integers(0, P, size=2, dtype=U64)) for _ in range(nc)] for _ in range(air.q)] if air.pairs else None
+        zs = (sm.permutation_zs(air, nc, traces[table], sets)[0] if air.pairs else []) + [v.z for v in data[table]]
+        trace_q = orc.lde(orc.ifft(traces[table]), air.qdb)
+        zs_q = orc.lde(orc.ifft(np.array(zs, dtype=U64)), air.qdb)
+        alphas = [int(v) for v in rng.integers(0, P, size=nc, dtype=U64)]
+        values = cm.quotient_values(orc, air, nc, lg_n, trace_q, zs_q, sets, alphas, [], data[table])
+        coeffs = orc.coset_ifft(np.array(values, dtype=U64), 7)
+        assert coeffs.shape == (nc, 2 * n << (air.qdb - 1)) and not coeffs[:, air.q * n:].any(), "table %d: the quotient's degree is too high" % table
+        if table == airs.MUL:
+            assert coeffs[:, 4 * n - 5].all() and not coeffs[:, 4 * n - 4:].any()
+        zs_bad = np.array(zs, dtype=U64)
+        zs_bad[-1][n // 2] = (int(zs_bad[-1][n // 2]) + 1) % P
+        bad = cm.quotient_values(orc, air, nc, lg_n, trace_q, orc.lde(orc.ifft(zs_bad), air.qdb), sets, alphas, [], data[table])
+        assert orc.coset_ifft(np.array(bad, dtype=U64), 7)[:, air.q * n:].any()
+        # a row with used = 2 satisfies used (a b - c) = 0 where a b = c, but not used^5 = used
+        if table == airs.MUL:
+            broken = traces[table].copy()
+            broken[3][int(np.flatnonzero(broken[3])[0])] = 2
+            values = cm.quotient_values(orc, air, nc, lg_n, orc.lde(orc.ifft(broken), air.qdb), zs_q, sets, [0] * (nc - 1) + [1], [], [])
+            assert orc.coset_ifft(np.array(values, dtype=U64), 7)[:, air.q * n:].any()
+
+
 def test_compact_against_a_hand_run_of_the_duplex_sponge(orc):
     # challenger.rs:146-152 by hand on the permutation: pending input is written over the first words of the state and permuted; the
     # outputs are dropped, so the next challenge permutes again

@@ -1,6 +1,7 @@
 """CPU tests of the STARK seam's host code (csrc/stark.hip): gl_stark_check's refusals, each beside the boundary case it accepts, and
-gl_stark_verify on the committed proof tests/golden/stark_fibonacci_n32.bin (tools/make_stark_fixture.py wrote it on the GPU; the GPU
-test test_the_committed_fixture_is_current holds it current) next to the model verifier of tests/stark_model.py."""
+gl_stark_verify on the committed proofs tests/golden/stark_fibonacci_n32.bin (two challenges, q = 1) and stark_nonic_n32_nc3.bin (three
+challenges, q = 8 at rate_bits 3) next to the model verifier of tests/stark_model.py.  tools/make_stark_fixture.py wrote them on the GPU;
+the GPU tests test_the_committed_*fixture_is_current hold them current."""
 import ctypes
 import json
 import os
@@ -94,11 +95,15 @@ def test_gl_stark_check_refuses_and_accepts_the_boundary(p, what, refused, code,
 
 
 def test_gl_stark_check_takes_null_arguments_and_the_four_airs(p):
+    # (every AIR of stark_airs.py by now, under each num_challenges)
     assert p.api.lib.gl_stark_check(None, None) == ARG
     for air in stark_airs.AIRS.values():
         config = p.StarkConfig.standard_fast_config()
         config.rate_bits = air.rate_bits
-        p.StarkDesc(air.num_columns, air.num_public_inputs, air.constraint_degree, air.constraints, air.pairs).check(config, 5)
+        for nc in (1, 2, 3, 4):
+            config.num_challenges = nc
+            for degree_bits in (5, 7, 12):
+                p.StarkDesc(air.num_columns, air.num_public_inputs, air.constraint_degree, air.constraints, air.pairs).check(config, degree_bits)
     # the description api.fibonacci_stark gives is the one the tests' model runs on
     desc, generate = p.fibonacci_stark(32)
     air = stark_airs.fibonacci
@@ -112,34 +117,50 @@ def test_gl_stark_check_takes_null_arguments_and_the_four_airs(p):
 NC = 2
 
 
-@pytest.fixture(scope="module")
-def fixture(p):
-    with open(os.path.join(GOLDEN, "stark_fibonacci_n32.bin"), "rb") as f:
+def load(p, stem, desc_of):
+    """(proof, meta, desc, config, params, air, num_challenges) of a committed proof"""
+    with open(os.path.join(GOLDEN, stem + ".bin"), "rb") as f:
         proof = f.read()
-    with open(os.path.join(GOLDEN, "stark_fibonacci_n32.json")) as f:
+    with open(os.path.join(GOLDEN, stem + ".json")) as f:
         meta = json.load(f)
-    desc, _ = p.fibonacci_stark(meta["num_rows"])
+    air = stark_airs.AIRS[meta["air"]]
     config = p.StarkConfig.standard_fast_config()
+    config.num_challenges, config.rate_bits = meta["num_challenges"], meta["params"]["rate_bits"]
     params = config.fri_params(meta["params"]["degree_bits"])
     assert {k: getattr(params, k) for k in meta["params"]} == meta["params"] and meta["num_bytes"] == len(proof)
-    return proof, meta, desc, config, params
+    return proof, meta, desc_of(meta, air), config, params, air, meta["num_challenges"]
+
+
+@pytest.fixture(scope="module")
+def fixture(p):
+    f = load(p, "stark_fibonacci_n32", lambda meta, air: p.fibonacci_stark(meta["num_rows"])[0])
+    assert f[6] == NC and f[4].rate_bits == 1                            # standard_fast_config as it stands
+    return f
+
+
+@pytest.fixture(scope="module")
+def nonic_fixture(p):
+    f = load(p, "stark_nonic_n32_nc3", lambda meta, air: p.StarkDesc(air.num_columns, air.num_public_inputs, air.constraint_degree, air.constraints, air.pairs))
+    assert (f[5].name, f[5].q, f[6], f[4].rate_bits, f[4].degree_bits) == ("nonic", 8, 3, 3, 5)
+    return f
 
 
 def library(p, fixture, proof):
-    _, meta, desc, config, _ = fixture
+    _, meta, desc, config = fixture[:4]
     ok, why, code = p.stark_verify(desc, config, meta["params"]["degree_bits"], proof)
     assert ok == (code == 0)
     return code
 
 
 def model(orc, fixture, proof):
-    params = fixture[4]
-    return sm.verify(stark_airs.fibonacci, NC, params, proof, poseidon_challenger(orc), fom.poseidon_verify_path(orc))
+    params, air, nc = fixture[4:7]
+    return sm.verify(air, nc, params, proof, poseidon_challenger(orc), fom.poseidon_verify_path(orc))
 
 
-def layout(params):
-    """(region name, first byte, length, in the transcript?, the check a flip there fails or None) of the fibonacci proof at 2^5: no FRI reduction"""
-    air, cap = stark_airs.fibonacci, 32 << params.cap_height
+def layout(params, air=stark_airs.fibonacci, nc=NC):
+    """(region name, first byte, length, in the transcript?, the check a flip there fails or None) of a proof at 2^5: no FRI reduction"""
+    cap, nz = 32 << params.cap_height, sm.num_zs(air, nc)
+    assert nz and not params.reduction_arity_bits
     siblings = params.degree_bits + params.rate_bits - params.cap_height
     regions, at = [], 0
 
@@ -149,10 +170,11 @@ def layout(params):
         at += length
     for name in ("trace_cap", "permutation_zs_cap", "quotient_polys_cap"):
         add(name, cap, True, None)
-    for name, k in (("local_values", 4), ("next_values", 4), ("permutation_zs", 2), ("permutation_zs_next", 2), ("quotient_polys", 2)):
+    for name, k in (("local_values", air.num_columns), ("next_values", air.num_columns), ("permutation_zs", nz), ("permutation_zs_next", nz),
+                    ("quotient_polys", air.q * nc)):
         add(name, 16 * k, True, None)
     for q in range(params.num_query_rounds):
-        for o, k in enumerate((air.num_columns, 2, 2)):
+        for o, k in enumerate((air.num_columns, nz, air.q * nc)):
             add("query %d leaf %d" % (q, o), 8 * k, False, fom.INITIAL_MERKLE)
             add("query %d path length %d" % (q, o), 1, False, "decode")
             add("query %d siblings %d" % (q, o), 32 * siblings, False, fom.INITIAL_MERKLE)
@@ -163,7 +185,7 @@ def layout(params):
 
 
 def test_the_fixture_is_accepted_by_the_library_and_by_the_model(p, orc, fixture):
-    proof, meta, _, _, params = fixture
+    proof, meta, params = fixture[0], fixture[1], fixture[4]
     regions, size = layout(params)
     assert size == len(proof) == 24060
     assert library(p, fixture, proof) == 0 and model(orc, fixture, proof) == 0
@@ -172,13 +194,18 @@ def test_the_fixture_is_accepted_by_the_library_and_by_the_model(p, orc, fixture
     assert (pp.trace_cap[0], pp.zs_cap[0], pp.quotient_cap[0]) == (meta["trace_cap_first_words"], meta["permutation_zs_cap_first_words"], meta["quotient_polys_cap_first_words"])
 
 
-def test_single_bit_flips_in_every_region_are_rejected_by_both(p, orc, fixture):
-    proof, _, _, _, params = fixture
-    regions, _ = layout(params)
-    rng = np.random.Generator(np.random.PCG64(2024))
+def kinds_of(regions):
     by_kind = {}
     for r in regions:
         by_kind.setdefault(r[0].split(" ", 2)[-1] if r[0].startswith("query") else r[0], []).append(r)
+    return by_kind
+
+
+def test_single_bit_flips_in_every_region_are_rejected_by_both(p, orc, fixture):
+    proof, params = fixture[0], fixture[4]
+    regions, _ = layout(params)
+    rng = np.random.Generator(np.random.PCG64(2024))
+    by_kind = kinds_of(regions)
     picks = []
     for kind, rs in by_kind.items():                                     # three flips in every kind of region, 20 kinds ...
         for _ in range(3):
@@ -186,8 +213,15 @@ def test_single_bit_flips_in_every_region_are_rejected_by_both(p, orc, fixture):
     while len(picks) < 64:                                               # ... and the rest anywhere
         picks.append(regions[int(rng.integers(0, len(regions)))])
     assert len(picks) == 64 and len(by_kind) == 20
-    for name, first, length, transcript, check in picks:
-        byte, bit = first + int(rng.integers(0, length)), int(rng.integers(0, 8))
+    flips_are_rejected_by_both(p, orc, fixture, rng, picks)
+
+
+def flips_are_rejected_by_both(p, orc, fixture, rng, picks):
+    """picks: regions, or (region, first byte inside it, length) to flip within a part of one"""
+    proof = fixture[0]
+    for pick in picks:
+        (name, first, length, transcript, check), at, span = pick if len(pick) == 3 else (pick, 0, pick[2])
+        byte, bit = first + at + int(rng.integers(0, span)), int(rng.integers(0, 8))
         if "path length" in name:
             bit = int(rng.integers(0, 3))                                # a length the proof could hold: 2 -> 3, 0 or 6
         bad = bytearray(proof)
@@ -206,6 +240,42 @@ def test_truncation_and_a_trailing_byte(p, orc, fixture):
     for cut in (1, 8, 24, 25, len(proof) - 100, len(proof)):
         assert library(p, fixture, proof[:len(proof) - cut]) == fom.TRUNCATED == model(orc, fixture, proof[:len(proof) - cut])
     assert library(p, fixture, proof + b"\0") == fom.LENGTH == model(orc, fixture, proof + b"\0")
+
+
+# ------------------------------------------------------------------------------- the same on three challenges and eight chunks
+def test_the_nonic_fixture_is_accepted_by_the_library_and_by_the_model(p, orc, nonic_fixture):
+    proof, meta, _, _, params, air, nc = nonic_fixture
+    regions, size = layout(params, air, nc)
+    assert size == len(proof)
+    assert library(p, nonic_fixture, proof) == 0 and model(orc, nonic_fixture, proof) == 0
+    pp = sm.ParsedStarkProof(air, nc, params, proof)
+    assert pp.public_inputs == meta["public_inputs"] == air.trace(meta["num_rows"], seed=meta["trace_seed"])[1]
+    assert (len(pp.zs), len(pp.quotient)) == (2, 24)                     # ceil(3 pairs x 3 challenges / 8), 3 x 8 chunks
+    assert (pp.trace_cap[0], pp.zs_cap[0], pp.quotient_cap[0]) == (meta["trace_cap_first_words"], meta["permutation_zs_cap_first_words"], meta["quotient_polys_cap_first_words"])
+
+
+def test_the_nonic_fixture_changed_anywhere_is_rejected_by_both_with_the_same_check(p, orc, nonic_fixture):
+    proof, _, _, _, params, air, nc = nonic_fixture
+    regions, _ = layout(params, air, nc)
+    rng = np.random.Generator(np.random.PCG64(2025))
+    by_kind = kinds_of(regions)
+    assert len(by_kind) == 20
+    picks = [rs[int(rng.integers(0, len(rs)))] for rs in by_kind.values()]                    # every cap, opening family and part of a query
+    named = {r[0]: r for r in regions}
+    quotient = named["quotient_polys"]
+    assert quotient[2] == 16 * nc * air.q
+    picks += [(quotient, 16 * (2 * air.q + k), 16) for k in (0, air.q - 1)]                   # the first and the last chunk of challenge 2 ...
+    picks += [(quotient, 16 * (air.q - 1), 16), (named["permutation_zs"], 16, 16), (named["permutation_zs_next"], 16, 16)]      # ... chunk 7, the partial batch's Z
+    picks += [(named["public_inputs"], 8 * i, 8) for i in range(air.num_public_inputs)]
+    picks += [(named["local_values"], 16 * c, 16) for c in (0, air.num_columns - 1)] + [(named["next_values"], 0, 16)]
+    flips_are_rejected_by_both(p, orc, nonic_fixture, rng, picks)
+
+
+def test_the_nonic_fixture_truncated_or_with_a_trailing_byte(p, orc, nonic_fixture):
+    proof = nonic_fixture[0]
+    for cut in (1, 8, 16, 17, len(proof) - 100, len(proof)):
+        assert library(p, nonic_fixture, proof[:len(proof) - cut]) == fom.TRUNCATED == model(orc, nonic_fixture, proof[:len(proof) - cut])
+    assert library(p, nonic_fixture, proof + b"\0") == fom.LENGTH == model(orc, nonic_fixture, proof + b"\0")
 
 
 def test_every_stark_kernel_compiles_without_scratch_and_the_committed_report_is_current():
