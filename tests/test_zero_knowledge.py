@@ -2,52 +2,20 @@
 
 The randomness is pinned against a numpy ChaCha20 written from RFC 8439 (checked against the RFC's own vectors), the blinding layout
 against a restatement of circuit_builder.rs:713-818, and every salted commitment against the CPU oracle's Merkle tree over leaves
-built here.  The oracle cannot build a zero-knowledge circuit, so a whole zk proof is pinned by the native verifier only."""
+built here.  The oracle cannot build a zero-knowledge circuit; whole zk proofs are pinned byte for byte against an integer derivation in
+tests/test_zk_model.py, which shares the restatements of tests/zk_circuits.py with this file."""
 import copy
-import math
 
 import numpy as np
 import pytest
 
 from oracle_lib import P, rand_field
+# the restatements shared with the zk model tests (tests/zk_circuits.py)
+from zk_circuits import bitrev as _bitrev, blinding_counts, chacha20_blocks, fri_arity_bits, model_blinded_wires as _model_blinded_wires      # noqa: F401
+from zk_circuits import model_elements, padded_degree_bits, salted_cap as _salted_cap      # noqa: F401
 
 SEED = bytes(range(32))
 SEED2 = bytes(range(100, 132))
-
-
-# ---------------------------------------------------------------------------------------------------- ChaCha20 model (RFC 8439 2.3)
-def chacha20_blocks(key, nonce_words, counters):
-    """Serialised keystream blocks [len(counters)][16] (u32 words) of the RFC 8439 block function."""
-    counters = np.asarray(counters, dtype=np.uint32)
-    init = np.zeros((16, counters.size), dtype=np.uint32)
-    init[0:4] = np.array([0x61707865, 0x3320646E, 0x79622D32, 0x6B206574], dtype=np.uint32)[:, None]
-    init[4:12] = np.frombuffer(bytes(key), dtype="<u4")[:, None]
-    init[12] = counters
-    init[13:16] = np.array(nonce_words, dtype=np.uint32)[:, None]
-    x = init.copy()
-
-    def qr(a, b, c, d):
-        for (p, q, r, rot) in ((a, b, d, 16), (c, d, b, 12), (a, b, d, 8), (c, d, b, 7)):
-            x[p] += x[q]
-            x[r] ^= x[p]
-            x[r] = (x[r] << np.uint32(rot)) | (x[r] >> np.uint32(32 - rot))
-
-    for _ in range(10):
-        qr(0, 4, 8, 12); qr(1, 5, 9, 13); qr(2, 6, 10, 14); qr(3, 7, 11, 15)
-        qr(0, 5, 10, 15); qr(1, 6, 11, 12); qr(2, 7, 8, 13); qr(3, 4, 9, 14)
-    return (x + init).T.copy()
-
-
-def model_elements(seed, stream, first, count):
-    """Element i = (w_2i + 2^64 w_2i+1) mod p over the little-endian u64 words of stream `stream`'s keystream (nonce = stream, 0, 0)."""
-    if count == 0:
-        return np.zeros(0, dtype=np.uint64)
-    b0, b1 = first // 4, (first + count - 1) // 4
-    words = chacha20_blocks(seed, (stream, 0, 0), np.arange(b0, b1 + 1)).astype(np.uint64).reshape(-1, 4)
-    lo = (words[:, 0] | (words[:, 1] << np.uint64(32))).astype(object)
-    hi = (words[:, 2] | (words[:, 3] << np.uint64(32))).astype(object)
-    vals = np.array((lo + hi * (1 << 64)) % P, dtype=np.uint64)
-    return vals[first - 4 * b0: first - 4 * b0 + count]
 
 
 def keystream_bytes(blocks):
@@ -95,37 +63,6 @@ def test_host_elements_match_the_model(stream, first, count):
 
 
 # ---------------------------------------------------------------------------------------------------- blinding layout
-def fri_arity_bits(lg, rate_bits=3, cap_height=4):
-    """ConstantArityBits(4, 5) (fri/reduction_strategies.rs:39-49)."""
-    out, db = [], lg
-    while db > 5 and db + rate_bits - 4 >= cap_height:
-        out.append(4)
-        db -= 4
-    return out
-
-
-def num_blinding_gates(degree_estimate, num_query_rounds=28, D=2):
-    arities = [1 << a for a in fri_arity_bits(degree_estimate.bit_length() - 1)]
-    total_points = sum(a - 1 for a in arities)
-    final_poly_coeffs = degree_estimate // math.prod(arities)
-    fri_openings = num_query_rounds * (1 + D * total_points + D * final_poly_coeffs)
-    return D + fri_openings, 2 * D + fri_openings
-
-
-def blinding_counts(num_gates):
-    degree_estimate = 1 << (num_gates - 1).bit_length()
-    while True:
-        regular, z = num_blinding_gates(degree_estimate)
-        if num_gates + regular + 2 * z <= degree_estimate:
-            return regular, z
-        degree_estimate *= 2
-
-
-def padded_degree_bits(num_gates, zk):
-    total = num_gates + (sum(x * k for x, k in zip(blinding_counts(num_gates), (1, 2))) if zk else 0)
-    return (total - 1).bit_length()
-
-
 def first_occurrence_labels(classes):
     """A copy-class matrix relabelled by first occurrence: equal labels = the same partition, whatever ids the builder used."""
     flat = classes.reshape(-1)
@@ -232,42 +169,6 @@ def test_zk_common_data_round_trips_and_mixed_flags_are_refused():
 
 
 # ---------------------------------------------------------------------------------------------------- GPU
-def _bitrev(lg):
-    idx = np.arange(1 << lg, dtype=np.int64)
-    r = np.zeros_like(idx)
-    for i in range(lg):
-        r |= ((idx >> i) & 1) << (lg - 1 - i)
-    return r
-
-
-def _salted_cap(orc, cols, from_values, oracle, seed, cap_height=4, rate_bits=3):
-    """The cap of a blinded PolynomialBatch built here: the oracle's LDE leaves (Merkle order) followed by the model's salt."""
-    ob = orc.batch(cols, rate_bits, cap_height, from_values=from_values, threads=8)
-    leaves = ob.leaves()
-    N = leaves.shape[0]
-    salt = np.stack([model_elements(seed, 0x200 + 4 * oracle + j, 0, N) for j in range(4)])
-    rev = _bitrev(N.bit_length() - 1)
-    full = np.concatenate([leaves, salt[:, rev].T], axis=1)
-    return orc.merkle(full, cap_height).cap
-
-
-def _model_blinded_wires(wires, g, seed):
-    """Expected witness after blind(): the RandomValueGenerators and CopyGenerators of circuit_builder.rs:777-818, zeros elsewhere."""
-    out = wires.copy()
-    n = out.shape[1]
-    regular, pairs = blinding_counts(g)
-    out[:, g:] = 0
-    for w in range(135):
-        vals = model_elements(seed, 0x100 + w, g, regular + 2 * pairs)
-        out[w, g:g + regular] = vals[:regular]
-        if w < 80:
-            first = vals[regular::2]
-            out[w, g + regular:g + regular + 2 * pairs:2] = first
-            out[w, g + regular + 1:g + regular + 2 * pairs:2] = first
-    assert g + regular + 2 * pairs <= n
-    return out
-
-
 def _zk_proof(p, ctx, hc, cd, a, b, seed, filler_seed=5):
     wires, pis = hc.witness(a, b, filler_seed=filler_seed)
     buf = ctx.alloc(135 * hc.n * 8)
