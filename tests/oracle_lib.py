@@ -474,6 +474,16 @@ def load():
     return _cached
 
 
+def m1_desc(orc, lg_n, rounds=0):
+    """the m = 1 matmul description at another length: degree_bits and the FRI reduction rounds (arity 16) edited in place"""
+    d = orc.circuit(1, threads=4).product_desc()
+    assert d.num_lookup_polys == 0 and d.num_gate_rows == 0 and d.cap_height == 4
+    d.degree_bits, d.num_fri_rounds = lg_n, rounds
+    for r in range(8):
+        d.fri_arity_bits[r] = 4 if r < rounds else 0
+    return d
+
+
 def splitmix64(seed, count):
     """Deterministic canonical field elements (splitmix64 streams mod p)."""
     out = np.empty(count, dtype=np.uint64)

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import prover_phase_model as pm
+from oracle_lib import m1_desc
 from proof_parser import ParsedProof
 from test_prover_phase_model import ZETAS, lookup_rows, pairs
 from test_quotient_model import EDGES, edge_targets
@@ -37,16 +38,6 @@ def draw(rng, k):
 
 def canonical(ch):
     return {key: [v % P for v in vals] for key, vals in ch.items()}
-
-
-def m1_desc(orc, lg_n, rounds=0):
-    """the m = 1 matmul description at another length: degree_bits and the FRI reduction rounds (arity 16) edited in place"""
-    d = orc.circuit(1, threads=4).product_desc()
-    assert d.num_lookup_polys == 0 and d.num_gate_rows == 0 and d.cap_height == 4
-    d.degree_bits, d.num_fri_rounds = lg_n, rounds
-    for r in range(8):
-        d.fri_arity_bits[r] = 4 if r < rounds else 0
-    return d
 
 
 def edge_columns(seed, ncols, n):
