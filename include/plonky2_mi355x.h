@@ -589,6 +589,64 @@ int gl_stark_prove_device(gl_ctx* ctx, const gl_stark* s, const uint64_t* d_cols
  * gl_verify_openings' checks in its order.  The verifier takes FRI arity bits 1..8, as gl_verify_openings does. */
 int gl_stark_verify(const gl_stark_desc* desc, const gl_fri_params* params, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check);
 
+/* ---- STARK constraints as an expression DAG -----------------------------------------------------------
+ * The other form of a table's constraints: the straight-line program a Stark writes in eval_packed_generic, with shared
+ * subexpressions, for AIRs whose expanded form passes GL_STARK_MAX_TERMS.  A gl_stark_dag is passed BESIDE a
+ * gl_stark_desc that carries num_constraints = 0 and null term tables; columns, public inputs, constraint_degree, num_challenges and
+ * the pairs keep their meaning.  It is one form or the other per table.
+ * Node k is  node_op[k](node_a[k], node_b[k]),  nodes in SSA order.  An operand word is  kind << 28 | index  (GL_STARK_OPERAND): LOCAL /
+ * NEXT a trace column, PUBLIC a public input, NODE an EARLIER node, CONST an index into constants[] (64-bit words, may be
+ * non-canonical).  Constraint c is constraint_operand[c] -- one operand word of any kind -- under constraint_filter[c], in the order
+ * the Stark yields them.
+ * Degree, counted formally: LOCAL / NEXT 1, PUBLIC / CONST 0, ADD / SUB the maximum of their operands, MUL the sum.  A constraint's
+ * operand has degree at most q + 1 under GL_STARK_ALL / TRANSITION and at most q under FIRST_ROW / LAST_ROW.
+ * Scheduling and liveness, the same in the host check, the kernel's program and the verifier: the nodes run in the given order; a
+ * node no constraint reaches is dropped; constraint c is consumed at the first position -- before node 0, or right after a node -- at
+ * which its value exists and constraint c - 1 has been consumed, so the Horner order in alpha is the yield order.  A value is live
+ * from its definition to its last use by a node or by a constraint's consumption; live(k) counts the values defined at or before
+ * node k whose last use is after node k (an operand that dies at node k does not count: node k may take its slot).  max live above
+ * GL_STARK_DAG_MAX_LIVE is refused: on the device every thread keeps its live values in LDS.
+ * Proof bytes -- PARITY UNPINNED, as for gl_stark_prove: the layout is the same, and a DAG that states the same polynomials as a
+ * term list yields the same bytes. */
+#define GL_STARK_NODE 3u         /* operand kinds beyond GL_STARK_PUBLIC, in an operand word of a gl_stark_dag only */
+#define GL_STARK_CONST 4u
+#define GL_STARK_OPERAND(kind, index) ((uint32_t)(kind) << 28 | (uint32_t)(index))    /* index < 2^28 */
+#define GL_STARK_OP_ADD 0u
+#define GL_STARK_OP_SUB 1u
+#define GL_STARK_OP_MUL 2u
+#define GL_STARK_DAG_MAX_NODES 65536u
+#define GL_STARK_DAG_MAX_CONSTANTS 65536u
+#define GL_STARK_DAG_MAX_LIVE 128u      /* values live at once: 64 KiB of LDS per 64-thread workgroup at the cap */
+typedef struct gl_stark_dag {
+    uint32_t num_nodes;
+    const uint32_t* node_op;                   /* [num_nodes] GL_STARK_OP_ADD / SUB / MUL */
+    const uint32_t* node_a;                    /* [num_nodes] operand words */
+    const uint32_t* node_b;                    /* [num_nodes] */
+    uint32_t num_constants;
+    const uint64_t* constants;                 /* [num_constants] may be non-canonical */
+    uint32_t num_constraints;
+    const uint32_t* constraint_filter;         /* [num_constraints] GL_STARK_ALL .. LAST_ROW, in the order the Stark yields them */
+    const uint32_t* constraint_operand;        /* [num_constraints] operand words of any kind */
+} gl_stark_dag;
+/* gl_stark_check for a table in DAG form.  GL_ERR_ARG for: a null dag (use gl_stark_check), a desc that carries a term list as well
+ * (num_constraints != 0 or a non-null term table), a count outside the caps (at least 1 constraint), a null table, an unknown op,
+ * filter or operand kind, an index out of range, a NODE operand that is no earlier node (forward or self reference), a constraint
+ * above the degree rule, max live above GL_STARK_DAG_MAX_LIVE; and everything gl_stark_check refuses in the rest of the desc and in
+ * the params, with its status. */
+int gl_stark_dag_check(const gl_stark_desc* desc, const gl_stark_dag* dag, const gl_fri_params* params);
+/* What the definitions above give for a DAG that passes the DAG's own rules (params are not looked at): max live, the largest
+ * degree of a constraint, and the number of instructions of the compiled program (one per node kept, one per constraint).  Any
+ * out pointer may be null. */
+int gl_stark_dag_stats(const gl_stark_desc* desc, const gl_stark_dag* dag, uint32_t* max_live, uint32_t* max_degree, uint32_t* num_instructions);
+/* gl_stark_create for a table in DAG form: the DAG is compiled once into instructions (`op dst_slot, a, b` and `emit filter, a`, four
+ * words each; the host is the scheduler and a linear-scan slot allocator, the constants are canonicalised) and uploaded.  The handle is an ordinary
+ * gl_stark: every entry above that takes one works on it unchanged, and the proof's layout is the one documented there. */
+int gl_stark_dag_create(gl_ctx* ctx, const gl_stark_desc* desc, const gl_stark_dag* dag, const gl_fri_params* params, gl_stark** out);
+/* gl_stark_verify for a table in DAG form: the same checks in the same order with the same GL_CHECK_* codes; the constraints at zeta
+ * come from a host interpreter of the same compiled program over the extension field. */
+int gl_stark_dag_verify(const gl_stark_desc* desc, const gl_stark_dag* dag, const gl_fri_params* params, const uint8_t* proof_bytes, size_t num_bytes,
+                        uint32_t* check);
+
 /* ---- STARK table sets: cross-table lookups as data ----------------------------------------------------
  * evm/src/cross_table_lookup.rs for any number of tables: every table is a gl_stark_desc with its gl_fri_params (degree_bits may
  * differ per table), and the lookups between them are data.  What is here: the description and its validation; the CTL running
@@ -705,6 +763,14 @@ int gl_stark_set_prove_device(gl_ctx* ctx, const gl_stark_set* s, const uint64_t
  * FRI checks of its table (the batch at g^-1 no longer matches the committed polynomial), not by GL_CHECK_CTL; GL_CHECK_CTL is what
  * an honestly proven but inconsistent system gets. */
 int gl_stark_set_verify(const gl_stark_set_desc* desc, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check, uint32_t* table);
+/* The same three for a set some of whose tables are in DAG form: dags[num_tables], a null entry = that table's term list, a non-null
+ * one = a gl_stark_dag beside a table desc without a term list (gl_stark_dag_check's rules).  A null dags is the plain entry.  The
+ * handle is an ordinary gl_stark_set: every gl_stark_set_* phase and prove entry works on it unchanged, and the CTL checks follow the
+ * DAG's constraints and the permutation checks exactly as they follow a term list's. */
+int gl_stark_set_dag_check(const gl_stark_set_desc* desc, const gl_stark_dag* const* dags);
+int gl_stark_set_dag_create(gl_ctx* ctx, const gl_stark_set_desc* desc, const gl_stark_dag* const* dags, gl_stark_set** out);
+int gl_stark_set_dag_verify(const gl_stark_set_desc* desc, const gl_stark_dag* const* dags, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check,
+                            uint32_t* table);
 
 /* ---- prove() ---------------------------------------------------------------------------------------*/
 /* plonk::prover::prove (plonky2/src/plonk/prover.rs:102-329) from step 4 on, i.e. given the FULL witness matrix

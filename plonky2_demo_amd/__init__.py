@@ -8,6 +8,8 @@ Names and argument meaning follow the reference so that the parity tests read li
 from ._lib import LIB_PATH, FriInstance, FriParams, Plonky2Mi355xError  # noqa: F401
 from ._lib import (  # noqa: F401  (gl_stark_desc filters and operand kinds)
     GL_STARK_ALL, GL_STARK_TRANSITION, GL_STARK_FIRST_ROW, GL_STARK_LAST_ROW, GL_STARK_LOCAL, GL_STARK_NEXT, GL_STARK_PUBLIC,
+    GL_STARK_NODE, GL_STARK_CONST, GL_STARK_OP_ADD, GL_STARK_OP_SUB, GL_STARK_OP_MUL, GL_STARK_DAG_MAX_NODES, GL_STARK_DAG_MAX_LIVE, GL_STARK_MAX_TERMS,
+    stark_operand,
 )
 from . import api  # noqa: F401
 from .api import (  # noqa: F401
@@ -15,5 +17,6 @@ from .api import (  # noqa: F401
     lde_onto_coset, poseidon, pow_grind, random_elements, GOLDILOCKS_ORDER, COSET_SHIFT,
     hash_from_bytes, hash_or_noop_host, hash_to_bytes, hash_to_elements, two_to_one_host, verify_fri_proof,
     Stark, StarkConfig, StarkDesc, fibonacci_stark, stark_verify,
+    StarkDagBuilder, StarkDagDesc, StarkDagExpr, stark_dag_verify,
     CrossTableLookup, CtlColumn, StarkSet, StarkSetDesc, TableWithColumns, stark_set_verify,
 )

@@ -195,6 +195,14 @@ SIGNATURES = {
     "gl_stark_prove": (c_int, [c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp, c_sz, ctypes.POINTER(c_sz)]),
     "gl_stark_prove_device": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(c_sz)]),
     "gl_stark_verify": (c_int, [c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(c_u32)]),
+    # STARK constraints as an expression DAG (gl_stark_desc*, gl_stark_dag*, ...)
+    "gl_stark_dag_check": (c_int, [c_vp, c_vp, c_vp]),
+    "gl_stark_dag_stats": (c_int, [c_vp, c_vp, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
+    "gl_stark_dag_create": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)]),
+    "gl_stark_dag_verify": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(c_u32)]),
+    "gl_stark_set_dag_check": (c_int, [c_vp, c_vp]),
+    "gl_stark_set_dag_create": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)]),
+    "gl_stark_set_dag_verify": (c_int, [c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
     # STARK table sets: cross-table lookups as data (gl_stark_set_desc*, ...)
     "gl_challenger_compact": (c_int, [c_vp]),
     "gl_stark_set_check": (c_int, [c_vp]),
@@ -340,6 +348,39 @@ class StarkDescStruct(ctypes.Structure):
         self.constraint_filter, self.constraint_num_terms = table(c_u32, filters), table(c_u32, num_terms)
         self.term_coeff, self.term_num_factors, self.factors = table(c_u64, coeffs), table(c_u32, num_factors), table(c_u32, factors)
         self.pair_len, self.pair_columns = table(c_u32, pair_len), table(c_u32, pair_columns)
+
+
+(GL_STARK_NODE, GL_STARK_CONST) = (3, 4)                                                   # operand kinds of a gl_stark_dag only
+(GL_STARK_OP_ADD, GL_STARK_OP_SUB, GL_STARK_OP_MUL) = range(3)
+GL_STARK_DAG_MAX_NODES, GL_STARK_DAG_MAX_LIVE, GL_STARK_MAX_TERMS, GL_STARK_MAX_CONSTRAINTS = 65536, 128, 65536, 4096
+
+
+def stark_operand(kind, index):
+    """GL_STARK_OPERAND: an operand word of a gl_stark_dag"""
+    return (int(kind) << 28 | int(index)) & 0xFFFFFFFF
+
+
+class StarkDagStruct(ctypes.Structure):
+    """gl_stark_dag.  nodes: [(op, operand word a, operand word b), ...] in SSA order; constants: 64-bit words; constraints: [(filter,
+    operand word), ...] in the order the Stark yields them.  Nothing is checked here: refusing is gl_stark_dag_check's."""
+    _fields_ = [("num_nodes", c_u32), ("node_op", ctypes.POINTER(c_u32)), ("node_a", ctypes.POINTER(c_u32)), ("node_b", ctypes.POINTER(c_u32)),
+                ("num_constants", c_u32), ("constants", ctypes.POINTER(c_u64)),
+                ("num_constraints", c_u32), ("constraint_filter", ctypes.POINTER(c_u32)), ("constraint_operand", ctypes.POINTER(c_u32))]
+
+    def __init__(self, nodes, constants, constraints):
+        super().__init__()
+        self._keep = []
+
+        def table(ctype, values):
+            arr = (ctype * max(len(values), 1))(*values)
+            self._keep.append(arr)
+            return ctypes.cast(arr, ctypes.POINTER(ctype))
+        self.num_nodes, self.num_constants, self.num_constraints = len(nodes), len(constants), len(constraints)
+        self.node_op = table(c_u32, [int(op) & 0xFFFFFFFF for op, _, _ in nodes])
+        self.node_a, self.node_b = table(c_u32, [int(a) & 0xFFFFFFFF for _, a, _ in nodes]), table(c_u32, [int(b) & 0xFFFFFFFF for _, _, b in nodes])
+        self.constants = table(c_u64, [int(v) & 0xFFFFFFFFFFFFFFFF for v in constants])
+        self.constraint_filter = table(c_u32, [int(f) & 0xFFFFFFFF for f, _ in constraints])
+        self.constraint_operand = table(c_u32, [int(w) & 0xFFFFFFFF for _, w in constraints])
 
 
 class StarkSetDescStruct(ctypes.Structure):

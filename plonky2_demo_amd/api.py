@@ -1057,6 +1057,126 @@ class StarkDesc:
         check(lib.gl_stark_check(ctypes.byref(self.struct(config.num_challenges)), ctypes.byref(params)))
 
 
+class StarkDagDesc(StarkDesc):
+    """A Stark whose constraints are an expression DAG (gl_stark_dag beside a gl_stark_desc without a term list): nodes = [(op, operand
+    word a, operand word b), ...] in SSA order, constants = 64-bit words, constraints = [(filter, operand word), ...] in the order the
+    Stark yields them; operand words are _lib.stark_operand(kind, index).  StarkDagBuilder writes one.  Stark, StarkSetDesc and
+    stark_verify take it wherever they take a StarkDesc."""
+
+    def __init__(self, num_columns, num_public_inputs, constraint_degree, nodes, constants, constraints, pairs=()):
+        super().__init__(num_columns, num_public_inputs, constraint_degree, [], pairs)
+        self.nodes, self.constants = [tuple(int(w) for w in node) for node in nodes], [int(v) for v in constants]
+        self.dag_constraints = [(int(f), int(w)) for f, w in constraints]
+
+    def struct(self, num_challenges):
+        st = super().struct(num_challenges)
+        for field in ("constraint_filter", "constraint_num_terms", "term_coeff", "term_num_factors", "factors"):
+            setattr(st, field, None)                                   # one form or the other per table
+        return st
+
+    def dag_struct(self):
+        return _lib.StarkDagStruct(self.nodes, self.constants, self.dag_constraints)
+
+    def check(self, config, degree_bits, hasher="poseidon"):
+        """gl_stark_dag_check: raises Plonky2Mi355xError with the refusal; needs no GPU."""
+        params = config.fri_params(degree_bits, hasher)
+        check(lib.gl_stark_dag_check(ctypes.byref(self.struct(config.num_challenges)), ctypes.byref(self.dag_struct()), ctypes.byref(params)))
+
+    def stats(self):
+        """gl_stark_dag_stats -> (max live, the largest degree of a constraint, instructions of the compiled program); needs no GPU."""
+        a, b, c = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        check(lib.gl_stark_dag_stats(ctypes.byref(self.struct(1)), ctypes.byref(self.dag_struct()), ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
+
+
+class StarkDagExpr:
+    """A value of a StarkDagBuilder: an operand word.  + - * build nodes; an int is coerced to a constant."""
+    __slots__ = ("builder", "word")
+
+    def __init__(self, builder, word):
+        self.builder, self.word = builder, word
+
+    def __add__(self, other):
+        return self.builder._node(_lib.GL_STARK_OP_ADD, self, other)
+
+    def __radd__(self, other):
+        return self.builder._node(_lib.GL_STARK_OP_ADD, other, self)
+
+    def __sub__(self, other):
+        return self.builder._node(_lib.GL_STARK_OP_SUB, self, other)
+
+    def __rsub__(self, other):
+        return self.builder._node(_lib.GL_STARK_OP_SUB, other, self)
+
+    def __mul__(self, other):
+        return self.builder._node(_lib.GL_STARK_OP_MUL, self, other)
+
+    def __rmul__(self, other):
+        return self.builder._node(_lib.GL_STARK_OP_MUL, other, self)
+
+
+class StarkDagBuilder:
+    """Writes a StarkDagDesc the way a Stark writes eval_packed_generic: local(c) / next(c) / public(i) / const(v) are the leaves, + - *
+    on them the nodes, and constraint* the ConstraintConsumer's four methods, in the order they are called.  Expressions are
+    hash-consed: the same op on the same operands, written twice, is one node; a constant written twice is one constant."""
+
+    def __init__(self, num_columns, num_public_inputs):
+        self.num_columns, self.num_public_inputs = num_columns, num_public_inputs
+        self.nodes, self.constants, self.constraints = [], [], []
+        self._node_of, self._const_of = {}, {}
+
+    def local(self, c):
+        return StarkDagExpr(self, _lib.stark_operand(_lib.GL_STARK_LOCAL, c))
+
+    def next(self, c):
+        return StarkDagExpr(self, _lib.stark_operand(_lib.GL_STARK_NEXT, c))
+
+    def public(self, i):
+        return StarkDagExpr(self, _lib.stark_operand(_lib.GL_STARK_PUBLIC, i))
+
+    def const(self, v):
+        """a 64-bit word as it stands (it may be non-canonical); any other int mod p"""
+        v = int(v)
+        if not 0 <= v < 1 << 64:
+            v %= GOLDILOCKS_ORDER
+        if v not in self._const_of:
+            self._const_of[v] = len(self.constants)
+            self.constants.append(v)
+        return StarkDagExpr(self, _lib.stark_operand(_lib.GL_STARK_CONST, self._const_of[v]))
+
+    def _expr(self, e):
+        if isinstance(e, StarkDagExpr):
+            if e.builder is not self:
+                raise ValueError("an expression of another builder")
+            return e
+        return self.const(e)
+
+    def _node(self, op, a, b):
+        key = (op, self._expr(a).word, self._expr(b).word)
+        if key not in self._node_of:
+            self._node_of[key] = len(self.nodes)
+            self.nodes.append(key)
+        return StarkDagExpr(self, _lib.stark_operand(_lib.GL_STARK_NODE, self._node_of[key]))
+
+    def _constraint(self, filt, e):
+        self.constraints.append((filt, self._expr(e).word))
+
+    def constraint(self, e):
+        self._constraint(_lib.GL_STARK_ALL, e)
+
+    def constraint_transition(self, e):
+        self._constraint(_lib.GL_STARK_TRANSITION, e)
+
+    def constraint_first_row(self, e):
+        self._constraint(_lib.GL_STARK_FIRST_ROW, e)
+
+    def constraint_last_row(self, e):
+        self._constraint(_lib.GL_STARK_LAST_ROW, e)
+
+    def build(self, constraint_degree, pairs=()):
+        return StarkDagDesc(self.num_columns, self.num_public_inputs, constraint_degree, self.nodes, self.constants, self.constraints, pairs)
+
+
 class Stark(_Owned):
     """A checked description with its tables in HBM (gl_stark): starky's prove() and verify, and the two STARK-only prover phases on their
     own, every polynomial device-resident."""
@@ -1066,7 +1186,11 @@ class Stark(_Owned):
         self.ctx, self.desc, self.config, self.degree_bits = _ctx(ctx), desc, config, degree_bits
         self.params = config.fri_params(degree_bits, hasher)
         h = ctypes.c_void_p()
-        check(lib.gl_stark_create(self.ctx.handle, ctypes.byref(desc.struct(config.num_challenges)), ctypes.byref(self.params), ctypes.byref(h)))
+        if isinstance(desc, StarkDagDesc):
+            check(lib.gl_stark_dag_create(self.ctx.handle, ctypes.byref(desc.struct(config.num_challenges)), ctypes.byref(desc.dag_struct()),
+                                          ctypes.byref(self.params), ctypes.byref(h)))
+        else:
+            check(lib.gl_stark_create(self.ctx.handle, ctypes.byref(desc.struct(config.num_challenges)), ctypes.byref(self.params), ctypes.byref(h)))
         self.handle = h.value
 
     def commit_trace(self, trace):
@@ -1152,11 +1276,24 @@ class Stark(_Owned):
 
 
 def stark_verify(desc, config, degree_bits, proof, hasher="poseidon"):
-    """gl_stark_verify: needs no GPU and no Stark handle -> (accepted, message, GL_CHECK_* code)."""
+    """gl_stark_verify (gl_stark_dag_verify for a StarkDagDesc): needs no GPU and no Stark handle -> (accepted, message, GL_CHECK_* code)."""
+    if isinstance(desc, StarkDagDesc):
+        return stark_dag_verify(desc, config, degree_bits, proof, hasher)
     params = config.fri_params(degree_bits, hasher)
     buf = np.frombuffer(bytes(proof), dtype=np.uint8)
     code = ctypes.c_uint32()
     st = lib.gl_stark_verify(ctypes.byref(desc.struct(config.num_challenges)), ctypes.byref(params), _p(buf) if buf.size else None, buf.size, ctypes.byref(code))
+    ok, why = _verdict(st)
+    return ok, why, code.value
+
+
+def stark_dag_verify(desc, config, degree_bits, proof, hasher="poseidon"):
+    """gl_stark_dag_verify of a StarkDagDesc -> (accepted, message, GL_CHECK_* code)."""
+    params = config.fri_params(degree_bits, hasher)
+    buf = np.frombuffer(bytes(proof), dtype=np.uint8)
+    code = ctypes.c_uint32()
+    st = lib.gl_stark_dag_verify(ctypes.byref(desc.struct(config.num_challenges)), ctypes.byref(desc.dag_struct()), ctypes.byref(params),
+                                 _p(buf) if buf.size else None, buf.size, ctypes.byref(code))
     ok, why = _verdict(st)
     return ok, why, code.value
 
@@ -1233,12 +1370,25 @@ class StarkSetDesc:
         return _lib.StarkSetDescStruct([(d.struct(self.config.num_challenges), self.config.fri_params(lg, self.hasher)) for d, lg in self.tables],
                                        [l.flat() for l in self.lookups])
 
+    def dags(self):
+        """(gl_stark_dag*[num_tables] with a null entry per table in term-list form, or None where every table is; what keeps it alive)"""
+        structs = [d.dag_struct() if isinstance(d, StarkDagDesc) else None for d, _ in self.tables]
+        if not any(s is not None for s in structs):
+            return None, structs
+        return (ctypes.c_void_p * len(structs))(*[ctypes.addressof(s) if s is not None else None for s in structs]), structs
+
     def check(self):
-        """gl_stark_set_check: raises Plonky2Mi355xError with the refusal; needs no GPU."""
-        check(lib.gl_stark_set_check(ctypes.byref(self.struct())))
+        """gl_stark_set_check (gl_stark_set_dag_check with a StarkDagDesc among the tables): raises Plonky2Mi355xError with the refusal."""
+        dags, keep = self.dags()
+        check(lib.gl_stark_set_check(ctypes.byref(self.struct())) if dags is None else lib.gl_stark_set_dag_check(ctypes.byref(self.struct()), dags))
 
     def num_zs(self, table):
         """(permutation Zs, CTL Zs) of a table: stark.rs:216-221 and cross_table_lookup.rs:178-185."""
+        if self.dags()[0] is not None:                                 # the counts do not depend on the constraints' form
+            self.check()
+            nc = self.config.num_challenges
+            twcs = [t for l in self.lookups for t in list(l.looking_tables) + [l.looked_table]]
+            return self.tables[table][0].num_permutation_batches(nc), nc * sum(1 for t in twcs if t.table == table)
         a, b = ctypes.c_uint32(), ctypes.c_uint32()
         check(lib.gl_stark_set_num_zs(ctypes.byref(self.struct()), table, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
@@ -1251,7 +1401,11 @@ class StarkSet(_Owned):
     def __init__(self, desc, ctx=None):
         self.ctx, self.desc = _ctx(ctx), desc
         h = ctypes.c_void_p()
-        check(lib.gl_stark_set_create(self.ctx.handle, ctypes.byref(desc.struct()), ctypes.byref(h)))
+        dags, keep = desc.dags()
+        if dags is None:
+            check(lib.gl_stark_set_create(self.ctx.handle, ctypes.byref(desc.struct()), ctypes.byref(h)))
+        else:
+            check(lib.gl_stark_set_dag_create(self.ctx.handle, ctypes.byref(desc.struct()), dags, ctypes.byref(h)))
         self.handle = h.value
         self.counts = [desc.num_zs(t) for t in range(len(desc.tables))]
 
@@ -1353,7 +1507,11 @@ def stark_set_verify(desc, proof):
     """gl_stark_set_verify: needs no GPU and no handle -> (accepted, message, GL_CHECK_* code, table the check failed in)."""
     buf = np.frombuffer(bytes(proof), dtype=np.uint8)
     code, table = ctypes.c_uint32(), ctypes.c_uint32()
-    st = lib.gl_stark_set_verify(ctypes.byref(desc.struct()), _p(buf) if buf.size else None, buf.size, ctypes.byref(code), ctypes.byref(table))
+    dags, keep = desc.dags()
+    if dags is None:
+        st = lib.gl_stark_set_verify(ctypes.byref(desc.struct()), _p(buf) if buf.size else None, buf.size, ctypes.byref(code), ctypes.byref(table))
+    else:
+        st = lib.gl_stark_set_dag_verify(ctypes.byref(desc.struct()), dags, _p(buf) if buf.size else None, buf.size, ctypes.byref(code), ctypes.byref(table))
     ok, why = _verdict(st)
     return ok, why, code.value, table.value
 

@@ -45,17 +45,23 @@ struct StarkInstance {
 
 }  // namespace
 
-int glstark::stark_check(const gl_stark_desc* desc, const gl_fri_params* params, StarkShape* shape, bool prover) {
+int glstark::stark_check(const gl_stark_desc* desc, const gl_fri_params* params, StarkShape* shape, bool prover, const gl_stark_dag* dag, DagProgram* prog) {
     GL_REQUIRE(desc && params, GL_ERR_ARG, "gl_stark: null description / params");
     const gl_stark_desc& d = *desc;
     GL_REQUIRE(d.num_columns >= 1 && d.num_columns <= GL_STARK_MAX_COLUMNS, GL_ERR_ARG, "gl_stark: 1..1024 columns");
     GL_REQUIRE(d.num_public_inputs <= GL_STARK_MAX_PUBLIC_INPUTS, GL_ERR_ARG, "gl_stark: at most 256 public inputs");
     GL_REQUIRE(d.constraint_degree >= 1 && d.constraint_degree <= GL_STARK_MAX_DEGREE, GL_ERR_ARG, "gl_stark: constraint degree is 1..9");
     GL_REQUIRE(d.num_challenges >= 1 && d.num_challenges <= GL_STARK_MAX_CHALLENGES, GL_ERR_ARG, "gl_stark: 1..4 challenges");
-    GL_REQUIRE(d.num_constraints >= 1 && d.num_constraints <= GL_STARK_MAX_CONSTRAINTS, GL_ERR_ARG, "gl_stark: 1..4096 constraints");
-    GL_REQUIRE(d.constraint_filter && d.constraint_num_terms && d.term_coeff && d.term_num_factors && d.factors, GL_ERR_ARG, "gl_stark: null constraint table");
+    if (dag) {          // one form or the other per table
+        GL_REQUIRE(!d.num_constraints && !d.constraint_filter && !d.constraint_num_terms && !d.term_coeff && !d.term_num_factors && !d.factors, GL_ERR_ARG,
+                   "gl_stark_dag: the description carries a term list as well (num_constraints = 0 and null term tables go with a dag)");
+    } else {
+        GL_REQUIRE(d.num_constraints >= 1 && d.num_constraints <= GL_STARK_MAX_CONSTRAINTS, GL_ERR_ARG, "gl_stark: 1..4096 constraints");
+        GL_REQUIRE(d.constraint_filter && d.constraint_num_terms && d.term_coeff && d.term_num_factors && d.factors, GL_ERR_ARG, "gl_stark: null constraint table");
+    }
     GL_REQUIRE(d.num_permutation_pairs <= GL_STARK_MAX_PAIRS, GL_ERR_ARG, "gl_stark: at most 64 permutation pairs");
     GL_REQUIRE(!d.num_permutation_pairs || (d.pair_len && d.pair_columns), GL_ERR_ARG, "gl_stark: null permutation pair table");
+    if (dag) GL_TRY(dag_compile(desc, dag, prog));
     StarkShape s;
     s.q = d.constraint_degree > 2 ? d.constraint_degree - 1 : 1;                 // stark.rs:79-81
     while ((1u << s.qdb) < s.q) s.qdb++;                                         // log2_ceil
@@ -113,9 +119,15 @@ extern "C" void gl_stark_free(gl_stark* s) noexcept {
 extern "C" int gl_stark_create(gl_ctx* ctx, const gl_stark_desc* desc, const gl_fri_params* params, gl_stark** out) try {
     GL_REQUIRE(out, GL_ERR_ARG, "gl_stark_create: null out");
     *out = nullptr;
+    return stark_create(ctx, desc, nullptr, params, out);
+} catch (...) { return gl_caught(); }
+
+// gl_stark_create and gl_stark_dag_create: with a dag its compiled program stands in the tables where the term program would
+int glstark::stark_create(gl_ctx* ctx, const gl_stark_desc* desc, const gl_stark_dag* dag, const gl_fri_params* params, gl_stark** out) {
     GL_REQUIRE(ctx, GL_ERR_ARG, "gl_stark_create: null context");
     StarkShape sh;
-    GL_TRY(stark_check(desc, params, &sh));
+    DagProgram prog;
+    GL_TRY(stark_check(desc, params, &sh, true, dag, &prog));
     GL_TRY(ctx->activate());
     const gl_stark_desc& d = *desc;
     std::unique_ptr<gl_stark, void (*)(gl_stark*)> s(new gl_stark(), gl_stark_free);
@@ -135,12 +147,16 @@ extern "C" int gl_stark_create(gl_ctx* ctx, const gl_stark_desc* desc, const gl_
     }
     // one host image of the tables, 8-byte words first
     const size_t npairs = d.num_permutation_pairs;
-    std::vector<gl_t> words(sh.terms + 8);
+    const size_t nconst = prog.constants.size();
+    std::vector<gl_t> words(sh.terms + nconst + 8);
     for (size_t t = 0; t < sh.terms; t++) words[t] = gl_canon(d.term_coeff[t]);
-    for (uint32_t i = 0; i < 8; i++) words[sh.terms + i] = zh[i];
+    for (size_t i = 0; i < nconst; i++) words[sh.terms + i] = prog.constants[i];
+    for (uint32_t i = 0; i < 8; i++) words[sh.terms + nconst + i] = zh[i];
     std::vector<uint32_t> u32;
     const size_t o_filter = 0, o_num_terms = o_filter + d.num_constraints, o_term_nf = o_num_terms + d.num_constraints, o_factors = o_term_nf + sh.terms,
-                 o_pair_off = o_factors + sh.factors, o_pair_cols = o_pair_off + npairs + 1, total32 = o_pair_cols + 2 * sh.column_pairs;
+                 o_pair_off = o_factors + sh.factors, o_pair_cols = o_pair_off + npairs + 1, end32 = o_pair_cols + 2 * sh.column_pairs,
+                 o_dag = end32 + ((4 - (2 * words.size() + end32) % 4) % 4),       // the compiled DAG on a 16-byte boundary of the block
+                 total32 = o_dag + prog.instr.size();
     u32.resize(total32 + 2);
     for (uint32_t c = 0; c < d.num_constraints; c++) { u32[o_filter + c] = d.constraint_filter[c]; u32[o_num_terms + c] = d.constraint_num_terms[c]; }
     for (size_t t = 0; t < sh.terms; t++) u32[o_term_nf + t] = d.term_num_factors[t];
@@ -149,15 +165,18 @@ extern "C" int gl_stark_create(gl_ctx* ctx, const gl_stark_desc* desc, const gl_
     for (size_t pr = 0; pr < npairs; pr++) { u32[o_pair_off + pr] = off; off += d.pair_len[pr]; }
     u32[o_pair_off + npairs] = off;
     for (size_t k = 0; k < 2 * sh.column_pairs; k++) u32[o_pair_cols + k] = d.pair_columns[k];
+    for (size_t k = 0; k < prog.instr.size(); k++) u32[o_dag + k] = prog.instr[k];
     const size_t bytes64 = words.size() * sizeof(gl_t), bytes32 = u32.size() * sizeof(uint32_t);
     GL_TRY(ctx->pool_alloc(bytes64 + bytes32, &s->d_tables));
     GL_TRY(gl_copy_h2d(ctx, s->d_tables, words.data(), bytes64));
     GL_TRY(gl_copy_h2d(ctx, (char*)s->d_tables + bytes64, u32.data(), bytes32));
     s->d_coeff = (const gl_t*)s->d_tables;
-    const gl_t* d_zh = s->d_coeff + sh.terms;
+    const gl_t* d_zh = s->d_coeff + sh.terms + nconst;
+    s->dag = dag != nullptr; s->d_dag_const = s->d_coeff + sh.terms;
+    s->dag_num_instructions = prog.num_instructions; s->dag_max_live = prog.max_live;
     const uint32_t* d32 = (const uint32_t*)((const char*)s->d_tables + bytes64);
     s->d_filter = d32 + o_filter; s->d_num_terms = d32 + o_num_terms; s->d_term_nf = d32 + o_term_nf; s->d_factors = d32 + o_factors;
-    s->d_pair_off = d32 + o_pair_off; s->d_pair_cols = d32 + o_pair_cols;
+    s->d_pair_off = d32 + o_pair_off; s->d_pair_cols = d32 + o_pair_cols; s->d_dag_instr = d32 + o_dag;
     GL_TRY(ctx->get_pow_table(gl_host_root_of_unity(lgS), GL_MULT_GENERATOR, (uint32_t)((s->size + 2047) >> 11), &s->xt));
     GL_TRY(ctx->pool_alloc(2 * s->size * sizeof(gl_t), (void**)&s->d_lagrange));
     hipLaunchKernelGGL(k_stark_lagrange_on_coset, dim3((unsigned)((s->size + 255) / 256)), dim3(256), 0, ctx->stream, s->xt.lo, s->xt.hi, (uint32_t)s->size,
@@ -166,7 +185,7 @@ extern "C" int gl_stark_create(gl_ctx* ctx, const gl_stark_desc* desc, const gl_
     GL_CHECK_HIP(gl_stream_wait(ctx->stream));
     *out = s.release();
     return GL_OK;
-} catch (...) { return gl_caught(); }
+}
 
 namespace {
 
@@ -222,6 +241,7 @@ namespace {
 
 // compute_quotient_polys up to the coset_ifft (prover.rs:198-311): d_out[num_challenges][size] values on the quotient coset
 int quotient_values(gl_ctx* ctx, const gl_stark* s, const gl_batch* trace, const gl_batch* zs, const gl_t* d_ch, const uint64_t* alphas, const gl_t* d_pub, gl_t* d_out) {
+    if (s->dag) return quotient_dag_launch(ctx, s, trace, zs, d_ch, alphas, d_pub, d_out);      // k_stark_quotient_dag (stark_dag.hip)
     GlStarkQuot q;
     ::memset((void*)&q, 0, sizeof q);
     q.trace = trace->lde; q.zs = zs ? zs->lde : nullptr; q.stride = trace->N();
@@ -421,7 +441,7 @@ int glstark::stark_reject(uint32_t code, uint32_t* check) {
 
 // eval_vanishing_poly at zeta over the extension field (vanishing_poly.rs, verifier.rs:81-106): the host interpreter of the term list
 void glstark::vanishing_at(const gl_stark_desc& d, const StarkShape& s, const gl2_t* local, const gl2_t* next, const gl_t* pub, const gl_t* alphas, gl2_t z_last,
-                  gl2_t l_first, gl2_t l_last, const gl2_t* zs, const gl2_t* zs_next, const gl_t* sets, gl2_t* accs) {
+                  gl2_t l_first, gl2_t l_last, const gl2_t* zs, const gl2_t* zs_next, const gl_t* sets, gl2_t* accs, const DagProgram* prog) {
     const uint32_t nc = d.num_challenges;
     for (uint32_t j = 0; j < nc; j++) accs[j] = gl2_make(0, 0);
     auto consume = [&](gl2_t c) { for (uint32_t j = 0; j < nc; j++) accs[j] = gl2_add(gl2_scalar(accs[j], alphas[j]), c); };
@@ -439,6 +459,7 @@ void glstark::vanishing_at(const gl_stark_desc& d, const StarkShape& s, const gl
         const uint32_t filt = d.constraint_filter[c];
         consume(filt == GL_STARK_TRANSITION ? gl2_mul(C, z_last) : filt == GL_STARK_FIRST_ROW ? gl2_mul(C, l_first) : filt == GL_STARK_LAST_ROW ? gl2_mul(C, l_last) : C);
     }
+    if (prog) dag_constraints_at(*prog, local, next, pub, z_last, l_first, l_last, consume);             // the other form: no term list above
     for (uint32_t b = 0; b < s.nz; b++) consume(gl2_mul(gl2_sub(zs[b], gl2_make(1, 0)), l_first));      // permutation.rs:282-285
     std::vector<uint32_t> pair_off(d.num_permutation_pairs + 1, 0);
     for (uint32_t pr = 0; pr < d.num_permutation_pairs; pr++) pair_off[pr + 1] = pair_off[pr] + d.pair_len[pr];
@@ -483,8 +504,14 @@ extern "C" int gl_stark_prove(gl_ctx* ctx, const gl_stark* s, const uint64_t* co
 
 extern "C" int gl_stark_verify(const gl_stark_desc* desc, const gl_fri_params* params, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check) try {
     if (check) *check = GL_CHECK_ACCEPTED;
+    return stark_verify(desc, nullptr, params, proof_bytes, num_bytes, check);
+} catch (...) { return gl_caught(); }
+
+// gl_stark_verify and gl_stark_dag_verify
+int glstark::stark_verify(const gl_stark_desc* desc, const gl_stark_dag* dag, const gl_fri_params* params, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check) {
     StarkShape s;
-    GL_TRY(stark_check(desc, params, &s, false));
+    DagProgram prog;
+    GL_TRY(stark_check(desc, params, &s, false, dag, &prog));
     GL_REQUIRE(proof_bytes || !num_bytes, GL_ERR_ARG, "gl_stark_verify: null proof");
     const gl_stark_desc& d = *desc; const gl_fri_params& p = *params;
     const uint32_t nc = d.num_challenges, ncols = d.num_columns, nz = s.nz, nq = s.q * nc;
@@ -530,7 +557,7 @@ extern "C" int gl_stark_verify(const gl_stark_desc* desc, const gl_fri_params* p
     const gl2_t l_last = gl2_mul(z_h, gl2_inv(gl2_scalar(gl2_sub(gl2_scalar(zeta, g), gl2_make(1, 0)), n_field)));
     const gl2_t z_last = gl2_sub(zeta, e_of(gl_inv(g)));
     gl2_t accs[GL_STARK_MAX_CHALLENGES];
-    vanishing_at(d, s, local, next, pub.data(), alphas, z_last, l_first, l_last, zl, zn, sets.data(), accs);
+    vanishing_at(d, s, local, next, pub.data(), alphas, z_last, l_first, l_last, zl, zn, sets.data(), accs, dag ? &prog : nullptr);
     for (uint32_t j = 0; j < nc; j++) {
         gl2_t t = gl2_make(0, 0);                                                                                       // reduce_with_powers(chunk, zeta^n)
         for (uint32_t k = s.q; k-- > 0;) t = gl2_add(gl2_mul(t, zeta_pow), ql[j * s.q + k]);
@@ -539,7 +566,7 @@ extern "C" int gl_stark_verify(const gl_stark_desc* desc, const gl_fri_params* p
     }
     const StarkInstance si(ncols, nc, s, zeta, gl2_canon(gl2_scalar(zeta, g)));
     return gl_verify_openings(&p, &si.inst, caps.data(), openings.data(), &ch, fri, fri_len, check);
-} catch (...) { return gl_caught(); }
+}
 
 // the launches of k_stark_seg_products and k_stark_seg_scan for the other running products (stark_set.hip): d_seg[nz][nseg] becomes the
 // exclusive prefix of the segment products of d_fac[nz][n]

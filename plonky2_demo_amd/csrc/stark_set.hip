@@ -20,6 +20,7 @@ struct SetShape {
     std::vector<std::vector<CtlZ>> ctl_zs;      // per table, in cross_table_lookup_data's order
     std::vector<uint32_t> col_off;              // [Columns + 1] start of each Column's terms
     std::vector<uint32_t> twc_col0;             // [twcs] first Column of each TableWithColumns
+    std::vector<DagProgram> progs;              // per table: its compiled DAG where dags[t] is given (gl_stark_set_dag_*)
 };
 
 // the FriInstanceInfo of evm/src/stark.rs:83-142: oracles trace, Z (permutation Zs, then CTL Zs), quotient; batches [trace, Z, quotient] at
@@ -49,15 +50,16 @@ struct StarkSetInstance {
     }
 };
 
-int stark_set_check(const gl_stark_set_desc* desc, SetShape* shape, bool prover = true) {
+// dags: null, or [num_tables] with a null entry for a table in term-list form
+int stark_set_check(const gl_stark_set_desc* desc, SetShape* shape, bool prover = true, const gl_stark_dag* const* dags = nullptr) {
     GL_REQUIRE(desc, GL_ERR_ARG, "gl_stark_set: null description");
     const gl_stark_set_desc& d = *desc;
     GL_REQUIRE(d.num_tables >= 1 && d.num_tables <= GL_STARK_SET_MAX_TABLES, GL_ERR_ARG, "gl_stark_set: 1..8 tables");
     GL_REQUIRE(d.tables && d.params, GL_ERR_ARG, "gl_stark_set: null tables / params");
     SetShape s;
     s.num_tables = d.num_tables; s.nc = d.tables[0].num_challenges;
-    s.shapes.resize(d.num_tables); s.ctl_zs.resize(d.num_tables);
-    for (uint32_t t = 0; t < d.num_tables; t++) GL_TRY(stark_check(&d.tables[t], &d.params[t], &s.shapes[t], prover));
+    s.shapes.resize(d.num_tables); s.ctl_zs.resize(d.num_tables); s.progs.resize(d.num_tables);
+    for (uint32_t t = 0; t < d.num_tables; t++) GL_TRY(stark_check(&d.tables[t], &d.params[t], &s.shapes[t], prover, dags ? dags[t] : nullptr, &s.progs[t]));
     // one StarkConfig for the set (evm/src/config.rs): only degree_bits, and with it the number of reductions, is a table's own
     const gl_fri_params& p0 = d.params[0];
     uint32_t arity = 0;
@@ -139,6 +141,10 @@ extern "C" int gl_stark_set_check(const gl_stark_set_desc* desc) try {
     return stark_set_check(desc, nullptr);
 } catch (...) { return gl_caught(); }
 
+extern "C" int gl_stark_set_dag_check(const gl_stark_set_desc* desc, const gl_stark_dag* const* dags) try {
+    return stark_set_check(desc, nullptr, true, dags);
+} catch (...) { return gl_caught(); }
+
 extern "C" int gl_stark_set_num_zs(const gl_stark_set_desc* desc, uint32_t table, uint32_t* num_permutation_zs, uint32_t* num_ctl_zs) try {
     SetShape sh;
     GL_TRY(stark_set_check(desc, &sh, false));
@@ -158,19 +164,36 @@ extern "C" void gl_stark_set_free(gl_stark_set* s) noexcept {
     delete s;
 }
 
+namespace {
+int set_create(gl_ctx* ctx, const gl_stark_set_desc* desc, const gl_stark_dag* const* dags, gl_stark_set** out);
+int set_verify(const gl_stark_set_desc* desc, const gl_stark_dag* const* dags, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check, uint32_t* table);
+}  // namespace
+
 extern "C" int gl_stark_set_create(gl_ctx* ctx, const gl_stark_set_desc* desc, gl_stark_set** out) try {
     GL_REQUIRE(out, GL_ERR_ARG, "gl_stark_set_create: null out");
     *out = nullptr;
+    return set_create(ctx, desc, nullptr, out);
+} catch (...) { return gl_caught(); }
+
+extern "C" int gl_stark_set_dag_create(gl_ctx* ctx, const gl_stark_set_desc* desc, const gl_stark_dag* const* dags, gl_stark_set** out) try {
+    GL_REQUIRE(out, GL_ERR_ARG, "gl_stark_set_dag_create: null out");
+    *out = nullptr;
+    return set_create(ctx, desc, dags, out);
+} catch (...) { return gl_caught(); }
+
+namespace {
+
+int set_create(gl_ctx* ctx, const gl_stark_set_desc* desc, const gl_stark_dag* const* dags, gl_stark_set** out) {
     GL_REQUIRE(ctx, GL_ERR_ARG, "gl_stark_set_create: null context");
     SetShape sh;
-    GL_TRY(stark_set_check(desc, &sh));
+    GL_TRY(stark_set_check(desc, &sh, true, dags));
     GL_TRY(ctx->activate());
     const gl_stark_set_desc& d = *desc;
     std::unique_ptr<gl_stark_set, void (*)(gl_stark_set*)> s(new gl_stark_set(), gl_stark_set_free);
     s->ctx = ctx; ctx->retain();
     s->num_tables = d.num_tables; s->nc = sh.nc;
     for (uint32_t t = 0; t < d.num_tables; t++) {
-        GL_TRY(gl_stark_create(ctx, &d.tables[t], &d.params[t], &s->tables[t]));
+        GL_TRY(stark_create(ctx, &d.tables[t], dags ? dags[t] : nullptr, &d.params[t], &s->tables[t]));
         const std::vector<CtlZ>& zs = sh.ctl_zs[t];
         s->nctl[t] = (uint32_t)zs.size();
         ::memset((void*)&s->prog[t], 0, sizeof s->prog[t]);
@@ -204,9 +227,7 @@ extern "C" int gl_stark_set_create(gl_ctx* ctx, const gl_stark_set_desc* desc, g
     }
     *out = s.release();
     return GL_OK;
-} catch (...) { return gl_caught(); }
-
-namespace {
+}
 
 int check_set_args(gl_ctx* ctx, const gl_stark_set* s, uint32_t table) {
     GL_REQUIRE(ctx && s, GL_ERR_ARG, "gl_stark_set: null context / set");
@@ -491,8 +512,20 @@ extern "C" int gl_stark_set_prove(gl_ctx* ctx, const gl_stark_set* s, const uint
 
 extern "C" int gl_stark_set_verify(const gl_stark_set_desc* desc, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check, uint32_t* table) try {
     if (check) *check = GL_CHECK_ACCEPTED;
+    return set_verify(desc, nullptr, proof_bytes, num_bytes, check, table);
+} catch (...) { return gl_caught(); }
+
+extern "C" int gl_stark_set_dag_verify(const gl_stark_set_desc* desc, const gl_stark_dag* const* dags, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check,
+                                       uint32_t* table) try {
+    if (check) *check = GL_CHECK_ACCEPTED;
+    return set_verify(desc, dags, proof_bytes, num_bytes, check, table);
+} catch (...) { return gl_caught(); }
+
+namespace {
+
+int set_verify(const gl_stark_set_desc* desc, const gl_stark_dag* const* dags, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check, uint32_t* table) {
     SetShape sh;
-    GL_TRY(stark_set_check(desc, &sh, false));
+    GL_TRY(stark_set_check(desc, &sh, false, dags));
     GL_REQUIRE(proof_bytes || !num_bytes, GL_ERR_ARG, "gl_stark_set_verify: null proof");
     const gl_stark_set_desc& d = *desc;
     const uint32_t T = d.num_tables, nc = sh.nc;
@@ -558,7 +591,7 @@ extern "C" int gl_stark_set_verify(const gl_stark_set_desc* desc, const uint8_t*
         const gl2_t l_last = gl2_mul(z_h, gl2_inv(gl2_scalar(gl2_sub(gl2_scalar(zeta, g), one), n_field)));
         const gl2_t z_last = gl2_sub(zeta, e_of(g_inv));
         gl2_t accs[GL_STARK_MAX_CHALLENGES];
-        vanishing_at(td, s, local, next, pub.data(), alphas, z_last, l_first, l_last, zl, zn, sets.data(), accs);
+        vanishing_at(td, s, local, next, pub.data(), alphas, z_last, l_first, l_last, zl, zn, sets.data(), accs, dags && dags[t] ? &sh.progs[t] : nullptr);
         auto consume = [&](gl2_t c) { for (uint32_t j = 0; j < nc; j++) accs[j] = gl2_add(gl2_scalar(accs[j], alphas[j]), c); };
         // eval_cross_table_lookup_checks on the Zs after the permutation ones (CtlCheckVars::from_proofs, cross_table_lookup.rs:325-414)
         for (uint32_t k = 0; k < nctl; k++) {
@@ -605,4 +638,6 @@ extern "C" int gl_stark_set_verify(const gl_stark_set_desc* desc, const uint8_t*
         twc += looking + 1;
     }
     return GL_OK;
-} catch (...) { return gl_caught(); }
+}
+
+}  // namespace
