@@ -461,7 +461,7 @@ typedef struct gl_fri_instance {        /* FriInstanceInfo (fri/structure.rs) */
  * writes the initial-tree proofs of all num_oracles oracles in order. */
 int gl_fri_combine_instance(gl_ctx* ctx, const gl_fri_params* params, const gl_fri_instance* instance, const gl_batch* const* batches,
                             const uint64_t alpha[2], gl_fri** out);
-/* Diagnostic: the same result by the sequence gl_fri_combine runs, one batch after the other (four launches per batch, a column read
+/* Diagnostic: the same result by the sequence gl_fri_combine ran before it used the one-pass kernels, one batch after the other (four launches per batch, a column read
  * once per batch that lists it), for measuring the one-pass kernels against it (tools/openings_rate.py) and testing them against it. */
 int gl_fri_combine_instance_per_batch(gl_ctx* ctx, const gl_fri_params* params, const gl_fri_instance* instance,
                                       const gl_batch* const* batches, const uint64_t alpha[2], gl_fri** out);

@@ -570,35 +570,43 @@ static int fri_combine(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* const
     const gl2_t gzeta = gl2_canon(gl2_scalar(zeta, gl_host_root_of_unity(d.degree_bits)));
     f->coef.reset(new DevBuf(ctx)); GL_TRY(f->coef->alloc(2 * n * sizeof(gl_t)));            // planes a, b of alpha^2 Q0 + Q1
     {
-        DevBuf d_F(ctx), d_heads(ctx), d_cols(ctx), d_apow(ctx);
+        // Both opening points in one pass (k_fri_combine_points<2> and the k_div_points_* launches, as gl_fri_combine_instance runs them):
+        // the columns opened at g zeta are among those opened at zeta, so every column is read once and carries two weights.
+        DevBuf d_F(ctx), d_heads(ctx), d_cols(ctx), d_wts(ctx);
         const uint32_t seg_len = (uint32_t)(n / 1024 > 32 ? n / 1024 : (n >= 32 ? 32 : n));      // at most 1024 segments
         const uint32_t nseg = (uint32_t)((n + seg_len - 1) / seg_len);
-        GL_TRY(d_F.alloc(2 * n * sizeof(gl_t)));
-        GL_TRY(d_heads.alloc(2 * (size_t)nseg * sizeof(gl_t)));
-        GL_TRY(d_cols.alloc((nopen + nnext) * sizeof(gl_t*)));
-        GL_TRY(d_apow.alloc(2 * (nopen + nnext) * sizeof(gl_t)));
+        GL_TRY(d_F.alloc(4 * n * sizeof(gl_t)));
+        GL_TRY(d_heads.alloc(4 * (size_t)nseg * sizeof(gl_t)));
+        GL_TRY(d_cols.alloc(nopen * sizeof(gl_t*)));
+        GL_TRY(d_wts.alloc(4 * nopen * sizeof(gl_t)));
         std::vector<const gl_t*>& cols = f->h_cols;
         cols = std::move(op.cols);
-        std::vector<gl_t>& apow = f->h_apow; apow.assign(2 * (nopen + nnext), 0);
-        { gl2_t x = gl2_make(1, 0); for (size_t j = 0; j < nopen; j++) { apow[2 * j] = x.a; apow[2 * j + 1] = x.b; x = gl2_canon(gl2_mul(x, fri_alpha)); } }
+        std::vector<gl_t>& wts = f->h_apow; wts.assign(4 * nopen, 0);      // [nopen][2 batches][2]; the powers of alpha depend on the proof
+        { gl2_t x = gl2_make(1, 0); for (size_t j = 0; j < nopen; j++) { wts[4 * j] = x.a; wts[4 * j + 1] = x.b; x = gl2_canon(gl2_mul(x, fri_alpha)); } }
         gl2_t shift = gl2_make(1, 0);     // alpha^(#polys of batch 1) (reducing.rs:103-106)
-        { gl2_t x = gl2_make(1, 0); for (size_t j = 0; j < nnext; j++) { apow[2 * (nopen + j)] = x.a; apow[2 * (nopen + j) + 1] = x.b; x = gl2_canon(gl2_mul(x, fri_alpha)); } shift = x; }
-        GL_TRY(h2d_async(ctx, d_cols.p, cols.data(), cols.size() * sizeof(gl_t*)));
-        GL_TRY(h2d_async(ctx, d_apow.p, apow.data(), apow.size() * sizeof(gl_t)));
-        gl_t* Fa = d_F.as<gl_t>(); gl_t* Fb = Fa + n;
+        {
+            gl2_t x = gl2_make(1, 0);
+            for (size_t k = 0; k < nnext; k++) {      // polynomial k of batch 1 is column j of batch 0: the two Zs, then the lookup polynomials
+                const size_t j = k < 2 ? op.zs() + k : op.lookups() + (k - 2);
+                GL_REQUIRE(cols[j] == cols[nopen + k], GL_ERR_INTERNAL, "gl_fri_combine: a polynomial opened at g zeta is not where it is opened at zeta");
+                wts[4 * j + 2] = x.a; wts[4 * j + 3] = x.b;
+                x = gl2_canon(gl2_mul(x, fri_alpha));
+            }
+            shift = x;
+        }
+        GlFriPoints pt = {};
+        pt.z[0][0] = zeta.a; pt.z[0][1] = zeta.b; pt.scale[0][0] = shift.a; pt.scale[0][1] = shift.b;      // batch 0: all polynomials at zeta
+        pt.z[1][0] = gzeta.a; pt.z[1][1] = gzeta.b; pt.scale[1][0] = 1;                                    // batch 1: the Z polynomials at g * zeta
+        GL_TRY(h2d_async(ctx, d_cols.p, cols.data(), nopen * sizeof(gl_t*)));
+        GL_TRY(h2d_async(ctx, d_wts.p, wts.data(), wts.size() * sizeof(gl_t)));
+        gl_t* F = d_F.as<gl_t>();
         gl_t* Qa = f->coef->as<gl_t>(); gl_t* Qb = Qa + n;
-        const unsigned gb = (unsigned)((n + 63) / 64), sb = (nseg + 63) / 64;      // k_fri_combine: 64 coefficients per workgroup
+        const unsigned gb = (unsigned)((n + 63) / 64), sb = (nseg + 63) / 64;      // k_fri_combine_points: 64 coefficients per workgroup
         ctx->timing_begin("reduce batch + divide by linear");
-        // batch 0: all polynomials at zeta
-        hipLaunchKernelGGL(k_fri_combine, dim3(gb), dim3(256), 0, st, d_cols.as<const gl_t*>(), d_apow.as<gl_t>(), (uint32_t)nopen, (uint32_t)n, Fa, Fb);
-        hipLaunchKernelGGL(k_div_linear_heads, dim3(sb), dim3(64), 0, st, Fa, Fb, (uint32_t)n, seg_len, zeta.a, zeta.b, d_heads.as<gl_t>());
-        hipLaunchKernelGGL(k_div_linear_carries, dim3(1), dim3(1024), 0, st, d_heads.as<gl_t>(), (uint32_t)n, seg_len, zeta.a, zeta.b);
-        hipLaunchKernelGGL(k_div_linear_apply, dim3(sb), dim3(64), 0, st, Fa, Fb, (uint32_t)n, seg_len, zeta.a, zeta.b, d_heads.as<gl_t>(), shift.a, shift.b, Qa, Qb, 0);
-        // batch 1: the Z polynomials at g * zeta
-        hipLaunchKernelGGL(k_fri_combine, dim3(gb), dim3(256), 0, st, d_cols.as<const gl_t*>() + nopen, d_apow.as<gl_t>() + 2 * nopen, (uint32_t)nnext, (uint32_t)n, Fa, Fb);
-        hipLaunchKernelGGL(k_div_linear_heads, dim3(sb), dim3(64), 0, st, Fa, Fb, (uint32_t)n, seg_len, gzeta.a, gzeta.b, d_heads.as<gl_t>());
-        hipLaunchKernelGGL(k_div_linear_carries, dim3(1), dim3(1024), 0, st, d_heads.as<gl_t>(), (uint32_t)n, seg_len, gzeta.a, gzeta.b);
-        hipLaunchKernelGGL(k_div_linear_apply, dim3(sb), dim3(64), 0, st, Fa, Fb, (uint32_t)n, seg_len, gzeta.a, gzeta.b, d_heads.as<gl_t>(), (gl_t)1, (gl_t)0, Qa, Qb, 1);
+        hipLaunchKernelGGL(k_fri_combine_points<2>, dim3(gb), dim3(256), 0, st, d_cols.as<const gl_t*>(), d_wts.as<gl_t>(), (uint32_t)nopen, (uint32_t)n, F);
+        hipLaunchKernelGGL(k_div_points_heads, dim3(sb, 2), dim3(64), 0, st, F, (uint32_t)n, seg_len, pt, d_heads.as<gl_t>());
+        hipLaunchKernelGGL(k_div_points_carries, dim3(1, 2), dim3(1024), 0, st, d_heads.as<gl_t>(), (uint32_t)n, seg_len, pt);
+        hipLaunchKernelGGL(k_div_points_apply<2>, dim3(sb), dim3(64), 0, st, F, (uint32_t)n, seg_len, pt, d_heads.as<gl_t>(), Qa, Qb);
         ctx->timing_end();
         GL_CHECK_HIP(hipGetLastError());
     }
@@ -753,28 +761,33 @@ static int fri_query_blob(gl_fri* f, const uint32_t* x_index, uint32_t nq, std::
         fleaf_piece[r] = {total, (size_t)nq * (2u << ab)}; total += fleaf_piece[r].words;
         fpath_piece[r] = {total, (size_t)nq * lv * 4}; total += fpath_piece[r].words;
     }
-    DevBuf d_stage(ctx), d_idx(ctx);
-    GL_TRY(d_stage.alloc((total + 8) * sizeof(gl_t)));
-    GL_TRY(d_idx.alloc((size_t)nq * (2 + d.num_fri_rounds) * sizeof(uint32_t)));
-    std::vector<uint32_t> idx_host((size_t)nq * (2 + d.num_fri_rounds));
+    // one upload: the piece table of k_gather_pieces, then the index lists [2 + rounds][nq]: Merkle leaf indices, natural LDE rows
+    // (= bitrev(leaf)), and per FRI round the leaf index in that round's tree
+    const size_t max_pieces = 2 * (no + d.num_fri_rounds), idx_words = (size_t)nq * (2 + d.num_fri_rounds);
+    GL_REQUIRE(max_pieces <= GLG_MAX_PIECES, GL_ERR_INTERNAL, "gl_fri_query: more pieces than the gather table holds");
+    static_assert(sizeof(GlGatherPiece) == 64, "the table is laid out in 64-byte entries ahead of the indices");
+    std::vector<uint64_t> up_host(max_pieces * (sizeof(GlGatherPiece) / 8) + (idx_words + 1) / 2);
+    GlGatherPiece* pieces = reinterpret_cast<GlGatherPiece*>(up_host.data());
+    uint32_t* idx_host = reinterpret_cast<uint32_t*>(pieces + max_pieces);
     for (uint32_t q = 0; q < nq; q++) { idx_host[q] = x_index[q]; idx_host[nq + q] = host_bitrev32(x_index[q], lgN); }
     {
         std::vector<uint32_t> xi(x_index, x_index + nq);
         for (unsigned r = 0; r < d.num_fri_rounds; r++) for (uint32_t q = 0; q < nq; q++) { xi[q] >>= d.fri_arity_bits[r]; idx_host[(size_t)(2 + r) * nq + q] = xi[q]; }
     }
-    GL_TRY(h2d_async(ctx, d_idx.p, idx_host.data(), idx_host.size() * sizeof(uint32_t)));
-    const uint32_t* d_leaf = d_idx.as<uint32_t>();            // Merkle leaf indices
-    const uint32_t* d_rows = d_leaf + nq;                     // natural LDE rows = bitrev(leaf)
-    gl_t* stage = d_stage.as<gl_t>();
-    ctx->timing_begin("FRI query gathers");
+    uint32_t npieces = 0, nblocks = 0;
+    auto add_piece = [&](uint32_t kind, const gl_t* src, const gl_t* src2, const uint64_t* level_off, uint64_t stride, uint32_t a, uint32_t b2, size_t count,
+                         size_t idx_off, size_t out_off) {
+        if (!count) return;
+        pieces[npieces++] = GlGatherPiece{src, src2, level_off, stride, (uint64_t)out_off, kind, a, b2, (uint32_t)count, (uint32_t)idx_off, 0};
+        nblocks += (uint32_t)((count + 255) / 256);
+    };
     for (size_t o2 = 0; o2 < no; o2++) {
         const gl_batch* b = f->oracles[o2];
         const uint64_t* d_lo = nullptr;
         GL_TRY(ctx->get_offsets_table(b->tree.level_off.data(), b->tree.level_off.size(), &d_lo));
-        unsigned cnt = nq * (unsigned)b->leaf_len();      // the whole leaf: with blinding the salt follows the values (query rounds open salted leaves)
-        hipLaunchKernelGGL(k_gather_rows, dim3((cnt + 255) / 256), dim3(256), 0, st, b->lde, (uint64_t)N, (uint32_t)b->leaf_len(), d_rows, nq, stage + row_piece[o2].off);
-        cnt = nq * init_levels * 4;
-        if (cnt) hipLaunchKernelGGL(k_gather_paths, dim3((cnt + 255) / 256), dim3(256), 0, st, b->tree.digests, d_lo, init_levels, d_leaf, nq, stage + path_piece[o2].off);
+        // the whole leaf: with blinding the salt follows the values (query rounds open salted leaves)
+        add_piece(GLG_ROWS, b->lde, nullptr, nullptr, (uint64_t)N, (uint32_t)b->leaf_len(), 0, (size_t)nq * b->leaf_len(), nq, row_piece[o2].off);
+        add_piece(GLG_PATHS, b->tree.digests, nullptr, d_lo, 0, init_levels, 0, (size_t)nq * init_levels * 4, 0, path_piece[o2].off);
     }
     for (unsigned r = 0; r < d.num_fri_rounds; r++) {
         const uint32_t ab = d.fri_arity_bits[r], lv = f->lg[r] - ab - d.cap_height;
@@ -782,12 +795,18 @@ static int fri_query_blob(gl_fri* f, const uint32_t* x_index, uint32_t nq, std::
         const uint64_t* d_lo = nullptr;
         GL_TRY(ctx->get_offsets_table(t.level_off.data(), t.level_off.size(), &d_lo));
         const gl_t* va = f->vals[r]->as<gl_t>(); const gl_t* vb = va + (size_t(1) << f->lg[r]);
-        const uint32_t* d_fl = d_idx.as<uint32_t>() + (size_t)(2 + r) * nq;
-        unsigned cnt = nq << ab;
-        hipLaunchKernelGGL(k_gather_fri_leaves, dim3((cnt + 255) / 256), dim3(256), 0, st, va, vb, f->lg[r], ab, d_fl, nq, stage + fleaf_piece[r].off);
-        cnt = nq * lv * 4;
-        if (cnt) hipLaunchKernelGGL(k_gather_paths, dim3((cnt + 255) / 256), dim3(256), 0, st, t.digests, d_lo, lv, d_fl, nq, stage + fpath_piece[r].off);
+        add_piece(GLG_FRI_LEAVES, va, vb, nullptr, 0, ab, f->lg[r], (size_t)nq << ab, (size_t)(2 + r) * nq, fleaf_piece[r].off);
+        add_piece(GLG_PATHS, t.digests, nullptr, d_lo, 0, lv, 0, (size_t)nq * lv * 4, (size_t)(2 + r) * nq, fpath_piece[r].off);
     }
+    DevBuf d_stage(ctx), d_up(ctx);
+    GL_TRY(d_stage.alloc((total + 8) * sizeof(gl_t)));
+    GL_TRY(d_up.alloc(up_host.size() * sizeof(uint64_t)));
+    GL_TRY(h2d_async(ctx, d_up.p, up_host.data(), up_host.size() * sizeof(uint64_t)));
+    gl_t* stage = d_stage.as<gl_t>();
+    ctx->timing_begin("FRI query gathers");
+    if (nblocks)
+        hipLaunchKernelGGL(k_gather_pieces, dim3(nblocks), dim3(256), 0, st, d_up.as<GlGatherPiece>(), npieces,
+                           reinterpret_cast<const uint32_t*>(d_up.as<GlGatherPiece>() + max_pieces), stage);
     ctx->timing_end();
     GL_CHECK_HIP(hipGetLastError());
     std::vector<gl_t> host_stage(total + 8);
@@ -835,7 +854,7 @@ static int check_instance_batches(gl_ctx* ctx, const gl_fri_params& p, const gl_
     }
     return GL_OK;
 }
-// `per_batch`: the sequence gl_fri_combine runs, one batch after the other (k_fri_combine + the three division launches, every listed
+// `per_batch`: the sequence gl_fri_combine ran before it used the one-pass kernels, one batch after the other (k_fri_combine + the three division launches, every listed
 // column read where it is listed) -- what tools/openings_rate.py measures the one-pass kernels against
 static int fri_combine_instance(gl_ctx* ctx, const gl_fri_params* params, const gl_fri_instance* instance, const gl_batch* const* batches, const uint64_t alpha_in[2], gl_fri** out,
                                 bool per_batch = false) {

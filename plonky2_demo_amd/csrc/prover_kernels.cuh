@@ -1059,27 +1059,46 @@ __global__ __launch_bounds__(256) void k_kck_pow_grind(GlPowParams p) {
 }
 
 // ---- gathers for the query phase -----------------------------------------------------------------------------------------
-// rows of a column-major matrix: out[q][c] = base[c * stride + rows[q]]
-__global__ void k_gather_rows(const gl_t* base, uint64_t stride, uint32_t ncols, const uint32_t* rows, uint32_t nq, gl_t* out) {
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= nq * ncols) return;
-    const uint32_t q = idx / ncols, c = idx % ncols;
-    out[idx] = base[(uint64_t)c * stride + rows[q]];
-}
-// Merkle paths: out[q][l][4] = digests[level_off[l] + ((leaf[q] >> l) ^ 1)]
-__global__ void k_gather_paths(const gl_t* digests, const uint64_t* level_off, uint32_t nlevels, const uint32_t* leaves, uint32_t nq, gl_t* out) {
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= nq * nlevels * 4) return;
-    const uint32_t k = idx & 3, l = (idx >> 2) % nlevels, q = (idx >> 2) / nlevels;
-    out[idx] = digests[4 * (level_off[l] + ((leaves[q] >> l) ^ 1u)) + k];
-}
-// FRI step leaves: leaf j of a tree over an ext SoA array = positions bitrev(arity*j + k): out[q][k][2]
-__global__ void k_gather_fri_leaves(const gl_t* va, const gl_t* vb, uint32_t lg_len, uint32_t arity_bits, const uint32_t* leaves, uint32_t nq, gl_t* out) {
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t arity = 1u << arity_bits;
-    if (idx >= nq * arity) return;
-    const uint32_t q = idx >> arity_bits, k = idx & (arity - 1);
-    const uint32_t pos = (leaves[q] << arity_bits) | k;                       // index in the bit-reversed array
-    const uint32_t nat = lg_len ? (__brev(pos) >> (32 - lg_len)) : 0;         // natural-order index
-    out[2 * idx] = va[nat]; out[2 * idx + 1] = vb[nat];
+// Every piece of the query phase's staging buffer in ONE launch, driven by a table: a piece is nq rows, paths or FRI leaves of one
+// tree, its items (one per thread) numbered 0 .. count - 1 in the order they are stored at out + out_off.
+//   GLG_ROWS        rows of a column-major matrix:  item q * a + c          = src[c * stride + idx[q]]                 (a = columns)
+//   GLG_PATHS       Merkle paths:                   item (q * a + l) * 4 + k = src[4 (level_off[l] + ((idx[q] >> l) ^ 1)) + k]   (a = levels)
+//   GLG_FRI_LEAVES  FRI step leaves, leaf j of a tree over an ext SoA array = positions bitrev(arity * j + k):
+//                                                   items 2 ((q << a) + k), + 1 = src[nat], src2[nat]   (a = arity bits, b = log2 length;
+//                                                   one thread per PAIR: count = nq << a)
+// A workgroup finds its piece by walking the table (workgroups are dealt to the pieces in order, ceil(count / 256) each).
+enum { GLG_ROWS = 0, GLG_PATHS = 1, GLG_FRI_LEAVES = 2 };
+#define GLG_MAX_PIECES 32       // two per initial oracle (GL_MAX_FRI_ORACLES = 8) and two per FRI round (8)
+struct GlGatherPiece {
+    const gl_t* src; const gl_t* src2;      // src2: the second plane (GLG_FRI_LEAVES)
+    const uint64_t* level_off;              // GLG_PATHS
+    uint64_t stride, out_off;               // out_off in words
+    uint32_t kind, a, b, count, idx_off, pad_;      // idx_off: where the piece's nq indices start in `idx`
+};
+__global__ __launch_bounds__(256) void k_gather_pieces(const GlGatherPiece* __restrict__ pieces, uint32_t npieces, const uint32_t* __restrict__ idx,
+                                                       gl_t* __restrict__ out) {
+    uint32_t blk = blockIdx.x, p = 0;
+    for (; p < npieces; p++) {
+        const uint32_t nb = (pieces[p].count + 255) / 256;
+        if (blk < nb) break;
+        blk -= nb;
+    }
+    if (p == npieces) return;
+    const GlGatherPiece& pc = pieces[p];
+    const uint32_t i = blk * 256 + threadIdx.x;
+    if (i >= pc.count) return;
+    const uint32_t* ix = idx + pc.idx_off;
+    gl_t* o = out + pc.out_off;
+    if (pc.kind == GLG_ROWS) {
+        const uint32_t q = i / pc.a, c = i % pc.a;
+        o[i] = pc.src[(uint64_t)c * pc.stride + ix[q]];
+    } else if (pc.kind == GLG_PATHS) {
+        const uint32_t k = i & 3, l = (i >> 2) % pc.a, q = (i >> 2) / pc.a;
+        o[i] = pc.src[4 * (pc.level_off[l] + ((ix[q] >> l) ^ 1u)) + k];
+    } else {
+        const uint32_t q = i >> pc.a, k = i & ((1u << pc.a) - 1);
+        const uint32_t pos = (ix[q] << pc.a) | k;                             // index in the bit-reversed array
+        const uint32_t nat = pc.b ? (__brev(pos) >> (32 - pc.b)) : 0;         // natural-order index
+        o[2 * i] = pc.src[nat]; o[2 * i + 1] = pc.src2[nat];
+    }
 }

@@ -4,7 +4,9 @@ k_div_points_*: gl_fri_combine_instance) against one pass per batch (k_fri_combi
 taken alternately.  Timed with the context's device events (gl_ctx_timing_*: one event pair around the stage's launches); each window
 of `inner` alternating pairs follows an untimed run-in of the same pairs (~50 ms of the same work, profiles/README.md), and is repeated
 `reps` times: median, min and max of the per-call means.
-  (a) the m = 64 Plonk instance (everything at zeta, the two Z polynomials at g zeta): gl_fri_combine_instance against gl_fri_combine
+  (a) the m = 64 Plonk instance (everything at zeta, the two Z polynomials at g zeta): gl_fri_combine_instance against the same instance
+      through gl_fri_combine_instance_per_batch (the sequence gl_fri_combine ran before it became a caller of the one-pass kernels);
+      gl_fri_combine itself is held equal to both first
   (b) a STARK-shaped instance a user would run (n = 2^20, rate_bits 1, 128 + 2 + 4 columns, the first two oracles opened twice):
       gl_fri_combine_instance against the same instance through gl_fri_combine_instance_per_batch
     python tools/openings_rate.py [reps=9] [inner=20]
@@ -18,7 +20,7 @@ import plonky2_demo_amd as p
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 9
 inner = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 P = p.GOLDILOCKS_ORDER
-OLD_PLONK, OLD_PER_BATCH, NEW = "reduce batch + divide by linear", "reduce batch + divide by linear, batch after batch", "reduce batches + divide by linear"
+OLD_PER_BATCH, NEW = "reduce batch + divide by linear, batch after batch", "reduce batches + divide by linear"
 ctx = p.default_context()
 
 
@@ -62,13 +64,16 @@ names = [[(o, c) for c in range(w)] for o, w in enumerate((ncs, 135, 20, 16))]
 inst = p.FriInstance([(ncs, False), (135, False), (20, False), (16, False)],
                      [(zeta, names[0] + names[1] + names[2] + names[3]), ([zeta[0] * g % P, zeta[1] * g % P], names[2][:2])])
 params = p.FriParams.of_circuit(d)
-a_old, a_new = cd.fri(batches, zeta, alpha, ctx=ctx), p.FriProver.from_instance(inst, batches, alpha, params, ctx=ctx)
+a_plonk, a_old, a_new = [cd.fri(batches, zeta, alpha, ctx=ctx)] + [p.FriProver.from_instance(inst, batches, alpha, params, ctx=ctx, per_batch=pb) for pb in (True, False)]
 for _ in range(d.num_fri_rounds):
-    assert (a_old.commit_round() == a_new.commit_round()).all()
-    a_old.fold([9, 9]); a_new.fold([9, 9])
-assert (a_old.final_poly() == a_new.final_poly()).all(), "the two paths differ"
-res = measure(lambda: cd.fri(batches, zeta, alpha, ctx=ctx), lambda: p.FriProver.from_instance(inst, batches, alpha, params, ctx=ctx), OLD_PLONK)
-rows.append({"shape": "(a) Plonk m = 64, n = 2^%d, %d + 2 openings" % (d.degree_bits, ncs + 171), "old": "gl_fri_combine", "old_us": res[OLD_PLONK], "new_us": res[NEW]})
+    cap = a_plonk.commit_round()
+    assert (a_old.commit_round() == cap).all() and (a_new.commit_round() == cap).all()
+    a_plonk.fold([9, 9]); a_old.fold([9, 9]); a_new.fold([9, 9])
+assert (a_old.final_poly() == a_new.final_poly()).all() and (a_plonk.final_poly() == a_new.final_poly()).all(), "the paths differ"
+a_plonk.close(); a_old.close(); a_new.close()
+res = measure(lambda: p.FriProver.from_instance(inst, batches, alpha, params, ctx=ctx, per_batch=True),
+              lambda: p.FriProver.from_instance(inst, batches, alpha, params, ctx=ctx), OLD_PER_BATCH)
+rows.append({"shape": "(a) Plonk m = 64, n = 2^%d, %d + 2 openings" % (d.degree_bits, ncs + 171), "old": "per-batch sequence", "old_us": res[OLD_PER_BATCH], "new_us": res[NEW]})
 
 # (b) a STARK-shaped instance
 lg = 20
