@@ -879,6 +879,48 @@ int gl_batch_verifier_verify(gl_batch_verifier* v, const uint8_t* const* proofs,
                              int32_t* verdicts /* [count] */, uint32_t* checks /* [count], may be null */);
 void gl_batch_verifier_free(gl_batch_verifier* v) GL_NOEXCEPT;
 
+/* verify_fri_proof (fri/verifier.rs:62-241) for `count` claims over one (gl_fri_params, gl_fri_instance): the batched
+ * gl_verify_openings.  Per claim everything gl_verify_openings does before its query loop runs on the host (the coset check of the
+ * claim's points, the decode, the challenges, the proof of work, the reduced openings; on up to host_threads threads; 0 means 1, at
+ * most 64); the Merkle paths and the queries of all claims that pass run on the device in two launches per chunk of max_batch
+ * (1..4096) claims, on the context's stream.  The instance's own points are ignored: every claim brings its own.
+ * gl_openings_batch_verifier_new accepts what gl_verify_openings accepts of params and instance, with its checks, order, codes and
+ * texts; in addition a fri_arity_bits[r] > 4 is GL_ERR_UNSUPPORTED, and a proof above 2^24 words or a batch above 2^31 paths is
+ * GL_ERR_ARG.  Device and pinned staging for max_batch claims is allocated once, there.
+ * gl_openings_batch_verifier_verify returns GL_OK when every claim was judged, whatever the verdicts, and another code only for a
+ * failure of the machinery (HIP, memory, a null argument).  verdicts[i] is what gl_verify_openings returns for claim i alone: GL_OK,
+ * GL_ERR_VERIFY, or GL_ERR_ARG (a point on the LDE coset, a challenger under another hasher than the params'); checks[i] (may be
+ * null) the GL_CHECK_* code it reports first.  count may exceed max_batch and may be 0.  A claim's challenger is consumed: its state
+ * after the call is unspecified, and two claims must not share one.  Calls on one verifier are serialised; verifiers on different
+ * contexts run side by side. */
+typedef struct gl_openings_claim {     /* one verify_fri_proof */
+    const uint64_t* caps;              /* [num_oracles][2^cap_height][4] */
+    const uint64_t* openings;          /* as gl_verify_openings */
+    const uint64_t (*points)[2];       /* [num_batches]: this claim's opening points */
+    gl_challenger* challenger;         /* in the state gl_verify_openings expects; one per claim */
+    const uint8_t* proof; size_t num_bytes;
+} gl_openings_claim;
+typedef struct gl_openings_batch_verifier gl_openings_batch_verifier;
+int gl_openings_batch_verifier_new(gl_ctx* ctx, const gl_fri_params* params, const gl_fri_instance* instance /* points ignored */,
+                                   uint32_t max_batch, uint32_t host_threads, gl_openings_batch_verifier** out);
+int gl_openings_batch_verifier_verify(gl_openings_batch_verifier* v, const gl_openings_claim* claims, size_t count,
+                                      int32_t* verdicts /* [count] */, uint32_t* checks /* [count], may be null */);
+void gl_openings_batch_verifier_free(gl_openings_batch_verifier* v) GL_NOEXCEPT;
+
+/* verify_stark_proof (starky/src/verifier.rs:21-145) for `count` proofs of one Stark, on top of the above.  Per proof everything
+ * gl_stark_verify / gl_stark_dag_verify (dag != NULL) does before its final gl_verify_openings runs on the host threads: the byte
+ * count, caps, openings, get_challenges, the vanishing identity at zeta through the term list or the compiled DAG; then the proof's
+ * FriProof is a claim of the batch above at its own zeta and g zeta.  gl_stark_batch_verifier_new accepts exactly what
+ * gl_stark_check (gl_stark_dag_check) accepts, with its codes and texts (a reduction of arity other than 16 is GL_ERR_UNSUPPORTED,
+ * hiding too), copies the description and compiles the DAG once.  verdicts[i] / checks[i] are gl_stark_verify's (gl_stark_dag_verify's)
+ * for proofs[i] alone; everything else is as for gl_openings_batch_verifier_verify. */
+typedef struct gl_stark_batch_verifier gl_stark_batch_verifier;
+int gl_stark_batch_verifier_new(gl_ctx* ctx, const gl_stark_desc* desc, const gl_stark_dag* dag /* null: the term-list form */,
+                                const gl_fri_params* params, uint32_t max_batch, uint32_t host_threads, gl_stark_batch_verifier** out);
+int gl_stark_batch_verifier_verify(gl_stark_batch_verifier* v, const uint8_t* const* proofs, const size_t* num_bytes, size_t count,
+                                   int32_t* verdicts /* [count] */, uint32_t* checks /* [count], may be null */);
+void gl_stark_batch_verifier_free(gl_stark_batch_verifier* v) GL_NOEXCEPT;
+
 /* ---- circuit data as bytes --------------------------------------------------------------------------*/
 /* The reference's serialised forms (plonky2/src/plonk/circuit_data.rs:125-142,208-238; util/serialization/mod.rs:739-800,
  * 1736-1790 CommonCircuitData, :909-930,1889-1906 VerifierOnlyCircuitData, :1908-1919 VerifierCircuitData = verifier_only ||

@@ -19,4 +19,5 @@ from .api import (  # noqa: F401
     Stark, StarkConfig, StarkDesc, fibonacci_stark, stark_verify,
     StarkDagBuilder, StarkDagDesc, StarkDagExpr, stark_dag_verify,
     CrossTableLookup, CtlColumn, StarkSet, StarkSetDesc, TableWithColumns, stark_set_verify,
+    OpeningsBatchVerifier, StarkBatchVerifier,
 )

@@ -217,6 +217,13 @@ SIGNATURES = {
     "gl_stark_set_prove": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(c_sz)]),
     "gl_stark_set_prove_device": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(c_sz)]),
     "gl_stark_set_verify": (c_int, [c_vp, c_vp, c_sz, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
+    # batch verification of FRI openings of any instance, and of STARK proofs on top of it (device Merkle paths and FRI queries)
+    "gl_openings_batch_verifier_new": (c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, ctypes.POINTER(c_vp)]),
+    "gl_openings_batch_verifier_verify": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "gl_openings_batch_verifier_free": (None, [c_vp]),
+    "gl_stark_batch_verifier_new": (c_int, [c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, ctypes.POINTER(c_vp)]),
+    "gl_stark_batch_verifier_verify": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "gl_stark_batch_verifier_free": (None, [c_vp]),
 }
 GL_MAX_FRI_ORACLES, GL_MAX_FRI_BATCHES = 8, 4
 
@@ -310,6 +317,11 @@ class FriInstance(ctypes.Structure):
     @property
     def num_opened(self):
         return sum(len(polys) for _, polys in self.batches)
+
+
+class OpeningsClaim(ctypes.Structure):
+    """gl_openings_claim: one verify_fri_proof of gl_openings_batch_verifier_verify."""
+    _fields_ = [("caps", c_vp), ("openings", c_vp), ("points", c_vp), ("challenger", c_vp), ("proof", c_vp), ("num_bytes", c_sz)]
 
 
 (GL_STARK_ALL, GL_STARK_TRANSITION, GL_STARK_FIRST_ROW, GL_STARK_LAST_ROW) = range(4)      # constraint filters

@@ -1003,6 +1003,49 @@ def verify_fri_proof(instance, caps, openings, challenger, proof, fri_params):
     return ok, why, code.value
 
 
+def _batch_verdicts(verdicts, checks, what):
+    """[(accepted, message, code)] of a batch call's per-item verdicts; one that is neither accept nor reject raises, as alone"""
+    out = []
+    for i, (st, c) in enumerate(zip(verdicts, checks)):
+        if st not in (_lib.GL_OK, _lib.GL_ERR_VERIFY):
+            raise _lib.Plonky2Mi355xError(int(st), verify_check_message(c) or "%s %d was refused, as it is alone" % (what, i))
+        out.append((st == _lib.GL_OK, verify_check_message(c), int(c)))
+    return out
+
+
+class OpeningsBatchVerifier(_Owned):
+    """verify_fri_proof (fri/verifier.rs:62-241) for many claims over one (instance, fri_params) per call (gl_openings_batch_verifier):
+    per claim what verify_fri_proof does before its query loop on `host_threads` host threads, the Merkle paths and the queries of all
+    of them in two launches per `max_batch` claims on the context's stream.  The instance's own points are ignored."""
+    _free = "gl_openings_batch_verifier_free"
+
+    def __init__(self, instance, fri_params, ctx=None, max_batch=64, host_threads=1):
+        ctx = _ctx(ctx)
+        h = ctypes.c_void_p()
+        check(lib.gl_openings_batch_verifier_new(ctx.handle, ctypes.byref(fri_params), ctypes.byref(instance), int(max_batch), int(host_threads), ctypes.byref(h)))
+        self.handle, self.ctx, self.instance, self.params = h.value, ctx, instance, fri_params
+
+    def verify(self, claims):
+        """claims: [(caps, openings, points, challenger, proof)] with caps [num_oracles][2^cap_height][4], openings every batch's values
+        in order, points [num_batches][2], a Challenger of its own per claim (consumed) -> [(accepted, message, GL_CHECK_* code)], what
+        verify_fri_proof gives for each alone (the message without the source position)."""
+        n = len(claims)
+        arr, keep = (_lib.OpeningsClaim * max(n, 1))(), []
+        listed = self.instance.num_opened
+        for i, (caps, openings, points, challenger, proof) in enumerate(claims):
+            caps, openings, points = _u64(caps).reshape(-1), _u64(openings).reshape(-1), _u64(points).reshape(-1)
+            by = bytes(proof)
+            buf = np.frombuffer(by or b"\0", dtype=np.uint8)                # (an empty proof: a pointer to read nothing from)
+            if caps.size < self.instance.num_oracles * (4 << self.params.cap_height) or openings.size < 2 * listed or points.size < 2 * self.instance.num_batches:
+                raise ValueError("caps are [num_oracles][2^cap_height][4], openings one extension value per listed polynomial, points [num_batches][2]")
+            keep.append((caps, openings, points, challenger, buf))
+            arr[i] = _lib.OpeningsClaim(caps.ctypes.data, openings.ctypes.data, points.ctypes.data, challenger.handle, buf.ctypes.data, len(by))
+        verdicts, checks = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.uint32)
+        check(lib.gl_openings_batch_verifier_verify(self.handle, arr, n, _p(verdicts), _p(checks)))
+        self.verdicts, self.checks = [int(v) for v in verdicts[:n]], [int(c) for c in checks[:n]]      # (kept for a caller whom a refusal below leaves without the list)
+        return _batch_verdicts(self.verdicts, self.checks, "claim")
+
+
 # ------------------------------------------------------------------------------------- STARK: an AIR as data
 class StarkConfig:
     """starky::config::StarkConfig (starky/src/config.rs): num_challenges and the FriConfig."""
@@ -1274,6 +1317,10 @@ class Stark(_Owned):
         """verify_stark_proof (verifier.rs:21-145), host code -> (accepted, message, GL_CHECK_* code)."""
         return stark_verify(self.desc, self.config, self.degree_bits, proof, hasher=self.params.hasher)
 
+    def batch_verifier(self, max_batch=64, host_threads=1):
+        """A StarkBatchVerifier for this Stark on its context."""
+        return StarkBatchVerifier(self.desc, self.config, self.degree_bits, self.params.hasher, self.ctx, max_batch, host_threads)
+
 
 def stark_verify(desc, config, degree_bits, proof, hasher="poseidon"):
     """gl_stark_verify (gl_stark_dag_verify for a StarkDagDesc): needs no GPU and no Stark handle -> (accepted, message, GL_CHECK_* code)."""
@@ -1296,6 +1343,34 @@ def stark_dag_verify(desc, config, degree_bits, proof, hasher="poseidon"):
                                  _p(buf) if buf.size else None, buf.size, ctypes.byref(code))
     ok, why = _verdict(st)
     return ok, why, code.value
+
+
+class StarkBatchVerifier(_Owned):
+    """verify_stark_proof for many proofs of one Stark per call (gl_stark_batch_verifier): per proof what gl_stark_verify
+    (gl_stark_dag_verify for a StarkDagDesc) does before its verify_fri_proof on `host_threads` host threads, the Merkle paths and the FRI
+    queries of all of them in two launches per `max_batch` proofs on the context's stream."""
+    _free = "gl_stark_batch_verifier_free"
+
+    def __init__(self, desc, config, degree_bits, hasher="poseidon", ctx=None, max_batch=64, host_threads=1):
+        ctx = _ctx(ctx)
+        self.params = config.fri_params(degree_bits, hasher)
+        dag = desc.dag_struct() if isinstance(desc, StarkDagDesc) else None
+        h = ctypes.c_void_p()
+        check(lib.gl_stark_batch_verifier_new(ctx.handle, ctypes.byref(desc.struct(config.num_challenges)), ctypes.byref(dag) if dag is not None else None,
+                                              ctypes.byref(self.params), int(max_batch), int(host_threads), ctypes.byref(h)))
+        self.handle, self.ctx, self.desc, self.config, self.degree_bits = h.value, ctx, desc, config, degree_bits
+
+    def verify(self, proofs):
+        """[(accepted, message, GL_CHECK_* code)] for `proofs` (bytes), what Stark.verify gives for each alone (the message without the
+        source position)."""
+        bufs = [bytes(p) for p in proofs]
+        n = len(bufs)
+        ptrs = (ctypes.c_char_p * max(n, 1))(*bufs)
+        sizes = (ctypes.c_size_t * max(n, 1))(*[len(b) for b in bufs])
+        verdicts, checks = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.uint32)
+        check(lib.gl_stark_batch_verifier_verify(self.handle, ptrs, sizes, n, _p(verdicts), _p(checks)))
+        self.verdicts, self.checks = [int(v) for v in verdicts[:n]], [int(c) for c in checks[:n]]
+        return _batch_verdicts(self.verdicts, self.checks, "proof")
 
 
 # ------------------------------------------------------------------------------------- STARK table sets: cross-table lookups

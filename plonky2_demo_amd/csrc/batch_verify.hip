@@ -15,6 +15,7 @@
 #include "context.hpp"
 #include "host_circuit.hpp"
 #include "lanes.hpp"
+#include "verify_lane.cuh"
 #include "verify_stage.hpp"
 #include <memory>
 
@@ -57,62 +58,14 @@ __global__ __launch_bounds__(256) void k_verify_merkle_paths(const gl_t* __restr
     const gl_t* __restrict__ leaf = Q + P.slot_leaf[slot];
     const gl_t* __restrict__ sib = Q + P.slot_sib[slot];
     const uint32_t len = P.slot_leaf_len[slot], nsib = P.slot_nsib[slot];
-    uint32_t idx = (uint32_t)T[P.t_words + CH_X + q] >> P.slot_shift[slot];
-    uint64_t cur[4] = {0, 0, 0, 0};
-    if constexpr (HASHER == GL_HASHER_KECCAK) {
-        if (len * 8 <= KCK_HASH_BYTES) {
-#pragma unroll
-            for (int e = 0; e < 3; e++) if ((uint32_t)e < len) cur[e] = leaf[e];
-        } else {
-            kck_state s;
-            kck_absorb_leaf(s, len, [&](uint32_t e) { return leaf[e]; });
-            kck_digest25(s, cur);
-        }
-        for (uint32_t l = 0; l < nsib; l++, idx >>= 1) {
-            uint64_t a[4], b[4], out[4];
-            const bool right = idx & 1;
-            for (int k = 0; k < 4; k++) { const uint64_t sv = sib[4 * l + k]; a[k] = right ? sv : cur[k]; b[k] = right ? cur[k] : sv; }
-            kck_two_to_one(a, b, out);
-            for (int k = 0; k < 4; k++) cur[k] = out[k];
-        }
-    } else {
-        gl_t s[12];
-#pragma unroll
-        for (int i = 0; i < 12; i++) s[i] = 0;
-        if (len <= 4) {
-#pragma unroll
-            for (int e = 0; e < 4; e++) if ((uint32_t)e < len) s[e] = leaf[e];
-        } else {
-            for (uint32_t e0 = 0; e0 < len; e0 += 8) {
-                const uint32_t c = len - e0 < 8 ? len - e0 : 8;
-#pragma unroll
-                for (int i = 0; i < 8; i++) if ((uint32_t)i < c) s[i] = leaf[e0 + i];
-                psd_permute(s);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) cur[k] = gl_canon(s[k]);
-        for (uint32_t l = 0; l < nsib; l++, idx >>= 1) {
-            const bool right = idx & 1;
-#pragma unroll
-            for (int k = 0; k < 4; k++) { const gl_t sv = sib[4 * l + k]; s[k] = right ? sv : cur[k]; s[4 + k] = right ? cur[k] : sv; s[8 + k] = 0; }
-            psd_permute(s);
-#pragma unroll
-            for (int k = 0; k < 4; k++) cur[k] = gl_canon(s[k]);
-        }
-    }
-    // idx < 2^cap_height now: the path has lg(leaves) - cap_height levels
+    const uint32_t idx = (uint32_t)T[P.t_words + CH_X + q] >> P.slot_shift[slot];
+    // idx >> nsib < 2^cap_height: the path has lg(leaves) - cap_height levels
     const gl_t* __restrict__ cap = slot == 0 ? cap0 : slot < NUM_INITIAL_TREES ? T + P.o_caps + 4 * P.ncap * (slot - 1) : T + P.o_fcaps + 4 * P.ncap * (slot - NUM_INITIAL_TREES);
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 4; k++) ok = ok && cur[k] == cap[4 * idx + k];
-    pass[gid] = ok ? 1 : 0;
+    pass[gid] = d_path_opens_to_cap<HASHER>(leaf, len, sib, nsib, idx, cap) ? 1 : 0;
 }
 
 // ---- the arithmetic of one query (fri/verifier.rs:124-241) ----
 typedef gl2_t E;
-__device__ __forceinline__ E d_ext(const gl_t* __restrict__ w) { return gl2_make(w[0], w[1]); }
-__device__ __forceinline__ bool d_eq(E x, E y) { x = gl2_canon(x); y = gl2_canon(y); return x.a == y.a && x.b == y.b; }
 // acc = acc * alpha + v[i] for i = last - 1 down to first (base-field values)
 __device__ __forceinline__ E d_horner_base(E acc, E alpha, const gl_t* __restrict__ v, uint32_t first, uint32_t last) {
     for (uint32_t i = last; i-- > first;) { acc = gl2_mul(acc, alpha); acc.a = gl_add(acc.a, v[i]); }
@@ -148,24 +101,7 @@ __global__ __launch_bounds__(64) void k_verify_fri_queries(const gl_t* __restric
         const uint32_t ab = P.arity_bits[r], arity = 1u << ab, within = x & (arity - 1);
         const gl_t* __restrict__ leaf = Q + P.slot_leaf[NUM_INITIAL_TREES + r];
         if (!d_eq(d_ext(leaf + 2 * within), eval)) bad |= 1u << r;
-        // compute_evaluation (fri/verifier.rs:21-47): the interpolant through the coset x * g^{-rev(within)} * g^k at beta, the values in
-        // bit-reversed order.  The points are regenerated by running products, so nothing is indexed but memory
-        const E beta = d_ext(C + CH_BETAS + 2 * r);
-        const gl_t g = P.w_arity[r];
-        const gl_t start = gl_canon(gl_mul(subgroup_x, gl_exp(g, arity - (__brev(within) >> (32 - ab)))));
-        E acc = gl2_make(0, 0);
-        gl_t pa = start;
-        for (uint32_t a = 0; a < arity; a++) {
-            E numer = gl2_make(1, 0);
-            gl_t denom = 1, pb = start;
-            for (uint32_t b = 0; b < arity; b++) {
-                if (b != a) { numer = gl2_mul(numer, gl2_sub(beta, gl2_make(pb, 0))); denom = gl_mul(denom, gl_sub(pa, pb)); }
-                pb = gl_canon(gl_mul(pb, g));
-            }
-            acc = gl2_add(acc, gl2_mul(d_ext(leaf + 2 * (__brev(a) >> (32 - ab))), gl2_scalar(numer, gl_inv(denom))));
-            pa = gl_canon(gl_mul(pa, g));
-        }
-        eval = acc;                                    // the host carries its own value on as well (and stops at the first failure)
+        eval = d_compute_evaluation(subgroup_x, within, ab, P.w_arity[r], leaf, d_ext(C + CH_BETAS + 2 * r));      // the host carries its own value on as well (and stops at the first failure)
         for (uint32_t i = 0; i < ab; i++) subgroup_x = gl_sqr(subgroup_x);
         x >>= ab;
     }

@@ -15,6 +15,18 @@ inline size_t total_polys(const gl_fri_instance& in) { size_t t = 0; for (uint32
 inline uint32_t salt_of(const gl_fri_params& p, const gl_fri_instance& in, uint32_t o) { return p.hiding && in.oracle_blinding[o] ? SALT_SIZE : 0; }
 inline gl2_t point_of(const gl_fri_instance& in, uint32_t b) { return gl2_make(gl_canon(in.points[b][0]), gl_canon(in.points[b][1])); }
 
+// a point 7 w with w^N = 1 is an LDE point: the quotient by (X - point) has a pole there (the reference panics dividing by zero)
+inline int check_points(const gl_fri_params& p, uint32_t num_batches, const uint64_t (*points)[2]) {
+    const gl_t inv7 = gl_inv(GL_MULT_GENERATOR);
+    for (uint32_t b = 0; b < num_batches; b++) {
+        if (gl_canon(points[b][1]) != 0) continue;
+        gl_t w = gl_mul(gl_canon(points[b][0]), inv7);
+        for (uint32_t i = 0; i < p.degree_bits + p.rate_bits; i++) w = gl_sqr(w);
+        GL_REQUIRE(gl_canon(w) != 1, GL_ERR_ARG, "FRI openings: an opening point lies on the LDE coset");
+    }
+    return GL_OK;
+}
+
 // the checks of include/plonky2_mi355x.h ("Validation"); `prover`: the two calls that fold by 16 only
 inline int check(const gl_fri_params* params, const gl_fri_instance* instance, bool prover) {
     GL_REQUIRE(params && instance, GL_ERR_ARG, "FRI openings: null params / instance");
@@ -48,15 +60,7 @@ inline int check(const gl_fri_params* params, const gl_fri_instance* instance, b
     for (size_t k = 0; k < listed; k++)
         GL_REQUIRE(in.polys[2 * k] < in.num_oracles && in.polys[2 * k + 1] < in.oracle_num_polys[in.polys[2 * k]], GL_ERR_ARG,
                    "FRI openings: oracle / polynomial index out of range");
-    // a point 7 w with w^N = 1 is an LDE point: the quotient by (X - point) has a pole there (the reference panics dividing by zero)
-    const gl_t inv7 = gl_inv(GL_MULT_GENERATOR);
-    for (uint32_t b = 0; b < in.num_batches; b++) {
-        const gl2_t z = point_of(in, b);
-        if (z.b != 0) continue;
-        gl_t w = gl_mul(z.a, inv7);
-        for (uint32_t i = 0; i < p.degree_bits + p.rate_bits; i++) w = gl_sqr(w);
-        GL_REQUIRE(gl_canon(w) != 1, GL_ERR_ARG, "FRI openings: an opening point lies on the LDE coset");
-    }
+    GL_TRY(check_points(p, in.num_batches, in.points));
     if (prover)
         for (unsigned r = 0; r < p.num_fri_rounds; r++) GL_REQUIRE(p.fri_arity_bits[r] == 4, GL_ERR_UNSUPPORTED, "FRI arity must be 16");
     return GL_OK;

@@ -4,6 +4,7 @@
 // the existing PolynomialBatch code; nothing is copied from it.
 #include "context.hpp"
 #include "fri_instance.hpp"
+#include "openings_stage.hpp"
 #include "proof.hpp"
 #include "stark_internal.hpp"
 #include "stark_kernels.cuh"
@@ -507,13 +508,12 @@ extern "C" int gl_stark_verify(const gl_stark_desc* desc, const gl_fri_params* p
     return stark_verify(desc, nullptr, params, proof_bytes, num_bytes, check);
 } catch (...) { return gl_caught(); }
 
-// gl_stark_verify and gl_stark_dag_verify
-int glstark::stark_verify(const gl_stark_desc* desc, const gl_stark_dag* dag, const gl_fri_params* params, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check) {
-    StarkShape s;
-    DagProgram prog;
-    GL_TRY(stark_check(desc, params, &s, false, dag, &prog));
+// gl_stark_verify and gl_stark_dag_verify up to their final gl_verify_openings, for a description that passed stark_check (prog: its
+// compiled DAG, or null): the byte count, caps, openings, get_challenges, the vanishing identity; what is left is the claim
+int glstark::stark_host_stage(const gl_stark_desc& d, const StarkShape& s, const DagProgram* prog, const gl_fri_params& p, const uint8_t* proof_bytes, size_t num_bytes,
+                              StarkClaim& out, uint32_t* check) {
+    if (check) *check = GL_CHECK_ACCEPTED;
     GL_REQUIRE(proof_bytes || !num_bytes, GL_ERR_ARG, "gl_stark_verify: null proof");
-    const gl_stark_desc& d = *desc; const gl_fri_params& p = *params;
     const uint32_t nc = d.num_challenges, ncols = d.num_columns, nz = s.nz, nq = s.q * nc;
     const size_t ncap = size_t(1) << p.cap_height, total = stark_proof_bytes(p, ncols, d.num_public_inputs, nc, s);
     // the layout's counts are fixed by the description and the params
@@ -521,19 +521,22 @@ int glstark::stark_verify(const gl_stark_desc* desc, const gl_stark_dag* dag, co
     if (num_bytes > total) return stark_reject(GL_CHECK_LENGTH, check);
     VCursor cur{proof_bytes, num_bytes};
     const uint32_t noracles = nz ? 3 : 2;
-    std::vector<gl_t> caps(4 * ncap * noracles), pub(d.num_public_inputs + 1);
+    std::vector<gl_t>& caps = out.caps;
+    std::vector<gl_t> pub(d.num_public_inputs + 1);
+    caps.resize(4 * ncap * noracles);
     cur.hashes(p.hasher, caps.data(), ncap * noracles);
     const size_t nopen = 2 * (size_t)ncols + 2 * nz + nq;
     std::vector<gl_t> w(2 * nopen);
     cur.words(w.data(), w.size());
     const gl2_t* ext = (const gl2_t*)w.data();
     const gl2_t *local = ext, *next = ext + ncols, *zl = ext + 2 * ncols, *zn = zl + nz, *ql = zn + nz;
-    const uint8_t* fri = proof_bytes + cur.pos;
-    const size_t fri_len = fri_proof_bytes(p, ncols, nc, s);
-    cur.pos += fri_len;
+    out.fri = proof_bytes + cur.pos;
+    out.fri_len = fri_proof_bytes(p, ncols, nc, s);
+    cur.pos += out.fri_len;
     cur.words(pub.data(), d.num_public_inputs);
     // get_challenges (get_challenges.rs:21-59)
-    gl_challenger ch{glhost::HostChallenger(p.hasher)};
+    gl_challenger& ch = out.ch;
+    ch.ch = glhost::HostChallenger(p.hasher);
     ch.ch.observe_hashes(p.hasher, caps.data(), ncap);
     std::vector<gl_t> sets;
     if (nz) {
@@ -545,7 +548,8 @@ int glstark::stark_verify(const gl_stark_desc* desc, const gl_stark_dag* dag, co
     ch.ch.observe_hashes(p.hasher, caps.data() + 4 * ncap * (noracles - 1), ncap);
     const gl2_t zeta = ch.ch.challenge_ext();
     // FriOpenings order (proof.rs:161-182)
-    std::vector<gl_t> openings;
+    std::vector<gl_t>& openings = out.openings;
+    openings.clear();
     openings.reserve(2 * nopen);
     auto push = [&](const gl2_t* v, size_t k) { for (size_t i = 0; i < k; i++) { openings.push_back(v[i].a); openings.push_back(v[i].b); } };
     push(local, ncols); push(zl, nz); push(ql, nq); push(next, ncols); push(zn, nz);
@@ -557,16 +561,88 @@ int glstark::stark_verify(const gl_stark_desc* desc, const gl_stark_dag* dag, co
     const gl2_t l_last = gl2_mul(z_h, gl2_inv(gl2_scalar(gl2_sub(gl2_scalar(zeta, g), gl2_make(1, 0)), n_field)));
     const gl2_t z_last = gl2_sub(zeta, e_of(gl_inv(g)));
     gl2_t accs[GL_STARK_MAX_CHALLENGES];
-    vanishing_at(d, s, local, next, pub.data(), alphas, z_last, l_first, l_last, zl, zn, sets.data(), accs, dag ? &prog : nullptr);
+    vanishing_at(d, s, local, next, pub.data(), alphas, z_last, l_first, l_last, zl, zn, sets.data(), accs, prog);
     for (uint32_t j = 0; j < nc; j++) {
         gl2_t t = gl2_make(0, 0);                                                                                       // reduce_with_powers(chunk, zeta^n)
         for (uint32_t k = s.q; k-- > 0;) t = gl2_add(gl2_mul(t, zeta_pow), ql[j * s.q + k]);
         const gl2_t lhs = gl2_canon(accs[j]), rhs = gl2_canon(gl2_mul(z_h, t));
         if (lhs.a != rhs.a || lhs.b != rhs.b) return stark_reject(GL_CHECK_VANISHING, check);
     }
-    const StarkInstance si(ncols, nc, s, zeta, gl2_canon(gl2_scalar(zeta, g)));
-    return gl_verify_openings(&p, &si.inst, caps.data(), openings.data(), &ch, fri, fri_len, check);
+    const gl2_t zeta_next = gl2_canon(gl2_scalar(zeta, g));
+    out.points[0][0] = zeta.a; out.points[0][1] = zeta.b; out.points[1][0] = zeta_next.a; out.points[1][1] = zeta_next.b;
+    return GL_OK;
 }
+
+// gl_stark_verify and gl_stark_dag_verify: the host stage, then verify_fri_proof on the STARK's instance at this proof's zeta and g zeta
+int glstark::stark_verify(const gl_stark_desc* desc, const gl_stark_dag* dag, const gl_fri_params* params, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check) {
+    StarkShape s;
+    DagProgram prog;
+    GL_TRY(stark_check(desc, params, &s, false, dag, &prog));
+    StarkClaim claim;
+    GL_TRY(stark_host_stage(*desc, s, dag ? &prog : nullptr, *params, proof_bytes, num_bytes, claim, check));
+    const StarkInstance si(desc->num_columns, desc->num_challenges, s, gl2_make(claim.points[0][0], claim.points[0][1]), gl2_make(claim.points[1][0], claim.points[1][1]));
+    return gl_verify_openings(params, &si.inst, claim.caps.data(), claim.openings.data(), &claim.ch, claim.fri, claim.fri_len, check);
+}
+
+// ---- verify_stark_proof for many proofs of one Stark: the host stage per proof on host threads, each proof's FriProof a claim of the
+// device batch verifier for the STARK's instance (openings_verify.hip) ----
+struct gl_stark_batch_verifier {
+    gl_openings_batch_verifier* inner = nullptr;
+    gl_fri_params params;
+    StarkShape shape;
+    gl_stark_desc desc;                                // its tables point into the vectors below: the caller's may go away
+    std::vector<uint32_t> filter, num_terms, term_nf, factors, pair_len, pair_columns;
+    std::vector<uint64_t> coeff;
+    bool dag = false;
+    DagProgram prog;                                   // compiled once
+    std::vector<StarkClaim> lanes;                     // one per host thread
+};
+
+extern "C" void gl_stark_batch_verifier_free(gl_stark_batch_verifier* v) noexcept {
+    if (!v) return;
+    gl_openings_batch_verifier_free(v->inner);
+    delete v;
+}
+
+extern "C" int gl_stark_batch_verifier_new(gl_ctx* ctx, const gl_stark_desc* desc, const gl_stark_dag* dag, const gl_fri_params* params, uint32_t max_batch,
+                                           uint32_t host_threads, gl_stark_batch_verifier** out) try {
+    GL_REQUIRE(out, GL_ERR_ARG, "gl_stark_batch_verifier_new: null argument");
+    *out = nullptr;
+    GL_REQUIRE(ctx && desc && params, GL_ERR_ARG, "gl_stark_batch_verifier_new: null argument");
+    std::unique_ptr<gl_stark_batch_verifier, void (*)(gl_stark_batch_verifier*)> v(new gl_stark_batch_verifier(), gl_stark_batch_verifier_free);
+    GL_TRY(stark_check(desc, params, &v->shape, true, dag, &v->prog));            // gl_stark_check (gl_stark_dag_check) itself: reductions by 16 only
+    const StarkShape& s = v->shape;
+    const gl_stark_desc& d = *desc;
+    v->params = *params; v->dag = dag != nullptr; v->desc = d;
+    auto keep = [](auto& vec, const auto* from, size_t k) { if (from && k) vec.assign(from, from + k); return vec.empty() ? decltype(vec.data())(nullptr) : vec.data(); };
+    v->desc.constraint_filter = keep(v->filter, d.constraint_filter, d.num_constraints);
+    v->desc.constraint_num_terms = keep(v->num_terms, d.constraint_num_terms, d.num_constraints);
+    v->desc.term_coeff = keep(v->coeff, d.term_coeff, s.terms);
+    v->desc.term_num_factors = keep(v->term_nf, d.term_num_factors, s.terms);
+    v->desc.factors = keep(v->factors, d.factors, s.factors);
+    v->desc.pair_len = keep(v->pair_len, d.pair_len, d.num_permutation_pairs);
+    v->desc.pair_columns = keep(v->pair_columns, d.pair_columns, 2 * s.column_pairs);
+    const StarkInstance si(d.num_columns, d.num_challenges, s, gl2_make(0, 1), gl2_make(0, 1));
+    GL_TRY(glopen::batch_new(ctx, params, &si.inst, max_batch, host_threads, &v->inner));
+    v->lanes.resize(host_threads ? host_threads : 1);
+    *out = v.release();
+    return GL_OK;
+} catch (...) { return gl_caught(); }
+
+extern "C" int gl_stark_batch_verifier_verify(gl_stark_batch_verifier* v, const uint8_t* const* proofs, const size_t* num_bytes, size_t count, int32_t* verdicts,
+                                              uint32_t* checks) try {
+    GL_REQUIRE(v, GL_ERR_ARG, "gl_stark_batch_verifier_verify: null verifier");
+    if (!count) return GL_OK;
+    GL_REQUIRE(proofs && num_bytes && verdicts, GL_ERR_ARG, "gl_stark_batch_verifier_verify: null argument");
+    return glopen::batch_verify(v->inner, count, [&](size_t lane, size_t i, gl_openings_claim& claim, uint32_t* check) -> int {
+        GL_REQUIRE(proofs[i], GL_ERR_ARG, "gl_stark_batch_verifier_verify: null proof");
+        StarkClaim& c = v->lanes[lane];
+        GL_TRY(stark_host_stage(v->desc, v->shape, v->dag ? &v->prog : nullptr, v->params, proofs[i], num_bytes[i], c, check));
+        claim.caps = c.caps.data(); claim.openings = c.openings.data(); claim.points = c.points; claim.challenger = &c.ch;
+        claim.proof = c.fri; claim.num_bytes = c.fri_len;
+        return GL_OK;
+    }, verdicts, checks);
+} catch (...) { return gl_caught(); }
 
 // the launches of k_stark_seg_products and k_stark_seg_scan for the other running products (stark_set.hip): d_seg[nz][nseg] becomes the
 // exclusive prefix of the segment products of d_fac[nz][n]

@@ -64,6 +64,16 @@ void vanishing_at(const gl_stark_desc& d, const StarkShape& s, const gl2_t* loca
 int stark_check(const gl_stark_desc* desc, const gl_fri_params* params, StarkShape* shape, bool prover = true, const gl_stark_dag* dag = nullptr,
                 DagProgram* prog = nullptr);
 int stark_create(gl_ctx* ctx, const gl_stark_desc* desc, const gl_stark_dag* dag, const gl_fri_params* params, gl_stark** out);
+// what stark_host_stage leaves of a proof for verify_fri_proof: the oracles' caps, the openings in FriOpenings order, the transcript where
+// gl_verify_openings takes it over, zeta and g zeta, and the FriProof inside the proof bytes
+struct StarkClaim {
+    std::vector<gl_t> caps, openings;
+    gl_challenger ch{glhost::HostChallenger(GL_HASHER_POSEIDON)};
+    uint64_t points[2][2] = {};
+    const uint8_t* fri = nullptr; size_t fri_len = 0;
+};
+int stark_host_stage(const gl_stark_desc& d, const StarkShape& s, const DagProgram* prog, const gl_fri_params& p, const uint8_t* proof_bytes, size_t num_bytes,
+                     StarkClaim& out, uint32_t* check);
 int stark_verify(const gl_stark_desc* desc, const gl_stark_dag* dag, const gl_fri_params* params, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check);
 // stark_dag.hip: the DAG's own rules and its compilation; the constraints of a compiled program at zeta, consumed in order; the launch
 // of k_stark_quotient_dag with everything k_stark_quotient takes

@@ -10,6 +10,7 @@
 #include "context.hpp"
 #include "host_circuit.hpp"
 #include "fri_instance.hpp"
+#include "openings_stage.hpp"
 #include "verify_stage.hpp"
 
 namespace {
@@ -601,23 +602,58 @@ extern "C" int gl_host_circuit_verify(const gl_host_circuit* hc, const uint64_t*
 // ---- verify_fri_proof for any FriInstanceInfo (fri/verifier.rs:62-241, fri/challenges.rs:24-64, fri/validate_shape.rs) ----
 // The FriProof alone, in write_fri_proof order (util/serialization/mod.rs:1568-1582), on the caller's Challenger.  gl_verify above keeps
 // its own query loop over the Plonk layout; the two share path_opens_to_cap, compute_evaluation, the Cursor and the rejection table.
-extern "C" int gl_verify_openings(const gl_fri_params* params, const gl_fri_instance* instance, const uint64_t* caps, const uint64_t* openings,
-                                  gl_challenger* challenger, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check) try {
-    if (check) *check = GL_CHECK_ACCEPTED;
+// Like gl_verify it is two halves (openings_stage.hpp): the shape and the host stage, which the device batch verifier
+// (openings_verify.hip) runs as well, and the query loop over the table T.
+int glopen::shape_of(const gl_fri_params* params, const gl_fri_instance* instance, Shape& s) {
     GL_TRY(glfri::check(params, instance, false));
-    GL_REQUIRE(caps && openings && challenger && proof_bytes, GL_ERR_ARG, "gl_verify_openings: null argument");
     const gl_fri_params& p = *params; const gl_fri_instance& in = *instance;
+    s = Shape();
+    s.hasher = p.hasher; s.num_queries = p.num_query_rounds; s.num_rounds = p.num_fri_rounds; s.num_oracles = in.num_oracles; s.num_batches = in.num_batches;
+    s.cap_height = p.cap_height; s.lgN = p.degree_bits + p.rate_bits;
+    s.ncap = size_t(1) << p.cap_height;
+    s.final_len = size_t(1) << p.degree_bits;
+    for (unsigned r = 0; r < p.num_fri_rounds; r++) { s.arity_bits[r] = p.fri_arity_bits[r]; s.final_len >>= p.fri_arity_bits[r]; }
+    size_t in_query = 0;
+    for (uint32_t o = 0; o < in.num_oracles; o++) {
+        s.slot_leaf[o] = in_query; s.slot_leaf_len[o] = (size_t)in.oracle_num_polys[o] + glfri::salt_of(p, in, o); s.slot_nsib[o] = s.lgN - p.cap_height;
+        s.slot_sib[o] = in_query + s.slot_leaf_len[o];
+        in_query = s.slot_sib[o] + 4 * s.slot_nsib[o];
+    }
+    unsigned lg_cur = s.lgN;
+    for (unsigned r = 0; r < p.num_fri_rounds; r++) {             // (glfri::check: the reductions stay above the cap)
+        const uint32_t slot = in.num_oracles + r;
+        lg_cur -= p.fri_arity_bits[r];
+        s.slot_leaf[slot] = in_query; s.slot_leaf_len[slot] = size_t(2) << p.fri_arity_bits[r]; s.slot_nsib[slot] = lg_cur - p.cap_height;
+        s.slot_sib[slot] = in_query + s.slot_leaf_len[slot];
+        in_query = s.slot_sib[slot] + 4 * s.slot_nsib[slot];
+    }
+    s.query_stride = in_query;
+    s.o_fcaps = 0;
+    s.o_query0 = (size_t)p.num_fri_rounds * 4 * s.ncap;
+    s.o_final = s.o_query0 + in_query * p.num_query_rounds;
+    s.t_words = s.o_final + 2 * s.final_len;
+    for (uint32_t b = 0; b < in.num_batches; b++) s.first[b + 1] = s.first[b] + in.batch_len[b];
+    s.src.resize(s.first[in.num_batches]);
+    for (size_t j = 0; j < s.src.size(); j++) s.src[j] = (uint32_t)(s.slot_leaf[in.polys[2 * j]] + in.polys[2 * j + 1]);
+    return GL_OK;
+}
+
+int glopen::host_stage(const gl_fri_params& p, const gl_fri_instance& in, const Shape& s, const uint64_t (*points)[2], const uint64_t* caps,
+                       const uint64_t* openings, gl_challenger* challenger, const uint8_t* proof_bytes, size_t num_bytes, std::vector<gl_t>& T, Challenges& ch,
+                       uint32_t* check) {
+    if (check) *check = GL_CHECK_ACCEPTED;
+    GL_REQUIRE(points, GL_ERR_ARG, "gl_verify_openings: null argument");
+    GL_TRY(glfri::check_points(p, in.num_batches, points));
+    GL_REQUIRE(caps && openings && challenger && proof_bytes, GL_ERR_ARG, "gl_verify_openings: null argument");
     GL_REQUIRE(challenger->ch.hasher == p.hasher, GL_ERR_ARG, "gl_verify_openings: the challenger runs under another hasher than the params'");
     const uint32_t hasher = p.hasher, no = in.num_oracles, B = in.num_batches, nq = p.num_query_rounds;
-    const unsigned lgN = p.degree_bits + p.rate_bits;
-    const size_t N = size_t(1) << lgN, ncap = size_t(1) << p.cap_height;
-    size_t final_len = size_t(1) << p.degree_bits;
-    for (unsigned r = 0; r < p.num_fri_rounds; r++) final_len >>= p.fri_arity_bits[r];
+    const unsigned lgN = s.lgN;
+    const size_t N = size_t(1) << lgN, ncap = s.ncap, final_len = s.final_len;
     if (!glhost::hashes_well_formed(hasher, caps, no * ncap)) return reject(GL_CHECK_VERIFIER_DATA, check);
 
     // ---- decode: words canonical (read_field takes a word >= p mod p), 25-byte hashes in four-word slots ----
     Cursor cur(proof_bytes, num_bytes);
-    std::vector<gl_t> T;
+    T.clear();
     T.reserve(num_bytes / 8 + 8);
     auto words = [&](size_t k) { size_t at = T.size(); for (size_t i = 0; i < k && cur.ok; i++) T.push_back(gl_canon(cur.u64())); return at; };
     auto hashes = [&](size_t k) {
@@ -626,22 +662,17 @@ extern "C" int gl_verify_openings(const gl_fri_params* params, const gl_fri_inst
         for (size_t i = 0; i < k && cur.ok; i++) { for (int w = 0; w < 3; w++) T.push_back(cur.u64()); T.push_back(cur.u8()); }
         return at;
     };
-    struct Query { size_t leaf[GL_MAX_FRI_ORACLES], sib[GL_MAX_FRI_ORACLES], step_leaf[8], step_sib[8]; };
-    std::vector<Query> queries(nq);
-    size_t leaf_len[GL_MAX_FRI_ORACLES];
-    for (uint32_t o = 0; o < no; o++) leaf_len[o] = (size_t)in.oracle_num_polys[o] + glfri::salt_of(p, in, o);
     const size_t o_fcaps = hashes((size_t)p.num_fri_rounds * ncap);
     for (uint32_t q = 0; q < nq && cur.ok; q++) {
-        Query& Q = queries[q];
         unsigned init_nsib[GL_MAX_FRI_ORACLES];
         for (uint32_t o = 0; o < no; o++) {
-            Q.leaf[o] = words(leaf_len[o]);
-            init_nsib[o] = cur.u8(); Q.sib[o] = hashes(init_nsib[o]);
+            (void)words(s.slot_leaf_len[o]);
+            init_nsib[o] = cur.u8(); (void)hashes(init_nsib[o]);
         }
         unsigned lg_cur = lgN;
         for (unsigned r = 0; r < p.num_fri_rounds; r++) {
-            Q.step_leaf[r] = words(size_t(2) << p.fri_arity_bits[r]);
-            const unsigned nsib = cur.u8(); Q.step_sib[r] = hashes(nsib);
+            (void)words(size_t(2) << p.fri_arity_bits[r]);
+            const unsigned nsib = cur.u8(); (void)hashes(nsib);
             lg_cur -= p.fri_arity_bits[r];
             if (cur.ok && nsib + p.cap_height != lg_cur) return reject(GL_CHECK_STEP_PATH_LENGTH, check);
         }
@@ -652,69 +683,88 @@ extern "C" int gl_verify_openings(const gl_fri_params* params, const gl_fri_inst
     const gl_t pow_witness = gl_canon(cur.u64());
     if (!cur.ok) return reject(GL_CHECK_TRUNCATED, check);
     if (cur.pos != num_bytes) return reject(GL_CHECK_LENGTH, check);
-    auto ext_at = [&](size_t off, size_t i) { return gl2_make(T[off + 2 * i], T[off + 2 * i + 1]); };
+    // every path has the length the params give it, so the table lies where the shape says (what the queries index by)
+    GL_REQUIRE(T.size() == s.t_words && o_fcaps == s.o_fcaps && o_final == s.o_final, GL_ERR_INTERNAL,
+               "gl_verify_openings: the decoded proof does not lie where its shape puts it");
 
     // ---- challenges (fri/challenges.rs:24-64) ----
     glhost::HostChallenger& tr = challenger->ch;
     const E alpha = tr.challenge_ext();
-    E betas[8];
-    for (unsigned r = 0; r < p.num_fri_rounds; r++) { tr.observe_hashes(hasher, &T[o_fcaps + (size_t)r * 4 * ncap], ncap); betas[r] = tr.challenge_ext(); }
+    ch.alpha = alpha;
+    for (unsigned r = 0; r < p.num_fri_rounds; r++) { tr.observe_hashes(hasher, &T[o_fcaps + (size_t)r * 4 * ncap], ncap); ch.betas[r] = tr.challenge_ext(); }
+    for (unsigned r = p.num_fri_rounds; r < MAX_FRI_ROUNDS; r++) ch.betas[r] = e_of(0);
     tr.observe_many(&T[o_final], 2 * final_len);
     tr.observe(pow_witness);
     const gl_t pow_response = tr.challenge();
-    std::vector<size_t> x_index(nq);
-    for (auto& x : x_index) x = tr.challenge() % (uint64_t)N;
+    ch.x_index.resize(nq);
+    for (auto& x : ch.x_index) x = tr.challenge() % (uint64_t)N;
     if (pow_response != 0 && (unsigned)__builtin_clzll(pow_response) < p.proof_of_work_bits) return reject(GL_CHECK_POW, check);
 
     // PrecomputedReducedOpenings (fri/verifier.rs:243-260): per batch Horner in alpha over its opened values; alpha^len of each batch
-    E red[GL_MAX_FRI_BATCHES], alpha_len[GL_MAX_FRI_BATCHES], point[GL_MAX_FRI_BATCHES];
-    size_t first[GL_MAX_FRI_BATCHES + 1] = {0};
-    for (uint32_t b = 0; b < B; b++) {
-        first[b + 1] = first[b] + in.batch_len[b];
+    for (uint32_t b = 0; b < GL_MAX_FRI_BATCHES; b++) {
         E acc = e_of(0), pw = e_of(1);
-        for (size_t j = first[b + 1]; j-- > first[b];) {
-            acc = e_add(e_mul(acc, alpha), gl2_make(gl_canon(openings[2 * j]), gl_canon(openings[2 * j + 1])));
-            pw = e_mul(pw, alpha);
-        }
-        red[b] = acc; alpha_len[b] = pw; point[b] = glfri::point_of(in, b);
+        if (b < B)
+            for (size_t j = s.first[b + 1]; j-- > s.first[b];) {
+                acc = e_add(e_mul(acc, alpha), gl2_make(gl_canon(openings[2 * j]), gl_canon(openings[2 * j + 1])));
+                pw = e_mul(pw, alpha);
+            }
+        ch.red[b] = acc; ch.alpha_len[b] = pw;
+        ch.point[b] = b < B ? gl2_make(gl_canon(points[b][0]), gl_canon(points[b][1])) : e_of(0);
     }
+    return GL_OK;
+}
 
-    // ---- the queries (fri/verifier.rs:163-241) ----
+extern "C" int gl_verify_openings(const gl_fri_params* params, const gl_fri_instance* instance, const uint64_t* caps, const uint64_t* openings,
+                                  gl_challenger* challenger, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check) try {
+    if (check) *check = GL_CHECK_ACCEPTED;
+    glopen::Shape s;
+    GL_TRY(glopen::shape_of(params, instance, s));
+    const gl_fri_params& p = *params; const gl_fri_instance& in = *instance;
+    std::vector<gl_t> T;
+    glopen::Challenges ch;
+    GL_TRY(glopen::host_stage(p, in, s, in.points, caps, openings, challenger, proof_bytes, num_bytes, T, ch, check));
+    auto ext_at = [&](size_t off, size_t i) { return gl2_make(T[off + 2 * i], T[off + 2 * i + 1]); };
+    const uint32_t hasher = p.hasher, no = in.num_oracles, B = in.num_batches, nq = p.num_query_rounds;
+    const unsigned lgN = s.lgN;
+    const size_t ncap = s.ncap;
+    const E alpha = ch.alpha;
+
+    // ---- the queries (fri/verifier.rs:163-241); k_verify_paths_any and k_verify_openings_queries are this loop on the device ----
     const gl_t wN = glhost::root_of_unity(lgN);
     for (uint32_t q = 0; q < nq; q++) {
-        const Query& Q = queries[q];
-        size_t x = x_index[q];
+        size_t x = ch.x_index[q];
         for (uint32_t o = 0; o < no; o++)
-            if (!path_opens_to_cap(hasher, &T[Q.leaf[o]], leaf_len[o], x, &T[Q.sib[o]], lgN - p.cap_height, caps + (size_t)o * 4 * ncap, ncap))
+            if (!path_opens_to_cap(hasher, &T[s.leaf_at(q, o)], s.slot_leaf_len[o], x, &T[s.sib_at(q, o)], s.slot_nsib[o], caps + (size_t)o * 4 * ncap, ncap))
                 return reject(GL_CHECK_INITIAL_MERKLE, check);
         size_t rev = 0;
         for (unsigned i = 0; i < lgN; i++) rev |= ((x >> i) & 1) << (lgN - 1 - i);
         gl_t subgroup_x = gl_canon(gl_mul(GL_MULT_GENERATOR, gl_exp(wN, rev)));
         // fri_combine_initial (fri/verifier.rs:122-161): a polynomial's index is below its oracle's column count, so only the unsalted
         // prefix of a leaf is read (unsalted_eval)
+        const gl_t* Q = &T[s.o_query0 + q * s.query_stride];
         const E sx = e_of(subgroup_x);
         E eval = e_of(0);
         for (uint32_t b = 0; b < B; b++) {
             E h = e_of(0);
-            for (size_t j = first[b + 1]; j-- > first[b];) h = e_add(e_mul(h, alpha), e_of(T[Q.leaf[in.polys[2 * j]] + in.polys[2 * j + 1]]));
-            eval = e_add(e_mul(eval, alpha_len[b]), e_mul(e_sub(h, red[b]), gl2_inv(e_sub(sx, point[b]))));
+            for (size_t j = s.first[b + 1]; j-- > s.first[b];) h = e_add(e_mul(h, alpha), e_of(Q[s.src[j]]));
+            eval = e_add(e_mul(eval, ch.alpha_len[b]), e_mul(e_sub(h, ch.red[b]), gl2_inv(e_sub(sx, ch.point[b]))));
         }
-        unsigned lg_cur = lgN;
         for (unsigned r = 0; r < p.num_fri_rounds; r++) {
             const unsigned ab = p.fri_arity_bits[r];
-            const size_t arity = size_t(1) << ab, coset = x >> ab, within = x & (arity - 1), leaf = Q.step_leaf[r];
-            lg_cur -= ab;
+            const uint32_t slot = no + r;
+            const size_t arity = size_t(1) << ab, coset = x >> ab, within = x & (arity - 1), leaf = s.leaf_at(q, slot);
             if (!e_eq(ext_at(leaf, within), eval)) return reject(GL_CHECK_FRI_CONSISTENCY, check);
-            eval = compute_evaluation(subgroup_x, within, ab, &T[leaf], betas[r]);
-            if (!path_opens_to_cap(hasher, &T[leaf], 2 * arity, coset, &T[Q.step_sib[r]], lg_cur - p.cap_height, &T[o_fcaps + (size_t)r * 4 * ncap], ncap))
+            eval = compute_evaluation(subgroup_x, within, ab, &T[leaf], ch.betas[r]);
+            if (!path_opens_to_cap(hasher, &T[leaf], 2 * arity, coset, &T[s.sib_at(q, slot)], s.slot_nsib[slot], &T[s.o_fcaps + (size_t)r * 4 * ncap], ncap))
                 return reject(GL_CHECK_STEP_MERKLE, check);
             for (unsigned i = 0; i < ab; i++) subgroup_x = gl_sqr(subgroup_x);
             x = coset;
         }
         E fin = e_of(0);
         const E sxf = e_of(gl_canon(subgroup_x));
-        for (size_t i = final_len; i-- > 0;) fin = e_add(e_mul(fin, sxf), ext_at(o_final, i));
+        for (size_t i = s.final_len; i-- > 0;) fin = e_add(e_mul(fin, sxf), ext_at(s.o_final, i));
         if (!e_eq(fin, eval)) return reject(GL_CHECK_FINAL_POLY, check);
     }
     return GL_OK;
 } catch (...) { return gl_caught(); }
+
