@@ -772,6 +772,29 @@ int gl_stark_set_dag_create(gl_ctx* ctx, const gl_stark_set_desc* desc, const gl
 int gl_stark_set_dag_verify(const gl_stark_set_desc* desc, const gl_stark_dag* const* dags, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check,
                             uint32_t* table);
 
+/* ---- STARK lookups: the permuted columns of a range check ----------------------------------------------
+ * evm/src/lookup.rs: a table is range-checked with the Halo2-style lookup argument.  Its two constraints (eval_lookups, lookup.rs:13-34)
+ * are ordinary terms of a gl_stark_desc and its two permutations ordinary pairs; what is here are its COLUMNS, permuted_cols
+ * (lookup.rs:65-127), the one generic trace-generation function of the reference: both columns canonicalised and sorted ascending as
+ * unsigned 64-bit integers (:79-88); then the merge of :93-117, which gives input position i the table value equal to it where one is
+ * left, else the top of a LIFO stack of the table values passed over, else defers it; the deferred positions and the positions the loop
+ * did not reach take the stack's values from the bottom followed by the table values the loop did not reach (:119-124).
+ * ArithmeticStark::generate_range_checks calls it once per shared column against one RANGE_COUNTER column (arithmetic_stark.rs:97-118),
+ * MemoryStark once (memory_stark.rs:148). */
+typedef struct gl_stark_lookup { uint32_t col_input, col_table, col_permuted_input, col_permuted_table; } gl_stark_lookup;
+/* permuted_cols for `count` lookups of one device trace d_cols[num_columns][n], in place: for every lookup column col_permuted_input
+ * becomes the sorted canonical input column and col_permuted_table exactly the permuted_table of the reference's loop.  Input and
+ * table columns are left untouched and may hold non-canonical words; outputs are canonical.  Defined for any input: a value that is not
+ * in the table is no error here (the reference does not assert; such a trace fails the constraints).  Two lookups may share an input
+ * or a table column -- a shared column is sorted once (a shared table once per call, a shared input once per chunk of 2^23 / n lookups:
+ * DESIGN.md section 19) -- but not an output.  Stream-ordered on the context; temporaries come from its pool.  No per-lookup serial pass: sorts, binary searches, two prefix sums and a stable sort by stack level.
+ * GL_ERR_ARG for: a null pointer; count == 0 or count > 1024; n no power of two, n < 2 or n > 2^24; a column index >= num_columns; an
+ * output column that is also an input, table or output column of any lookup of the call. */
+int gl_stark_lookup_columns(gl_ctx* ctx, uint64_t* d_cols, uint32_t num_columns, size_t n, const gl_stark_lookup* lookups, uint32_t count);
+/* The same function on host arrays, any n >= 1: the reference's sequential algorithm, statement by statement (lookup.rs:65-127).  No
+ * GPU.  The outputs may not overlap the inputs. */
+int gl_permuted_cols_host(const uint64_t* h_inputs, const uint64_t* h_table, size_t n, uint64_t* h_permuted_inputs, uint64_t* h_permuted_table);
+
 /* ---- prove() ---------------------------------------------------------------------------------------*/
 /* plonk::prover::prove (plonky2/src/plonk/prover.rs:102-329) from step 4 on, i.e. given the FULL witness matrix
  * `MatrixWitness.wire_values` (iop/witness.rs:256-258) h_wires[num_wires][n] and the public inputs.  Every

@@ -20,4 +20,5 @@ from .api import (  # noqa: F401
     StarkDagBuilder, StarkDagDesc, StarkDagExpr, stark_dag_verify,
     CrossTableLookup, CtlColumn, StarkSet, StarkSetDesc, TableWithColumns, stark_set_verify,
     OpeningsBatchVerifier, StarkBatchVerifier,
+    lookup_constraints, permuted_cols, permuted_cols_host,
 )

@@ -217,6 +217,9 @@ SIGNATURES = {
     "gl_stark_set_prove": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(c_sz)]),
     "gl_stark_set_prove_device": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.POINTER(c_sz)]),
     "gl_stark_set_verify": (c_int, [c_vp, c_vp, c_sz, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
+    # STARK lookups: permuted_cols (ctx, d_cols, num_columns, n, gl_stark_lookup*, count) and its host form
+    "gl_stark_lookup_columns": (c_int, [c_vp, c_vp, c_u32, c_sz, c_vp, c_u32]),
+    "gl_permuted_cols_host": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
     # batch verification of FRI openings of any instance, and of STARK proofs on top of it (device Merkle paths and FRI queries)
     "gl_openings_batch_verifier_new": (c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, ctypes.POINTER(c_vp)]),
     "gl_openings_batch_verifier_verify": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),

@@ -130,6 +130,12 @@ class Context(_Owned):
         check(lib.gl_ctx_timing_report(self.handle, buf, len(buf)))
         return json.loads(buf.value.decode())
 
+    def lookup_columns(self, d_cols_ptr, num_columns, n, lookups):
+        """gl_stark_lookup_columns: permuted_cols (evm/src/lookup.rs:65-127) for every lookup of the device trace d_cols[num_columns][n],
+        in place.  lookups = [(col_input, col_table, col_permuted_input, col_permuted_table), ...]."""
+        flat = np.ascontiguousarray([[int(c) for c in lk] for lk in lookups], dtype=np.uint32).reshape(-1, 4) if len(lookups) else np.zeros((0, 4), dtype=np.uint32)
+        check(lib.gl_stark_lookup_columns(self.handle, d_cols_ptr, int(num_columns), int(n), _p(flat) if flat.size else None, flat.shape[0]))
+
 
 _default = None
 
@@ -1612,6 +1618,46 @@ def fibonacci_stark(num_rows):
         rows[num_rows - 1][3] = 0                      # so that columns 2 and 3 are permutations of one another
         return np.array(rows, dtype=np.uint64).T.copy()
     return desc, generate_trace
+
+
+# ------------------------------------------------------------------------------------- STARK lookups (evm/src/lookup.rs)
+def lookup_constraints(col_permuted_input, col_permuted_table):
+    """eval_lookups (lookup.rs:13-34) as two constraints of a StarkDesc, in the order it yields them:
+    constraint((next_in - local_in)(next_in - next_table)), expanded to four terms, and constraint_last_row(next_in - next_table)."""
+    L, N, m1 = _lib.GL_STARK_LOCAL, _lib.GL_STARK_NEXT, GOLDILOCKS_ORDER - 1
+    i, t = col_permuted_input, col_permuted_table
+    return [
+        (_lib.GL_STARK_ALL, [(1, [(N, i), (N, i)]), (m1, [(N, i), (N, t)]), (m1, [(L, i), (N, i)]), (1, [(L, i), (N, t)])]),
+        (_lib.GL_STARK_LAST_ROW, [(1, [(N, i)]), (m1, [(N, t)])]),
+    ]
+
+
+def permuted_cols_host(inputs, table):
+    """permuted_cols (lookup.rs:65-127) on the host, the reference's sequential algorithm -> (permuted_inputs, permuted_table)."""
+    a, t = _u64(inputs).ravel(), _u64(table).ravel()
+    if a.size != t.size or a.size == 0:
+        raise ValueError("inputs and table are two columns of one length >= 1")
+    pin, ptab = np.empty(a.size, dtype=np.uint64), np.empty(a.size, dtype=np.uint64)
+    check(lib.gl_permuted_cols_host(_p(a), _p(t), a.size, _p(pin), _p(ptab)))
+    return pin, ptab
+
+
+def permuted_cols(inputs, table, ctx=None):
+    """permuted_cols (lookup.rs:65-127) through the device entry: a four-column trace whose columns 0 and 1 are uploaded and whose
+    columns 2 and 3 come back -> (permuted_inputs, permuted_table)."""
+    ctx = _ctx(ctx)
+    a, t = _u64(inputs).ravel(), _u64(table).ravel()
+    if a.size != t.size:
+        raise ValueError("inputs and table are two columns of one length")
+    n = a.size
+    d = DeviceBuffer(ctx, max(1, 4 * n * 8)).upload(np.stack([a, t]))
+    try:
+        ctx.lookup_columns(d.ptr, 4, n, [(0, 1, 2, 3)])
+        out = np.empty((2, n), dtype=np.uint64)
+        check(lib.gl_copy_d2h(ctx.handle, _p(out), d.ptr + 2 * n * 8, out.nbytes))
+    finally:
+        d.free()
+    return out[0], out[1]
 
 
 def pow_grind(sponge_state, input_buffer, min_leading_zeros, ctx=None, hasher="poseidon"):

@@ -159,3 +159,42 @@ extern "C" int gl_random_elements_host(const uint8_t seed[32], uint32_t stream, 
     for (uint64_t i = 0; i < count; i++) h_out[i] = gl_random_element(key, stream, first + i);
     return GL_OK;
 } catch (...) { return gl_caught(); }
+
+// ---- lookups on the host ----------------------------------------------------------------------------------------------------
+// permuted_cols (evm/src/lookup.rs:65-127), the reference's sequential algorithm statement by statement; gl_stark_lookup_columns
+// (stark_lookup.hip) is the device form
+extern "C" int gl_permuted_cols_host(const uint64_t* h_inputs, const uint64_t* h_table, size_t n, uint64_t* h_permuted_inputs, uint64_t* h_permuted_table) try {
+    GL_REQUIRE(h_inputs && h_table && h_permuted_inputs && h_permuted_table && n >= 1, GL_ERR_ARG, "gl_permuted_cols_host: null argument or n == 0");
+    std::vector<uint64_t> sorted_inputs(n), sorted_table(n);                           // :79-88  to_canonical, sorted by to_noncanonical_u64
+    for (size_t k = 0; k < n; k++) { sorted_inputs[k] = gl_canon(h_inputs[k]); sorted_table[k] = gl_canon(h_table[k]); }
+    std::sort(sorted_inputs.begin(), sorted_inputs.end());
+    std::sort(sorted_table.begin(), sorted_table.end());
+    std::vector<size_t> unused_table_inds;                                             // :90-92
+    std::vector<uint64_t> unused_table_vals;
+    unused_table_inds.reserve(n);
+    unused_table_vals.reserve(n);
+    std::vector<uint64_t> permuted_table(n, 0);
+    size_t i = 0, j = 0;
+    while (j < n && i < n) {                                                           // :95-117
+        const uint64_t input_val = sorted_inputs[i], table_val = sorted_table[j];
+        if (input_val > table_val) {
+            unused_table_vals.push_back(sorted_table[j]);
+            j++;
+        } else if (input_val < table_val) {
+            if (!unused_table_vals.empty()) { permuted_table[i] = unused_table_vals.back(); unused_table_vals.pop_back(); }
+            else unused_table_inds.push_back(i);
+            i++;
+        } else {
+            permuted_table[i] = sorted_table[j];
+            i++;
+            j++;
+        }
+    }
+    for (; j < n; j++) unused_table_vals.push_back(sorted_table[j]);                   // :119-120
+    for (; i < n; i++) unused_table_inds.push_back(i);
+    GL_REQUIRE(unused_table_inds.size() == unused_table_vals.size(), GL_ERR_INTERNAL, "gl_permuted_cols_host: zip_eq of unequal lengths");      // :122
+    for (size_t k = 0; k < unused_table_inds.size(); k++) permuted_table[unused_table_inds[k]] = unused_table_vals[k];
+    memcpy(h_permuted_inputs, sorted_inputs.data(), n * sizeof(uint64_t));
+    memcpy(h_permuted_table, permuted_table.data(), n * sizeof(uint64_t));
+    return GL_OK;
+} catch (...) { return gl_caught(); }
