@@ -3,6 +3,7 @@
 #pragma once
 #include "context.hpp"
 #include "host_circuit.hpp"
+#include "proof.hpp"
 
 // C handle of the Challenger for callers of the phase API that have no transcript of their own (C / C++ / Python)
 struct gl_challenger { glhost::HostChallenger ch; };
@@ -14,6 +15,18 @@ enum { MAX_LISTED_POLYS = 65536, SALT_SIZE = 4 };
 inline size_t total_polys(const gl_fri_instance& in) { size_t t = 0; for (uint32_t b = 0; b < in.num_batches; b++) t += in.batch_len[b]; return t; }
 inline uint32_t salt_of(const gl_fri_params& p, const gl_fri_instance& in, uint32_t o) { return p.hiding && in.oracle_blinding[o] ? SALT_SIZE : 0; }
 inline gl2_t point_of(const gl_fri_instance& in, uint32_t b) { return gl2_make(gl_canon(in.points[b][0]), gl_canon(in.points[b][1])); }
+
+// the size of gl_prove_openings' FriProof (write_fri_proof, util/serialization/mod.rs:1568-1582): the params and the instance fix it
+inline size_t proof_bytes(const gl_fri_params& p, const gl_fri_instance& in) {
+    const size_t hb = hash_wire_bytes(p.hasher), lgN = p.degree_bits + p.rate_bits;
+    size_t per_query = 0, lg = lgN, final_len = size_t(1) << p.degree_bits;
+    for (uint32_t o = 0; o < in.num_oracles; o++) per_query += 8 * (size_t)(in.oracle_num_polys[o] + salt_of(p, in, o)) + 1 + hb * (lgN - p.cap_height);
+    for (unsigned r = 0; r < p.num_fri_rounds; r++) {
+        lg -= p.fri_arity_bits[r]; final_len >>= p.fri_arity_bits[r];
+        per_query += (size_t(16) << p.fri_arity_bits[r]) + 1 + hb * (lg - p.cap_height);
+    }
+    return (size_t)p.num_fri_rounds * (hb << p.cap_height) + (size_t)p.num_query_rounds * per_query + 16 * final_len + 8;
+}
 
 // a point 7 w with w^N = 1 is an LDE point: the quotient by (X - point) has a pole there (the reference panics dividing by zero)
 inline int check_points(const gl_fri_params& p, uint32_t num_batches, const uint64_t (*points)[2]) {

@@ -974,14 +974,7 @@ extern "C" int gl_prove_openings(gl_ctx* ctx, const gl_fri_params* params, const
     GL_TRY(check_instance_batches(ctx, p, in, batches));
     GL_REQUIRE(challenger->ch.hasher == p.hasher, GL_ERR_ARG, "gl_prove_openings: the challenger runs under another hasher than the params'");
     const uint32_t lgN = p.degree_bits + p.rate_bits, ncap = 4u << p.cap_height;
-    const size_t N = size_t(1) << lgN, hash_bytes = p.hasher == GL_HASHER_KECCAK ? 25 : 32;
-    size_t per_query = 0, final_len = size_t(1) << p.degree_bits;
-    for (uint32_t o = 0; o < in.num_oracles; o++) per_query += 8 * (size_t)(in.oracle_num_polys[o] + glfri::salt_of(p, in, o)) + 1 + (lgN - p.cap_height) * hash_bytes;
-    for (uint32_t r = 0, lg = lgN; r < p.num_fri_rounds; r++) {
-        lg -= p.fri_arity_bits[r]; final_len >>= p.fri_arity_bits[r];
-        per_query += 8 * (size_t(2) << p.fri_arity_bits[r]) + 1 + (lg - p.cap_height) * hash_bytes;
-    }
-    const size_t size = (size_t)p.num_fri_rounds * (ncap / 4) * hash_bytes + per_query * p.num_query_rounds + 16 * final_len + 8;
+    const size_t N = size_t(1) << lgN, size = glfri::proof_bytes(p, in);
     *num_bytes = size;
     if (!h_out) return GL_OK;                          // the size alone: nothing ran, the challenger is where it was
     GL_REQUIRE(cap_bytes >= size, GL_ERR_ARG, "gl_prove_openings: output too small");

@@ -11,40 +11,36 @@
 #include <algorithm>
 #include <cstring>
 #include <memory>
+#include <string>
 #include <vector>
 
 using namespace glstark;
 
-namespace {
-
-
-// the FriInstanceInfo of stark.rs:88-137 at the points zeta, g zeta: oracles trace, (Z), quotient; batches [trace, Z, quotient] at zeta
-// and [trace, Z] at g zeta
-struct StarkInstance {
-    gl_fri_instance inst;
-    std::vector<uint32_t> polys;
-    StarkInstance(const StarkInstance&) = delete;
-    StarkInstance(uint32_t num_columns, uint32_t num_challenges, const StarkShape& s, gl2_t zeta, gl2_t zeta_next) {
-        ::memset((void*)&inst, 0, sizeof inst);
-        uint32_t o = 0;
-        const uint32_t trace_o = o; inst.oracle_num_polys[o++] = num_columns;
-        const uint32_t zs_o = o; if (s.nz) inst.oracle_num_polys[o++] = s.nz;
-        const uint32_t quot_o = o; inst.oracle_num_polys[o++] = s.q * num_challenges;
-        inst.num_oracles = o;
-        inst.num_batches = 2;
-        inst.points[0][0] = zeta.a; inst.points[0][1] = zeta.b; inst.points[1][0] = zeta_next.a; inst.points[1][1] = zeta_next.b;
-        for (int b = 0; b < 2; b++) {
-            const size_t before = polys.size() / 2;
-            for (uint32_t c = 0; c < num_columns; c++) { polys.push_back(trace_o); polys.push_back(c); }
-            for (uint32_t c = 0; c < s.nz; c++) { polys.push_back(zs_o); polys.push_back(c); }
-            if (b == 0) for (uint32_t c = 0; c < s.q * num_challenges; c++) { polys.push_back(quot_o); polys.push_back(c); }
-            inst.batch_len[b] = (uint32_t)(polys.size() / 2 - before);
-        }
-        inst.polys = polys.data();
+glstark::StarkInstance::StarkInstance(uint32_t num_columns, uint32_t num_challenges, const StarkShape& s, uint32_t nctl, uint32_t degree_bits, gl2_t zeta) {
+    ::memset((void*)&inst, 0, sizeof inst);
+    const uint32_t nzs = s.nz + nctl, nq = s.q * num_challenges;
+    uint32_t o = 0;
+    const uint32_t trace_o = o; inst.oracle_num_polys[o++] = num_columns;
+    const uint32_t zs_o = o; if (nzs) inst.oracle_num_polys[o++] = nzs;
+    const uint32_t quot_o = o; inst.oracle_num_polys[o++] = nq;
+    inst.num_oracles = o;
+    inst.num_batches = nctl ? 3 : 2;
+    const gl_t g = gl_host_root_of_unity(degree_bits);
+    const gl2_t zeta_next = gl2_canon(gl2_scalar(zeta, g));
+    inst.points[0][0] = zeta.a; inst.points[0][1] = zeta.b; inst.points[1][0] = zeta_next.a; inst.points[1][1] = zeta_next.b;
+    polys.reserve(2 * (2 * (size_t)num_columns + 2 * nzs + nq + nctl));
+    if (nctl) inst.points[2][0] = gl_canon(gl_inv(g));
+    for (int b = 0; b < 2; b++) {
+        const size_t before = polys.size() / 2;
+        for (uint32_t c = 0; c < num_columns; c++) { polys.push_back(trace_o); polys.push_back(c); }
+        for (uint32_t c = 0; c < nzs; c++) { polys.push_back(zs_o); polys.push_back(c); }
+        if (b == 0) for (uint32_t c = 0; c < nq; c++) { polys.push_back(quot_o); polys.push_back(c); }
+        inst.batch_len[b] = (uint32_t)(polys.size() / 2 - before);
     }
-};
-
-}  // namespace
+    for (uint32_t c = 0; c < nctl; c++) { polys.push_back(zs_o); polys.push_back(s.nz + c); }
+    inst.batch_len[2] = nctl;
+    inst.polys = polys.data();
+}
 
 int glstark::stark_check(const gl_stark_desc* desc, const gl_fri_params* params, StarkShape* shape, bool prover, const gl_stark_dag* dag, DagProgram* prog) {
     GL_REQUIRE(desc && params, GL_ERR_ARG, "gl_stark: null description / params");
@@ -95,7 +91,7 @@ int glstark::stark_check(const gl_stark_desc* desc, const gl_fri_params* params,
     }
     GL_REQUIRE(params->hiding == 0, GL_ERR_UNSUPPORTED, "gl_stark: hiding is not supported (StarkConfig::fri_params passes false)");
     // the gl_fri_params rules are gl_prove_openings' own, on the STARK's instance (an opening point off the base field passes its coset check)
-    const StarkInstance si(d.num_columns, d.num_challenges, s, gl2_make(0, 1), gl2_make(0, 1));
+    const StarkInstance si(d.num_columns, d.num_challenges, s, 0, params->degree_bits);
     GL_TRY(glfri::check(params, &si.inst, prover));
     GL_REQUIRE(s.qdb <= params->rate_bits, GL_ERR_UNSUPPORTED, "gl_stark: constraints of degree higher than the rate are not supported (prover.rs:222-225)");
     if (shape) *shape = s;
@@ -136,6 +132,7 @@ int glstark::stark_create(gl_ctx* ctx, const gl_stark_desc* desc, const gl_stark
     s->params = *params; s->s = sh;
     s->num_columns = d.num_columns; s->num_public_inputs = d.num_public_inputs; s->nc = d.num_challenges; s->num_constraints = d.num_constraints;
     s->n = size_t(1) << params->degree_bits; s->size = s->n << sh.qdb;
+    s->proof_bytes = table_proof_bytes(*params, d.num_columns, d.num_public_inputs, d.num_challenges, sh, 0);
     const uint32_t lgS = params->degree_bits + sh.qdb, nzh = 1u << sh.qdb;
     // per-degree_bits constants: g^-1, 1/n, Z_H and 1/Z_H on the coset (ZeroPolyOnCoset, field/src/zero_poly_coset.rs:19-36)
     s->last = gl_canon(gl_inv(gl_host_root_of_unity(params->degree_bits)));
@@ -269,23 +266,37 @@ int quotient_values(gl_ctx* ctx, const gl_stark* s, const gl_batch* trace, const
 
 }  // namespace
 
-// what the two quotient entries share: argument checks, the uploads, the kernel; d_q[num_challenges][size]
+// what the quotient entries share: argument checks, the uploads, the kernel and a set's CTL pass behind it; d_q[num_challenges][size]
 int glstark::quotient_phase(gl_ctx* ctx, const gl_stark* s, const gl_batch* trace, const gl_batch* zs, const uint64_t* challenges, const uint64_t* alphas,
-                   const uint64_t* public_inputs, DevBuf& d_q, uint32_t ctl_zs) {
+                   const uint64_t* public_inputs, DevBuf& d_q, const TableCtl* ctl) {
+    const uint32_t nz = s ? s->s.nz : 0, nctl = nctl_of(ctl);
     GL_TRY(check_stark_args(ctx, s));
     GL_REQUIRE(alphas && (public_inputs || !s->num_public_inputs), GL_ERR_ARG, "gl_stark quotient: null alphas / public inputs");
     GL_TRY(check_stark_batch(s, trace, s->num_columns, "gl_stark quotient: the trace batch does not match the description / params"));
-    GL_REQUIRE((s->s.nz != 0) == (zs != nullptr) && (s->s.nz == 0 || challenges), GL_ERR_ARG,
+    GL_REQUIRE((nz + nctl != 0) == (zs != nullptr) && (nz == 0 || challenges), GL_ERR_ARG,
                "gl_stark quotient: the Z batch and the challenge sets go with permutation pairs (null without)");
-    if (zs) GL_TRY(check_stark_batch(s, zs, s->s.nz + ctl_zs, "gl_stark quotient: the Z batch does not match the description / params"));   // a set's: CTL Zs follow
+    if (zs) GL_TRY(check_stark_batch(s, zs, nz + nctl, "gl_stark quotient: the Z batch does not match the description / params"));   // a set's: CTL Zs follow
     DevBuf d_ch(ctx), d_pub(ctx);
-    if (zs) GL_TRY(upload_challenges(ctx, s, challenges, d_ch));
+    if (nz) GL_TRY(upload_challenges(ctx, s, challenges, d_ch));
     std::vector<gl_t> pub(s->num_public_inputs + 1, 0);
     for (uint32_t i = 0; i < s->num_public_inputs; i++) pub[i] = gl_canon(public_inputs[i]);
     GL_TRY(d_pub.alloc(pub.size() * sizeof(gl_t)));
     GL_TRY(gl_copy_h2d(ctx, d_pub.p, pub.data(), pub.size() * sizeof(gl_t)));
     GL_TRY(d_q.alloc((size_t)s->nc * s->size * sizeof(gl_t)));
-    return quotient_values(ctx, s, trace, zs, d_ch.as<const gl_t>(), alphas, d_pub.as<const gl_t>(), d_q.as<gl_t>());
+    GL_TRY(quotient_values(ctx, s, trace, nz ? zs : nullptr, d_ch.as<const gl_t>(), alphas, d_pub.as<const gl_t>(), d_q.as<gl_t>()));
+    return nctl ? ctl_quotient_pass(ctx, *ctl, trace, zs, alphas, d_q) : GL_OK;
+}
+
+int glstark::zs_commit(gl_ctx* ctx, const gl_stark* s, const TableCtl* ctl, const uint64_t* d_trace_values, const uint64_t* challenges, gl_batch** zs) {
+    const uint32_t nz = s->s.nz, nctl = nctl_of(ctl);
+    DevBuf d_ch(ctx), d_z(ctx);
+    GL_TRY(d_z.alloc((size_t)(nz + nctl) * s->n * sizeof(gl_t)));
+    if (nz) {
+        GL_TRY(upload_challenges(ctx, s, challenges, d_ch));
+        GL_TRY(permutation_z_values(ctx, s, d_trace_values, d_ch.as<const gl_t>(), d_z.as<gl_t>()));
+    }
+    if (nctl) GL_TRY(ctl_z_values(ctx, *ctl, d_trace_values, d_z.as<gl_t>() + (size_t)nz * s->n));
+    return gl_batch_from_device_h(ctx, s->params.hasher, d_z.as<uint64_t>(), nz + nctl, s->n, s->params.rate_bits, s->params.cap_height, 1, zs);
 }
 
 extern "C" int gl_stark_permutation_zs(gl_ctx* ctx, const gl_stark* s, const uint64_t* d_trace_values, const uint64_t* challenges, gl_batch** zs) try {
@@ -294,11 +305,7 @@ extern "C" int gl_stark_permutation_zs(gl_ctx* ctx, const gl_stark* s, const uin
     GL_TRY(check_stark_args(ctx, s));
     GL_REQUIRE(d_trace_values && challenges, GL_ERR_ARG, "gl_stark_permutation_zs: null argument");
     GL_REQUIRE(s->s.nz, GL_ERR_ARG, "gl_stark_permutation_zs: the description has no permutation pairs");
-    DevBuf d_ch(ctx), d_z(ctx);
-    GL_TRY(upload_challenges(ctx, s, challenges, d_ch));
-    GL_TRY(d_z.alloc((size_t)s->s.nz * s->n * sizeof(gl_t)));
-    GL_TRY(permutation_z_values(ctx, s, d_trace_values, d_ch.as<const gl_t>(), d_z.as<gl_t>()));
-    return gl_batch_from_device_h(ctx, s->params.hasher, d_z.as<uint64_t>(), s->s.nz, s->n, s->params.rate_bits, s->params.cap_height, 1, zs);
+    return zs_commit(ctx, s, nullptr, d_trace_values, challenges, zs);
 } catch (...) { return gl_caught(); }
 
 extern "C" int gl_stark_quotient_values(gl_ctx* ctx, const gl_stark* s, const gl_batch* trace, const gl_batch* zs, const uint64_t* challenges,
@@ -343,91 +350,96 @@ extern "C" int gl_stark_quotient_polys(gl_ctx* ctx, const gl_stark* s, const gl_
 } catch (...) { return gl_caught(); }
 
 // ---- the whole prover and the verifier (starky/src/prover.rs:32-194, verifier.rs:21-145) -------------------------------------------
-namespace {
-
-// the size of gl_prove_openings' FriProof (write_fri_proof, util/serialization/mod.rs:1568-1582) on the STARK's instance
-size_t fri_proof_bytes(const gl_fri_params& p, uint32_t num_columns, uint32_t nc, const StarkShape& s) {
-    const size_t hb = hash_wire_bytes(p.hasher), lgN = p.degree_bits + p.rate_bits;
-    size_t per_query = 0, lg = lgN, total_arity = 0;
-    const uint32_t leaf[3] = {num_columns, s.nz, s.q * nc};
-    for (int o = 0; o < 3; o++) if (leaf[o]) per_query += 8 * (size_t)leaf[o] + 1 + hb * (lgN - p.cap_height);
-    for (unsigned r = 0; r < p.num_fri_rounds; r++) {
-        lg -= p.fri_arity_bits[r]; total_arity += p.fri_arity_bits[r];
-        per_query += (size_t(16) << p.fri_arity_bits[r]) + 1 + hb * (lg - p.cap_height);
-    }
-    return (size_t)p.num_fri_rounds * (hb << p.cap_height) + (size_t)p.num_query_rounds * per_query + 16 * ((size_t(1) << p.degree_bits) >> total_arity) + 8;
+size_t glstark::table_proof_bytes(const gl_fri_params& p, uint32_t num_columns, uint32_t num_public_inputs, uint32_t nc, const StarkShape& s, uint32_t nctl) {
+    const StarkInstance si(num_columns, nc, s, nctl, p.degree_bits);
+    return si.inst.num_oracles * (hash_wire_bytes(p.hasher) << p.cap_height) + 16 * (2 * (size_t)num_columns + 2 * (size_t)(s.nz + nctl) + (size_t)s.q * nc) +
+           8 * (size_t)nctl + glfri::proof_bytes(p, si.inst) + 8 * (size_t)num_public_inputs;
 }
-size_t stark_proof_bytes(const gl_fri_params& p, uint32_t num_columns, uint32_t num_public_inputs, uint32_t nc, const StarkShape& s) {
-    return (s.nz ? 3 : 2) * (hash_wire_bytes(p.hasher) << p.cap_height) + 16 * (2 * (size_t)num_columns + 2 * (size_t)s.nz + (size_t)s.q * nc) +
-           fri_proof_bytes(p, num_columns, nc, s) + 8 * (size_t)num_public_inputs;
-}
-}  // namespace
 gl2_t glstark::ext_pow2(gl2_t x, unsigned k) { for (unsigned i = 0; i < k; i++) x = gl2_mul(x, x); return gl2_canon(x); }
+
+int glstark::prove_table(gl_ctx* ctx, const gl_stark* s, const TableCtl* ctl, const uint64_t* d_cols, const gl_batch* trace, const uint64_t* h_public_inputs,
+                         gl_challenger& ch, std::vector<uint8_t>& o, const char* who) {
+    const gl_fri_params& p = s->params;
+    const size_t ncap = size_t(1) << p.cap_height, start = o.size() - hash_wire_bytes(p.hasher) * ncap;      // where the trace cap stands
+    const uint32_t nz = s->s.nz, nctl = nctl_of(ctl), nzs = nz + nctl, nq = s->s.q * s->nc, ncols = s->num_columns;
+    auto fail = [&](int code, const char* what) { return gl_fail(code, (std::string(who) + what).c_str(), __FILE__, __LINE__); };
+    std::vector<gl_t> cap(4 * ncap);
+    BatchHolder zs, quot;
+    // permutation challenge sets, the Z polynomials (a set's CTL Zs behind them), their commitment (prover.rs:76-111)
+    std::vector<gl_t> sets;
+    if (nz) for (uint32_t i = 0; i < 2 * s->s.q * s->nc; i++) sets.push_back(ch.ch.challenge());          // set after set: (beta, gamma) per challenge
+    if (nzs) {
+        GL_TRY(zs_commit(ctx, s, ctl, d_cols, nz ? sets.data() : nullptr, &zs.b));
+        GL_TRY(gl_batch_cap(zs.b, cap.data()));
+        put_hashes(o, p.hasher, cap.data(), ncap);
+        ch.ch.observe_hashes(p.hasher, cap.data(), ncap);
+    }
+    // alphas, the quotient, its commitment (prover.rs:113-146)
+    gl_t alphas[GL_STARK_MAX_CHALLENGES];
+    for (uint32_t j = 0; j < s->nc; j++) alphas[j] = ch.ch.challenge();
+    {
+        DevBuf d_q(ctx);
+        GL_TRY(quotient_phase(ctx, s, trace, zs.b, nz ? sets.data() : nullptr, alphas, h_public_inputs, d_q, ctl));
+        GL_TRY(quotient_commit(ctx, s, d_q, &quot.b));
+    }
+    GL_TRY(gl_batch_cap(quot.b, cap.data()));
+    put_hashes(o, p.hasher, cap.data(), ncap);
+    ch.ch.observe_hashes(p.hasher, cap.data(), ncap);
+    // zeta off the subgroup (prover.rs:148-157); the instance holds zeta, g zeta and g^-1
+    const gl2_t zeta = ch.ch.challenge_ext();
+    const gl2_t zn = ext_pow2(zeta, p.degree_bits);
+    if (zn.a == 1 && zn.b == 0) return fail(GL_ERR_ZETA_IN_SUBGROUP, ": opening point is in the subgroup");
+    const StarkInstance si(ncols, s->nc, s->s, nctl, p.degree_bits, zeta);
+    const uint64_t *zw = si.inst.points[0], *znw = si.inst.points[1], *lw = si.inst.points[2];
+    // StarkOpeningSet::new (proof.rs:138-159, evm/src/proof.rs:224-259)
+    std::vector<gl_t> local(2 * ncols), next(2 * ncols), zl(2 * nzs), zn_(2 * nzs), last(2 * nctl), ql(2 * nq);
+    GL_TRY(gl_open_at(ctx, trace, zw, 0, ncols, local.data()));
+    GL_TRY(gl_open_at(ctx, trace, znw, 0, ncols, next.data()));
+    if (nzs) { GL_TRY(gl_open_at(ctx, zs.b, zw, 0, nzs, zl.data())); GL_TRY(gl_open_at(ctx, zs.b, znw, 0, nzs, zn_.data())); }
+    if (nctl) GL_TRY(gl_open_at(ctx, zs.b, lw, nz, nctl, last.data()));
+    GL_TRY(gl_open_at(ctx, quot.b, zw, 0, nq, ql.data()));
+    for (uint32_t k = 0; k < nctl; k++) if (gl_canon(last[2 * k + 1]) != 0) return fail(GL_ERR_INTERNAL, ": a base-field opening left the base field");
+    put_words(o, local.data(), local.size()); put_words(o, next.data(), next.size());
+    put_words(o, zl.data(), zl.size()); put_words(o, zn_.data(), zn_.size());
+    for (uint32_t k = 0; k < nctl; k++) put_u64(o, gl_canon(last[2 * k]));
+    put_words(o, ql.data(), ql.size());
+    // observe_openings(to_fri_openings) (proof.rs:161-182): [local, zs, quotient] at zeta, [next, zs_next] at g zeta, [ctl_zs_last lifted] at g^-1
+    ch.ch.observe_many(local.data(), local.size()); ch.ch.observe_many(zl.data(), zl.size()); ch.ch.observe_many(ql.data(), ql.size());
+    ch.ch.observe_many(next.data(), next.size()); ch.ch.observe_many(zn_.data(), zn_.size());
+    ch.ch.observe_many(last.data(), last.size());
+    // prove_openings on the table's instance (prover.rs:172-186)
+    const gl_batch* batches[3] = {trace, nzs ? zs.b : quot.b, quot.b};
+    const size_t at = o.size(), fri_len = glfri::proof_bytes(p, si.inst);
+    size_t fri_bytes = 0;
+    o.resize(at + fri_len);
+    GL_TRY(gl_prove_openings(ctx, &p, &si.inst, batches, &ch, o.data() + at, fri_len, &fri_bytes));
+    if (fri_bytes != fri_len) return fail(GL_ERR_INTERNAL, ": the FriProof has another size than the params and the instance fix");
+    for (uint32_t i = 0; i < s->num_public_inputs; i++) put_u64(o, gl_canon(h_public_inputs[i]));
+    if (o.size() - start != table_proof_bytes(p, ncols, s->num_public_inputs, s->nc, s->s, nctl))
+        return fail(GL_ERR_INTERNAL, ": a table's proof has another size than the description and the params fix");
+    return GL_OK;
+}
+
 namespace {
 
 int stark_prove_device(gl_ctx* ctx, const gl_stark* s, const uint64_t* d_cols, const uint64_t* h_public_inputs, uint8_t* h_out, size_t cap_bytes, size_t* num_bytes) {
     GL_TRY(check_stark_args(ctx, s));
     GL_REQUIRE(d_cols && num_bytes && (h_public_inputs || !s->num_public_inputs), GL_ERR_ARG, "gl_stark_prove: null argument");
     const gl_fri_params& p = s->params;
-    const size_t total = stark_proof_bytes(p, s->num_columns, s->num_public_inputs, s->nc, s->s);
+    const size_t total = gl_stark_proof_size(s), ncap = size_t(1) << p.cap_height;
     *num_bytes = total;
     GL_REQUIRE(h_out && cap_bytes >= total, GL_ERR_ARG, "gl_stark_prove: output too small (gl_stark_proof_size)");
-    const size_t ncap = size_t(1) << p.cap_height;
-    const uint32_t nz = s->s.nz, nq = s->s.q * s->nc;
     std::vector<uint8_t> o;
     o.reserve(total);
     gl_challenger ch{glhost::HostChallenger(p.hasher)};
     std::vector<gl_t> cap(4 * ncap);
-    BatchHolder trace, zs, quot;
-    // 1. the trace commitment (prover.rs:52-68)
+    BatchHolder trace;
+    // the trace commitment (prover.rs:52-68), then the table's body
     GL_TRY(gl_batch_from_device_h(ctx, p.hasher, d_cols, s->num_columns, s->n, p.rate_bits, p.cap_height, 1, &trace.b));
     GL_TRY(gl_batch_cap(trace.b, cap.data()));
     put_hashes(o, p.hasher, cap.data(), ncap);
     ch.ch.observe_hashes(p.hasher, cap.data(), ncap);
-    // 2. permutation challenge sets, Z polynomials, their commitment (prover.rs:76-111)
-    std::vector<gl_t> sets;
-    if (nz) {
-        for (uint32_t i = 0; i < 2 * s->s.q * s->nc; i++) sets.push_back(ch.ch.challenge());      // set after set: (beta, gamma) per challenge
-        GL_TRY(gl_stark_permutation_zs(ctx, s, d_cols, sets.data(), &zs.b));
-        GL_TRY(gl_batch_cap(zs.b, cap.data()));
-        put_hashes(o, p.hasher, cap.data(), ncap);
-        ch.ch.observe_hashes(p.hasher, cap.data(), ncap);
-    }
-    // 3./4. alphas, the quotient, its commitment (prover.rs:113-146)
-    gl_t alphas[GL_STARK_MAX_CHALLENGES];
-    for (uint32_t j = 0; j < s->nc; j++) alphas[j] = ch.ch.challenge();
-    GL_TRY(gl_stark_quotient_polys(ctx, s, trace.b, zs.b, nz ? sets.data() : nullptr, alphas, h_public_inputs, &quot.b));
-    GL_TRY(gl_batch_cap(quot.b, cap.data()));
-    put_hashes(o, p.hasher, cap.data(), ncap);
-    ch.ch.observe_hashes(p.hasher, cap.data(), ncap);
-    // 5./6. zeta off the subgroup (prover.rs:148-157)
-    const gl2_t zeta = ch.ch.challenge_ext();
-    const gl2_t zn = ext_pow2(zeta, p.degree_bits);
-    GL_REQUIRE(!(zn.a == 1 && zn.b == 0), GL_ERR_ZETA_IN_SUBGROUP, "gl_stark_prove: opening point is in the subgroup");
-    const gl_t g = gl_host_root_of_unity(p.degree_bits);
-    const gl2_t zeta_next = gl2_canon(gl2_scalar(zeta, g));
-    const gl_t zw[2] = {zeta.a, zeta.b}, znw[2] = {zeta_next.a, zeta_next.b};
-    // 7. StarkOpeningSet::new (proof.rs:138-159)
-    std::vector<gl_t> local(2 * s->num_columns), next(2 * s->num_columns), zl(2 * nz), zn_(2 * nz), ql(2 * nq);
-    GL_TRY(gl_open_at(ctx, trace.b, zw, 0, s->num_columns, local.data()));
-    GL_TRY(gl_open_at(ctx, trace.b, znw, 0, s->num_columns, next.data()));
-    if (nz) { GL_TRY(gl_open_at(ctx, zs.b, zw, 0, nz, zl.data())); GL_TRY(gl_open_at(ctx, zs.b, znw, 0, nz, zn_.data())); }
-    GL_TRY(gl_open_at(ctx, quot.b, zw, 0, nq, ql.data()));
-    put_words(o, local.data(), local.size()); put_words(o, next.data(), next.size());
-    put_words(o, zl.data(), zl.size()); put_words(o, zn_.data(), zn_.size());
-    put_words(o, ql.data(), ql.size());
-    // observe_openings(to_fri_openings) (proof.rs:161-182): [local, zs, quotient] at zeta, then [next, zs_next] at g zeta
-    ch.ch.observe_many(local.data(), local.size()); ch.ch.observe_many(zl.data(), zl.size()); ch.ch.observe_many(ql.data(), ql.size());
-    ch.ch.observe_many(next.data(), next.size()); ch.ch.observe_many(zn_.data(), zn_.size());
-    // 8. prove_openings on the STARK's instance (prover.rs:172-186)
-    const StarkInstance si(s->num_columns, s->nc, s->s, zeta, zeta_next);
-    const gl_batch* batches[3] = {trace.b, nz ? zs.b : quot.b, quot.b};
-    const size_t at = o.size();
-    size_t fri_bytes = 0;
-    o.resize(at + fri_proof_bytes(p, s->num_columns, s->nc, s->s));
-    GL_TRY(gl_prove_openings(ctx, &p, &si.inst, batches, &ch, o.data() + at, o.size() - at, &fri_bytes));
-    GL_REQUIRE(at + fri_bytes == o.size(), GL_ERR_INTERNAL, "gl_stark_prove: the FriProof has another size than the params and the instance fix");
-    for (uint32_t i = 0; i < s->num_public_inputs; i++) put_u64(o, gl_canon(h_public_inputs[i]));
+    GL_TRY(prove_table(ctx, s, nullptr, d_cols, trace.b, h_public_inputs, ch, o, "gl_stark_prove"));
     GL_REQUIRE(o.size() == total, GL_ERR_INTERNAL, "gl_stark_prove: the proof has another size than gl_stark_proof_size");
     ::memcpy(h_out, o.data(), total);
     return GL_OK;
@@ -442,7 +454,7 @@ int glstark::stark_reject(uint32_t code, uint32_t* check) {
 
 // eval_vanishing_poly at zeta over the extension field (vanishing_poly.rs, verifier.rs:81-106): the host interpreter of the term list
 void glstark::vanishing_at(const gl_stark_desc& d, const StarkShape& s, const gl2_t* local, const gl2_t* next, const gl_t* pub, const gl_t* alphas, gl2_t z_last,
-                  gl2_t l_first, gl2_t l_last, const gl2_t* zs, const gl2_t* zs_next, const gl_t* sets, gl2_t* accs, const DagProgram* prog) {
+                  gl2_t l_first, gl2_t l_last, const gl2_t* zs, const gl2_t* zs_next, const gl_t* sets, gl2_t* accs, const DagProgram* prog, const TableCtl* ctl) {
     const uint32_t nc = d.num_challenges;
     for (uint32_t j = 0; j < nc; j++) accs[j] = gl2_make(0, 0);
     auto consume = [&](gl2_t c) { for (uint32_t j = 0; j < nc; j++) accs[j] = gl2_add(gl2_scalar(accs[j], alphas[j]), c); };
@@ -479,10 +491,11 @@ void glstark::vanishing_at(const gl_stark_desc& d, const StarkShape& s, const gl
         }
         consume(gl2_sub(prd, pl));
     }
+    if (nctl_of(ctl)) ctl_checks_at(*ctl, local, next, zs + s.nz, zs_next + s.nz, l_first, z_last, consume);      // the Zs after the permutation ones
 }
 
 extern "C" size_t gl_stark_proof_size(const gl_stark* s) noexcept {
-    return s ? stark_proof_bytes(s->params, s->num_columns, s->num_public_inputs, s->nc, s->s) : 0;
+    return s ? s->proof_bytes : 0;
 }
 
 extern "C" int gl_stark_prove_device(gl_ctx* ctx, const gl_stark* s, const uint64_t* d_cols, const uint64_t* h_public_inputs, uint8_t* h_out,
@@ -508,60 +521,59 @@ extern "C" int gl_stark_verify(const gl_stark_desc* desc, const gl_fri_params* p
     return stark_verify(desc, nullptr, params, proof_bytes, num_bytes, check);
 } catch (...) { return gl_caught(); }
 
-// gl_stark_verify and gl_stark_dag_verify up to their final gl_verify_openings, for a description that passed stark_check (prog: its
-// compiled DAG, or null): the byte count, caps, openings, get_challenges, the vanishing identity; what is left is the claim
-int glstark::stark_host_stage(const gl_stark_desc& d, const StarkShape& s, const DagProgram* prog, const gl_fri_params& p, const uint8_t* proof_bytes, size_t num_bytes,
-                              StarkClaim& out, uint32_t* check) {
+int glstark::stark_host_stage(const gl_stark_desc& d, const StarkShape& s, const DagProgram* prog, const gl_fri_params& p, const TableCtl* ctl, const uint8_t* proof_bytes,
+                              size_t num_bytes, size_t total, gl_challenger& ch, StarkClaim& out, uint32_t* check) {
     if (check) *check = GL_CHECK_ACCEPTED;
     GL_REQUIRE(proof_bytes || !num_bytes, GL_ERR_ARG, "gl_stark_verify: null proof");
-    const uint32_t nc = d.num_challenges, ncols = d.num_columns, nz = s.nz, nq = s.q * nc;
-    const size_t ncap = size_t(1) << p.cap_height, total = stark_proof_bytes(p, ncols, d.num_public_inputs, nc, s);
-    // the layout's counts are fixed by the description and the params
+    const uint32_t nc = d.num_challenges, ncols = d.num_columns, nz = s.nz, nctl = nctl_of(ctl), nzs = nz + nctl, nq = s.q * nc;
+    const size_t ncap = size_t(1) << p.cap_height;
+    // the layout's counts are fixed by the description and the params (a set's are decided on the whole set's size before)
     if (num_bytes < total) return stark_reject(GL_CHECK_TRUNCATED, check);
     if (num_bytes > total) return stark_reject(GL_CHECK_LENGTH, check);
     VCursor cur{proof_bytes, num_bytes};
-    const uint32_t noracles = nz ? 3 : 2;
+    const uint32_t noracles = nzs ? 3 : 2;
     std::vector<gl_t>& caps = out.caps;
     std::vector<gl_t> pub(d.num_public_inputs + 1);
     caps.resize(4 * ncap * noracles);
     cur.hashes(p.hasher, caps.data(), ncap * noracles);
-    const size_t nopen = 2 * (size_t)ncols + 2 * nz + nq;
-    std::vector<gl_t> w(2 * nopen);
-    cur.words(w.data(), w.size());
+    const size_t nopen = 2 * (size_t)ncols + 2 * nzs + nq;
+    std::vector<gl_t> w(2 * nopen);                    // local, next, zs, zs_next | quotient, with ctl_zs_last between them in the proof
+    cur.words(w.data(), w.size() - 2 * nq);
+    out.ctl_zs_last.resize(nctl);
+    cur.words(out.ctl_zs_last.data(), nctl);
+    cur.words(w.data() + w.size() - 2 * nq, 2 * nq);
     const gl2_t* ext = (const gl2_t*)w.data();
-    const gl2_t *local = ext, *next = ext + ncols, *zl = ext + 2 * ncols, *zn = zl + nz, *ql = zn + nz;
+    const gl2_t *local = ext, *next = ext + ncols, *zl = ext + 2 * ncols, *zn = zl + nzs, *ql = zn + nzs;
     out.fri = proof_bytes + cur.pos;
-    out.fri_len = fri_proof_bytes(p, ncols, nc, s);
+    out.fri_len = total - cur.pos - 8 * (size_t)d.num_public_inputs;
     cur.pos += out.fri_len;
     cur.words(pub.data(), d.num_public_inputs);
-    // get_challenges (get_challenges.rs:21-59)
-    gl_challenger& ch = out.ch;
-    ch.ch = glhost::HostChallenger(p.hasher);
-    ch.ch.observe_hashes(p.hasher, caps.data(), ncap);
+    // get_challenges (get_challenges.rs:21-59; evm/src/get_challenges.rs:95-149 behind the set's trace caps, CTL challenges and the compact of :39)
+    if (ctl) ch.ch.compact();
+    else ch.ch.observe_hashes(p.hasher, caps.data(), ncap);
     std::vector<gl_t> sets;
-    if (nz) {
-        for (uint32_t i = 0; i < 2 * s.q * nc; i++) sets.push_back(ch.ch.challenge());
-        ch.ch.observe_hashes(p.hasher, caps.data() + 4 * ncap, ncap);
-    }
+    if (nz) for (uint32_t i = 0; i < 2 * s.q * nc; i++) sets.push_back(ch.ch.challenge());
+    if (nzs) ch.ch.observe_hashes(p.hasher, caps.data() + 4 * ncap, ncap);
     gl_t alphas[GL_STARK_MAX_CHALLENGES];
     for (uint32_t j = 0; j < nc; j++) alphas[j] = ch.ch.challenge();
     ch.ch.observe_hashes(p.hasher, caps.data() + 4 * ncap * (noracles - 1), ncap);
     const gl2_t zeta = ch.ch.challenge_ext();
-    // FriOpenings order (proof.rs:161-182)
+    // FriOpenings order (proof.rs:161-182): [local, zs, quotient], [next, zs_next], [ctl_zs_last lifted]
     std::vector<gl_t>& openings = out.openings;
     openings.clear();
-    openings.reserve(2 * nopen);
+    openings.reserve(2 * nopen + 2 * nctl);
     auto push = [&](const gl2_t* v, size_t k) { for (size_t i = 0; i < k; i++) { openings.push_back(v[i].a); openings.push_back(v[i].b); } };
-    push(local, ncols); push(zl, nz); push(ql, nq); push(next, ncols); push(zn, nz);
+    push(local, ncols); push(zl, nzs); push(ql, nq); push(next, ncols); push(zn, nzs);
+    for (gl_t last : out.ctl_zs_last) { openings.push_back(last); openings.push_back(0); }
     ch.ch.observe_many(openings.data(), openings.size());
     // verifier.rs:81-124: the identity vanishing(zeta) = Z_H(zeta) t(zeta) per challenge
-    const gl_t g = gl_host_root_of_unity(p.degree_bits), n_field = gl_t(1) << p.degree_bits;
+    const gl_t g = gl_host_root_of_unity(p.degree_bits), n_field = gl_t(1) << p.degree_bits, g_inv = gl_canon(gl_inv(g));
     const gl2_t zeta_pow = ext_pow2(zeta, p.degree_bits), z_h = gl2_sub(zeta_pow, gl2_make(1, 0));
     const gl2_t l_first = gl2_mul(z_h, gl2_inv(gl2_scalar(gl2_sub(zeta, gl2_make(1, 0)), n_field)));                      // eval_l_0_and_l_last (verifier.rs:221-228)
     const gl2_t l_last = gl2_mul(z_h, gl2_inv(gl2_scalar(gl2_sub(gl2_scalar(zeta, g), gl2_make(1, 0)), n_field)));
-    const gl2_t z_last = gl2_sub(zeta, e_of(gl_inv(g)));
+    const gl2_t z_last = gl2_sub(zeta, e_of(g_inv));
     gl2_t accs[GL_STARK_MAX_CHALLENGES];
-    vanishing_at(d, s, local, next, pub.data(), alphas, z_last, l_first, l_last, zl, zn, sets.data(), accs, prog);
+    vanishing_at(d, s, local, next, pub.data(), alphas, z_last, l_first, l_last, zl, zn, sets.data(), accs, prog, ctl);
     for (uint32_t j = 0; j < nc; j++) {
         gl2_t t = gl2_make(0, 0);                                                                                       // reduce_with_powers(chunk, zeta^n)
         for (uint32_t k = s.q; k-- > 0;) t = gl2_add(gl2_mul(t, zeta_pow), ql[j * s.q + k]);
@@ -569,19 +581,26 @@ int glstark::stark_host_stage(const gl_stark_desc& d, const StarkShape& s, const
         if (lhs.a != rhs.a || lhs.b != rhs.b) return stark_reject(GL_CHECK_VANISHING, check);
     }
     const gl2_t zeta_next = gl2_canon(gl2_scalar(zeta, g));
-    out.points[0][0] = zeta.a; out.points[0][1] = zeta.b; out.points[1][0] = zeta_next.a; out.points[1][1] = zeta_next.b;
+    out.points[0][0] = zeta.a; out.points[0][1] = zeta.b; out.points[1][0] = zeta_next.a; out.points[1][1] = zeta_next.b; out.points[2][0] = g_inv;
     return GL_OK;
 }
 
-// gl_stark_verify and gl_stark_dag_verify: the host stage, then verify_fri_proof on the STARK's instance at this proof's zeta and g zeta
+int glstark::verify_table(const gl_stark_desc& d, const StarkShape& s, const DagProgram* prog, const gl_fri_params& p, const TableCtl* ctl, const uint8_t* proof_bytes,
+                          size_t num_bytes, size_t total, gl_challenger& ch, StarkClaim& claim, uint32_t* check) {
+    GL_TRY(stark_host_stage(d, s, prog, p, ctl, proof_bytes, num_bytes, total, ch, claim, check));
+    const StarkInstance si(d.num_columns, d.num_challenges, s, nctl_of(ctl), p.degree_bits, gl2_make(claim.points[0][0], claim.points[0][1]));
+    return gl_verify_openings(&p, &si.inst, claim.caps.data(), claim.openings.data(), &ch, claim.fri, claim.fri_len, check);
+}
+
+// gl_stark_verify and gl_stark_dag_verify
 int glstark::stark_verify(const gl_stark_desc* desc, const gl_stark_dag* dag, const gl_fri_params* params, const uint8_t* proof_bytes, size_t num_bytes, uint32_t* check) {
     StarkShape s;
     DagProgram prog;
     GL_TRY(stark_check(desc, params, &s, false, dag, &prog));
     StarkClaim claim;
-    GL_TRY(stark_host_stage(*desc, s, dag ? &prog : nullptr, *params, proof_bytes, num_bytes, claim, check));
-    const StarkInstance si(desc->num_columns, desc->num_challenges, s, gl2_make(claim.points[0][0], claim.points[0][1]), gl2_make(claim.points[1][0], claim.points[1][1]));
-    return gl_verify_openings(params, &si.inst, claim.caps.data(), claim.openings.data(), &claim.ch, claim.fri, claim.fri_len, check);
+    gl_challenger ch{glhost::HostChallenger(params->hasher)};
+    const size_t total = table_proof_bytes(*params, desc->num_columns, desc->num_public_inputs, desc->num_challenges, s, 0);
+    return verify_table(*desc, s, dag ? &prog : nullptr, *params, nullptr, proof_bytes, num_bytes, total, ch, claim, check);
 }
 
 // ---- verify_stark_proof for many proofs of one Stark: the host stage per proof on host threads, each proof's FriProof a claim of the
@@ -595,7 +614,9 @@ struct gl_stark_batch_verifier {
     std::vector<uint64_t> coeff;
     bool dag = false;
     DagProgram prog;                                   // compiled once
-    std::vector<StarkClaim> lanes;                     // one per host thread
+    struct Lane { StarkClaim claim; gl_challenger ch{glhost::HostChallenger(GL_HASHER_POSEIDON)}; };
+    std::vector<Lane> lanes;                           // one per host thread
+    size_t proof_bytes = 0;
 };
 
 extern "C" void gl_stark_batch_verifier_free(gl_stark_batch_verifier* v) noexcept {
@@ -622,9 +643,10 @@ extern "C" int gl_stark_batch_verifier_new(gl_ctx* ctx, const gl_stark_desc* des
     v->desc.factors = keep(v->factors, d.factors, s.factors);
     v->desc.pair_len = keep(v->pair_len, d.pair_len, d.num_permutation_pairs);
     v->desc.pair_columns = keep(v->pair_columns, d.pair_columns, 2 * s.column_pairs);
-    const StarkInstance si(d.num_columns, d.num_challenges, s, gl2_make(0, 1), gl2_make(0, 1));
+    const StarkInstance si(d.num_columns, d.num_challenges, s, 0, params->degree_bits);
     GL_TRY(glopen::batch_new(ctx, params, &si.inst, max_batch, host_threads, &v->inner));
     v->lanes.resize(host_threads ? host_threads : 1);
+    v->proof_bytes = table_proof_bytes(*params, d.num_columns, d.num_public_inputs, d.num_challenges, s, 0);
     *out = v.release();
     return GL_OK;
 } catch (...) { return gl_caught(); }
@@ -636,9 +658,11 @@ extern "C" int gl_stark_batch_verifier_verify(gl_stark_batch_verifier* v, const 
     GL_REQUIRE(proofs && num_bytes && verdicts, GL_ERR_ARG, "gl_stark_batch_verifier_verify: null argument");
     return glopen::batch_verify(v->inner, count, [&](size_t lane, size_t i, gl_openings_claim& claim, uint32_t* check) -> int {
         GL_REQUIRE(proofs[i], GL_ERR_ARG, "gl_stark_batch_verifier_verify: null proof");
-        StarkClaim& c = v->lanes[lane];
-        GL_TRY(stark_host_stage(v->desc, v->shape, v->dag ? &v->prog : nullptr, v->params, proofs[i], num_bytes[i], c, check));
-        claim.caps = c.caps.data(); claim.openings = c.openings.data(); claim.points = c.points; claim.challenger = &c.ch;
+        StarkClaim& c = v->lanes[lane].claim;
+        gl_challenger& ch = v->lanes[lane].ch;
+        ch.ch = glhost::HostChallenger(v->params.hasher);
+        GL_TRY(stark_host_stage(v->desc, v->shape, v->dag ? &v->prog : nullptr, v->params, nullptr, proofs[i], num_bytes[i], v->proof_bytes, ch, c, check));
+        claim.caps = c.caps.data(); claim.openings = c.openings.data(); claim.points = c.points; claim.challenger = &ch;
         claim.proof = c.fri; claim.num_bytes = c.fri_len;
         return GL_OK;
     }, verdicts, checks);

@@ -278,6 +278,20 @@ def test_the_tamper_matrix(p, orc, fixture):
         assert got[1] == reported and (got[0] in check if isinstance(check, tuple) else got[0] == check), (table, name, word, got)
 
 
+def test_a_flipped_ctl_zs_last_word_of_every_table(p, orc, fixture):
+    # the words the per-table stage hands to the product across the tables: the last word of each table's, the looked table's among them
+    # (the matrix above holds ops' first and ops2's second).  The table's own batch at g^-1 answers, before the product check.
+    proof, meta, reg = fixture[0], fixture[1], regions(fixture)
+    for table in (airs.OPS, airs.OPS2, airs.MUL):
+        first, size = reg[table, "ctl_zs_last"]
+        assert size == 8 * meta["num_ctl_zs"][table] > 0
+        bad = bytearray(proof)
+        bad[first + size - 8] ^= 1
+        got = library(p, fixture, bytes(bad))
+        assert got == model(orc, fixture, bytes(bad)), (table, got)
+        assert got[0] in FRI_CHECKS and got[1] == table, (table, got)
+
+
 def test_swapped_tables_and_truncation(p, orc, fixture):
     proof, reg = fixture[0], regions(fixture)
     (a0, al), (b0, bl), (c0, cl) = reg[airs.OPS, "all"], reg[airs.OPS2, "all"], reg[airs.MUL, "all"]
