@@ -1,16 +1,18 @@
-// Batch verify_fri_proof for any FriInstanceInfo (fri/verifier.rs:62-241, hash/merkle_proofs.rs:54-75): the batched gl_verify_openings.
+// Batch verify_fri_proof (fri/verifier.rs:62-241, hash/merkle_proofs.rs:54-75): the one device batch core, and the generic entry on it.
 //
-// What runs where.  Per claim the host stage of gl_verify_openings (openings_stage.hpp: the points' coset check, decode, challenges,
-// proof of work, reduced openings) runs on host threads: the Challenger is a sequential sponge.  What is left is the query phase --
+// What runs where.  Per proof a host stage (openings_stage.hpp: decode, challenges, proof of work, reduced openings, and whatever the
+// entry checks in front of them) runs on host threads: the Challenger is a sequential sponge.  What is left is the query phase --
 // num_queries x (num_oracles + num_fri_rounds) Merkle paths, independent of each other, and the field arithmetic of the queries.
-// They read one record per claim, so a chunk of claims is one upload, two launches and one download of the flags:
-//   record:  T (openings_stage.hpp) | challenge block (CH_* below) | x_index[num_queries] | caps[num_oracles][ncap][4]
-//   k_verify_paths_any<HASHER>      one lane per (slot, claim, query), slot-major: leaf hash, path, comparison with the cap entry
-//   k_verify_openings_queries       one lane per (claim, query): fri_combine_initial over the instance's flattened source table, per
+// They read one record per proof, so a chunk of proofs is one upload, two launches and one download of the flags:
+//   record:  T (up to the final polynomial's end) | challenge block (CH_* below) | x_index[num_queries] | caps[num_oracles][ncap][4]
+//   k_verify_paths_any<HASHER>      one lane per (slot, proof, query), slot-major: leaf hash, path, comparison with the cap entry
+//   k_verify_openings_queries       one lane per (proof, query): fri_combine_initial over the instance's flattened source table, per
 //                                   reduction the consistency comparison and compute_evaluation, the final-polynomial Horner
-// The host merges the flags in gl_verify_openings' order, so a rejected claim reports the check gl_verify_openings reports first.
-// Nothing on the device trusts proof bytes: every index follows from the shape (glopen::Shape), which the decode has held the proof
-// against, from the instance's source table, checked at construction, and from x_index < 2^lgN.
+// The host merges the flags in the host query loop's order, so a rejected proof reports the check gl_verify / gl_verify_openings
+// reports first.  Nothing on the device trusts proof bytes: every index follows from the shape (glopen::Shape), which the decode has
+// held the proof against and whose every read the core has held against the record at construction, and from x_index < 2^lgN.
+// Three entries stand on the core: gl_openings_batch_verifier (below), gl_stark_batch_verifier (stark.hip, through the generic
+// entry) and gl_batch_verifier (batch_verify.hip: circuit proofs).
 // Not run on the device: reductions of arity above 16 (refused at construction).
 #include "context.hpp"
 #include "host_circuit.hpp"
@@ -24,15 +26,15 @@ namespace {
 using glopen::MAX_FRI_ROUNDS;
 using glopen::MAX_SLOTS;
 
-// the challenge block behind a claim's table: extension elements as word pairs; per batch b its reduced opening, alpha^len and point
+// the challenge block behind a proof's table: extension elements as word pairs; per batch b its reduced opening, alpha^len and point
 enum : uint32_t { CH_ALPHA = 0, CH_BETAS = 2, CH_BATCH = CH_BETAS + 2 * MAX_FRI_ROUNDS, CH_RED = 0, CH_ALPHA_LEN = 2, CH_POINT = 4, CH_BATCH_WORDS = 6,
                   CH_WORDS = CH_BATCH + CH_BATCH_WORDS * GL_MAX_FRI_BATCHES };
 constexpr uint32_t FLAG_FINAL = 1u << MAX_FRI_ROUNDS;      // k_verify_openings_queries: bit r = reduction r's consistency comparison failed
 
-// glopen::Shape as the kernels read it (offsets in words inside one claim's record)
+// glopen::Shape as the kernels read it (offsets in words inside one proof's record)
 struct OParams {
     uint32_t num_queries, num_rounds, num_oracles, num_slots, num_batches, lgN, ncap;
-    uint32_t stride;                                   // words per claim in the upload
+    uint32_t stride;                                   // words per proof in the upload
     uint32_t o_fcaps, o_query0, query_stride, o_final, final_len, o_ch, o_x, o_caps;
     uint32_t first[GL_MAX_FRI_BATCHES + 1];
     uint32_t arity_bits[MAX_FRI_ROUNDS];
@@ -41,7 +43,7 @@ struct OParams {
     gl_t w_N, w_arity[MAX_FRI_ROUNDS];                 // primitive roots of order 2^lgN and 2^arity_bits[r]
 };
 
-// ---- Merkle paths: the lane body of k_verify_merkle_paths (verify_lane.cuh) on the generic record ----
+// ---- Merkle paths (verify_lane.cuh holds the lane body) ----
 // Slot-major: the lanes of a wave share leaf length and path length (but for the one wave across a slot boundary).  An initial tree's
 // cap is the claim's own, behind its table; a step tree's the commit-phase cap inside the table.
 template <uint32_t HASHER>
@@ -99,28 +101,34 @@ __global__ __launch_bounds__(64) void k_verify_openings_queries(const gl_t* __re
     flags[gid] = bad;
 }
 
-struct Lane { std::vector<gl_t> T; glopen::Challenges ch; };
+using glopen::Lane;
+
+// a refusal in the entry's own name
+int refuse(int code, const glopen::Names& names, const char* what) {
+    char text[256];
+    snprintf(text, sizeof text, "%s_new: %s", names.entry, what);
+    return gl_fail(code, text, __FILE__, __LINE__);
+}
 
 }  // namespace
 
-struct gl_openings_batch_verifier {
+struct glopen::BatchCore {
     gl_ctx* ctx = nullptr;
-    gl_fri_params params;
-    gl_fri_instance instance;                          // polys points into `polys`
-    std::vector<uint32_t> polys;
-    glopen::Shape shape;
+    Shape shape;
+    Names names;
+    std::string verify_name;                           // "<entry>_verify", for the lanes' failures
     OParams P;
     uint32_t max_batch = 0, host_threads = 1;
-    size_t stride = 0, flag_bytes = 0;                 // words per claim in the upload; bytes of flags per claim
+    size_t stride = 0, flag_bytes = 0;                 // words per proof in the upload; bytes of flags per proof
     gl_t *d_in = nullptr, *h_in = nullptr;
     uint32_t* d_src = nullptr;
     uint8_t *d_flags = nullptr, *h_flags = nullptr;
     std::vector<Lane> lanes;                           // one per host thread
-    std::vector<uint32_t> place;                       // chunk-local claim -> its place in the upload
-    std::mutex mu;                                     // calls on one verifier are serialised (one staging area)
+    std::vector<uint32_t> place;                       // chunk-local proof -> its place in the upload
+    std::mutex mu;                                     // calls on one core are serialised (one staging area)
 };
 
-extern "C" void gl_openings_batch_verifier_free(gl_openings_batch_verifier* v) noexcept {
+void glopen::core_free(BatchCore* v) noexcept {
     if (!v) return;
     if (v->ctx) {
         (void)hipSetDevice(v->ctx->device);
@@ -135,36 +143,55 @@ extern "C" void gl_openings_batch_verifier_free(gl_openings_batch_verifier* v) n
     delete v;
 }
 
-int glopen::batch_new(gl_ctx* c, const gl_fri_params* params, const gl_fri_instance* instance, uint32_t max_batch, uint32_t host_threads,
-                      gl_openings_batch_verifier** out) {
-    GL_REQUIRE(c, GL_ERR_ARG, "gl_openings_batch_verifier_new: null argument");
-    GL_REQUIRE(max_batch >= 1 && max_batch <= 4096, GL_ERR_ARG, "gl_openings_batch_verifier_new: max_batch is 1..4096");
-    GL_REQUIRE(host_threads <= GL_MAX_LANES, GL_ERR_ARG, "gl_openings_batch_verifier_new: at most 64 host threads");
-    std::unique_ptr<gl_openings_batch_verifier, void (*)(gl_openings_batch_verifier*)> v(new gl_openings_batch_verifier(), gl_openings_batch_verifier_free);
-    GL_REQUIRE(params && instance, GL_ERR_ARG, "FRI openings: null params / instance");
-    // the instance without its points: every claim brings its own (an opening point off the base field passes the coset check)
-    v->params = *params; v->instance = *instance;
-    for (uint32_t b = 0; b < GL_MAX_FRI_BATCHES; b++) { v->instance.points[b][0] = 0; v->instance.points[b][1] = 1; }
-    GL_TRY(glopen::shape_of(&v->params, &v->instance, v->shape));
-    const glopen::Shape& s = v->shape;
-    v->polys.assign(instance->polys, instance->polys + 2 * s.src.size());
-    v->instance.polys = v->polys.data();
-    for (uint32_t r = 0; r < s.num_rounds; r++) GL_REQUIRE(s.arity_bits[r] <= 4, GL_ERR_UNSUPPORTED, "gl_openings_batch_verifier_new: a FRI arity above 16 is not supported");
+int glopen::check_batch(const Names& names, uint32_t max_batch, uint32_t host_threads) {
+    if (!(max_batch >= 1 && max_batch <= 4096)) return refuse(GL_ERR_ARG, names, "max_batch is 1..4096");
+    if (host_threads > GL_MAX_LANES) return refuse(GL_ERR_ARG, names, "at most 64 host threads");
+    return GL_OK;
+}
+
+int glopen::core_new(gl_ctx* c, const Shape& s, uint32_t max_batch, uint32_t host_threads, const Names& names, BatchCore** out) {
+    std::unique_ptr<BatchCore, void (*)(BatchCore*)> v(new BatchCore(), core_free);      // error paths free everything
+    v->shape = s; v->names = names; v->verify_name = std::string(names.entry) + "_verify";
+    for (uint32_t r = 0; r < s.num_rounds; r++) if (s.arity_bits[r] > 4) return refuse(GL_ERR_UNSUPPORTED, names, "a FRI arity above 16 is not supported");
+    // the record: T | challenge block | x_index | caps
     const size_t cap_words = (size_t)s.num_oracles * 4 * s.ncap;
-    v->stride = s.t_words + CH_WORDS + s.num_queries + cap_words;
+    const bool small = s.t_words <= (size_t(1) << 24);                  // (SIZE_MAX: a table that fits no size_t)
+    const size_t o_ch = small ? s.t_words : 0, o_x = o_ch + CH_WORDS, o_caps = o_x + s.num_queries;
+    v->stride = o_caps + cap_words;
     v->stride += v->stride & 1;
-    GL_REQUIRE(v->stride <= (size_t(1) << 24) && (uint64_t)max_batch * s.num_queries * s.num_slots() < (uint64_t(1) << 31), GL_ERR_ARG,
-               "gl_openings_batch_verifier_new: a proof of these params exceeds 2^24 words, or the batch 2^31 paths");
+    if (!(small && v->stride <= (size_t(1) << 24) && (uint64_t)max_batch * s.num_queries * s.num_slots() < (uint64_t(1) << 31))) {
+        char what[128];
+        snprintf(what, sizeof what, "a proof of %s exceeds 2^24 words, or the batch 2^31 paths", names.subject);
+        return refuse(GL_ERR_ARG, names, what);
+    }
     v->max_batch = max_batch; v->host_threads = host_threads ? host_threads : 1;
     v->lanes.resize(v->host_threads);
     v->place.resize(max_batch);
+    GL_TRY(c->activate());
+    v->ctx = c; c->retain();
+    if (!s.paths_fit) { *out = v.release(); return GL_OK; }      // the decode rejects every proof: nothing reaches the device, nothing is allocated
+    // Nothing checks an index on the device: every read of the kernels lies inside the record, or nothing is launched
+    bool inside = s.num_oracles >= 1 && s.num_oracles <= GL_MAX_FRI_ORACLES && s.num_batches <= GL_MAX_FRI_BATCHES && s.num_rounds <= MAX_FRI_ROUNDS &&
+                  s.lgN >= 1 && s.lgN <= 32 && s.ncap == size_t(1) << s.cap_height && s.first[s.num_batches] == s.src.size() &&
+                  s.query_stride <= (size_t(1) << 24) &&                                               // (and num_queries, by the stride)
+                  s.o_fcaps + (size_t)s.num_rounds * 4 * s.ncap <= s.o_query0 && s.o_query0 + s.num_queries * s.query_stride <= s.o_final &&
+                  s.o_final + 2 * s.final_len <= s.t_words && o_caps + cap_words <= v->stride;
+    for (uint32_t j : s.src) inside = inside && j < s.query_stride;
+    unsigned lg_cur = s.lgN;
+    for (uint32_t slot = 0; slot < s.num_slots() && inside; slot++) {
+        if (slot >= s.num_oracles) lg_cur -= s.arity_bits[slot - s.num_oracles];
+        inside = s.slot_leaf[slot] + s.slot_leaf_len[slot] <= s.query_stride && s.slot_sib[slot] + 4 * s.slot_nsib[slot] <= s.query_stride &&
+                 s.slot_nsib[slot] + s.cap_height == lg_cur &&                                         // the cap entry idx >> nsib exists
+                 (slot < s.num_oracles || (s.arity_bits[slot - s.num_oracles] >= 1 && s.slot_leaf_len[slot] == size_t(2) << s.arity_bits[slot - s.num_oracles]));
+    }
+    if (!inside) return refuse(GL_ERR_INTERNAL, names, "the shape's reads leave its record");
     v->flag_bytes = (size_t)s.num_queries * (sizeof(uint32_t) + s.num_slots());
     OParams& P = v->P;
     P = OParams();
     P.num_queries = s.num_queries; P.num_rounds = s.num_rounds; P.num_oracles = s.num_oracles; P.num_slots = s.num_slots(); P.num_batches = s.num_batches;
     P.lgN = s.lgN; P.ncap = (uint32_t)s.ncap; P.stride = (uint32_t)v->stride;
     P.o_fcaps = (uint32_t)s.o_fcaps; P.o_query0 = (uint32_t)s.o_query0; P.query_stride = (uint32_t)s.query_stride; P.o_final = (uint32_t)s.o_final;
-    P.final_len = (uint32_t)s.final_len; P.o_ch = (uint32_t)s.t_words; P.o_x = P.o_ch + CH_WORDS; P.o_caps = P.o_x + s.num_queries;
+    P.final_len = (uint32_t)s.final_len; P.o_ch = (uint32_t)o_ch; P.o_x = (uint32_t)o_x; P.o_caps = (uint32_t)o_caps;
     for (uint32_t b = 0; b <= GL_MAX_FRI_BATCHES; b++) P.first[b] = s.first[b];
     uint32_t consumed = 0;
     for (uint32_t slot = 0; slot < s.num_slots(); slot++) {
@@ -177,8 +204,6 @@ int glopen::batch_new(gl_ctx* c, const gl_fri_params* params, const gl_fri_insta
         P.slot_sib[slot] = (uint32_t)s.slot_sib[slot]; P.slot_nsib[slot] = (uint32_t)s.slot_nsib[slot]; P.slot_shift[slot] = consumed;
     }
     P.w_N = glhost::root_of_unity(s.lgN);
-    GL_TRY(c->activate());
-    v->ctx = c; c->retain();
     GL_CHECK_HIP(hipMalloc((void**)&v->d_in, v->stride * sizeof(gl_t) * max_batch));
     GL_CHECK_HIP(hipHostMalloc((void**)&v->h_in, v->stride * sizeof(gl_t) * max_batch, hipHostMallocDefault));
     GL_CHECK_HIP(hipMalloc((void**)&v->d_flags, v->flag_bytes * max_batch));
@@ -190,34 +215,21 @@ int glopen::batch_new(gl_ctx* c, const gl_fri_params* params, const gl_fri_insta
     return GL_OK;
 }
 
-extern "C" int gl_openings_batch_verifier_new(gl_ctx* c, const gl_fri_params* params, const gl_fri_instance* instance, uint32_t max_batch, uint32_t host_threads,
-                                              gl_openings_batch_verifier** out) try {
-    GL_REQUIRE(out, GL_ERR_ARG, "gl_openings_batch_verifier_new: null argument");
-    *out = nullptr;
-    GL_REQUIRE(c && params && instance, GL_ERR_ARG, "gl_openings_batch_verifier_new: null argument");
-    return glopen::batch_new(c, params, instance, max_batch, host_threads, out);
-} catch (...) { return gl_caught(); }
-
-// one chunk of at most max_batch claims: host stage on the lanes, then upload, two launches, download and the merge
-static int verify_chunk(gl_openings_batch_verifier* v, size_t first, size_t count, const glopen::ClaimSource& source, int32_t* verdicts, uint32_t* checks) {
+// one chunk of at most max_batch proofs: host stage on the lanes, then upload, two launches, download and the merge
+static int verify_chunk(glopen::BatchCore* v, size_t first, size_t count, const glopen::Stage& stage, int32_t* verdicts, uint32_t* checks) {
     const glopen::Shape& s = v->shape;
     constexpr uint32_t REJECTED = UINT32_MAX;
     const size_t cap_words = (size_t)s.num_oracles * 4 * s.ncap;
     std::atomic<uint32_t> live{0};
-    GL_TRY(gl_run_lanes(v->host_threads, count, "gl_openings_batch_verifier_verify", [&](size_t lane, size_t i) {
+    GL_TRY(gl_run_lanes(v->host_threads, count, v->verify_name.c_str(), [&](size_t lane, size_t i) {
         v->place[i] = REJECTED;
-        gl_openings_claim claim = {};
-        uint32_t check = GL_CHECK_ACCEPTED;
-        int st = source(lane, first + i, claim, &check);
-        if (st == GL_OK) {
-            Lane& L = v->lanes[lane];
-            st = glopen::host_stage(v->params, v->instance, s, claim.points, claim.caps, claim.openings, claim.challenger, claim.proof, claim.num_bytes, L.T, L.ch, &check);
-            if (st != GL_OK && st != GL_ERR_VERIFY && st != GL_ERR_ARG) return st;          // (GL_ERR_ARG: the claim's own points or challenger, a verdict)
-        } else if (st != GL_ERR_VERIFY) return st;
-        verdicts[i] = st;
-        if (checks) checks[i] = check;
-        if (st == GL_OK) {
-            Lane& L = v->lanes[lane];
+        Lane& L = v->lanes[lane];
+        L.caps = nullptr; L.verdict = GL_OK; L.check = GL_CHECK_ACCEPTED;
+        GL_TRY(stage(lane, first + i, L));
+        verdicts[i] = L.verdict;
+        if (checks) checks[i] = L.check;
+        if (L.verdict == GL_OK) {
+            GL_REQUIRE(v->h_in && L.caps && L.T.size() >= s.t_words && L.ch.x_index.size() == s.num_queries, GL_ERR_INTERNAL, "batch verification: a stage passed a proof it did not fill");
             const uint32_t at = live.fetch_add(1, std::memory_order_relaxed);
             v->place[i] = at;
             gl_t* dst = v->h_in + (size_t)at * v->stride;
@@ -232,19 +244,20 @@ static int verify_chunk(gl_openings_batch_verifier* v, size_t first, size_t coun
             }
             for (uint32_t q = 0; q < s.num_queries; q++) dst[v->P.o_x + q] = L.ch.x_index[q];
             // the caps as path_opens_to_cap compares them: a HashOut's words as field elements, a BytesHash<25>'s as they are
-            for (size_t k = 0; k < cap_words; k++) dst[v->P.o_caps + k] = s.hasher == GL_HASHER_KECCAK ? claim.caps[k] : gl_canon(claim.caps[k]);
+            for (size_t k = 0; k < cap_words; k++) dst[v->P.o_caps + k] = s.hasher == GL_HASHER_KECCAK ? L.caps[k] : gl_canon(L.caps[k]);
         }
         return GL_OK;
     }));
     const uint32_t n = live.load();
     if (!n) return GL_OK;
+    GL_REQUIRE(v->d_in, GL_ERR_INTERNAL, "batch verification: a proof passed the decode of a description no proof fits");
     gl_ctx* c = v->ctx;
     GL_TRY(c->activate());
     const uint32_t nq = s.num_queries, slots = s.num_slots(), per_slot = n * nq;
     uint32_t* d_fri = reinterpret_cast<uint32_t*>(v->d_flags);
     uint8_t* d_pass = v->d_flags + sizeof(uint32_t) * per_slot;
     {
-        GlTimed t(c, "openings_batch_verify");
+        GlTimed t(c, v->names.scope);
         GL_CHECK_HIP(hipMemcpyAsync(v->d_in, v->h_in, (size_t)n * v->stride * sizeof(gl_t), hipMemcpyHostToDevice, c->stream));
         if (s.hasher == GL_HASHER_KECCAK)
             hipLaunchKernelGGL(k_verify_paths_any<GL_HASHER_KECCAK>, dim3((per_slot * slots + 255) / 256), dim3(256), 0, c->stream, v->d_in, v->P, n, d_pass);
@@ -256,8 +269,8 @@ static int verify_chunk(gl_openings_batch_verifier* v, size_t first, size_t coun
         GL_CHECK_HIP(hipMemcpyAsync(v->h_flags, v->d_flags, v->flag_bytes * n, hipMemcpyDeviceToHost, c->stream));
     }
     GL_CHECK_HIP(gl_stream_wait(c->stream));
-    // gl_verify_openings' order: queries ascending; within one the initial trees in order, per reduction the consistency comparison
-    // before the step tree's Merkle proof, then the final polynomial.  The device evaluates every query of a claim and the host stops
+    // The host loop's order: queries ascending; within one the initial trees in order, per reduction the consistency comparison
+    // before the step tree's Merkle proof, then the final polynomial.  The device evaluates every query of a proof and the host stops
     // at the first failure; only the first failure is reported, so the first failing flag in this order is the host's check.
     const uint32_t* fri = reinterpret_cast<const uint32_t*>(v->h_flags);
     const uint8_t* pass = v->h_flags + sizeof(uint32_t) * per_slot;
@@ -279,13 +292,66 @@ static int verify_chunk(gl_openings_batch_verifier* v, size_t first, size_t coun
     return GL_OK;
 }
 
-int glopen::batch_verify(gl_openings_batch_verifier* v, size_t count, const ClaimSource& source, int32_t* verdicts, uint32_t* checks) {
+int glopen::core_verify(BatchCore* v, size_t count, const Stage& stage, int32_t* verdicts, uint32_t* checks) {
     std::lock_guard<std::mutex> lk(v->mu);
     for (size_t at = 0; at < count; at += v->max_batch) {
         const size_t k = count - at < v->max_batch ? count - at : v->max_batch;
-        GL_TRY(verify_chunk(v, at, k, source, verdicts + at, checks ? checks + at : nullptr));
+        GL_TRY(verify_chunk(v, at, k, stage, verdicts + at, checks ? checks + at : nullptr));
     }
     return GL_OK;
+}
+
+// ---- the generic entry: glfri::check in front of the core, glopen::host_stage as its stage ----
+struct gl_openings_batch_verifier {
+    gl_fri_params params;
+    gl_fri_instance instance;                          // polys points into `polys`
+    std::vector<uint32_t> polys;
+    glopen::Shape shape;
+    glopen::BatchCore* core = nullptr;
+};
+
+extern "C" void gl_openings_batch_verifier_free(gl_openings_batch_verifier* v) noexcept {
+    if (!v) return;
+    glopen::core_free(v->core);
+    delete v;
+}
+
+int glopen::batch_new(gl_ctx* c, const gl_fri_params* params, const gl_fri_instance* instance, uint32_t max_batch, uint32_t host_threads,
+                      gl_openings_batch_verifier** out) {
+    const Names names = {"gl_openings_batch_verifier", "these params", "openings_batch_verify"};
+    GL_REQUIRE(c, GL_ERR_ARG, "gl_openings_batch_verifier_new: null argument");
+    GL_TRY(check_batch(names, max_batch, host_threads));
+    std::unique_ptr<gl_openings_batch_verifier, void (*)(gl_openings_batch_verifier*)> v(new gl_openings_batch_verifier(), gl_openings_batch_verifier_free);
+    GL_REQUIRE(params && instance, GL_ERR_ARG, "FRI openings: null params / instance");
+    // the instance without its points: every claim brings its own (an opening point off the base field passes the coset check)
+    v->params = *params; v->instance = *instance;
+    for (uint32_t b = 0; b < GL_MAX_FRI_BATCHES; b++) { v->instance.points[b][0] = 0; v->instance.points[b][1] = 1; }
+    GL_TRY(shape_of(&v->params, &v->instance, v->shape));
+    const Shape& s = v->shape;
+    v->polys.assign(instance->polys, instance->polys + 2 * s.src.size());
+    v->instance.polys = v->polys.data();
+    GL_TRY(core_new(c, s, max_batch, host_threads, names, &v->core));
+    *out = v.release();
+    return GL_OK;
+}
+
+extern "C" int gl_openings_batch_verifier_new(gl_ctx* c, const gl_fri_params* params, const gl_fri_instance* instance, uint32_t max_batch, uint32_t host_threads,
+                                              gl_openings_batch_verifier** out) try {
+    GL_REQUIRE(out, GL_ERR_ARG, "gl_openings_batch_verifier_new: null argument");
+    *out = nullptr;
+    GL_REQUIRE(c && params && instance, GL_ERR_ARG, "gl_openings_batch_verifier_new: null argument");
+    return glopen::batch_new(c, params, instance, max_batch, host_threads, out);
+} catch (...) { return gl_caught(); }
+
+int glopen::batch_verify(gl_openings_batch_verifier* v, size_t count, const ClaimSource& source, int32_t* verdicts, uint32_t* checks) {
+    return core_verify(v->core, count, [&](size_t lane, size_t i, Lane& L) -> int {
+        gl_openings_claim claim = {};
+        const int st = source(lane, i, claim, &L.check);
+        if (st == GL_ERR_VERIFY) { L.verdict = st; return GL_OK; }
+        if (st != GL_OK) return st;
+        L.caps = claim.caps;
+        return L.judged(host_stage(v->params, v->instance, v->shape, claim.points, claim.caps, claim.openings, claim.challenger, claim.proof, claim.num_bytes, L.T, L.ch, &L.check));
+    }, verdicts, checks);
 }
 
 extern "C" int gl_openings_batch_verifier_verify(gl_openings_batch_verifier* v, const gl_openings_claim* claims, size_t count, int32_t* verdicts,

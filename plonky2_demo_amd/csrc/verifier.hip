@@ -5,8 +5,10 @@
 // Input is exactly what the reference's `VerifierCircuitData::verify` sees: CommonCircuitData (here the gl_circuit_desc),
 // VerifierOnlyCircuitData (constants_sigmas_cap, circuit_digest) and ProofWithPublicInputs::to_bytes().  The proof is
 // checked in place: one pass turns the byte string into a flat table of canonical words plus offsets, and every later
-// step indexes that table.  No GPU is involved.  The checks of the description and the per-proof stage up to the proof of work are
-// functions of their own (verify_stage.hpp): the batch verifier (batch_verify.hip) runs the same ones and gives the queries to the device.
+// step indexes that table.  No GPU is involved.  The checks of the description and the per-proof stage up to the queries are functions
+// of their own (verify_stage.hpp): the batch verifier (batch_verify.hip) runs the same ones and gives the queries to the device.  The
+// FRI half -- decode, challenge draw, reduced openings, query loop -- is one set of functions for a circuit proof and for a FriProof
+// of any FriInstanceInfo (gl_verify_openings at the end of this file; openings_stage.hpp).
 #include "context.hpp"
 #include "host_circuit.hpp"
 #include "fri_instance.hpp"
@@ -24,6 +26,7 @@ inline E e_scale(E x, gl_t s) { return gl2_scalar(x, s); }
 inline bool e_eq(E x, E y) { x = gl2_canon(x); y = gl2_canon(y); return x.a == y.a && x.b == y.b; }
 inline E e_sbox(E x) { E x2 = e_mul(x, x), x4 = e_mul(x2, x2); return e_mul(e_mul(x, x2), x4); }
 inline E e_pow2k(E x, unsigned k) { for (unsigned i = 0; i < k; i++) x = e_mul(x, x); return x; }
+inline E e_pow(E x, size_t k) { E r = e_of(1); for (; k; k >>= 1, x = e_mul(x, x)) if (k & 1) r = e_mul(r, x); return r; }
 
 // ---- Merkle path to a cap (hash/merkle_proofs.rs:54-75; leaf hash plonk/config.rs:55-66) ----
 // `hasher`: C::Hasher.  A HashOut's words compare as field elements; a BytesHash<25>'s as the bytes they are.
@@ -238,6 +241,32 @@ struct Cursor {                                        // little-endian reader o
     unsigned u8() { if (pos >= len) { ok = false; return 0; } return p[pos++]; }
 };
 
+// The decode: proof bytes into the table T, all words in wire order.  Like the reference's read_field (from_canonical_u64 without a
+// range check in release builds) a word >= p is taken mod p.  Both readers return where their words start; once the bytes have run
+// out (in.ok false) nothing more is read, and what T holds from there on is not looked at: the caller rejects the proof as truncated.
+struct Reader {
+    Cursor in; uint32_t hasher; std::vector<gl_t>& T;
+    Reader(const uint8_t* b, size_t n, uint32_t h, std::vector<gl_t>& table) : in(b, n), hasher(h), T(table) { T.clear(); T.reserve(n / 8 + 8); }
+    size_t words(size_t k) {                           // one bounds check and one resize for the run: the decode is a proof's every word
+        const size_t at = T.size();
+        if (!in.ok) return at;
+        if (k > (in.len - in.pos) / 8) { in.ok = false; return at; }
+        T.resize(at + k);
+        Cursor run(in.p + in.pos, 8 * k);
+        for (gl_t* w = T.data() + at; run.pos < run.len; w++) *w = gl_canon(run.u64());
+        in.pos += 8 * k;
+        return at;
+    }
+    // read_hash (util/serialization/mod.rs:1332-1338): k hashes into four-word slots -- a HashOut's four elements, or the 25 bytes of a
+    // BytesHash<25> (raw words, zero padding)
+    size_t hashes(size_t k) {
+        if (hasher != GL_HASHER_KECCAK) return words(4 * k);
+        size_t at = T.size();
+        for (size_t i = 0; i < k && in.ok; i++) { for (int w = 0; w < 3; w++) T.push_back(in.u64()); T.push_back(in.u8()); }
+        return at;
+    }
+};
+
 // every rejection goes through here: the code names the site, the table below holds its text
 int reject(uint32_t check, uint32_t* out = nullptr) {
     if (out) *out = check;
@@ -248,7 +277,138 @@ int reject(uint32_t check, uint32_t* out = nullptr) {
 inline size_t sat_add(size_t a, size_t b) { size_t r; return a == SIZE_MAX || b == SIZE_MAX || __builtin_add_overflow(a, b, &r) ? SIZE_MAX : r; }
 inline size_t sat_mul(size_t a, size_t b) { size_t r; return a == SIZE_MAX || b == SIZE_MAX || __builtin_mul_overflow(a, b, &r) ? SIZE_MAX : r; }
 
+// ---- verify_fri_proof (fri/verifier.rs:62-241, fri/challenges.rs:24-64, fri/validate_shape.rs) on a table T, for the host stages
+// of a circuit proof and of a generic claim and for the two entries' query loop ----
+// The FriProof in write_fri_proof order (util/serialization/mod.rs:1568-1582) up to its final polynomial, appended to T; the check of
+// a path of the wrong length, or GL_CHECK_ACCEPTED (the caller then looks at rd.in.ok)
+uint32_t decode_fri_proof(Reader& rd, const glopen::Shape& s) {
+    (void)rd.hashes((size_t)s.num_rounds * s.ncap);
+    for (uint32_t q = 0; q < s.num_queries && rd.in.ok; q++) {
+        unsigned init_nsib[GL_MAX_FRI_ORACLES];
+        for (uint32_t o = 0; o < s.num_oracles; o++) {
+            (void)rd.words(s.slot_leaf_len[o]);
+            init_nsib[o] = rd.in.u8(); (void)rd.hashes(init_nsib[o]);
+        }
+        unsigned lg_cur = s.lgN;
+        for (unsigned r = 0; r < s.num_rounds; r++) {
+            (void)rd.words(size_t(2) << s.arity_bits[r]);
+            const unsigned nsib = rd.in.u8(); (void)rd.hashes(nsib);
+            lg_cur -= s.arity_bits[r];
+            if (rd.in.ok && nsib + s.cap_height != lg_cur) return GL_CHECK_STEP_PATH_LENGTH;
+        }
+        for (uint32_t o = 0; o < s.num_oracles && rd.in.ok; o++)
+            if (init_nsib[o] + s.cap_height != s.lgN) return GL_CHECK_INITIAL_PATH_LENGTH;
+    }
+    (void)rd.words(2 * s.final_len);
+    return GL_CHECK_ACCEPTED;
+}
+
+// FriChallenges (fri/challenges.rs:24-64) from the transcript behind the observed openings: alpha, per reduction its cap and beta,
+// the final polynomial, the proof-of-work witness, the query indices.  Returns the proof-of-work response for pow_holds.
+gl_t draw_fri_challenges(glhost::HostChallenger& tr, const glopen::Shape& s, const gl_t* T, gl_t pow_witness, glopen::Challenges& ch) {
+    ch.alpha = tr.challenge_ext();
+    for (unsigned r = 0; r < s.num_rounds; r++) { tr.observe_hashes(s.hasher, T + s.o_fcaps + (size_t)r * 4 * s.ncap, s.ncap); ch.betas[r] = tr.challenge_ext(); }
+    for (unsigned r = s.num_rounds; r < glopen::MAX_FRI_ROUNDS; r++) ch.betas[r] = e_of(0);
+    tr.observe_many(T + s.o_final, 2 * s.final_len);
+    tr.observe(pow_witness);
+    const gl_t pow_response = tr.challenge();
+    ch.x_index.resize(s.num_queries);
+    for (auto& x : ch.x_index) x = tr.challenge() % (uint64_t(1) << s.lgN);
+    return pow_response;
+}
+inline bool pow_holds(gl_t pow_response, uint32_t bits) { return pow_response == 0 || (unsigned)__builtin_clzll(pow_response) >= bits; }
+
+// PrecomputedReducedOpenings (fri/verifier.rs:243-260): per batch Horner in alpha over its opened values (`openings`: extension
+// values as word pairs, flat in batch order); alpha^len of each batch; its point
+void reduce_openings(const glopen::Shape& s, const uint64_t* openings, const uint64_t (*points)[2], glopen::Challenges& ch) {
+    for (uint32_t b = 0; b < GL_MAX_FRI_BATCHES; b++) {
+        E acc = e_of(0);
+        if (b < s.num_batches)
+            for (size_t j = s.first[b + 1]; j-- > s.first[b];) acc = e_add(e_mul(acc, ch.alpha), gl2_make(gl_canon(openings[2 * j]), gl_canon(openings[2 * j + 1])));
+        ch.red[b] = acc; ch.alpha_len[b] = b < s.num_batches ? e_pow(ch.alpha, s.first[b + 1] - s.first[b]) : e_of(1);
+        ch.point[b] = b < s.num_batches ? gl2_make(gl_canon(points[b][0]), gl_canon(points[b][1])) : e_of(0);
+    }
+}
+
+// The queries (fri/verifier.rs:163-241) of a proof that passed a host stage; k_verify_paths_any and k_verify_openings_queries are this
+// loop on the device.  caps[o]: the cap of initial tree o.
+int verify_fri_queries(const glopen::Shape& s, const gl_t* T, const glopen::Challenges& ch, const gl_t* const caps[], uint32_t* check) {
+    auto ext_at = [&](size_t off, size_t i) { return gl2_make(T[off + 2 * i], T[off + 2 * i + 1]); };
+    const gl_t wN = glhost::root_of_unity(s.lgN);
+    const E alpha = ch.alpha;
+    const uint32_t* src = s.src.data();
+    for (uint32_t q = 0; q < s.num_queries; q++) {
+        size_t x = ch.x_index[q];
+        for (uint32_t o = 0; o < s.num_oracles; o++)
+            if (!path_opens_to_cap(s.hasher, &T[s.leaf_at(q, o)], s.slot_leaf_len[o], x, &T[s.sib_at(q, o)], s.slot_nsib[o], caps[o], s.ncap))
+                return reject(GL_CHECK_INITIAL_MERKLE, check);
+        // subgroup_x = g * w_N^{reverse_bits(x_index)} (fri/verifier.rs:183-186)
+        size_t rev = 0;
+        for (unsigned i = 0; i < s.lgN; i++) rev |= ((x >> i) & 1) << (s.lgN - 1 - i);
+        gl_t subgroup_x = gl_canon(gl_mul(GL_MULT_GENERATOR, gl_exp(wN, rev)));
+        // fri_combine_initial (fri/verifier.rs:122-161): per batch Horner in alpha from its last polynomial to its first.  A polynomial's
+        // index is below its oracle's column count, so only the unsalted prefix of a leaf is read (unsalted_eval)
+        const gl_t* Q = &T[s.o_query0 + q * s.query_stride];
+        const E sx = e_of(subgroup_x);
+        E eval = e_of(0);
+        for (uint32_t b = 0; b < s.num_batches; b++) {
+            E h = e_of(0);
+            for (size_t j = s.first[b + 1], j0 = s.first[b]; j-- > j0;) h = e_add(e_mul(h, alpha), e_of(Q[src[j]]));
+            eval = e_add(e_mul(eval, ch.alpha_len[b]), e_mul(e_sub(h, ch.red[b]), gl2_inv(e_sub(sx, ch.point[b]))));
+        }
+        for (unsigned r = 0; r < s.num_rounds; r++) {
+            const unsigned ab = s.arity_bits[r];
+            const uint32_t slot = s.num_oracles + r;
+            const size_t arity = size_t(1) << ab, coset = x >> ab, within = x & (arity - 1), leaf = s.leaf_at(q, slot);
+            if (!e_eq(ext_at(leaf, within), eval)) return reject(GL_CHECK_FRI_CONSISTENCY, check);
+            eval = compute_evaluation(subgroup_x, within, ab, &T[leaf], ch.betas[r]);
+            if (!path_opens_to_cap(s.hasher, &T[leaf], s.slot_leaf_len[slot], coset, &T[s.sib_at(q, slot)], s.slot_nsib[slot], &T[s.o_fcaps + (size_t)r * 4 * s.ncap], s.ncap))
+                return reject(GL_CHECK_STEP_MERKLE, check);
+            for (unsigned i = 0; i < ab; i++) subgroup_x = gl_sqr(subgroup_x);
+            x = coset;
+        }
+        E fin = e_of(0);
+        const E sxf = e_of(gl_canon(subgroup_x));
+        for (size_t i = s.final_len; i-- > 0;) fin = e_add(e_mul(fin, sxf), ext_at(s.o_final, i));
+        if (!e_eq(fin, eval)) return reject(GL_CHECK_FINAL_POLY, check);
+    }
+    return GL_OK;
+}
+
+// the polynomials of fri_openings() (prove.hip; circuit_data.rs:564-597) as (oracle, polynomial) pairs: batch 0 at zeta = constants and
+// sigmas, wires, Z and partial products, quotient, then the lookup polynomials (last in both batches); batch 1 at g zeta = Z, lookups
+void plonk_polys(size_t ncs, size_t nlk, uint32_t batch_len[2], std::vector<uint32_t>& polys) {
+    auto add = [&](uint32_t o, size_t first, size_t count) { for (size_t c = first; c < first + count; c++) { polys.push_back(o); polys.push_back((uint32_t)c); } };
+    add(0, 0, ncs); add(1, 0, 135); add(2, 0, 20); add(3, 0, 16); add(2, 20, nlk);
+    batch_len[0] = (uint32_t)(polys.size() / 2);
+    add(2, 0, 2); add(2, 20, nlk);
+    batch_len[1] = (uint32_t)(polys.size() / 2) - batch_len[0];
+}
+
 }  // namespace
+
+void glopen::lay_out(Shape& s, const size_t* leaf_lens, const uint32_t* batch_len, const uint32_t* polys, size_t base) {
+    size_t in_query = 0;
+    unsigned lg_cur = s.lgN;
+    for (uint32_t slot = 0; slot < s.num_slots(); slot++) {
+        if (slot >= s.num_oracles) {
+            lg_cur -= s.arity_bits[slot - s.num_oracles];
+            if (lg_cur < s.cap_height) { s.paths_fit = false; break; }
+        }
+        s.slot_leaf[slot] = in_query; s.slot_leaf_len[slot] = slot < s.num_oracles ? leaf_lens[slot] : size_t(2) << s.arity_bits[slot - s.num_oracles];
+        s.slot_nsib[slot] = lg_cur - s.cap_height;
+        s.slot_sib[slot] = sat_add(in_query, s.slot_leaf_len[slot]);
+        in_query = sat_add(s.slot_sib[slot], 4 * s.slot_nsib[slot]);
+    }
+    s.query_stride = in_query;
+    s.o_fcaps = base;
+    s.o_query0 = sat_add(base, (size_t)s.num_rounds * 4 * s.ncap);
+    s.o_final = sat_add(s.o_query0, sat_mul(in_query, s.num_queries));
+    s.t_words = sat_add(s.o_final, 2 * s.final_len);
+    for (uint32_t b = 0; b < s.num_batches; b++) s.first[b + 1] = s.first[b] + batch_len[b];
+    s.src.resize(s.first[s.num_batches]);
+    for (size_t j = 0; j < s.src.size(); j++) s.src[j] = (uint32_t)(s.slot_leaf[polys[2 * j]] + polys[2 * j + 1]);
+}
 
 const char* glverify::check_message(uint32_t check) noexcept {
     switch (check) {
@@ -288,115 +448,71 @@ int glverify::shape_of(const gl_circuit_desc& d, size_t num_bytes, Shape& s) {
     GL_REQUIRE(!glhost::gate_list_fault(d), GL_ERR_ARG, "gl_verify: bad gate / selector description");
     const size_t nch = 2, R = 80, W = 135, QF = 8, NPP = 9;            // partial products per challenge: ceil(80 / 8) - 1
     s = Shape();
-    s.hasher = d.hasher; s.num_queries = d.num_query_rounds; s.num_rounds = d.num_fri_rounds; s.cap_height = d.cap_height;
-    s.lgn = d.degree_bits; s.lgN = s.lgn + d.rate_bits;
-    s.ncap = size_t(1) << d.cap_height; s.num_constants = d.num_constants; s.num_public_inputs = d.num_public_inputs;
+    glopen::Shape& f = s.fri;
+    f.hasher = d.hasher; f.num_queries = d.num_query_rounds; f.num_rounds = d.num_fri_rounds; f.cap_height = d.cap_height;
+    f.num_oracles = 4; f.num_batches = 2;
+    s.lgn = d.degree_bits; f.lgN = s.lgn + d.rate_bits;
+    f.ncap = size_t(1) << d.cap_height; s.num_constants = d.num_constants; s.num_public_inputs = d.num_public_inputs;
     unsigned total_arity = 0;
     for (unsigned r = 0; r < d.num_fri_rounds; r++) {
         GL_REQUIRE(d.fri_arity_bits[r] >= 1 && d.fri_arity_bits[r] <= 8, GL_ERR_ARG, "gl_verify: bad FRI arity");
-        total_arity += d.fri_arity_bits[r]; s.arity_bits[r] = d.fri_arity_bits[r];
+        total_arity += d.fri_arity_bits[r]; f.arity_bits[r] = d.fri_arity_bits[r];
     }
     GL_REQUIRE(total_arity <= s.lgn, GL_ERR_ARG, "gl_verify: FRI reduces below the final polynomial");
-    s.final_len = size_t(1) << (s.lgn - total_arity);
+    f.final_len = size_t(1) << (s.lgn - total_arity);
     s.nlp = d.num_lookup_polys;                                         // lookup polynomials per challenge, behind Z and the partial products
-    s.nzp = nch * (1 + NPP);
     const size_t ncs = (size_t)d.num_constants + R;
-    const size_t widths[4] = {ncs, W, s.nzp + nch * s.nlp, nch * QF};
     // hiding: the leaves of the wires, Z / partial-products and quotient trees end in SALT_SIZE = 4 salt elements (mod.rs:431-456)
     const size_t salt = d.zero_knowledge ? 4 : 0;
-    for (int o = 0; o < 4; o++) { s.widths[o] = widths[o]; s.leaf_lens[o] = widths[o] + (o ? salt : 0); }
+    const size_t leaf_lens[4] = {ncs, W + salt, nch * (1 + NPP + s.nlp) + salt, nch * QF + salt};
     // the table in wire order (util/serialization/mod.rs:1939-1981; OpeningSet mod.rs:1409-1423: the lookup vectors sit between zs_next
-    // and the partial products)
+    // and the partial products), the FriProof behind the openings
     size_t at = 0;
     auto take = [&](size_t k) { const size_t here = at; at = sat_add(at, k); return here; };
-    s.o_caps = take(3 * 4 * s.ncap);
+    s.o_caps = take(3 * 4 * f.ncap);
     s.o_const = take(2 * s.num_constants); s.o_sig = take(2 * R); s.o_wires = take(2 * W); s.o_zs = take(2 * nch); s.o_zsn = take(2 * nch);
     s.o_lk = take(2 * nch * s.nlp); s.o_lkn = take(2 * nch * s.nlp); s.o_pp = take(2 * nch * NPP); s.o_quot = take(2 * nch * QF);
-    s.o_fcaps = take((size_t)d.num_fri_rounds * 4 * s.ncap);
-    s.o_query0 = at;
-    size_t in_query = 0;
-    for (uint32_t o = 0; o < NUM_INITIAL_TREES; o++) {
-        s.slot_leaf[o] = in_query; s.slot_leaf_len[o] = s.leaf_lens[o]; s.slot_nsib[o] = s.lgN - d.cap_height;
-        s.slot_sib[o] = in_query + s.leaf_lens[o];
-        in_query = s.slot_sib[o] + 4 * s.slot_nsib[o];
-    }
-    unsigned lg_cur = s.lgN;
-    for (unsigned r = 0; r < d.num_fri_rounds; r++) {
-        const uint32_t slot = NUM_INITIAL_TREES + r;
-        lg_cur -= d.fri_arity_bits[r];
-        if (lg_cur < d.cap_height) { s.paths_fit = false; break; }
-        s.slot_leaf[slot] = in_query; s.slot_leaf_len[slot] = size_t(2) << d.fri_arity_bits[r]; s.slot_nsib[slot] = lg_cur - d.cap_height;
-        s.slot_sib[slot] = in_query + s.slot_leaf_len[slot];
-        in_query = s.slot_sib[slot] + 4 * s.slot_nsib[slot];
-    }
-    s.query_stride = in_query;
-    (void)take(sat_mul(in_query, d.num_query_rounds));
-    s.o_final = take(2 * s.final_len);
-    s.o_pis = take(d.num_public_inputs);
-    s.t_words = at;
+    uint32_t batch_len[2];
+    std::vector<uint32_t> polys;
+    plonk_polys(ncs, nch * s.nlp, batch_len, polys);
+    glopen::lay_out(f, leaf_lens, batch_len, polys.data(), at);
+    s.o_pis = f.t_words;
+    s.t_words = sat_add(s.o_pis, d.num_public_inputs);
     return GL_OK;
 }
 
 int glverify::host_stage(const gl_circuit_desc& d, const Shape& s, const uint64_t* constants_sigmas_cap, const uint64_t circuit_digest[4],
-                         const uint8_t* proof_bytes, size_t num_bytes, std::vector<gl_t>& T, Challenges& ch, uint32_t* check) {
+                         const uint8_t* proof_bytes, size_t num_bytes, std::vector<gl_t>& T, glopen::Challenges& ch, uint32_t* check) {
     const size_t nch = 2, R = 80, W = 135, QF = 8, NPP = 9;
-    const size_t ncap = s.ncap, NLP = s.nlp, final_len = s.final_len;
-    const unsigned lgn = s.lgn, lgN = s.lgN;
-    const size_t n = size_t(1) << lgn, N = size_t(1) << lgN;
+    const glopen::Shape& f = s.fri;
+    const size_t ncap = f.ncap, NLP = s.nlp;
+    const unsigned lgn = s.lgn;
+    const size_t n = size_t(1) << lgn;
     *check = GL_CHECK_ACCEPTED;
 
     // ---- decode (util/serialization/mod.rs:1939-1981 read side, plonk/validate_shape.rs, fri/validate_shape.rs) ----
-    // like the reference's read_field (from_canonical_u64 without a range check in release builds) a word >= p is taken mod p
-    Cursor in(proof_bytes, num_bytes);
-    T.clear();                                         // all words of the proof in wire order, canonical
-    T.reserve(num_bytes / 8 + 8);
-    auto words = [&](size_t k) { size_t at = T.size(); for (size_t i = 0; i < k && in.ok; i++) T.push_back(gl_canon(in.u64())); return at; };
-    // read_hash (util/serialization/mod.rs:1332-1338): k hashes into four-word slots -- a HashOut's four elements, or the 25 bytes of a
-    // BytesHash<25> (raw words, zero padding)
     const uint32_t hasher = d.hasher;
-    auto hashes = [&](size_t k) {
-        if (hasher != GL_HASHER_KECCAK) return words(4 * k);
-        size_t at = T.size();
-        for (size_t i = 0; i < k && in.ok; i++) { for (int w = 0; w < 3; w++) T.push_back(in.u64()); T.push_back(in.u8()); }
-        return at;
-    };
+    Reader rd(proof_bytes, num_bytes, hasher, T);
     // the verifier data's own hashes arrive in four-word slots
     if (!glhost::hashes_well_formed(hasher, constants_sigmas_cap, ncap) || !glhost::hashes_well_formed(hasher, circuit_digest, 1))
         return reject(GL_CHECK_VERIFIER_DATA, check);
-    const size_t o_caps = hashes(3 * ncap);
+    const size_t o_caps = rd.hashes(3 * ncap);
     // OpeningSet in wire order (mod.rs:1409-1423): the lookup vectors sit between zs_next and the partial products
-    const size_t o_const = words(2 * d.num_constants), o_sig = words(2 * R), o_wires = words(2 * W), o_zs = words(2 * nch), o_zsn = words(2 * nch),
-                 o_lk = words(2 * nch * NLP), o_lkn = words(2 * nch * NLP), o_pp = words(2 * nch * NPP), o_quot = words(2 * nch * QF);
-    const size_t o_fcaps = hashes((size_t)d.num_fri_rounds * ncap);
-    size_t o_query0 = T.size();
-    for (unsigned q = 0; q < d.num_query_rounds && in.ok; q++) {
-        unsigned init_nsib[4];
-        if (q == 0) o_query0 = T.size();
-        for (int o = 0; o < 4; o++) {
-            (void)words(s.leaf_lens[o]);
-            init_nsib[o] = in.u8(); (void)hashes(init_nsib[o]);
-        }
-        unsigned lg_cur = lgN;
-        for (unsigned r = 0; r < d.num_fri_rounds; r++) {
-            (void)words(size_t(2) << d.fri_arity_bits[r]);
-            const unsigned nsib = in.u8(); (void)hashes(nsib);
-            lg_cur -= d.fri_arity_bits[r];
-            if (in.ok && nsib + d.cap_height != lg_cur) return reject(GL_CHECK_STEP_PATH_LENGTH, check);
-        }
-        for (int o = 0; o < 4 && in.ok; o++)
-            if (init_nsib[o] + d.cap_height != lgN) return reject(GL_CHECK_INITIAL_PATH_LENGTH, check);
-    }
-    const size_t o_final = words(2 * final_len);
-    const gl_t pow_witness = gl_canon(in.u64());
-    const uint64_t npis = in.u64();
-    if (!in.ok) return reject(GL_CHECK_TRUNCATED, check);
+    const size_t o_const = rd.words(2 * d.num_constants), o_sig = rd.words(2 * R), o_wires = rd.words(2 * W), o_zs = rd.words(2 * nch), o_zsn = rd.words(2 * nch),
+                 o_lk = rd.words(2 * nch * NLP), o_lkn = rd.words(2 * nch * NLP), o_pp = rd.words(2 * nch * NPP), o_quot = rd.words(2 * nch * QF);
+    const size_t o_fcaps = T.size();
+    if (const uint32_t bad = decode_fri_proof(rd, f)) return reject(bad, check);
+    const gl_t pow_witness = gl_canon(rd.in.u64());
+    const uint64_t npis = rd.in.u64();
+    if (!rd.in.ok) return reject(GL_CHECK_TRUNCATED, check);
     if (npis != d.num_public_inputs) return reject(GL_CHECK_PUBLIC_INPUT_COUNT, check);
-    const size_t o_pis = words(npis);
-    if (!in.ok || in.pos != num_bytes) return reject(GL_CHECK_LENGTH, check);
-    // every path has the length the description gives it, so the table lies where the shape says (what the queries index by)
-    GL_REQUIRE(s.paths_fit && T.size() == s.t_words && o_caps == s.o_caps && o_const == s.o_const && o_sig == s.o_sig && o_wires == s.o_wires &&
+    const size_t o_pis = rd.words(npis);
+    if (!rd.in.ok || rd.in.pos != num_bytes) return reject(GL_CHECK_LENGTH, check);
+    // every path has the length the description gives it, so the table lies where the shape says (what the queries index by).  The
+    // FriProof's own places are not compared one by one: decode_fri_proof walks the shape's counts, so its end says all of them
+    GL_REQUIRE(f.paths_fit && T.size() == s.t_words && o_caps == s.o_caps && o_const == s.o_const && o_sig == s.o_sig && o_wires == s.o_wires &&
                o_zs == s.o_zs && o_zsn == s.o_zsn && o_lk == s.o_lk && o_lkn == s.o_lkn && o_pp == s.o_pp && o_quot == s.o_quot &&
-               o_fcaps == s.o_fcaps && o_query0 == s.o_query0 && o_final == s.o_final && o_pis == s.o_pis,
+               o_fcaps == f.o_fcaps && o_pis == s.o_pis,
                GL_ERR_INTERNAL, "gl_verify: the decoded proof does not lie where its description puts it");
     auto ext_at = [&](size_t off, size_t i) { return gl2_make(T[off + 2 * i], T[off + 2 * i + 1]); };
 
@@ -415,18 +531,15 @@ int glverify::host_stage(const gl_circuit_desc& d, const Shape& s, const uint64_
     for (auto& a : alphas) a = tr.challenge();
     tr.observe_hashes(hasher, &T[o_caps + 8 * ncap], ncap);
     const E zeta = tr.challenge_ext();
-    // FriOpenings (plonk/proof.rs:346-380): constants, sigmas, wires, zs, partial products, quotient at zeta; zs_next at g zeta
-    tr.observe_many(&T[o_const], 2 * d.num_constants); tr.observe_many(&T[o_sig], 2 * R); tr.observe_many(&T[o_wires], 2 * W); tr.observe_many(&T[o_zs], 2 * nch);
-    tr.observe_many(&T[o_pp], 2 * nch * NPP); tr.observe_many(&T[o_quot], 2 * nch * QF); tr.observe_many(&T[o_lk], 2 * nch * NLP);
-    tr.observe_many(&T[o_zsn], 2 * nch); tr.observe_many(&T[o_lkn], 2 * nch * NLP);
-    const E fri_alpha = tr.challenge_ext();
-    for (unsigned r = 0; r < d.num_fri_rounds; r++) { tr.observe_hashes(hasher, &T[o_fcaps + (size_t)r * 4 * ncap], ncap); ch.fri_betas[r] = tr.challenge_ext(); }
-    for (unsigned r = d.num_fri_rounds; r < MAX_FRI_ROUNDS; r++) ch.fri_betas[r] = e_of(0);
-    tr.observe_many(&T[o_final], 2 * final_len);
-    tr.observe(pow_witness);
-    const gl_t pow_response = tr.challenge();
-    ch.x_index.resize(d.num_query_rounds);
-    for (auto& x : ch.x_index) x = tr.challenge() % (uint64_t)N;
+    // FriOpenings (plonk/proof.rs:346-380) in the instance's batch order, which is also the order the transcript observes them in:
+    // constants, sigmas, wires, zs, partial products, quotient, lookups at zeta; zs_next, lookups_next at g zeta
+    std::vector<gl_t> opened;
+    opened.reserve(o_fcaps - o_const);
+    auto put = [&](size_t off, size_t count) { opened.insert(opened.end(), T.data() + off, T.data() + off + 2 * count); };
+    put(o_const, d.num_constants); put(o_sig, R); put(o_wires, W); put(o_zs, nch); put(o_pp, nch * NPP); put(o_quot, nch * QF); put(o_lk, nch * NLP);
+    put(o_zsn, nch); put(o_lkn, nch * NLP);
+    tr.observe_many(opened.data(), opened.size());
+    const gl_t pow_response = draw_fri_challenges(tr, f, T.data(), pow_witness, ch);
 
     // ---- vanishing(zeta) == Z_H(zeta) * t(zeta) per challenge (plonk/verifier.rs:64-101, vanishing_poly.rs:54-160) ----
     {
@@ -518,19 +631,10 @@ int glverify::host_stage(const gl_circuit_desc& d, const Shape& s, const uint64_
     }
 
     // ---- FRI (fri/verifier.rs:62-260): the proof of work, and what every query needs ----
-    if (pow_response != 0 && (unsigned)__builtin_clzll(pow_response) < d.proof_of_work_bits) return reject(GL_CHECK_POW, check);
-    ch.zeta = zeta; ch.fri_alpha = fri_alpha;
-    ch.gzeta = e_scale(zeta, glhost::root_of_unity(lgn));
-    // PrecomputedReducedOpenings (fri/verifier.rs:243-260): Horner in fri_alpha over batch 0 = constants, sigmas, wires, zs, partial products,
-    // quotient, then the lookup polynomials (last in both batches: circuit_data.rs:564-597), and batch 1 = zs_next, lookups_next
-    E red0 = e_of(0), red1 = e_of(0);
-    auto horner = [&](E& acc, size_t off, size_t count) { for (size_t i = count; i-- > 0;) acc = e_add(e_mul(acc, fri_alpha), ext_at(off, i)); };
-    horner(red0, o_lk, nch * NLP); horner(red0, o_quot, nch * QF); horner(red0, o_pp, nch * NPP); horner(red0, o_zs, nch);
-    horner(red0, o_wires, W); horner(red0, o_sig, R); horner(red0, o_const, d.num_constants);
-    horner(red1, o_lkn, nch * NLP); horner(red1, o_zsn, nch);
-    ch.red0 = red0; ch.red1 = red1;
-    ch.alpha_shift = e_of(1);
-    for (size_t i = 0; i < nch + nch * NLP; i++) ch.alpha_shift = e_mul(ch.alpha_shift, fri_alpha);
+    if (!pow_holds(pow_response, d.proof_of_work_bits)) return reject(GL_CHECK_POW, check);
+    const E gzeta = e_scale(zeta, glhost::root_of_unity(lgn));
+    const uint64_t points[2][2] = {{zeta.a, zeta.b}, {gzeta.a, gzeta.b}};
+    reduce_openings(f, opened.data(), points, ch);
     return GL_OK;
 }
 
@@ -543,53 +647,11 @@ extern "C" int gl_verify(const gl_circuit_desc* desc, const uint64_t* constants_
     glverify::Shape s;
     GL_TRY(glverify::shape_of(d, num_bytes, s));
     std::vector<gl_t> T;
-    glverify::Challenges ch;
+    glopen::Challenges ch;
     uint32_t check;
     GL_TRY(glverify::host_stage(d, s, constants_sigmas_cap, circuit_digest, proof_bytes, num_bytes, T, ch, &check));
-    auto ext_at = [&](size_t off, size_t i) { return gl2_make(T[off + 2 * i], T[off + 2 * i + 1]); };
-    const size_t ncap = s.ncap, nch = 2;
-    const unsigned lgN = s.lgN;
-    const E zeta = ch.zeta, gzeta = ch.gzeta, fri_alpha = ch.fri_alpha;
-
-    // ---- the queries (fri/verifier.rs:167-241); k_verify_merkle_paths and k_verify_fri_queries are this loop on the device ----
-    const gl_t* caps[4] = {constants_sigmas_cap, &T[s.o_caps], &T[s.o_caps + 4 * ncap], &T[s.o_caps + 8 * ncap]};
-    const gl_t wN = glhost::root_of_unity(lgN);
-    for (unsigned q = 0; q < d.num_query_rounds; q++) {
-        size_t x = ch.x_index[q];
-        for (uint32_t o = 0; o < 4; o++)
-            if (!path_opens_to_cap(d.hasher, &T[s.leaf_at(q, o)], s.slot_leaf_len[o], x, &T[s.sib_at(q, o)], s.slot_nsib[o], caps[o], ncap)) return reject(GL_CHECK_INITIAL_MERKLE);
-        // subgroup_x = g * w_N^{reverse_bits(x_index)} (fri/verifier.rs:183-186)
-        size_t rev = 0;
-        for (unsigned i = 0; i < lgN; i++) rev |= ((x >> i) & 1) << (lgN - 1 - i);
-        gl_t subgroup_x = gl_canon(gl_mul(GL_MULT_GENERATOR, gl_exp(wN, rev)));
-        // fri_combine_initial (fri/verifier.rs:124-165): batch 0 = every polynomial at zeta, batch 1 = the Z polynomials at g zeta; the
-        // unsalted prefix of each leaf only (unsalted_eval); Horner in fri_alpha from the last polynomial of a batch to its first, the
-        // lookup polynomials last in both
-        const size_t leaf2 = s.leaf_at(q, 2);
-        E h0 = e_of(0), h1 = e_of(0);
-        auto horner = [&](E& acc, size_t off, size_t first, size_t last) { for (size_t i = last; i-- > first;) acc = e_add(e_mul(acc, fri_alpha), e_of(T[off + i])); };
-        horner(h0, leaf2, s.nzp, s.widths[2]);
-        for (uint32_t o = 4; o-- > 0;) horner(h0, s.leaf_at(q, o), 0, o == 2 ? s.nzp : s.widths[o]);
-        horner(h1, leaf2, s.nzp, s.widths[2]); horner(h1, leaf2, 0, nch);
-        const E sx = e_of(subgroup_x);
-        E eval = e_mul(e_sub(h0, ch.red0), gl2_inv(e_sub(sx, zeta)));
-        eval = e_add(e_mul(eval, ch.alpha_shift), e_mul(e_sub(h1, ch.red1), gl2_inv(e_sub(sx, gzeta))));
-        for (unsigned r = 0; r < d.num_fri_rounds; r++) {
-            const unsigned ab = d.fri_arity_bits[r];
-            const uint32_t slot = glverify::NUM_INITIAL_TREES + r;
-            const size_t arity = size_t(1) << ab, coset = x >> ab, within = x & (arity - 1), leaf = s.leaf_at(q, slot);
-            if (!e_eq(ext_at(leaf, within), eval)) return reject(GL_CHECK_FRI_CONSISTENCY);
-            eval = compute_evaluation(subgroup_x, within, ab, &T[leaf], ch.fri_betas[r]);
-            if (!path_opens_to_cap(d.hasher, &T[leaf], s.slot_leaf_len[slot], coset, &T[s.sib_at(q, slot)], s.slot_nsib[slot], &T[s.o_fcaps + (size_t)r * 4 * ncap], ncap)) return reject(GL_CHECK_STEP_MERKLE);
-            for (unsigned i = 0; i < ab; i++) subgroup_x = gl_sqr(subgroup_x);
-            x = coset;
-        }
-        E fin = e_of(0);
-        const E sxf = e_of(gl_canon(subgroup_x));
-        for (size_t i = s.final_len; i-- > 0;) fin = e_add(e_mul(fin, sxf), ext_at(s.o_final, i));
-        if (!e_eq(fin, eval)) return reject(GL_CHECK_FINAL_POLY);
-    }
-    return GL_OK;
+    const gl_t* caps[4] = {constants_sigmas_cap, &T[s.o_caps], &T[s.o_caps + 4 * s.fri.ncap], &T[s.o_caps + 8 * s.fri.ncap]};
+    return verify_fri_queries(s.fri, T.data(), ch, caps, nullptr);
 } catch (...) { return gl_caught(); }
 
 // convenience for callers that hold the host circuit: CircuitData::verify (plonk/circuit_data.rs:153-155)
@@ -599,11 +661,7 @@ extern "C" int gl_host_circuit_verify(const gl_host_circuit* hc, const uint64_t*
     return gl_verify(&hc->hc.desc, constants_sigmas_cap, circuit_digest, proof_bytes, num_bytes);
 } catch (...) { return gl_caught(); }
 
-// ---- verify_fri_proof for any FriInstanceInfo (fri/verifier.rs:62-241, fri/challenges.rs:24-64, fri/validate_shape.rs) ----
-// The FriProof alone, in write_fri_proof order (util/serialization/mod.rs:1568-1582), on the caller's Challenger.  gl_verify above keeps
-// its own query loop over the Plonk layout; the two share path_opens_to_cap, compute_evaluation, the Cursor and the rejection table.
-// Like gl_verify it is two halves (openings_stage.hpp): the shape and the host stage, which the device batch verifier
-// (openings_verify.hip) runs as well, and the query loop over the table T.
+// ---- verify_fri_proof for any FriInstanceInfo: the FriProof alone, on the caller's Challenger ----
 int glopen::shape_of(const gl_fri_params* params, const gl_fri_instance* instance, Shape& s) {
     GL_TRY(glfri::check(params, instance, false));
     const gl_fri_params& p = *params; const gl_fri_instance& in = *instance;
@@ -613,28 +671,9 @@ int glopen::shape_of(const gl_fri_params* params, const gl_fri_instance* instanc
     s.ncap = size_t(1) << p.cap_height;
     s.final_len = size_t(1) << p.degree_bits;
     for (unsigned r = 0; r < p.num_fri_rounds; r++) { s.arity_bits[r] = p.fri_arity_bits[r]; s.final_len >>= p.fri_arity_bits[r]; }
-    size_t in_query = 0;
-    for (uint32_t o = 0; o < in.num_oracles; o++) {
-        s.slot_leaf[o] = in_query; s.slot_leaf_len[o] = (size_t)in.oracle_num_polys[o] + glfri::salt_of(p, in, o); s.slot_nsib[o] = s.lgN - p.cap_height;
-        s.slot_sib[o] = in_query + s.slot_leaf_len[o];
-        in_query = s.slot_sib[o] + 4 * s.slot_nsib[o];
-    }
-    unsigned lg_cur = s.lgN;
-    for (unsigned r = 0; r < p.num_fri_rounds; r++) {             // (glfri::check: the reductions stay above the cap)
-        const uint32_t slot = in.num_oracles + r;
-        lg_cur -= p.fri_arity_bits[r];
-        s.slot_leaf[slot] = in_query; s.slot_leaf_len[slot] = size_t(2) << p.fri_arity_bits[r]; s.slot_nsib[slot] = lg_cur - p.cap_height;
-        s.slot_sib[slot] = in_query + s.slot_leaf_len[slot];
-        in_query = s.slot_sib[slot] + 4 * s.slot_nsib[slot];
-    }
-    s.query_stride = in_query;
-    s.o_fcaps = 0;
-    s.o_query0 = (size_t)p.num_fri_rounds * 4 * s.ncap;
-    s.o_final = s.o_query0 + in_query * p.num_query_rounds;
-    s.t_words = s.o_final + 2 * s.final_len;
-    for (uint32_t b = 0; b < in.num_batches; b++) s.first[b + 1] = s.first[b] + in.batch_len[b];
-    s.src.resize(s.first[in.num_batches]);
-    for (size_t j = 0; j < s.src.size(); j++) s.src[j] = (uint32_t)(s.slot_leaf[in.polys[2 * j]] + in.polys[2 * j + 1]);
+    size_t leaf_lens[GL_MAX_FRI_ORACLES];
+    for (uint32_t o = 0; o < in.num_oracles; o++) leaf_lens[o] = (size_t)in.oracle_num_polys[o] + glfri::salt_of(p, in, o);
+    lay_out(s, leaf_lens, in.batch_len, in.polys, 0);             // (glfri::check: the reductions stay above the cap)
     return GL_OK;
 }
 
@@ -646,71 +685,17 @@ int glopen::host_stage(const gl_fri_params& p, const gl_fri_instance& in, const 
     GL_TRY(glfri::check_points(p, in.num_batches, points));
     GL_REQUIRE(caps && openings && challenger && proof_bytes, GL_ERR_ARG, "gl_verify_openings: null argument");
     GL_REQUIRE(challenger->ch.hasher == p.hasher, GL_ERR_ARG, "gl_verify_openings: the challenger runs under another hasher than the params'");
-    const uint32_t hasher = p.hasher, no = in.num_oracles, B = in.num_batches, nq = p.num_query_rounds;
-    const unsigned lgN = s.lgN;
-    const size_t N = size_t(1) << lgN, ncap = s.ncap, final_len = s.final_len;
-    if (!glhost::hashes_well_formed(hasher, caps, no * ncap)) return reject(GL_CHECK_VERIFIER_DATA, check);
-
-    // ---- decode: words canonical (read_field takes a word >= p mod p), 25-byte hashes in four-word slots ----
-    Cursor cur(proof_bytes, num_bytes);
-    T.clear();
-    T.reserve(num_bytes / 8 + 8);
-    auto words = [&](size_t k) { size_t at = T.size(); for (size_t i = 0; i < k && cur.ok; i++) T.push_back(gl_canon(cur.u64())); return at; };
-    auto hashes = [&](size_t k) {
-        if (hasher != GL_HASHER_KECCAK) return words(4 * k);
-        size_t at = T.size();
-        for (size_t i = 0; i < k && cur.ok; i++) { for (int w = 0; w < 3; w++) T.push_back(cur.u64()); T.push_back(cur.u8()); }
-        return at;
-    };
-    const size_t o_fcaps = hashes((size_t)p.num_fri_rounds * ncap);
-    for (uint32_t q = 0; q < nq && cur.ok; q++) {
-        unsigned init_nsib[GL_MAX_FRI_ORACLES];
-        for (uint32_t o = 0; o < no; o++) {
-            (void)words(s.slot_leaf_len[o]);
-            init_nsib[o] = cur.u8(); (void)hashes(init_nsib[o]);
-        }
-        unsigned lg_cur = lgN;
-        for (unsigned r = 0; r < p.num_fri_rounds; r++) {
-            (void)words(size_t(2) << p.fri_arity_bits[r]);
-            const unsigned nsib = cur.u8(); (void)hashes(nsib);
-            lg_cur -= p.fri_arity_bits[r];
-            if (cur.ok && nsib + p.cap_height != lg_cur) return reject(GL_CHECK_STEP_PATH_LENGTH, check);
-        }
-        for (uint32_t o = 0; o < no && cur.ok; o++)
-            if (init_nsib[o] + p.cap_height != lgN) return reject(GL_CHECK_INITIAL_PATH_LENGTH, check);
-    }
-    const size_t o_final = words(2 * final_len);
-    const gl_t pow_witness = gl_canon(cur.u64());
-    if (!cur.ok) return reject(GL_CHECK_TRUNCATED, check);
-    if (cur.pos != num_bytes) return reject(GL_CHECK_LENGTH, check);
-    // every path has the length the params give it, so the table lies where the shape says (what the queries index by)
-    GL_REQUIRE(T.size() == s.t_words && o_fcaps == s.o_fcaps && o_final == s.o_final, GL_ERR_INTERNAL,
-               "gl_verify_openings: the decoded proof does not lie where its shape puts it");
-
-    // ---- challenges (fri/challenges.rs:24-64) ----
-    glhost::HostChallenger& tr = challenger->ch;
-    const E alpha = tr.challenge_ext();
-    ch.alpha = alpha;
-    for (unsigned r = 0; r < p.num_fri_rounds; r++) { tr.observe_hashes(hasher, &T[o_fcaps + (size_t)r * 4 * ncap], ncap); ch.betas[r] = tr.challenge_ext(); }
-    for (unsigned r = p.num_fri_rounds; r < MAX_FRI_ROUNDS; r++) ch.betas[r] = e_of(0);
-    tr.observe_many(&T[o_final], 2 * final_len);
-    tr.observe(pow_witness);
-    const gl_t pow_response = tr.challenge();
-    ch.x_index.resize(nq);
-    for (auto& x : ch.x_index) x = tr.challenge() % (uint64_t)N;
-    if (pow_response != 0 && (unsigned)__builtin_clzll(pow_response) < p.proof_of_work_bits) return reject(GL_CHECK_POW, check);
-
-    // PrecomputedReducedOpenings (fri/verifier.rs:243-260): per batch Horner in alpha over its opened values; alpha^len of each batch
-    for (uint32_t b = 0; b < GL_MAX_FRI_BATCHES; b++) {
-        E acc = e_of(0), pw = e_of(1);
-        if (b < B)
-            for (size_t j = s.first[b + 1]; j-- > s.first[b];) {
-                acc = e_add(e_mul(acc, alpha), gl2_make(gl_canon(openings[2 * j]), gl_canon(openings[2 * j + 1])));
-                pw = e_mul(pw, alpha);
-            }
-        ch.red[b] = acc; ch.alpha_len[b] = pw;
-        ch.point[b] = b < B ? gl2_make(gl_canon(points[b][0]), gl_canon(points[b][1])) : e_of(0);
-    }
+    if (!glhost::hashes_well_formed(p.hasher, caps, in.num_oracles * s.ncap)) return reject(GL_CHECK_VERIFIER_DATA, check);
+    Reader rd(proof_bytes, num_bytes, p.hasher, T);
+    if (const uint32_t bad = decode_fri_proof(rd, s)) return reject(bad, check);
+    const gl_t pow_witness = gl_canon(rd.in.u64());
+    if (!rd.in.ok) return reject(GL_CHECK_TRUNCATED, check);
+    if (rd.in.pos != num_bytes) return reject(GL_CHECK_LENGTH, check);
+    // every path has the length the params give it, and the decode walked the shape's own counts from word 0: the table's end says
+    // that every place inside it is where the shape puts it (what the queries index by)
+    GL_REQUIRE(T.size() == s.t_words, GL_ERR_INTERNAL, "gl_verify_openings: the decoded proof does not lie where its shape puts it");
+    if (!pow_holds(draw_fri_challenges(challenger->ch, s, T.data(), pow_witness, ch), p.proof_of_work_bits)) return reject(GL_CHECK_POW, check);
+    reduce_openings(s, openings, points, ch);
     return GL_OK;
 }
 
@@ -719,52 +704,10 @@ extern "C" int gl_verify_openings(const gl_fri_params* params, const gl_fri_inst
     if (check) *check = GL_CHECK_ACCEPTED;
     glopen::Shape s;
     GL_TRY(glopen::shape_of(params, instance, s));
-    const gl_fri_params& p = *params; const gl_fri_instance& in = *instance;
     std::vector<gl_t> T;
     glopen::Challenges ch;
-    GL_TRY(glopen::host_stage(p, in, s, in.points, caps, openings, challenger, proof_bytes, num_bytes, T, ch, check));
-    auto ext_at = [&](size_t off, size_t i) { return gl2_make(T[off + 2 * i], T[off + 2 * i + 1]); };
-    const uint32_t hasher = p.hasher, no = in.num_oracles, B = in.num_batches, nq = p.num_query_rounds;
-    const unsigned lgN = s.lgN;
-    const size_t ncap = s.ncap;
-    const E alpha = ch.alpha;
-
-    // ---- the queries (fri/verifier.rs:163-241); k_verify_paths_any and k_verify_openings_queries are this loop on the device ----
-    const gl_t wN = glhost::root_of_unity(lgN);
-    for (uint32_t q = 0; q < nq; q++) {
-        size_t x = ch.x_index[q];
-        for (uint32_t o = 0; o < no; o++)
-            if (!path_opens_to_cap(hasher, &T[s.leaf_at(q, o)], s.slot_leaf_len[o], x, &T[s.sib_at(q, o)], s.slot_nsib[o], caps + (size_t)o * 4 * ncap, ncap))
-                return reject(GL_CHECK_INITIAL_MERKLE, check);
-        size_t rev = 0;
-        for (unsigned i = 0; i < lgN; i++) rev |= ((x >> i) & 1) << (lgN - 1 - i);
-        gl_t subgroup_x = gl_canon(gl_mul(GL_MULT_GENERATOR, gl_exp(wN, rev)));
-        // fri_combine_initial (fri/verifier.rs:122-161): a polynomial's index is below its oracle's column count, so only the unsalted
-        // prefix of a leaf is read (unsalted_eval)
-        const gl_t* Q = &T[s.o_query0 + q * s.query_stride];
-        const E sx = e_of(subgroup_x);
-        E eval = e_of(0);
-        for (uint32_t b = 0; b < B; b++) {
-            E h = e_of(0);
-            for (size_t j = s.first[b + 1]; j-- > s.first[b];) h = e_add(e_mul(h, alpha), e_of(Q[s.src[j]]));
-            eval = e_add(e_mul(eval, ch.alpha_len[b]), e_mul(e_sub(h, ch.red[b]), gl2_inv(e_sub(sx, ch.point[b]))));
-        }
-        for (unsigned r = 0; r < p.num_fri_rounds; r++) {
-            const unsigned ab = p.fri_arity_bits[r];
-            const uint32_t slot = no + r;
-            const size_t arity = size_t(1) << ab, coset = x >> ab, within = x & (arity - 1), leaf = s.leaf_at(q, slot);
-            if (!e_eq(ext_at(leaf, within), eval)) return reject(GL_CHECK_FRI_CONSISTENCY, check);
-            eval = compute_evaluation(subgroup_x, within, ab, &T[leaf], ch.betas[r]);
-            if (!path_opens_to_cap(hasher, &T[leaf], 2 * arity, coset, &T[s.sib_at(q, slot)], s.slot_nsib[slot], &T[s.o_fcaps + (size_t)r * 4 * ncap], ncap))
-                return reject(GL_CHECK_STEP_MERKLE, check);
-            for (unsigned i = 0; i < ab; i++) subgroup_x = gl_sqr(subgroup_x);
-            x = coset;
-        }
-        E fin = e_of(0);
-        const E sxf = e_of(gl_canon(subgroup_x));
-        for (size_t i = s.final_len; i-- > 0;) fin = e_add(e_mul(fin, sxf), ext_at(s.o_final, i));
-        if (!e_eq(fin, eval)) return reject(GL_CHECK_FINAL_POLY, check);
-    }
-    return GL_OK;
+    GL_TRY(glopen::host_stage(*params, *instance, s, instance->points, caps, openings, challenger, proof_bytes, num_bytes, T, ch, check));
+    const gl_t* cap_of[GL_MAX_FRI_ORACLES];
+    for (uint32_t o = 0; o < s.num_oracles; o++) cap_of[o] = caps + (size_t)o * 4 * s.ncap;
+    return verify_fri_queries(s, T.data(), ch, cap_of, check);
 } catch (...) { return gl_caught(); }
-

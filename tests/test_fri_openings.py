@@ -252,6 +252,69 @@ def test_plonk_instance_with_lookups_reproduces_the_plonk_path(gpu, orc):
     check_plonk_route(gpu, orc, cd, w.wires(), w.public_inputs(), "poseidon", cd.desc.num_fri_rounds)
 
 
+# ------------------------------------------------------------------------------- B': the verifier side of the same fact (CPU)
+def _circuit_proofs(p, orc, name):
+    """(description, constants_sigmas_cap, circuit digest, proof bytes): oracle-made matmul proofs, or the committed GPU-made one"""
+    if name == "ext_gates":
+        import ext_gate_circuits as egc
+        d = egc.isolated([egc.ARITHMETIC_EXT, egc.MUL_EXT, egc.REDUCING, egc.REDUCING_EXT], 77, rows_per_gate=1).desc
+        with open(os.path.join(GOLDEN, "ext_gates_n8_proof.bin"), "rb") as f:
+            by = f.read()
+        with open(os.path.join(GOLDEN, "ext_gates_n8_verifier_only.bin"), "rb") as f:
+            cap, digest, _ = p.api.verifier_only_from_bytes(f.read())
+        return d, cap, digest, by
+    m = {"m2": 2, "m8": 8}[name]
+    oc = orc.circuit(m, threads=8)
+    a, b = rand_field(40 + m, m * m) % (2**32 - 1), rand_field(41 + m, m * m) % (2**32 - 1)
+    return p.MatmulCircuit(m).desc, oc.constants_sigmas_cap, oc.digest, oc.witness(a, b, filler_seed=0).prove(threads=8).to_bytes()
+
+
+@pytest.mark.parametrize("name,rounds", [("m2", 0), ("m8", 1), ("ext_gates", 0)])
+def test_the_fri_proof_cut_out_of_a_circuit_proof_gets_gl_verifys_check_from_gl_verify_openings(orc, name, rounds):
+    """A circuit proof is one more FRI instance, on the verifier side too: the FriProof section of its bytes, with plonk_instance, the
+    four caps, the openings in batch order and a Challenger advanced through the Plonk transcript up to the observed openings, is
+    accepted by gl_verify_openings where gl_verify accepts the whole proof, and for every mutant of test_batch_verify.py's query matrix
+    ((d) - (h) at queries 0 and 27) and the path-length mutant (l) both give the same GL_CHECK_* code."""
+    import plonky2_demo_amd as p
+    from proof_parser import ParsedProof, hash_bytes, opening_columns
+    from proof_mutants import _host_stage_mutants, _query_mutants
+    from transcript import FRI_OPENINGS, public_inputs_hash, replay_to_openings, replay_transcript
+    d, cap, digest, by = _circuit_proofs(p, orc, name)
+    assert d.num_fri_rounds == rounds and d.num_query_rounds == 28
+    pp = ParsedProof(d, by)
+    pi_hash = public_inputs_hash(orc, pp.public_inputs)
+    g = primitive_root(d.degree_bits)
+    fri_at = (3 << d.cap_height) * hash_bytes(d) + 16 * sum(k for _, k in opening_columns(d))
+    fri_end = len(by) - 8 * (1 + len(pp.public_inputs))                          # behind the proof-of-work witness
+    texts = {p.api.verify_check_message(c): c for c in range(1, 15)}
+
+    def whole(proof):
+        b = np.frombuffer(proof, dtype=np.uint8)
+        ok, why = p.api._verdict(p.api.lib.gl_verify(ctypes.byref(d), p.api._p(p.api._u64(cap)), p.api._p(p.api._u64(digest)), p.api._p(b), b.size))
+        return 0 if ok else texts[why.rsplit(" (", 1)[0]]
+
+    def cut_out(proof):
+        ch = LibraryChallenger(p, "keccak" if d.hasher else "poseidon")
+        zeta = replay_to_openings(d, ch, digest, pi_hash, pp)[-1]                 # (no mutant touches a cap, an opening or a public input)
+        inst = plonk_instance(p, d, zeta, scaled(zeta, g))
+        caps = np.concatenate([np.asarray(cap, dtype=U64).reshape(1, -1, 4)] + [c.reshape(1, -1, 4) for c in pp.caps])
+        openings = np.concatenate([pp.openings[k] for k in FRI_OPENINGS])
+        assert inst.num_opened == len(openings) // 2
+        return p.verify_fri_proof(inst, caps, openings, ch.ch, proof[fri_at:fri_end], p.FriParams.of_circuit(d))[2]
+
+    assert whole(by) == cut_out(by) == 0
+    x_index = replay_transcript(d, LibraryChallenger(p, "keccak" if d.hasher else "poseidon"), digest, pi_hash, pp)[2]
+    mutants = [mu for q in (0, 27) for mu in _query_mutants(d, by, x_index, q)] + [mu for mu in _host_stage_mutants(d, by) if mu[0].startswith("l:")]
+    assert len(mutants) == 2 * (6 + 3 * rounds) + 1
+    seen = set()
+    for what, bad in mutants:
+        assert len(bad) == len(by)
+        code = whole(bad)
+        assert code == cut_out(bad) != 0, what
+        seen.add(code)
+    assert len(seen) >= (4 if rounds else 2)                                      # path length, initial Merkle; consistency and step Merkle
+
+
 # ------------------------------------------------------------------------------- C: a STARK-shaped instance end to end
 STARK_WIDTHS = [7, 2, 4]            # trace, permutation Z, quotient chunks (starky/src/prover.rs)
 

@@ -80,10 +80,9 @@ def public_inputs_hash(orc, pis):
     return orc.hash_no_pad(pis) if len(pis) else np.zeros(4, dtype=U64)
 
 
-def replay_transcript(d, ch, digest, pi_hash, pp):
-    """prover.rs:158-227,273,298 / fri/prover.rs:91-93,111,153 of the parsed proof `pp` on the challenger `ch`: (challenges as
-    Proof.challenges() gives them, PoW response, query indices, lookup deltas or None).  The native verifier shares HostChallenger with the
-    prover, so this replay on a model challenger is what pins the transcript."""
+def replay_to_openings(d, ch, digest, pi_hash, pp):
+    """prover.rs:158-227 of the parsed proof `pp` on the challenger `ch`, up to and including the observed openings: where the FriProof's
+    own transcript starts (fri/prover.rs).  -> (betas, gammas, lookup deltas or None, alphas, zeta)"""
     ch.observe_hashes(digest)
     ch.observe_hashes(pi_hash, inner=True)
     ch.observe_hashes(pp.caps[0])
@@ -95,6 +94,14 @@ def replay_transcript(d, ch, digest, pi_hash, pp):
     zeta = ch.get(2)
     for name in FRI_OPENINGS:
         ch.observe(pp.openings[name])
+    return betas, gammas, deltas, alphas, zeta
+
+
+def replay_transcript(d, ch, digest, pi_hash, pp):
+    """prover.rs:158-227,273,298 / fri/prover.rs:91-93,111,153 of the parsed proof `pp` on the challenger `ch`: (challenges as
+    Proof.challenges() gives them, PoW response, query indices, lookup deltas or None).  The native verifier shares HostChallenger with the
+    prover, so this replay on a model challenger is what pins the transcript."""
+    betas, gammas, deltas, alphas, zeta = replay_to_openings(d, ch, digest, pi_hash, pp)
     fri_alpha = ch.get(2)
     fri_betas = []
     for cap in pp.fri_caps:
