@@ -8,6 +8,7 @@
 #include <time.h>
 #include <sys/prctl.h>
 #include <cstdio>
+#include <cstdlib>
 #include <exception>
 #include <map>
 #include <new>
@@ -91,6 +92,34 @@ inline hipError_t gl_stream_wait(hipStream_t s) {
         }
     }
 }
+
+// ---- wave priority of the small, dependent launches ---------------------------------------------------------
+// A launch of at most one wave per SIMD lasts as long as one wave's dependent chain, and with 16 proofs in flight that wave
+// lands beside the long-lived waves of the bulk kernels (a leaf-hash wave lives for 17 permutations).  VALU issue between
+// co-resident waves goes by priority, then age: at equal priority the newcomer gets the leftover slots, its launch lasts
+// several times its lone duration, and the hardware queue behind it -- shared by other proofs -- waits.  Such a launch is
+// *urgent*: its kernel raises its waves' priority as its first statement, gl_raise_prio(prio), prio being a kernel argument
+// (or a field of the params struct) and so wave-uniform: s_setprio ignores EXEC.  The instruction count does not change; the
+// bulk waves give up the issue slots the small launch needs anyway.
+// Only for kernels that never spin on memory: a raised wave that polls starves the wave it waits for.
+#ifndef GL_URGENT_PRIO
+#define GL_URGENT_PRIO 1                        // the one raised tier (priority 1 already outranks every other wave, all at 0)
+#endif
+// two waves per SIMD (256 CUs x 4): with 16 proofs in flight 2048 gave 339.2 proofs/s against 336.4 for 1024 and 320.1 for 0
+// with the tree levels and tops alone, 343.0 against 339.9 with the FRI / permutation chain and the NTT passes as well
+// (m = 64: the first level of a 2^18-leaf tree is 2048 waves).  The leaf-hash kernels are NOT guarded: with the leaf launches
+// of the small trees raised as well the rate fell back to 327 (profiles/urgent_prio_ab.txt) -- presumably because a leaf wave,
+// older and longer-lived, then outranks the level wave beside it again.
+#define GL_URGENT_MAX_WAVES_DEFAULT 2048u
+// tuning knob (environment GL_URGENT_MAX_WAVES): launches of at most this many waves are urgent; 0 = never
+inline uint32_t gl_urgent_max_waves() {
+    static const uint32_t v = [] { const char* e = getenv("GL_URGENT_MAX_WAVES"); return e ? (uint32_t)strtoul(e, nullptr, 10) : GL_URGENT_MAX_WAVES_DEFAULT; }();
+    return v;
+}
+// the priority argument of a launch of `total_threads` threads: 0, or GL_URGENT_PRIO when the launch is urgent
+inline int gl_launch_prio(uint64_t total_threads) { return (total_threads + 63) / 64 <= gl_urgent_max_waves() ? GL_URGENT_PRIO : 0; }
+// (the instruction takes its level as an immediate)
+__device__ __forceinline__ void gl_raise_prio(int prio) { if (prio) __builtin_amdgcn_s_setprio(GL_URGENT_PRIO); }
 
 static const gl_t GL_MULT_GENERATOR = 7;                          // field/src/goldilocks_field.rs:80
 static const gl_t GL_POW2_GENERATOR = 1753635133440165772ULL;     // field/src/goldilocks_field.rs:87

@@ -64,7 +64,9 @@ __global__ __launch_bounds__(256, WPE) void k_merkle_leaves(const gl_t* __restri
 
 // parent[i] = two_to_one(child[2i], child[2i+1])   (hashing.rs:98-115)
 // (5 waves per SIMD: the register budget the MFMA layer fits without spilling, as the leaf kernel's default below)
-__global__ __launch_bounds__(256, 5) void k_merkle_level(const gl_t* __restrict__ child, gl_t* __restrict__ parent, uint32_t count) {
+__global__ __launch_bounds__(256, 5) void k_merkle_level(const gl_t* __restrict__ child, gl_t* __restrict__ parent, uint32_t count,
+                                                         int prio /* gl_launch_prio */) {
+    gl_raise_prio(prio);
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x, i = gid < count ? gid : count - 1;
     const ulonglong2* in = reinterpret_cast<const ulonglong2*>(child + 8ull * i);
     ulonglong2 a = in[0], b = in[1], c = in[2], d = in[3];
@@ -109,7 +111,8 @@ __global__ __launch_bounds__(256) void k_merkle_leaves_coop(const gl_t* __restri
 // digests: level-ordered array, `lev_off[l]` = first digest of level l; first_level = level whose nodes are computed first.
 #define GL_TOP_NODES 64u                // 64 hashes x 16 lanes = one 1024-thread workgroup
 __global__ __launch_bounds__(1024) void k_merkle_top_coop(gl_t* __restrict__ digests, const uint64_t* __restrict__ lev_off, uint32_t first_level,
-                                                          uint32_t num_levels, uint32_t nodes_first /* per subtree at first_level */) {
+                                                          uint32_t num_levels, uint32_t nodes_first /* per subtree at first_level */, int prio) {
+    gl_raise_prio(prio);
     const uint32_t sub = blockIdx.x, g = threadIdx.x >> 4;
     const int l = (int)(threadIdx.x & 15);
     uint32_t nodes = nodes_first;
@@ -292,11 +295,11 @@ int gl_merkle_build(gl_ctx* c, const gl_t* base, const uint64_t* host_offsets, u
     for (uint32_t l = 1; l < top_first; l++) {
         const uint32_t cnt = 1u << (lg_leaves - l);
         if (cnt <= coop) hipLaunchKernelGGL(k_merkle_level_coop, dim3((cnt * 16 + 255) / 256), dim3(256), 0, c->stream, out->level_ptr(l - 1), out->level_ptr(l), cnt);
-        else hipLaunchKernelGGL(k_merkle_level, dim3((cnt + 255) / 256), dim3(256), 0, c->stream, out->level_ptr(l - 1), out->level_ptr(l), cnt);
+        else hipLaunchKernelGGL(k_merkle_level, dim3((cnt + 255) / 256), dim3(256), 0, c->stream, out->level_ptr(l - 1), out->level_ptr(l), cnt, gl_launch_prio(cnt));
     }
     if (top_first < levels)
         hipLaunchKernelGGL(k_merkle_top_coop, dim3(1u << cap_height), dim3(1024), 0, c->stream, out->digests, d_lev_off, top_first, levels,
-                           (1u << (lg_leaves - top_first)) >> cap_height);
+                           (1u << (lg_leaves - top_first)) >> cap_height, gl_launch_prio(1024ull << cap_height));
     c->timing_end();
     GL_CHECK_HIP(hipGetLastError());
     return GL_OK;

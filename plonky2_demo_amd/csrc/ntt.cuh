@@ -71,6 +71,7 @@ struct NttPassParams {
                                        // b is outer row (b & (2^out_shift - 1)) of polynomial b >> out_shift and output k of it goes to
                                        // (k << out_shift) + outer row.  A tile then holds ONE inner row (blockIdx.x) of T consecutive batch
                                        // entries (blockIdx.y * T ..), so that its scattered stores are T-element segments as well.
+    int prio;                          // gl_launch_prio of this launch (context.hpp), set by the launchers
 #ifdef NTT_ABLATION
     uint32_t debug;                    // diagnostic builds only (-DNTT_ABLATION, env GL_NTT_DEBUG): 1 skip stages, 2 skip loads, 4 skip stores
 #endif
@@ -492,6 +493,7 @@ __device__ __forceinline__ void ntt_col_tile(const NttPassParams& p, gl_t* lds, 
 }
 template <int LOGL, bool INV, bool ZP = false>
 __global__ __launch_bounds__(NTT_THREADS, NTT_WAVES_PER_SIMD) void ntt_col_pass(NttPassParams p) {
+    gl_raise_prio(p.prio);
     extern __shared__ __align__(16) gl_t lds[];
     ntt_col_tile<LOGL, INV, ZP>(p, lds, threadIdx.x, blockIdx.x, blockIdx.y);
 }
@@ -587,6 +589,7 @@ __device__ __forceinline__ void ntt_row_tile(const NttPassParams& p, gl_t* lds, 
 }
 template <int LOGL, bool INV, bool SINGLE>
 __global__ __launch_bounds__(NTT_THREADS, NTT_WAVES_PER_SIMD) void ntt_row_pass(NttPassParams p) {
+    gl_raise_prio(p.prio);
     extern __shared__ __align__(16) gl_t lds[];
     ntt_row_tile<LOGL, INV, SINGLE>(p, lds, threadIdx.x, blockIdx.x, blockIdx.y);
 }

@@ -58,7 +58,7 @@ int gl_ntt_local_tables(gl_ctx* c) {
 }
 // ---------------------------------------------------------------------------------------- launchers
 template <int LOGL, bool INV, bool ZP>
-static int launch_col_impl(gl_ctx* c, const NttPassParams& p, dim3 grid) {
+static int launch_col_impl(gl_ctx* c, NttPassParams p, dim3 grid) {
     constexpr size_t lds = NttGeom<LOGL>::LDS_BYTES;
     // once per instantiation and device; contexts on several host threads may get here together (setting it twice is harmless)
     static std::atomic<uint64_t> done{0};
@@ -67,6 +67,7 @@ static int launch_col_impl(gl_ctx* c, const NttPassParams& p, dim3 grid) {
         GL_CHECK_HIP(hipFuncSetAttribute((const void*)ntt_col_pass<LOGL, INV, ZP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         done.fetch_or(bit, std::memory_order_release);
     }
+    p.prio = gl_launch_prio((uint64_t)grid.x * grid.y * NTT_THREADS);
     GlTimed timed(c, INV ? "ntt_col_pass(inverse)" : "ntt_col_pass(forward)");
     hipLaunchKernelGGL((ntt_col_pass<LOGL, INV, ZP>), grid, dim3(NTT_THREADS), lds, c->stream, p);
     GL_CHECK_HIP(hipGetLastError());
@@ -82,7 +83,7 @@ static int launch_col(gl_ctx* c, const NttPassParams& p, dim3 grid) {
     return launch_col_impl<LOGL, INV, false>(c, p, grid);
 }
 template <int LOGL, bool INV, bool SINGLE>
-static int launch_row_impl(gl_ctx* c, const NttPassParams& p, dim3 grid) {
+static int launch_row_impl(gl_ctx* c, NttPassParams p, dim3 grid) {
     constexpr size_t lds = NttGeom<LOGL>::LDS_BYTES;
     static std::atomic<uint64_t> done{0};
     const uint64_t bit = uint64_t(1) << (c->device & 63);
@@ -90,6 +91,7 @@ static int launch_row_impl(gl_ctx* c, const NttPassParams& p, dim3 grid) {
         GL_CHECK_HIP(hipFuncSetAttribute((const void*)ntt_row_pass<LOGL, INV, SINGLE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         done.fetch_or(bit, std::memory_order_release);
     }
+    p.prio = gl_launch_prio((uint64_t)grid.x * grid.y * NTT_THREADS);
     GlTimed timed(c, INV ? "ntt_row_pass(inverse)" : "ntt_row_pass(forward)");
     hipLaunchKernelGGL((ntt_row_pass<LOGL, INV, SINGLE>), grid, dim3(NTT_THREADS), lds, c->stream, p);
     GL_CHECK_HIP(hipGetLastError());

@@ -318,9 +318,9 @@ static int partial_products_values(gl_ctx* ctx, const gl_circuit* cir, const gl_
     pp.n = (uint32_t)n; pp.chunk_prod = d_chunk.as<gl_t>(); pp.row_prod = d_rowp.as<gl_t>();
     ctx->timing_begin("compute partial products");
     hipLaunchKernelGGL(k_pp_chunk_terms, dim3((unsigned)((n + 255) / 256), 2 * GLP_CHUNKS), dim3(256), 0, st, pp, d_den.as<gl_t>());
-    hipLaunchKernelGGL(k_pp_chunk_products, dim3((unsigned)((n + 255) / 256), 2), dim3(256), 0, st, pp, d_den.as<const gl_t>());
-    hipLaunchKernelGGL(k_z_segment_products, dim3(nseg, 2), dim3(256), 0, st, d_rowp.as<gl_t>(), (uint32_t)n, d_seg.as<gl_t>());
-    hipLaunchKernelGGL(k_z_segment_scan, dim3(1), dim3(64), 0, st, d_seg.as<gl_t>(), nseg);
+    hipLaunchKernelGGL(k_pp_chunk_products, dim3((unsigned)((n + 255) / 256), 2), dim3(256), 0, st, pp, d_den.as<const gl_t>(), gl_launch_prio(2 * n));
+    hipLaunchKernelGGL(k_z_segment_products, dim3(nseg, 2), dim3(256), 0, st, d_rowp.as<gl_t>(), (uint32_t)n, d_seg.as<gl_t>(), gl_launch_prio(512ull * nseg));
+    hipLaunchKernelGGL(k_z_segment_scan, dim3(1), dim3(64), 0, st, d_seg.as<gl_t>(), nseg, gl_launch_prio(64));
     hipLaunchKernelGGL(k_z_finalize, dim3(nseg, 2), dim3(256), 0, st, d_rowp.as<gl_t>(), d_chunk.as<gl_t>(), d_seg.as<gl_t>(), (uint32_t)n, d_zs);
     ctx->timing_end();
     GL_CHECK_HIP(hipGetLastError());
@@ -604,8 +604,8 @@ static int fri_combine(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* const
         const unsigned gb = (unsigned)((n + 63) / 64), sb = (nseg + 63) / 64;      // k_fri_combine_points: 64 coefficients per workgroup
         ctx->timing_begin("reduce batch + divide by linear");
         hipLaunchKernelGGL(k_fri_combine_points<2>, dim3(gb), dim3(256), 0, st, d_cols.as<const gl_t*>(), d_wts.as<gl_t>(), (uint32_t)nopen, (uint32_t)n, F);
-        hipLaunchKernelGGL(k_div_points_heads, dim3(sb, 2), dim3(64), 0, st, F, (uint32_t)n, seg_len, pt, d_heads.as<gl_t>());
-        hipLaunchKernelGGL(k_div_points_carries, dim3(1, 2), dim3(1024), 0, st, d_heads.as<gl_t>(), (uint32_t)n, seg_len, pt);
+        hipLaunchKernelGGL(k_div_points_heads, dim3(sb, 2), dim3(64), 0, st, F, (uint32_t)n, seg_len, pt, d_heads.as<gl_t>(), gl_launch_prio(128ull * sb));
+        hipLaunchKernelGGL(k_div_points_carries, dim3(1, 2), dim3(1024), 0, st, d_heads.as<gl_t>(), (uint32_t)n, seg_len, pt, gl_launch_prio(2048));
         hipLaunchKernelGGL(k_div_points_apply<2>, dim3(sb), dim3(64), 0, st, F, (uint32_t)n, seg_len, pt, d_heads.as<gl_t>(), Qa, Qb);
         ctx->timing_end();
         GL_CHECK_HIP(hipGetLastError());
@@ -654,7 +654,7 @@ extern "C" int gl_fri_fold(gl_fri* f, const uint64_t beta_in[2]) try {
     GL_TRY(next->alloc(2 * next_n * sizeof(gl_t)));
     ctx->timing_begin("fold codewords in the commitment phase");
     hipLaunchKernelGGL(k_fri_fold, dim3((unsigned)((next_n + 255) / 256)), dim3(256), 0, ctx->stream, f->coef->as<gl_t>(), f->coef->as<gl_t>() + f->cur_n,
-                       (uint32_t)next_n, arity, beta.a, beta.b, next->as<gl_t>(), next->as<gl_t>() + next_n);
+                       (uint32_t)next_n, arity, beta.a, beta.b, next->as<gl_t>(), next->as<gl_t>() + next_n, gl_launch_prio(next_n));
     ctx->timing_end();
     GL_CHECK_HIP(hipGetLastError());
     // the next round's state is built beside the handle and moved in at the end: a failure on the way leaves the round as it was
@@ -722,7 +722,7 @@ extern "C" int gl_pow_grind_h(gl_ctx* ctx, uint32_t hasher, const uint64_t spong
     ctx->timing_begin("find proof-of-work witness");
     for (uint64_t base = 0; base < GL_P; base += batch) {
         GL_CHECK_HIP(hipMemsetAsync(d_res, 0xFF, sizeof(unsigned long long), st));
-        pw.base = base; pw.count = (GL_P - base < batch) ? GL_P - base : batch;
+        pw.base = base; pw.count = (GL_P - base < batch) ? GL_P - base : batch; pw.prio = gl_launch_prio(pw.count);
         if (hasher == GL_HASHER_KECCAK) hipLaunchKernelGGL(k_kck_pow_grind, dim3((unsigned)((pw.count + 255) / 256)), dim3(256), 0, st, pw);
         else hipLaunchKernelGGL(k_pow_grind, dim3((unsigned)((pw.count + 255) / 256)), dim3(256), 0, st, pw);
         GL_CHECK_HIP(hipGetLastError());
@@ -806,7 +806,7 @@ static int fri_query_blob(gl_fri* f, const uint32_t* x_index, uint32_t nq, std::
     ctx->timing_begin("FRI query gathers");
     if (nblocks)
         hipLaunchKernelGGL(k_gather_pieces, dim3(nblocks), dim3(256), 0, st, d_up.as<GlGatherPiece>(), npieces,
-                           reinterpret_cast<const uint32_t*>(d_up.as<GlGatherPiece>() + max_pieces), stage);
+                           reinterpret_cast<const uint32_t*>(d_up.as<GlGatherPiece>() + max_pieces), stage, gl_launch_prio(256ull * nblocks));
     ctx->timing_end();
     GL_CHECK_HIP(hipGetLastError());
     std::vector<gl_t> host_stage(total + 8);
@@ -940,8 +940,8 @@ static int fri_combine_instance(gl_ctx* ctx, const gl_fri_params* params, const 
 #define GLF_LAUNCH(NB)                                                                                                                               \
     case NB:                                                                                                                                         \
         hipLaunchKernelGGL(k_fri_combine_points<NB>, dim3(gb), dim3(256), 0, st, d_cols.as<const gl_t*>(), d_wts.as<gl_t>(), (uint32_t)ncols, (uint32_t)n, F); \
-        hipLaunchKernelGGL(k_div_points_heads, dim3(sb, NB), dim3(64), 0, st, F, (uint32_t)n, seg_len, pt, d_heads.as<gl_t>());                      \
-        hipLaunchKernelGGL(k_div_points_carries, dim3(1, NB), dim3(1024), 0, st, d_heads.as<gl_t>(), (uint32_t)n, seg_len, pt);                      \
+        hipLaunchKernelGGL(k_div_points_heads, dim3(sb, NB), dim3(64), 0, st, F, (uint32_t)n, seg_len, pt, d_heads.as<gl_t>(), gl_launch_prio(64ull * NB * sb)); \
+        hipLaunchKernelGGL(k_div_points_carries, dim3(1, NB), dim3(1024), 0, st, d_heads.as<gl_t>(), (uint32_t)n, seg_len, pt, gl_launch_prio(1024ull * NB)); \
         hipLaunchKernelGGL(k_div_points_apply<NB>, dim3(sb), dim3(64), 0, st, F, (uint32_t)n, seg_len, pt, d_heads.as<gl_t>(), Qa, Qb);               \
         break;
         switch (B) { GLF_LAUNCH(1) GLF_LAUNCH(2) GLF_LAUNCH(3) GLF_LAUNCH(4) }
@@ -1105,7 +1105,7 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, D
         // zeta^i and (g zeta)^i tabulated once per proof, shared by all polynomials
         DevBuf d_zpow(ctx); GL_TRY(d_zpow.alloc(4 * n * sizeof(gl_t)));
         gl_t* zp = d_zpow.as<gl_t>();
-        hipLaunchKernelGGL(k_ext_powers2, dim3((unsigned)((n + 255) / 256), 2), dim3(256), 0, st, zeta.a, zeta.b, gzeta.a, gzeta.b, (uint32_t)n, zp);
+        hipLaunchKernelGGL(k_ext_powers2, dim3((unsigned)((n + 255) / 256), 2), dim3(256), 0, st, zeta.a, zeta.b, gzeta.a, gzeta.b, (uint32_t)n, zp, gl_launch_prio(2 * n));
         // the list of coefficient columns goes up as a small pointer table
         DevBuf d_open_cols(ctx); GL_TRY(d_open_cols.alloc(op.cols.size() * sizeof(gl_t*)));
         GL_TRY(h2d_async(ctx, d_open_cols.p, op.cols.data(), op.cols.size() * sizeof(gl_t*)));

@@ -66,7 +66,8 @@ __global__ __launch_bounds__(256) void k_pp_chunk_terms(GlPermParams p, gl_t* __
     p.chunk_prod[((size_t)a * GLP_CHUNKS + c) * p.n + i] = np;
     den_prod[((size_t)a * GLP_CHUNKS + c) * p.n + i] = dp;
 }
-__global__ __launch_bounds__(256) void k_pp_chunk_products(GlPermParams p, const gl_t* __restrict__ den_prod) {
+__global__ __launch_bounds__(256) void k_pp_chunk_products(GlPermParams p, const gl_t* __restrict__ den_prod, int prio /* gl_launch_prio, context.hpp */) {
+    gl_raise_prio(prio);
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= p.n) return;
     const int a = blockIdx.y;
@@ -100,7 +101,8 @@ __global__ __launch_bounds__(256) void k_pp_chunk_products(GlPermParams p, const
 #define GLP_SEG 2048            // rows per workgroup segment (256 threads x 8)
 
 // S1: product of each segment
-__global__ __launch_bounds__(256) void k_z_segment_products(const gl_t* row_prod, uint32_t n, gl_t* seg_prod) {
+__global__ __launch_bounds__(256) void k_z_segment_products(const gl_t* row_prod, uint32_t n, gl_t* seg_prod, int prio) {
+    gl_raise_prio(prio);
     __shared__ gl_t sh[256];
     const uint32_t a = blockIdx.y, seg = blockIdx.x, t = threadIdx.x;
     const gl_t* rp = row_prod + (size_t)a * n;
@@ -113,7 +115,8 @@ __global__ __launch_bounds__(256) void k_z_segment_products(const gl_t* row_prod
     if (t == 0) seg_prod[(size_t)a * gridDim.x + seg] = gl_canon(sh[0]);
 }
 // S2: exclusive scan of the segment products (one thread per challenge; segment counts are tiny)
-__global__ void k_z_segment_scan(gl_t* seg_prod, uint32_t nseg) {
+__global__ void k_z_segment_scan(gl_t* seg_prod, uint32_t nseg, int prio) {
+    gl_raise_prio(prio);
     const uint32_t a = threadIdx.x;
     if (a >= 2) return;
     gl_t acc = 1;
@@ -775,7 +778,8 @@ __global__ __launch_bounds__(256) void k_eval_at_ext(const gl_t* coeffs, uint32_
 
 // tables of powers of two extension elements in one launch (grid.y = 2): out = [a(z0) | b(z0) | a(z1) | b(z1)], n entries each,
 // plane a / b of z^i at index i
-__global__ __launch_bounds__(256) void k_ext_powers2(gl_t z0a, gl_t z0b, gl_t z1a, gl_t z1b, uint32_t n, gl_t* out) {
+__global__ __launch_bounds__(256) void k_ext_powers2(gl_t z0a, gl_t z0b, gl_t z1a, gl_t z1b, uint32_t n, gl_t* out, int prio) {
+    gl_raise_prio(prio);
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const gl2_t z = blockIdx.y ? gl2_make(z1a, z1b) : gl2_make(z0a, z0b);
@@ -952,7 +956,8 @@ __device__ __forceinline__ gl2_t glf_point(const GlFriPoints& pt, uint32_t bt) {
     return gl2_make(za, zb);
 }
 // k_div_linear_heads / _carries with a batch dimension: blockIdx.y = batch; F planes [B][2][n], heads [B][nseg][2]
-__global__ void k_div_points_heads(const gl_t* F, uint32_t n, uint32_t seg, GlFriPoints pt, gl_t* heads) {
+__global__ void k_div_points_heads(const gl_t* F, uint32_t n, uint32_t seg, GlFriPoints pt, gl_t* heads, int prio) {
+    gl_raise_prio(prio);
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x, nseg = (n + seg - 1) / seg, bt = blockIdx.y;
     if (s >= nseg) return;
     const gl2_t z = glf_point(pt, bt);
@@ -963,7 +968,8 @@ __global__ void k_div_points_heads(const gl_t* F, uint32_t n, uint32_t seg, GlFr
     for (uint32_t k = hi; k > lo; k--) acc = gl2_add(gl2_mul(acc, z), gl2_make(ca[k - 1], cb[k - 1]));
     heads[2 * ((size_t)bt * nseg + s)] = acc.a; heads[2 * ((size_t)bt * nseg + s) + 1] = acc.b;
 }
-__global__ __launch_bounds__(1024) void k_div_points_carries(gl_t* heads, uint32_t n, uint32_t seg, GlFriPoints pt) {
+__global__ __launch_bounds__(1024) void k_div_points_carries(gl_t* heads, uint32_t n, uint32_t seg, GlFriPoints pt, int prio) {
+    gl_raise_prio(prio);
     __shared__ gl_t La[1024], Lb[1024], Za[1024], Zb[1024];
     const uint32_t s = threadIdx.x, nseg = (n + seg - 1) / seg, bt = blockIdx.y;
     const gl2_t z = glf_point(pt, bt);
@@ -1017,7 +1023,8 @@ __global__ void k_div_points_apply(const gl_t* F, uint32_t n, uint32_t seg, GlFr
 }
 
 // ---- FRI fold: out[k] = sum_{i < arity} beta^i in[arity k + i]   (fri/prover.rs:94-103, plonk_common.rs:116-128) ------
-__global__ __launch_bounds__(256) void k_fri_fold(const gl_t* ia, const gl_t* ib, uint32_t n_out, uint32_t arity, gl_t ba, gl_t bb, gl_t* oa, gl_t* ob) {
+__global__ __launch_bounds__(256) void k_fri_fold(const gl_t* ia, const gl_t* ib, uint32_t n_out, uint32_t arity, gl_t ba, gl_t bb, gl_t* oa, gl_t* ob, int prio) {
+    gl_raise_prio(prio);
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_out) return;
     const gl2_t beta = gl2_make(ba, bb);
@@ -1027,8 +1034,9 @@ __global__ __launch_bounds__(256) void k_fri_fold(const gl_t* ia, const gl_t* ib
 }
 
 // ---- proof of work: smallest w >= base with clz(permute(state with w at pos)[7]) >= bits ----------------------------------
-struct GlPowParams { gl_t state[12]; uint32_t pos, min_leading_zeros; uint64_t base, count; unsigned long long* result; };
+struct GlPowParams { gl_t state[12]; uint32_t pos, min_leading_zeros; uint64_t base, count; unsigned long long* result; int prio /* k_pow_grind: gl_launch_prio */; };
 __global__ __launch_bounds__(256, 5) void k_pow_grind(GlPowParams p) {
+    gl_raise_prio(p.prio);
     const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t cand = p.base + idx;
     gl_t s[12];
@@ -1076,7 +1084,8 @@ struct GlGatherPiece {
     uint32_t kind, a, b, count, idx_off, pad_;      // idx_off: where the piece's nq indices start in `idx`
 };
 __global__ __launch_bounds__(256) void k_gather_pieces(const GlGatherPiece* __restrict__ pieces, uint32_t npieces, const uint32_t* __restrict__ idx,
-                                                       gl_t* __restrict__ out) {
+                                                       gl_t* __restrict__ out, int prio) {
+    gl_raise_prio(prio);
     uint32_t blk = blockIdx.x, p = 0;
     for (; p < npieces; p++) {
         const uint32_t nb = (pieces[p].count + 255) / 256;
