@@ -152,6 +152,13 @@ typedef struct gl_circuit_desc {
 /* stream: a hipStream_t to enqueue on (e.g. torch.cuda.current_stream().cuda_stream), or NULL to let
  * the context create its own non-blocking stream. */
 int gl_ctx_create(int device, void* stream, gl_ctx** out);
+/* A context that creates its own stream asks for one with a hardware queue of its own, so that its kernels do not wait behind
+ * those of other contexts (the runtime otherwise folds all streams onto GPU_MAX_HW_QUEUES queues).  At most GL_LANE_QUEUES
+ * (environment, default 24, 0 = never; none at all when GPU_MAX_HW_QUEUES >= 16) such streams are live per device and process;
+ * contexts past that, and contexts on a caller's stream, share the runtime's pool.
+ * gl_ctx_has_own_queue: 1 if the context's stream has its own queue.  gl_lane_queues_live: such streams live on `device`. */
+int gl_ctx_has_own_queue(const gl_ctx* ctx) GL_NOEXCEPT;
+int gl_lane_queues_live(int device) GL_NOEXCEPT;
 /* drops the creator's reference (see "Lifetime" above); synchronises the stream first */
 void gl_ctx_destroy(gl_ctx* ctx) GL_NOEXCEPT;
 int gl_ctx_synchronize(gl_ctx* ctx);

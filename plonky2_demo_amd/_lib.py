@@ -46,6 +46,8 @@ c_int = ctypes.c_int
 # name -> (restype, argtypes); every symbol include/plonky2_mi355x.h declares must appear here
 SIGNATURES = {
     "gl_ctx_create": (c_int, [c_int, c_vp, ctypes.POINTER(c_vp)]),
+    "gl_ctx_has_own_queue": (c_int, [c_vp]),
+    "gl_lane_queues_live": (c_int, [c_int]),
     "gl_ctx_destroy": (None, [c_vp]),
     "gl_ctx_synchronize": (c_int, [c_vp]),
     "gl_ctx_set_scratch_elems": (c_int, [c_vp, c_sz]),

@@ -107,6 +107,11 @@ class Context(_Owned):
         self.handle = h.value
         self.device = device
 
+    @property
+    def has_own_queue(self):
+        """True if the context's stream has a hardware queue of its own (gl_ctx_has_own_queue; knob GL_LANE_QUEUES)."""
+        return bool(lib.gl_ctx_has_own_queue(self.handle))
+
     def synchronize(self):
         check(lib.gl_ctx_synchronize(self.handle))
 

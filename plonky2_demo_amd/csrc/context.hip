@@ -163,6 +163,65 @@ int gl_ctx::get_offsets_table(const uint64_t* host, size_t len, const uint64_t**
     return GL_OK;
 }
 
+// ------------------------------------------------------------------------------------------ lane queues
+// The runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and kernels of streams that
+// share a queue run one behind the other: with 16 proofs in flight on 4 queues, three proofs wait behind every launch that cannot
+// fill the chip.  A stream made with a CU mask gets a hardware queue of its own, outside that pool (profiles/queue_probe.txt);
+// with every CU enabled the mask restricts nothing.  A context that creates its own stream asks for such a stream, within a
+// process-wide budget per device; past the budget, or when the call fails, it gets the plain non-blocking stream of the pool.
+namespace {
+constexpr int GL_HW_QUEUE_CEILING = 32;          // pool maximum + own queues never exceeds this
+constexpr int GL_LANE_QUEUES_DEFAULT = 24;
+constexpr int GL_POOL_QUEUES_ENOUGH = 16;        // an environment that grants this many pool queues already gives every lane its own
+constexpr int GL_LANE_DEVICES = 64;
+std::atomic<int> g_lane_queues_live[GL_LANE_DEVICES];
+
+// the budget of own queues per device: environment GL_LANE_QUEUES (0 = none), read once
+int gl_lane_queue_cap() {
+    static const int cap = [] {
+        const char* q = getenv("GPU_MAX_HW_QUEUES");      // as this process was started: the runtime read it long before this library loaded
+        long pool = q ? strtol(q, nullptr, 10) : 4;
+        if (pool <= 0) pool = 4;
+        if (pool >= GL_POOL_QUEUES_ENOUGH) return 0;
+        const char* e = getenv("GL_LANE_QUEUES");
+        long want = e ? strtol(e, nullptr, 10) : GL_LANE_QUEUES_DEFAULT;
+        if (want < 0) want = 0;
+        const long room = GL_HW_QUEUE_CEILING - pool;
+        return (int)(want < room ? want : room);
+    }();
+    return cap;
+}
+bool gl_lane_queue_claim(int device) {
+    if (device < 0 || device >= GL_LANE_DEVICES) return false;
+    const int cap = gl_lane_queue_cap();
+    int live = g_lane_queues_live[device].load(std::memory_order_relaxed);
+    while (live < cap)
+        if (g_lane_queues_live[device].compare_exchange_weak(live, live + 1, std::memory_order_acq_rel)) return true;
+    return false;
+}
+void gl_lane_queue_release(int device) noexcept { g_lane_queues_live[device].fetch_sub(1, std::memory_order_acq_rel); }
+
+// A stream with a hardware queue of its own on the current device; on any error the caller falls back.  The entry point takes no
+// flags and its stream is a BLOCKING one (ordered against the null stream): measured, that costs a lone proof and 16 proofs in
+// flight nothing (profiles/lane_queues_ab.txt) -- the library never launches on the null stream.  Spreading the streams over the
+// priority classes instead (a pool of queues each) gains a third as much with two classes and nothing with three.
+hipError_t gl_own_queue_stream(hipStream_t* s) {
+    int dev = 0, cus = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e != hipSuccess) return e;
+    if (cus <= 0 || cus > 1024) return hipErrorInvalidValue;
+    uint32_t mask[32] = {0};
+    for (int cu = 0; cu < cus; cu++) mask[cu / 32] |= 1u << (cu % 32);
+    return hipExtStreamCreateWithCUMask(s, (uint32_t)((cus + 31) / 32), mask);
+}
+}      // namespace
+
+extern "C" int gl_ctx_has_own_queue(const gl_ctx* c) noexcept { return c && c->own_queue ? 1 : 0; }
+extern "C" int gl_lane_queues_live(int device) noexcept {
+    return device >= 0 && device < GL_LANE_DEVICES ? g_lane_queues_live[device].load(std::memory_order_acquire) : 0;
+}
+
 extern "C" int gl_ctx_create(int device, void* stream, gl_ctx** out) try {
     GL_REQUIRE(out != nullptr, GL_ERR_ARG, "gl_ctx_create: out is null");
     int count = 0;
@@ -175,7 +234,13 @@ extern "C" int gl_ctx_create(int device, void* stream, gl_ctx** out) try {
     c->device = device;
     if (const char* e = getenv("GL_NTT_SCRATCH_LOG")) { const int lg = atoi(e); if (lg >= 16 && lg <= 32) c->scratch_target = size_t(1) << lg; }      // tuning knob
     if (stream) { c->stream = (hipStream_t)stream; c->own_stream = false; }
-    else { GL_CHECK_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
+    else {
+        if (gl_lane_queue_claim(device)) {
+            if (gl_own_queue_stream(&c->stream) == hipSuccess) c->own_stream = c->own_queue = true;
+            else { gl_lane_queue_release(device); c->stream = nullptr; (void)hipGetLastError(); }      // the feature never costs a context its existence
+        }
+        if (!c->own_stream) { GL_CHECK_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
+    }
     GL_TRY(gl_ntt_local_tables(c));      // ntt.hip: the one step of creation that launches kernels
     *out = holder.release();
     return GL_OK;
@@ -197,6 +262,7 @@ static void gl_ctx_teardown(gl_ctx* c) {
     for (auto& pb : c->pin_free) (void)hipHostFree(pb.first);
     if (c->dev_small) (void)hipFree(c->dev_small);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
+    if (c->own_queue) gl_lane_queue_release(c->device);      // after the stream is gone: the count never understates the queues that exist
     delete c;
 }
 void gl_ctx_release(gl_ctx* c) {

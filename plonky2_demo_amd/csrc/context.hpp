@@ -146,6 +146,7 @@ struct gl_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
+    bool own_queue = false;                                       // the stream has a hardware queue of its own (context.hip "lane queues")
     gl_t* tw_local[2] = {nullptr, nullptr};                       // w_4096^e forward / inverse
     std::map<std::pair<gl_t, gl_t>, GlPowTable> pow_tables;       // (base, scale) -> table
     std::map<std::tuple<gl_t, gl_t, uint32_t>, gl_t*> pass_tables; // (w_N, scale, lgN1) -> scale * inter-pass twiddles in column-pass output order

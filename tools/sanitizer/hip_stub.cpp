@@ -56,6 +56,9 @@ hipError_t hipFree(void* p) { free(p); return hipSuccess; }
 hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = malloc(n ? n : 8); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) try { *s = (hipStream_t) new StubStream(); return hipSuccess; } catch (...) { return hipErrorOutOfMemory; }
+// (a context's own-queue stream, context.hip "lane queues": one more worker thread, like any other stream)
+hipError_t hipExtStreamCreateWithCUMask(hipStream_t* s, uint32_t, const uint32_t*) { return hipStreamCreateWithFlags(s, 0); }
+hipError_t hipDeviceGetAttribute(int* v, hipDeviceAttribute_t, int) { *v = 256; return hipSuccess; }
 hipError_t hipStreamDestroy(hipStream_t s) { delete (StubStream*)s; return hipSuccess; }
 hipError_t hipStreamQuery(hipStream_t s) { return (!s || ((StubStream*)s)->idle()) ? hipSuccess : hipErrorNotReady; }      // (null: the default stream, idle -- a context whose creation failed before it had a stream is torn down through it)
 hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind, hipStream_t s) try {
