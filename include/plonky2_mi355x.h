@@ -802,6 +802,65 @@ int gl_stark_lookup_columns(gl_ctx* ctx, uint64_t* d_cols, uint32_t num_columns,
  * GPU.  The outputs may not overlap the inputs. */
 int gl_permuted_cols_host(const uint64_t* h_inputs, const uint64_t* h_table, size_t n, uint64_t* h_permuted_inputs, uint64_t* h_permuted_table);
 
+/* ---- MemoryStark: evm's memory table, its description and its trace ------------------------------------
+ * evm/src/memory: the table every other table of evm/ feeds through ctl_memory (all_stark.rs:174-204).  What is here: its columns
+ * (memory/columns.rs), its constraints as a gl_stark_desc (memory_stark.rs:243-321, :450-459), and MemoryStark::generate_trace
+ * (memory_stark.rs:120-237) from a log of memory operations -- on the host, the reference's loops statement by statement, and on the
+ * device without a per-op serial pass.  evm's other tables, the CPU table's memory columns, eval_ext_circuit and
+ * timestamps above 32 bits stay out of scope. */
+#define GL_MEMORY_NUM_CHANNELS 6u                 /* memory/mod.rs: NUM_CHANNELS */
+#define GL_MEMORY_VALUE_LIMBS 8u                  /* memory/mod.rs: VALUE_LIMBS  */
+#define GL_MEMORY_FILTER 0u                       /* memory/columns.rs:7-38 */
+#define GL_MEMORY_TIMESTAMP 1u
+#define GL_MEMORY_IS_READ 2u
+#define GL_MEMORY_ADDR_CONTEXT 3u
+#define GL_MEMORY_ADDR_SEGMENT 4u
+#define GL_MEMORY_ADDR_VIRTUAL 5u
+#define GL_MEMORY_VALUE_START 6u                  /* value_limb(i) = GL_MEMORY_VALUE_START + i, i < 8 */
+#define GL_MEMORY_CONTEXT_FIRST_CHANGE 14u
+#define GL_MEMORY_SEGMENT_FIRST_CHANGE 15u
+#define GL_MEMORY_VIRTUAL_FIRST_CHANGE 16u        /* columns 17..21 are unused and zero: RANGE_CHECK = VIRTUAL_FIRST_CHANGE + NUM_CHANNELS */
+#define GL_MEMORY_RANGE_CHECK 22u
+#define GL_MEMORY_COUNTER 23u
+#define GL_MEMORY_RANGE_CHECK_PERMUTED 24u
+#define GL_MEMORY_COUNTER_PERMUTED 25u
+#define GL_MEMORY_NUM_COLUMNS 26u
+#define GL_MEMORY_MAX_LOG_ROWS 24u
+/* MemoryOp (witness/memory.rs:80-87), 56 bytes */
+typedef struct gl_memory_op {
+    uint32_t filter, is_read;             /* 0 / 1 */
+    uint32_t context, segment, virt;      /* MemoryAddress; 32 bits each, as new_u256s enforces */
+    uint32_t timestamp;                   /* clock * NUM_CHANNELS + channel; this library: < 2^32 */
+    uint32_t value[8];                    /* U256, little-endian 32-bit limbs */
+} gl_memory_op;
+/* MemoryStark as data (memory_stark.rs:243-321, :450-459): *out points at static tables, host code, no GPU.  26 columns, no public
+ * inputs, constraint_degree 3, num_challenges left 0 for the caller's StarkConfig to fill in a copy; the 21 constraints of
+ * eval_packed_generic in the order it yields them with their products expanded to term lists, then the two of eval_lookups on
+ * (RANGE_CHECK_PERMUTED, COUNTER_PERMUTED) (lookup.rs:13-34); the permutation pairs (22, 24) and (23, 25). */
+int gl_memory_stark_desc(const gl_stark_desc** out);
+/* MemoryStark::generate_trace (memory_stark.rs:120-237) on host memory, statement by statement, no GPU: the stable sort_by_key by
+ * (context, segment, virt, timestamp), fill_gaps (:163-192), pad_memory_ops (:194-212), the second sort, into_row (:52-70),
+ * generate_first_change_flags_and_rc (:73-118), COUNTER and permuted_cols (:143-151).  *n_rows = the trace's height n, a power of
+ * two; cols_out[26][n] canonical, or null to ask for n alone.  Refusals, all before anything is written: GL_ERR_ARG for a null ops
+ * or n_rows, num_ops == 0, a filter or is_read other than 0 / 1, a log on which the assertion of :112-116 fails (a context or segment
+ * step, minus one, that is >= n: fill_gaps does not fill those), and capacity_rows < n with a non-null cols_out; GL_ERR_UNSUPPORTED
+ * for n above 2^24. */
+int gl_memory_trace_host(const gl_memory_op* ops, size_t num_ops, uint64_t* cols_out, size_t capacity_rows, size_t* n_rows);
+/* The same on the device, as a handle: the height is known before the caller makes its gl_stark.  _new takes the log from host
+ * memory, _new_device from HBM (left untouched; it is not needed after the call returns); both sort it, count the rows fill_gaps
+ * will add per neighbour pair, and wait ONCE for the stream, for n.  The refusals and their codes are gl_memory_trace_host's.  The
+ * handle holds a reference to the context. */
+typedef struct gl_memory_trace gl_memory_trace;
+int gl_memory_trace_new(gl_ctx* ctx, const gl_memory_op* h_ops, size_t num_ops, gl_memory_trace** out);
+int gl_memory_trace_new_device(gl_ctx* ctx, const gl_memory_op* d_ops, size_t num_ops, gl_memory_trace** out);
+size_t gl_memory_trace_rows(const gl_memory_trace* t) GL_NOEXCEPT;
+/* All 26 columns of the trace, d_cols[26][n], the two permuted columns included (gl_stark_lookup_columns' body on the lookup
+ * (22, 23, 24, 25); a trace of one row is written without it).  Stream-ordered on the handle's context, temporaries from its pool, no
+ * host synchronisation; may be called any number of times.  No per-op serial pass: a prefix sum over the per-pair counts places every
+ * op, one thread per output row finds its source by binary search. */
+int gl_memory_trace_fill(gl_memory_trace* t, uint64_t* d_cols);
+void gl_memory_trace_free(gl_memory_trace* t) GL_NOEXCEPT;
+
 /* ---- prove() ---------------------------------------------------------------------------------------*/
 /* plonk::prover::prove (plonky2/src/plonk/prover.rs:102-329) from step 4 on, i.e. given the FULL witness matrix
  * `MatrixWitness.wire_values` (iop/witness.rs:256-258) h_wires[num_wires][n] and the public inputs.  Every

@@ -21,4 +21,5 @@ from .api import (  # noqa: F401
     CrossTableLookup, CtlColumn, StarkSet, StarkSetDesc, TableWithColumns, stark_set_verify,
     OpeningsBatchVerifier, StarkBatchVerifier,
     lookup_constraints, permuted_cols, permuted_cols_host,
+    MEMORY_OP_DTYPE, MemoryTrace, memory_ctl_data, memory_ctl_filter, memory_stark, memory_trace_host,
 )

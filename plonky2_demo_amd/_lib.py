@@ -222,6 +222,13 @@ SIGNATURES = {
     # STARK lookups: permuted_cols (ctx, d_cols, num_columns, n, gl_stark_lookup*, count) and its host form
     "gl_stark_lookup_columns": (c_int, [c_vp, c_vp, c_u32, c_sz, c_vp, c_u32]),
     "gl_permuted_cols_host": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "gl_memory_stark_desc": (c_int, [ctypes.POINTER(c_vp)]),
+    "gl_memory_trace_host": (c_int, [c_vp, c_sz, c_vp, c_sz, ctypes.POINTER(c_sz)]),
+    "gl_memory_trace_new": (c_int, [c_vp, c_vp, c_sz, ctypes.POINTER(c_vp)]),
+    "gl_memory_trace_new_device": (c_int, [c_vp, c_vp, c_sz, ctypes.POINTER(c_vp)]),
+    "gl_memory_trace_rows": (c_sz, [c_vp]),
+    "gl_memory_trace_fill": (c_int, [c_vp, c_vp]),
+    "gl_memory_trace_free": (None, [c_vp]),
     # batch verification of FRI openings of any instance, and of STARK proofs on top of it (device Merkle paths and FRI queries)
     "gl_openings_batch_verifier_new": (c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, ctypes.POINTER(c_vp)]),
     "gl_openings_batch_verifier_verify": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
@@ -365,6 +372,14 @@ class StarkDescStruct(ctypes.Structure):
         self.constraint_filter, self.constraint_num_terms = table(c_u32, filters), table(c_u32, num_terms)
         self.term_coeff, self.term_num_factors, self.factors = table(c_u64, coeffs), table(c_u32, num_factors), table(c_u32, factors)
         self.pair_len, self.pair_columns = table(c_u32, pair_len), table(c_u32, pair_columns)
+
+
+# MemoryStark's columns (include/plonky2_mi355x.h GL_MEMORY_*, evm/src/memory/columns.rs) and gl_memory_op as a numpy record
+GL_MEMORY_NUM_CHANNELS, GL_MEMORY_VALUE_LIMBS = 6, 8
+(GL_MEMORY_FILTER, GL_MEMORY_TIMESTAMP, GL_MEMORY_IS_READ, GL_MEMORY_ADDR_CONTEXT, GL_MEMORY_ADDR_SEGMENT, GL_MEMORY_ADDR_VIRTUAL, GL_MEMORY_VALUE_START) = range(7)
+(GL_MEMORY_CONTEXT_FIRST_CHANGE, GL_MEMORY_SEGMENT_FIRST_CHANGE, GL_MEMORY_VIRTUAL_FIRST_CHANGE) = (14, 15, 16)
+(GL_MEMORY_RANGE_CHECK, GL_MEMORY_COUNTER, GL_MEMORY_RANGE_CHECK_PERMUTED, GL_MEMORY_COUNTER_PERMUTED, GL_MEMORY_NUM_COLUMNS) = (22, 23, 24, 25, 26)
+MEMORY_OP_FIELDS = [("filter", "<u4"), ("is_read", "<u4"), ("context", "<u4"), ("segment", "<u4"), ("virt", "<u4"), ("timestamp", "<u4"), ("value", "<u4", (8,))]
 
 
 (GL_STARK_NODE, GL_STARK_CONST) = (3, 4)                                                   # operand kinds of a gl_stark_dag only

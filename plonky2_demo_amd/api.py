@@ -1665,6 +1665,81 @@ def permuted_cols(inputs, table, ctx=None):
     return out[0], out[1]
 
 
+# ------------------------------------------------------------------------------------- MemoryStark (evm/src/memory)
+MEMORY_OP_DTYPE = np.dtype(_lib.MEMORY_OP_FIELDS)                      # gl_memory_op: MemoryOp (witness/memory.rs:80-87), 56 bytes
+
+
+def memory_stark():
+    """MemoryStark (memory_stark.rs:243-321, :450-459) as a StarkDesc, read from the library's own tables (gl_memory_stark_desc)."""
+    ptr = ctypes.c_void_p()
+    check(lib.gl_memory_stark_desc(ctypes.byref(ptr)))
+    d = ctypes.cast(ptr, ctypes.POINTER(_lib.StarkDescStruct)).contents
+    constraints, t, f = [], 0, 0
+    for c in range(d.num_constraints):
+        terms = []
+        for _ in range(d.constraint_num_terms[c]):
+            ops = [(d.factors[f + k] >> 30, d.factors[f + k] & 0x3FFFFFFF) for k in range(d.term_num_factors[t])]
+            terms.append((int(d.term_coeff[t]), ops))
+            f += d.term_num_factors[t]
+            t += 1
+        constraints.append((int(d.constraint_filter[c]), terms))
+    pairs, k = [], 0
+    for p in range(d.num_permutation_pairs):
+        pairs.append([(int(d.pair_columns[2 * (k + i)]), int(d.pair_columns[2 * (k + i) + 1])) for i in range(d.pair_len[p])])
+        k += d.pair_len[p]
+    return StarkDesc(d.num_columns, d.num_public_inputs, d.constraint_degree, constraints, pairs)
+
+
+def memory_ctl_data():
+    """ctl_data (memory_stark.rs:30-36): IS_READ, the address, the eight value limbs, TIMESTAMP."""
+    cols = [_lib.GL_MEMORY_IS_READ, _lib.GL_MEMORY_ADDR_CONTEXT, _lib.GL_MEMORY_ADDR_SEGMENT, _lib.GL_MEMORY_ADDR_VIRTUAL]
+    cols += [_lib.GL_MEMORY_VALUE_START + i for i in range(_lib.GL_MEMORY_VALUE_LIMBS)]
+    return CtlColumn.singles(cols + [_lib.GL_MEMORY_TIMESTAMP])
+
+
+def memory_ctl_filter():
+    """ctl_filter (memory_stark.rs:38-40)."""
+    return CtlColumn.single(_lib.GL_MEMORY_FILTER)
+
+
+def _memory_ops(ops):
+    a = np.ascontiguousarray(ops)
+    if a.dtype != MEMORY_OP_DTYPE or a.ndim != 1:
+        raise ValueError("memory ops are a one-dimensional array of MEMORY_OP_DTYPE records")
+    return a
+
+
+def memory_trace_host(ops):
+    """MemoryStark::generate_trace (memory_stark.rs:120-237) on the host, the reference's loops -> [26][n]; needs no GPU."""
+    a = _memory_ops(ops)
+    n = ctypes.c_size_t()
+    check(lib.gl_memory_trace_host(_p(a) if a.size else None, a.size, None, 0, ctypes.byref(n)))
+    out = np.empty((_lib.GL_MEMORY_NUM_COLUMNS, n.value), dtype=np.uint64)
+    check(lib.gl_memory_trace_host(_p(a), a.size, _p(out), n.value, ctypes.byref(n)))
+    return out
+
+
+class MemoryTrace(_Owned):
+    """gl_memory_trace: a memory-operation log sorted and counted on the device.  `rows` is the trace's height, known before the Stark
+    is made; fill(d_ptr) writes all 26 columns of d_cols[26][rows], stream-ordered, any number of times.  ops: MEMORY_OP_DTYPE records,
+    or with device_ptr a log of num_ops records already in HBM."""
+    _free = "gl_memory_trace_free"
+
+    def __init__(self, ops=None, ctx=None, device_ptr=None, num_ops=None):
+        self.ctx = _ctx(ctx)
+        h = ctypes.c_void_p()
+        if device_ptr is not None:
+            check(lib.gl_memory_trace_new_device(self.ctx.handle, device_ptr, int(num_ops), ctypes.byref(h)))
+        else:
+            a = _memory_ops(ops)
+            check(lib.gl_memory_trace_new(self.ctx.handle, _p(a) if a.size else None, a.size, ctypes.byref(h)))
+        self.handle = h.value
+        self.rows = lib.gl_memory_trace_rows(self.handle)
+
+    def fill(self, d_cols_ptr):
+        check(lib.gl_memory_trace_fill(self.handle, d_cols_ptr))
+
+
 def pow_grind(sponge_state, input_buffer, min_leading_zeros, ctx=None, hasher="poseidon"):
     """fri_proof_of_work (fri/prover.rs:115-160): the smallest valid witness."""
     ctx = _ctx(ctx)

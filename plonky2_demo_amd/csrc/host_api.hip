@@ -7,8 +7,11 @@
 #include "fri_instance.hpp"
 #include "proof.hpp"
 #include "rng.cuh"
+#include <algorithm>
 #include <cstring>
+#include <map>
 #include <memory>
+#include <tuple>
 
 using glhost::HostChallenger;
 
@@ -196,5 +199,197 @@ extern "C" int gl_permuted_cols_host(const uint64_t* h_inputs, const uint64_t* h
     for (size_t k = 0; k < unused_table_inds.size(); k++) permuted_table[unused_table_inds[k]] = unused_table_vals[k];
     memcpy(h_permuted_inputs, sorted_inputs.data(), n * sizeof(uint64_t));
     memcpy(h_permuted_table, permuted_table.data(), n * sizeof(uint64_t));
+    return GL_OK;
+} catch (...) { return gl_caught(); }
+
+// ---- MemoryStark on the host ------------------------------------------------------------------------------------------------
+namespace {
+// A polynomial over the operand words of a gl_stark_desc, as eval_packed_generic's expressions expand to: sorted factor words -> coefficient
+struct MemPoly {
+    std::map<std::vector<uint32_t>, int64_t> terms;
+    static MemPoly constant(int64_t v) { MemPoly p; p.terms[{}] = v; return p; }
+    static MemPoly operand(uint32_t kind, uint32_t col) { MemPoly p; p.terms[{kind << 30 | col}] = 1; return p; }
+    MemPoly operator-(const MemPoly& o) const { MemPoly r = *this; for (const auto& t : o.terms) r.terms[t.first] -= t.second; return r; }
+    MemPoly operator+(const MemPoly& o) const { MemPoly r = *this; for (const auto& t : o.terms) r.terms[t.first] += t.second; return r; }
+    MemPoly operator*(const MemPoly& o) const {
+        MemPoly r;
+        for (const auto& a : terms)
+            for (const auto& b : o.terms) {
+                std::vector<uint32_t> f = a.first;
+                f.insert(f.end(), b.first.begin(), b.first.end());
+                std::sort(f.begin(), f.end());
+                r.terms[f] += a.second * b.second;
+            }
+        return r;
+    }
+};
+struct MemoryDescTables {
+    std::vector<uint32_t> filter, num_terms, num_factors, factors, pair_len, pair_columns;
+    std::vector<uint64_t> coeff;
+    gl_stark_desc desc{};
+    void yield(uint32_t filt, const MemPoly& p) {
+        uint32_t k = 0;
+        for (const auto& t : p.terms) {
+            if (!t.second) continue;
+            coeff.push_back(t.second > 0 ? (uint64_t)t.second : GL_P - (uint64_t)(-t.second));
+            num_factors.push_back((uint32_t)t.first.size());
+            factors.insert(factors.end(), t.first.begin(), t.first.end());
+            k++;
+        }
+        filter.push_back(filt);
+        num_terms.push_back(k);
+    }
+    void term(uint64_t c, std::initializer_list<uint32_t> f) { coeff.push_back(c); num_factors.push_back((uint32_t)f.size()); factors.insert(factors.end(), f.begin(), f.end()); }
+    MemoryDescTables() {
+        const auto local = [](uint32_t c) { return MemPoly::operand(GL_STARK_LOCAL, c); };
+        const auto next = [](uint32_t c) { return MemPoly::operand(GL_STARK_NEXT, c); };
+        const MemPoly one = MemPoly::constant(1);                                        // memory_stark.rs:251-264
+        const MemPoly timestamp = local(GL_MEMORY_TIMESTAMP), addr_context = local(GL_MEMORY_ADDR_CONTEXT), addr_segment = local(GL_MEMORY_ADDR_SEGMENT),
+                      addr_virtual = local(GL_MEMORY_ADDR_VIRTUAL);
+        const MemPoly next_timestamp = next(GL_MEMORY_TIMESTAMP), next_is_read = next(GL_MEMORY_IS_READ), next_addr_context = next(GL_MEMORY_ADDR_CONTEXT),
+                      next_addr_segment = next(GL_MEMORY_ADDR_SEGMENT), next_addr_virtual = next(GL_MEMORY_ADDR_VIRTUAL);
+        const MemPoly filter_ = local(GL_MEMORY_FILTER);                                 // :266-274
+        yield(GL_STARK_ALL, filter_ * (filter_ - one));
+        const MemPoly is_dummy = one - filter_, is_write = one - local(GL_MEMORY_IS_READ);
+        yield(GL_STARK_ALL, is_dummy * is_write);
+        const MemPoly context_first_change = local(GL_MEMORY_CONTEXT_FIRST_CHANGE), segment_first_change = local(GL_MEMORY_SEGMENT_FIRST_CHANGE),
+                      virtual_first_change = local(GL_MEMORY_VIRTUAL_FIRST_CHANGE);      // :276-287
+        const MemPoly address_unchanged = one - context_first_change - segment_first_change - virtual_first_change;
+        const MemPoly range_check = local(GL_MEMORY_RANGE_CHECK);
+        yield(GL_STARK_ALL, context_first_change * (one - context_first_change));       // :289-293
+        yield(GL_STARK_ALL, segment_first_change * (one - segment_first_change));
+        yield(GL_STARK_ALL, virtual_first_change * (one - virtual_first_change));
+        yield(GL_STARK_ALL, address_unchanged * (one - address_unchanged));
+        yield(GL_STARK_TRANSITION, segment_first_change * (next_addr_context - addr_context));      // :295-304
+        yield(GL_STARK_TRANSITION, virtual_first_change * (next_addr_context - addr_context));
+        yield(GL_STARK_TRANSITION, virtual_first_change * (next_addr_segment - addr_segment));
+        yield(GL_STARK_TRANSITION, address_unchanged * (next_addr_context - addr_context));
+        yield(GL_STARK_TRANSITION, address_unchanged * (next_addr_segment - addr_segment));
+        yield(GL_STARK_TRANSITION, address_unchanged * (next_addr_virtual - addr_virtual));
+        const MemPoly computed_range_check = context_first_change * (next_addr_context - addr_context - one)      // :306-311
+                                             + segment_first_change * (next_addr_segment - addr_segment - one)
+                                             + virtual_first_change * (next_addr_virtual - addr_virtual - one)
+                                             + address_unchanged * (next_timestamp - timestamp);
+        yield(GL_STARK_TRANSITION, range_check - computed_range_check);
+        for (uint32_t i = 0; i < GL_MEMORY_VALUE_LIMBS; i++)                             // :313-318
+            yield(GL_STARK_TRANSITION, next_is_read * address_unchanged * (next(GL_MEMORY_VALUE_START + i) - local(GL_MEMORY_VALUE_START + i)));
+        // eval_lookups (lookup.rs:13-34) on (RANGE_CHECK_PERMUTED, COUNTER_PERMUTED), term for term as api.py's lookup_constraints writes it
+        const uint32_t li = GL_STARK_LOCAL << 30 | GL_MEMORY_RANGE_CHECK_PERMUTED, ni = GL_STARK_NEXT << 30 | GL_MEMORY_RANGE_CHECK_PERMUTED,
+                       nt = GL_STARK_NEXT << 30 | GL_MEMORY_COUNTER_PERMUTED;
+        filter.push_back(GL_STARK_ALL); num_terms.push_back(4);
+        term(1, {ni, ni}); term(GL_P - 1, {ni, nt}); term(GL_P - 1, {li, ni}); term(1, {li, nt});
+        filter.push_back(GL_STARK_LAST_ROW); num_terms.push_back(2);
+        term(1, {ni}); term(GL_P - 1, {nt});
+        pair_len = {1, 1};                                                               // :454-459
+        pair_columns = {GL_MEMORY_RANGE_CHECK, GL_MEMORY_RANGE_CHECK_PERMUTED, GL_MEMORY_COUNTER, GL_MEMORY_COUNTER_PERMUTED};
+        desc.num_columns = GL_MEMORY_NUM_COLUMNS; desc.num_public_inputs = 0; desc.constraint_degree = 3; desc.num_challenges = 0;
+        desc.num_constraints = (uint32_t)filter.size();
+        desc.constraint_filter = filter.data(); desc.constraint_num_terms = num_terms.data(); desc.term_coeff = coeff.data();
+        desc.term_num_factors = num_factors.data(); desc.factors = factors.data();
+        desc.num_permutation_pairs = 2; desc.pair_len = pair_len.data(); desc.pair_columns = pair_columns.data();
+    }
+};
+}  // namespace
+
+extern "C" int gl_memory_stark_desc(const gl_stark_desc** out) try {
+    GL_REQUIRE(out, GL_ERR_ARG, "gl_memory_stark_desc: null argument");
+    static const MemoryDescTables tables;
+    *out = &tables.desc;
+    return GL_OK;
+} catch (...) { return gl_caught(); }
+
+// MemoryStark::generate_trace (memory_stark.rs:120-237), the reference's loops statement by statement; gl_memory_trace_fill
+// (memory_trace.hip) is the device form
+extern "C" int gl_memory_trace_host(const gl_memory_op* ops, size_t num_ops, uint64_t* cols_out, size_t capacity_rows, size_t* n_rows) try {
+    GL_REQUIRE(ops && n_rows, GL_ERR_ARG, "gl_memory_trace_host: null argument");
+    GL_REQUIRE(num_ops >= 1, GL_ERR_ARG, "gl_memory_trace_host: no memory ops");           // :195 expect("No memory ops?")
+    for (size_t i = 0; i < num_ops; i++)
+        GL_REQUIRE(ops[i].filter <= 1 && ops[i].is_read <= 1, GL_ERR_ARG, "gl_memory_trace_host: filter and is_read are 0 or 1");
+    GL_REQUIRE(num_ops <= (size_t(1) << GL_MEMORY_MAX_LOG_ROWS), GL_ERR_UNSUPPORTED, "gl_memory_trace_host: more than 2^24 rows");
+    const auto key_less = [](const gl_memory_op& a, const gl_memory_op& b) {               // MemoryOp::sorting_key, witness/memory.rs:117-124
+        return std::make_tuple(a.context, a.segment, a.virt, a.timestamp) < std::make_tuple(b.context, b.segment, b.virt, b.timestamp);
+    };
+    const auto next_power_of_two = [](size_t k) { size_t p = 1; while (p < k) p <<= 1; return p; };
+    std::vector<gl_memory_op> memory_ops(ops, ops + num_ops);
+    std::stable_sort(memory_ops.begin(), memory_ops.end(), key_less);                      // :125
+    const uint64_t max_rc = next_power_of_two(memory_ops.size()) - 1;                      // :164
+    // what fill_gaps is about to push, counted before it pushes: one pair can ask for 2^31 rows
+    uint64_t pushed = 0;
+    for (size_t i = 0; i + 1 < num_ops; i++) {
+        const gl_memory_op &curr = memory_ops[i], &next = memory_ops[i + 1];
+        if (curr.context != next.context || curr.segment != next.segment) continue;
+        if (curr.virt != next.virt) pushed += ((uint64_t)next.virt - curr.virt - 1) / (max_rc + 1);
+        else if (next.timestamp != curr.timestamp) pushed += ((uint64_t)next.timestamp - curr.timestamp - 1) / max_rc;
+    }
+    GL_REQUIRE(num_ops + pushed <= (uint64_t(1) << GL_MEMORY_MAX_LOG_ROWS), GL_ERR_UNSUPPORTED, "gl_memory_trace_host: more than 2^24 rows");
+    const std::vector<gl_memory_op> snapshot = memory_ops;                                 // :165 memory_ops.clone()
+    for (size_t i = 0; i + 1 < snapshot.size(); i++) {                                     // fill_gaps, :165-191
+        gl_memory_op curr = snapshot[i];
+        const gl_memory_op& next = snapshot[i + 1];
+        if (curr.context != next.context || curr.segment != next.segment) {
+        } else if (curr.virt != next.virt) {
+            while ((uint64_t)next.virt - curr.virt - 1 > max_rc) {
+                gl_memory_op dummy_read{};                                                 // new_dummy_read(dummy_address, 0, U256::zero())
+                dummy_read.is_read = 1;
+                dummy_read.context = curr.context; dummy_read.segment = curr.segment;
+                dummy_read.virt = curr.virt + (uint32_t)(max_rc + 1);
+                memory_ops.push_back(dummy_read);
+                curr = dummy_read;
+            }
+        } else {
+            while ((uint64_t)next.timestamp - curr.timestamp > max_rc) {
+                gl_memory_op dummy_read = curr;                                            // new_dummy_read(curr.address, curr.timestamp + max_rc, curr.value)
+                dummy_read.filter = 0; dummy_read.is_read = 1;
+                dummy_read.timestamp = curr.timestamp + (uint32_t)max_rc;
+                memory_ops.push_back(dummy_read);
+                curr = dummy_read;
+            }
+        }
+    }
+    gl_memory_op padding_op = memory_ops.back();                                           // pad_memory_ops, :194-212
+    padding_op.filter = 0; padding_op.is_read = 1;
+    const size_t n = next_power_of_two(memory_ops.size());
+    memory_ops.resize(n, padding_op);
+    std::stable_sort(memory_ops.begin(), memory_ops.end(), key_less);                      // :131
+    // generate_first_change_flags_and_rc's assertion (:112-116), looked at before anything is written
+    for (size_t idx = 0; idx + 1 < n; idx++) {
+        const gl_memory_op &row = memory_ops[idx], &next_row = memory_ops[idx + 1];
+        const uint64_t rc = row.context != next_row.context   ? (uint64_t)next_row.context - row.context - 1
+                            : row.segment != next_row.segment ? (uint64_t)next_row.segment - row.segment - 1
+                            : row.virt != next_row.virt       ? (uint64_t)next_row.virt - row.virt - 1
+                                                              : (uint64_t)next_row.timestamp - row.timestamp;
+        GL_REQUIRE(rc < n, GL_ERR_ARG, "gl_memory_trace_host: a range check is too large (a context or segment step of more than the trace's height)");
+    }
+    *n_rows = n;
+    if (!cols_out) return GL_OK;
+    GL_REQUIRE(capacity_rows >= n, GL_ERR_ARG, "gl_memory_trace_host: capacity_rows is below the trace's height");
+    std::vector<uint64_t> cols((size_t)GL_MEMORY_NUM_COLUMNS * n, 0);
+    const auto at = [&](uint32_t c, size_t i) -> uint64_t& { return cols[(size_t)c * n + i]; };
+    for (size_t i = 0; i < n; i++) {                                                       // into_row, :52-70
+        const gl_memory_op& op = memory_ops[i];
+        at(GL_MEMORY_FILTER, i) = op.filter; at(GL_MEMORY_TIMESTAMP, i) = op.timestamp; at(GL_MEMORY_IS_READ, i) = op.is_read;
+        at(GL_MEMORY_ADDR_CONTEXT, i) = op.context; at(GL_MEMORY_ADDR_SEGMENT, i) = op.segment; at(GL_MEMORY_ADDR_VIRTUAL, i) = op.virt;
+        for (uint32_t j = 0; j < GL_MEMORY_VALUE_LIMBS; j++) at(GL_MEMORY_VALUE_START + j, i) = op.value[j];
+    }
+    for (size_t idx = 0; idx + 1 < n; idx++) {                                             // generate_first_change_flags_and_rc, :73-118
+        const uint64_t context = at(GL_MEMORY_ADDR_CONTEXT, idx), segment = at(GL_MEMORY_ADDR_SEGMENT, idx), virt = at(GL_MEMORY_ADDR_VIRTUAL, idx),
+                       timestamp = at(GL_MEMORY_TIMESTAMP, idx);
+        const uint64_t next_context = at(GL_MEMORY_ADDR_CONTEXT, idx + 1), next_segment = at(GL_MEMORY_ADDR_SEGMENT, idx + 1),
+                       next_virt = at(GL_MEMORY_ADDR_VIRTUAL, idx + 1), next_timestamp = at(GL_MEMORY_TIMESTAMP, idx + 1);
+        const bool context_first_change = context != next_context;
+        const bool segment_first_change = segment != next_segment && !context_first_change;
+        const bool virtual_first_change = virt != next_virt && !segment_first_change && !context_first_change;
+        at(GL_MEMORY_CONTEXT_FIRST_CHANGE, idx) = context_first_change;
+        at(GL_MEMORY_SEGMENT_FIRST_CHANGE, idx) = segment_first_change;
+        at(GL_MEMORY_VIRTUAL_FIRST_CHANGE, idx) = virtual_first_change;
+        at(GL_MEMORY_RANGE_CHECK, idx) = context_first_change   ? next_context - context - 1
+                                         : segment_first_change ? next_segment - segment - 1
+                                         : virtual_first_change ? next_virt - virt - 1
+                                                                : next_timestamp - timestamp;
+    }
+    for (size_t i = 0; i < n; i++) at(GL_MEMORY_COUNTER, i) = i;                           // generate_trace_col_major, :143-151
+    GL_TRY(gl_permuted_cols_host(&at(GL_MEMORY_RANGE_CHECK, 0), &at(GL_MEMORY_COUNTER, 0), n, &at(GL_MEMORY_RANGE_CHECK_PERMUTED, 0),
+                                 &at(GL_MEMORY_COUNTER_PERMUTED, 0)));
+    memcpy(cols_out, cols.data(), cols.size() * sizeof(uint64_t));
     return GL_OK;
 } catch (...) { return gl_caught(); }

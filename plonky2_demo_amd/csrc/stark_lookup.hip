@@ -11,7 +11,7 @@
 // Lookups are worked in chunks of at most 2^23 / n (at least one): the temporaries of a chunk are bounded, and every phase of a chunk
 // is ONE launch over its lookups.  A source column that several lookups of a chunk share is sorted once; one that stands in the same
 // slot of the next chunk (a shared table does: tables take the first slots) is not sorted again.
-#include "context.hpp"
+#include "stark_lookup.hpp"
 #include "stark_lookup_kernels.cuh"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
@@ -23,12 +23,7 @@
 #define GLK_CHUNK_ELEMS (size_t(1) << 23)      // lookups x n per chunk: about 80 bytes of temporaries per element
 
 namespace {
-struct Chunk {
-    uint32_t first, count;                     // lookups [first, first + count) of the call
-    uint32_t num_slots, keep;                  // sorted source columns of the chunk; the first `keep` are the previous chunk's
-    size_t lk_off, slot_off, seg_off;          // offsets of its tables in the uploaded words
-};
-
+using gllookup::Chunk;
 // the sorts of slots [first, first + count): one segmented sort, or a loop of whole-array sorts (DESIGN.md section 19 has both times)
 int sort_slots(bool segmented, void* d_tmp, size_t& tmp_bytes, const uint64_t* in, uint64_t* out, uint32_t n, uint32_t first, uint32_t count,
                const uint32_t* d_seg_offsets, hipStream_t st) {
@@ -47,8 +42,9 @@ int sort_slots(bool segmented, void* d_tmp, size_t& tmp_bytes, const uint64_t* i
 }
 }  // namespace
 
-extern "C" int gl_stark_lookup_columns(gl_ctx* c, uint64_t* d_cols, uint32_t num_columns, size_t n_rows, const gl_stark_lookup* lookups, uint32_t count) try {
-    GL_REQUIRE(c && d_cols && lookups, GL_ERR_ARG, "gl_stark_lookup_columns: null argument");
+// the call's rules and its plan: chunks, and per chunk its lookups with their slots, the slots' columns and the segment offsets of the sort
+int gllookup::plan(uint32_t num_columns, size_t n_rows, const gl_stark_lookup* lookups, uint32_t count, Plan* out) {
+    GL_REQUIRE(lookups && out, GL_ERR_ARG, "gl_stark_lookup_columns: null argument");
     GL_REQUIRE(count >= 1 && count <= GLK_MAX_LOOKUPS, GL_ERR_ARG, "gl_stark_lookup_columns: 1..1024 lookups");
     GL_REQUIRE(n_rows >= 2 && n_rows <= (size_t(1) << GLK_MAX_LOG_N) && (n_rows & (n_rows - 1)) == 0, GL_ERR_ARG,
                "gl_stark_lookup_columns: n is a power of two, 2..2^24");
@@ -66,17 +62,12 @@ extern "C" int gl_stark_lookup_columns(gl_ctx* c, uint64_t* d_cols, uint32_t num
     GL_REQUIRE(std::adjacent_find(outputs.begin(), outputs.end()) == outputs.end(), GL_ERR_ARG, "gl_stark_lookup_columns: two outputs share a column");
     for (uint32_t o : outputs)
         GL_REQUIRE(!std::binary_search(sources.begin(), sources.end(), o), GL_ERR_ARG, "gl_stark_lookup_columns: an output column is also an input or table column");
-    GL_TRY(c->activate());
-    hipStream_t st = c->stream;
-    GlTimed timed(c, "lookup columns");
-
-    // ---- the plan: chunks, and per chunk its lookups with their slots, the slots' columns and the segment offsets of the sort ----
     uint32_t lg_n = 0;
     while ((size_t(1) << lg_n) < n_rows) lg_n++;
-    const uint32_t level_bits = lg_n + 2;                           // levels + n lie in [0, 2n]
     const uint32_t per_chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(count, GLK_CHUNK_ELEMS / n_rows));
-    std::vector<Chunk> chunks;
-    std::vector<uint32_t> words;                                    // every chunk's tables, uploaded once
+    std::vector<Chunk>& chunks = out->chunks;
+    std::vector<uint32_t>& words = out->words;                      // every chunk's tables, uploaded once
+    chunks.clear(); words.clear();
     std::vector<uint32_t> prev_slots;
     uint32_t max_slots = 0;
     for (uint32_t first = 0; first < count; first += per_chunk) {
@@ -108,6 +99,18 @@ extern "C" int gl_stark_lookup_columns(gl_ctx* c, uint64_t* d_cols, uint32_t num
         prev_slots = slots;
         chunks.push_back(ch);
     }
+    out->n = n; out->lg_n = lg_n; out->count = count; out->per_chunk = per_chunk; out->max_slots = max_slots;
+    return GL_OK;
+}
+
+// Every launch of the call on the context's stream, its tables already in HBM (d_words: plan.words); temporaries from the pool.  Nothing
+// here waits for the stream.
+int gllookup::run(gl_ctx* c, uint64_t* d_cols, const Plan& plan, const uint32_t* d_words) {
+    hipStream_t st = c->stream;
+    const uint32_t n = plan.n, lg_n = plan.lg_n, per_chunk = plan.per_chunk, max_slots = plan.max_slots;
+    const size_t n_rows = n;
+    const std::vector<Chunk>& chunks = plan.chunks;
+    const uint32_t level_bits = lg_n + 2;                           // levels + n lie in [0, 2n]
     // One segmented sort works a segment per workgroup: 2.1 ms flat at n = 2^16 whatever the number of columns, where a whole-array sort
     // costs 0.056 ms per column.  It pays from about 48 columns of 2^16 on, from fewer at smaller n.
     static const int sort_env = [] { const char* e = getenv("GL_LOOKUP_SEGMENTED_SORT"); return e ? atoi(e) : -1; }();      // tuning knob: 0 loop, 1 segmented
@@ -116,8 +119,7 @@ extern "C" int gl_stark_lookup_columns(gl_ctx* c, uint64_t* d_cols, uint32_t num
     // ---- temporaries from the pool ----
     const size_t chunk_elems = (size_t)per_chunk * 2 * n;           // merge positions of a chunk
     const uint32_t nseg = (2 * n + GLK_SEG - 1) / GLK_SEG;
-    DevBuf d_words(c), d_canon(c), d_sorted(c), d_w(c), d_ev(c), d_flag(c), d_keys(c), d_keys_out(c), d_vals_out(c), d_seg(c), d_tmp(c);
-    GL_TRY(d_words.alloc(words.size() * 4));
+    DevBuf d_canon(c), d_sorted(c), d_w(c), d_ev(c), d_flag(c), d_keys(c), d_keys_out(c), d_vals_out(c), d_seg(c), d_tmp(c);
     GL_TRY(d_canon.alloc((size_t)std::max(max_slots, per_chunk) * n * 8));      // the unsorted keys [slots][n]; afterwards the leftover values [lookups][n]
     GL_TRY(d_sorted.alloc((size_t)max_slots * n * 8));
     GL_TRY(d_w.alloc(chunk_elems * 4));                             // the events' weights; afterwards the leftover ranks
@@ -131,22 +133,21 @@ extern "C" int gl_stark_lookup_columns(gl_ctx* c, uint64_t* d_cols, uint32_t num
     for (const Chunk& ch : chunks) {
         size_t tb_cols = 0, tb_events = 0;
         if (ch.num_slots > ch.keep)
-            GL_TRY(sort_slots(segmented(ch.num_slots - ch.keep), nullptr, tb_cols, d_canon.as<uint64_t>(), d_sorted.as<uint64_t>(), n, ch.keep, ch.num_slots - ch.keep, d_words.as<uint32_t>(), st));
+            GL_TRY(sort_slots(segmented(ch.num_slots - ch.keep), nullptr, tb_cols, d_canon.as<uint64_t>(), d_sorted.as<uint64_t>(), n, ch.keep, ch.num_slots - ch.keep, d_words, st));
         GL_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_events, d_keys.as<const uint32_t>(), d_keys_out.as<uint32_t>(), d_ev.as<const uint32_t>(),
                                                         d_vals_out.as<uint32_t>(), (int)(ch.count * 2 * n), 0, (int)(level_bits + 32u - (uint32_t)__builtin_clz(ch.count)), st));
         tb_max = std::max(tb_max, std::max(tb_cols, tb_events));
     }
     GL_TRY(d_tmp.alloc(tb_max));
-    GL_CHECK_HIP(hipMemcpyAsync(d_words.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, st));
 
     for (const Chunk& ch : chunks) {
-        const GlLookupDev* lk = (const GlLookupDev*)(d_words.as<uint32_t>() + ch.lk_off);
-        const uint32_t* slot_col = d_words.as<uint32_t>() + ch.slot_off;
+        const GlLookupDev* lk = (const GlLookupDev*)(d_words + ch.lk_off);
+        const uint32_t* slot_col = d_words + ch.slot_off;
         const uint32_t fresh = ch.num_slots - ch.keep, total = ch.count * 2 * n;
         if (fresh) {
             hipLaunchKernelGGL(k_lookup_canon, dim3((n + 255) / 256, fresh), dim3(256), 0, st, (const uint64_t*)d_cols, n, slot_col, ch.keep, d_canon.as<uint64_t>());
             size_t tb = tb_max;
-            GL_TRY(sort_slots(segmented(fresh), d_tmp.p, tb, d_canon.as<uint64_t>(), d_sorted.as<uint64_t>(), n, ch.keep, fresh, d_words.as<uint32_t>() + ch.seg_off, st));
+            GL_TRY(sort_slots(segmented(fresh), d_tmp.p, tb, d_canon.as<uint64_t>(), d_sorted.as<uint64_t>(), n, ch.keep, fresh, d_words + ch.seg_off, st));
         }
         hipLaunchKernelGGL(k_lookup_classify, dim3((2 * n + 255) / 256, ch.count), dim3(256), 0, st, d_sorted.as<const uint64_t>(), lk, n, d_cols, d_w.as<int>(),
                            d_ev.as<uint32_t>(), d_flag.as<uint32_t>());
@@ -169,6 +170,19 @@ extern "C" int gl_stark_lookup_columns(gl_ctx* c, uint64_t* d_cols, uint32_t num
                            d_canon.as<const uint64_t>(), n, d_cols);
         GL_CHECK_HIP(hipGetLastError());
     }
-    GL_CHECK_HIP(gl_stream_wait(st));          // `words` (host source of the async upload) dies here
+    return GL_OK;
+}
+
+extern "C" int gl_stark_lookup_columns(gl_ctx* c, uint64_t* d_cols, uint32_t num_columns, size_t n_rows, const gl_stark_lookup* lookups, uint32_t count) try {
+    GL_REQUIRE(c && d_cols && lookups, GL_ERR_ARG, "gl_stark_lookup_columns: null argument");
+    gllookup::Plan plan;
+    GL_TRY(gllookup::plan(num_columns, n_rows, lookups, count, &plan));
+    GL_TRY(c->activate());
+    GlTimed timed(c, "lookup columns");
+    DevBuf d_words(c);
+    GL_TRY(d_words.alloc(plan.words.size() * 4));
+    GL_CHECK_HIP(hipMemcpyAsync(d_words.p, plan.words.data(), plan.words.size() * 4, hipMemcpyHostToDevice, c->stream));
+    GL_TRY(gllookup::run(c, d_cols, plan, d_words.as<uint32_t>()));
+    GL_CHECK_HIP(gl_stream_wait(c->stream));   // `plan.words` (host source of the async upload) dies here
     return GL_OK;
 } catch (...) { return gl_caught(); }
