@@ -438,7 +438,9 @@ void gl_challenger_free(gl_challenger* c) GL_NOEXCEPT;
  * PolynomialBatch::prove_openings (fri/oracle.rs:162-219) and verify_fri_proof (fri/verifier.rs:62-241) for an arbitrary
  * FriInstanceInfo (fri/structure.rs): any number of oracles, any (point, polynomials) batches, any rate_bits / cap_height, salted
  * oracles, either hasher.  This is the call through which provers other than plonk::prover (starky/src/prover.rs) reach the seam.
- * gl_fri_combine / gl_prove* / gl_verify above keep their own Plonk-shaped path. */
+ * A circuit proof is the instance of four oracles (constants||sigmas, wires, Z||partial products(||lookups), quotient; the last three
+ * blinded) and two batches (everything at zeta; the Zs and the lookup polynomials at g zeta): gl_verify above verifies it through
+ * gl_verify_openings' code; gl_fri_combine / gl_prove* above keep a combine and a fri_proof loop of their own over the same list. */
 #define GL_MAX_FRI_ORACLES 8
 #define GL_MAX_FRI_BATCHES 4
 typedef struct gl_fri_params {          /* FriParams (fri/mod.rs) + C::Hasher */

@@ -3,7 +3,7 @@
 // What runs where.  Per proof the host stage of gl_verify (verify_stage.hpp: decode, transcript, vanishing identity at zeta, proof of
 // work, reduced openings) runs on host threads: its sponges are sequential (the public-input hash, the Challenger), so a proof gives a
 // device lane nothing to do side by side.  What is left is the query phase of a FRI proof like any other: the circuit's FRI instance
-// is the four oracles and two batches of fri_openings() (prove.hip), so the proof's table goes to the batch core of
+// is the four oracles and two batches of glfri::PlonkInstance (fri_instance.hpp), so the proof's table goes to the batch core of
 // openings_verify.hip as it is, with a cap block of constants_sigmas_cap and the proof's three caps.  No kernel lives here.
 #include "context.hpp"
 #include "verify_stage.hpp"

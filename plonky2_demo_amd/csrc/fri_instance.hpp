@@ -1,5 +1,6 @@
-// What gl_fri_combine_instance, gl_prove_openings (prove.hip) and gl_verify_openings (verifier.hip) share: the Challenger's C handle and
-// the validation of a FriParams / FriInstanceInfo pair (fri/mod.rs, fri/structure.rs).  Host code.
+// What gl_fri_combine_instance, gl_prove_openings (prove.hip) and gl_verify_openings (verifier.hip) share: the Challenger's C handle, the
+// validation of a FriParams / FriInstanceInfo pair (fri/mod.rs, fri/structure.rs), and the one instance both sides build themselves: a
+// circuit's (PlonkInstance, for gl_fri_combine / gl_prove* and gl_verify).  Host code.
 #pragma once
 #include "context.hpp"
 #include "host_circuit.hpp"
@@ -78,5 +79,27 @@ inline int check(const gl_fri_params* params, const gl_fri_instance* instance, b
         for (unsigned r = 0; r < p.num_fri_rounds; r++) GL_REQUIRE(p.fri_arity_bits[r] == 4, GL_ERR_UNSUPPORTED, "FRI arity must be 16");
     return GL_OK;
 }
+
+// A circuit's FriInstanceInfo (fri_all_polys / fri_next_batch_polys, circuit_data.rs:564-597, in FriOpenings order, proof.rs:346-380) without
+// its points: oracles constants||sigmas, wires, Z||partial products(||lookups), quotient, the last three blinded (prover.rs:151,218,266);
+// batch 0 at zeta = constants and sigmas, wires, the 20 of Z and partial products, the 16 quotient chunks, then the lookup polynomials;
+// batch 1 at g zeta = the 2 Zs and the lookup polynomials.  The lookup polynomials come LAST in both batches.  This is the only place
+// that spells the order out; it depends on the description alone, a proof writes its two points into a copy of `inst`.
+struct PlonkInstance {
+    gl_fri_instance inst;
+    std::vector<uint32_t> polys;
+    PlonkInstance(const PlonkInstance&) = delete;
+    explicit PlonkInstance(const gl_circuit_desc& d) : inst() {
+        const uint32_t nlk = 2 * d.num_lookup_polys, widths[4] = {d.num_constants + 80, 135, 20 + nlk, 16};
+        inst.num_oracles = 4; inst.num_batches = 2;
+        for (uint32_t o = 0; o < 4; o++) { inst.oracle_num_polys[o] = widths[o]; inst.oracle_blinding[o] = o != 0; }
+        auto add = [&](uint32_t o, uint32_t first, uint32_t count) { for (uint32_t c = first; c < first + count; c++) { polys.push_back(o); polys.push_back(c); } };
+        add(0, 0, widths[0]); add(1, 0, 135); add(2, 0, 20); add(3, 0, 16); add(2, 20, nlk);
+        inst.batch_len[0] = (uint32_t)(polys.size() / 2);
+        add(2, 0, 2); add(2, 20, nlk);
+        inst.batch_len[1] = (uint32_t)(polys.size() / 2) - inst.batch_len[0];
+        inst.polys = polys.data();
+    }
+};
 
 }  // namespace glfri

@@ -5,8 +5,8 @@
 // PrecomputedReducedOpenings.  What is left after the stage, the Merkle paths and the FRI queries of fri/verifier.rs:163-241, reads only
 // T, the challenges and the caps, in one query loop on the host (gl_verify, gl_verify_openings) or on the device
 // (k_verify_paths_any, k_verify_openings_queries).  There are three stages: glopen::host_stage for any FriInstanceInfo,
-// glverify::host_stage (verify_stage.hpp) for a circuit proof, whose instance is the four oracles and two batches of fri_openings()
-// (prove.hip), and the STARK stage (stark.hip), which ends in glopen::host_stage.
+// glverify::host_stage (verify_stage.hpp) for a circuit proof, whose instance is the four oracles and two batches of
+// glfri::PlonkInstance (fri_instance.hpp), and the STARK stage (stark.hip), which ends in glopen::host_stage.
 #pragma once
 #include "context.hpp"
 #include "fri_instance.hpp"

@@ -29,6 +29,7 @@ struct gl_circuit {
     gl_t* d_sigmas = nullptr;         // sigma VALUES [80][n]
     gl_t* d_l0_coset = nullptr;       // L_0 on the LDE coset [8n]
     gl_t circuit_digest[4];
+    std::unique_ptr<const glfri::PlonkInstance> plonk;      // the FRI instance of every proof of it, but for the two points
 };
 
 
@@ -116,6 +117,7 @@ static void zh_on_coset(const gl_circuit_desc& d, gl_t zh[8]) {
 static int circuit_finish(gl_ctx* ctx, const gl_circuit_desc* desc, const gl_t* d_cs, gl_circuit** out) {
     std::unique_ptr<gl_circuit, void (*)(gl_circuit*)> c(new gl_circuit(), gl_circuit_free);
     c->ctx = ctx; ctx->retain(); c->desc = *desc; c->n = size_t(1) << desc->degree_bits;
+    c->plonk.reset(new glfri::PlonkInstance(*desc));
     const size_t n = c->n, ncs = desc->num_constants + 80;
     GL_TRY(gl_batch_from_device_h(ctx, desc->hasher, d_cs, ncs, n, desc->rate_bits, desc->cap_height, 1, &c->cs_batch));      // circuit_builder.rs:1020-1028
     GL_TRY(ctx->pool_alloc(80 * n * sizeof(gl_t), (void**)&c->d_sigmas));
@@ -492,11 +494,10 @@ extern "C" int gl_open_at(gl_ctx* ctx, const gl_batch* b, const uint64_t z[2], s
     return d2h(ctx, h_out, d_open, 2 * num_cols * sizeof(gl_t));
 } catch (...) { return gl_caught(); }
 
-// fri_all_polys / fri_next_batch_polys (circuit_data.rs:564-597) in FriOpenings order (proof.rs:346-380) over the oracles constants||sigmas,
-// wires, Z||partial products(||lookups), quotient: at zeta the constants, sigmas, wires, zs, partial products, quotient chunks, lookup
-// polynomials; at g zeta the zs and the lookup polynomials.  The lookup polynomials come LAST in both batches.
+// The coefficient columns of the circuit's instance (glfri::PlonkInstance) over its four oracles, and where each group of the OpeningSet
+// starts among them
 struct FriOpenings {
-    std::vector<const gl_t*> cols;          // coefficient columns: the nopen opened at zeta, then the nnext opened at g zeta
+    std::vector<const gl_t*> cols;          // the nopen opened at zeta, then the nnext opened at g zeta
     size_t ncs = 0, nlk = 0, nopen = 0, nnext = 0;
     size_t wires() const { return ncs; }    // where each group starts in `cols`
     size_t zs() const { return ncs + 135; }
@@ -506,14 +507,11 @@ struct FriOpenings {
     size_t zs_next() const { return nopen; }
     size_t lookups_next() const { return nopen + 2; }
 };
-static FriOpenings fri_openings(const gl_batch* const oracles[4]) {
+static FriOpenings fri_openings(const gl_fri_instance& in, const gl_batch* const oracles[4]) {
     FriOpenings f;
-    f.ncs = oracles[0]->ncols; f.nlk = oracles[2]->ncols - 20;
-    auto add = [&](int o, size_t first, size_t count) { for (size_t c = first; c < first + count; c++) f.cols.push_back(oracles[o]->coeffs + c * oracles[o]->n); };
-    add(0, 0, f.ncs); add(1, 0, 135); add(2, 0, 20); add(3, 0, 16); add(2, 20, f.nlk);
-    f.nopen = f.cols.size();
-    add(2, 0, 2); add(2, 20, f.nlk);
-    f.nnext = f.cols.size() - f.nopen;
+    f.ncs = in.oracle_num_polys[0]; f.nlk = in.oracle_num_polys[2] - 20; f.nopen = in.batch_len[0]; f.nnext = in.batch_len[1];
+    f.cols.reserve(f.nopen + f.nnext);
+    for (size_t k = 0; k < f.nopen + f.nnext; k++) { const gl_batch* b = oracles[in.polys[2 * k]]; f.cols.push_back(b->coeffs + in.polys[2 * k + 1] * b->n); }
     return f;
 }
 
@@ -558,9 +556,9 @@ static int fri_combine(gl_ctx* ctx, const gl_circuit* cir, const gl_batch* const
     GL_REQUIRE(batches && zeta_in && alpha_in && out, GL_ERR_ARG, "gl_fri_combine: null argument");
     const gl_circuit_desc& d = cir->desc;
     const size_t n = cir->n, N = n << d.rate_bits;
-    const size_t want[4] = {d.num_constants + 80, 135, 20 + 2 * (size_t)d.num_lookup_polys, 16};
-    for (int o = 0; o < 4; o++) GL_TRY(check_batch(cir, batches[o], want[o], "gl_fri_combine: oracle order is constants||sigmas, wires, Z||partial products(||lookups), quotient"));
-    FriOpenings op = fri_openings(batches);
+    const gl_fri_instance& in = cir->plonk->inst;
+    for (int o = 0; o < 4; o++) GL_TRY(check_batch(cir, batches[o], in.oracle_num_polys[o], "gl_fri_combine: oracle order is constants||sigmas, wires, Z||partial products(||lookups), quotient"));
+    FriOpenings op = fri_openings(in, batches);
     const size_t nopen = op.nopen, nnext = op.nnext;
     hipStream_t st = ctx->stream;
     std::unique_ptr<gl_fri, void (*)(gl_fri*)> f(new gl_fri(), gl_fri_free);
@@ -1095,7 +1093,7 @@ static int prove_impl(gl_ctx* ctx, const gl_circuit* cir, const gl_t* d_wires, D
 
     // ---- 12. openings (proof.rs:306-344): all of them in one launch behind one sync (gl_open_at is one batch per call) ----
     const gl_batch* oracles[4] = {cir->cs_batch, wires.b, zs.b, quot.b};
-    const FriOpenings op = fri_openings(oracles);
+    const FriOpenings op = fri_openings(cir->plonk->inst, oracles);
     GL_REQUIRE(op.nopen + op.nnext <= DS_OPEN_MAX, GL_ERR_INTERNAL, "too many openings for the staging area");
     std::vector<gl_t> opened(2 * (op.nopen + op.nnext));                       // extension values, in op.cols order
     {

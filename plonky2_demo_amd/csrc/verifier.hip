@@ -7,8 +7,9 @@
 // checked in place: one pass turns the byte string into a flat table of canonical words plus offsets, and every later
 // step indexes that table.  No GPU is involved.  The checks of the description and the per-proof stage up to the queries are functions
 // of their own (verify_stage.hpp): the batch verifier (batch_verify.hip) runs the same ones and gives the queries to the device.  The
-// FRI half -- decode, challenge draw, reduced openings, query loop -- is one set of functions for a circuit proof and for a FriProof
-// of any FriInstanceInfo (gl_verify_openings at the end of this file; openings_stage.hpp).
+// FRI half -- decode, challenge draw, reduced openings, query loop -- is one set of functions for a circuit proof (whose instance is
+// glfri::PlonkInstance, fri_instance.hpp, the prover's too) and for a FriProof of any FriInstanceInfo (gl_verify_openings at the end of
+// this file; openings_stage.hpp).
 #include "context.hpp"
 #include "host_circuit.hpp"
 #include "fri_instance.hpp"
@@ -375,16 +376,6 @@ int verify_fri_queries(const glopen::Shape& s, const gl_t* T, const glopen::Chal
     return GL_OK;
 }
 
-// the polynomials of fri_openings() (prove.hip; circuit_data.rs:564-597) as (oracle, polynomial) pairs: batch 0 at zeta = constants and
-// sigmas, wires, Z and partial products, quotient, then the lookup polynomials (last in both batches); batch 1 at g zeta = Z, lookups
-void plonk_polys(size_t ncs, size_t nlk, uint32_t batch_len[2], std::vector<uint32_t>& polys) {
-    auto add = [&](uint32_t o, size_t first, size_t count) { for (size_t c = first; c < first + count; c++) { polys.push_back(o); polys.push_back((uint32_t)c); } };
-    add(0, 0, ncs); add(1, 0, 135); add(2, 0, 20); add(3, 0, 16); add(2, 20, nlk);
-    batch_len[0] = (uint32_t)(polys.size() / 2);
-    add(2, 0, 2); add(2, 20, nlk);
-    batch_len[1] = (uint32_t)(polys.size() / 2) - batch_len[0];
-}
-
 }  // namespace
 
 void glopen::lay_out(Shape& s, const size_t* leaf_lens, const uint32_t* batch_len, const uint32_t* polys, size_t base) {
@@ -461,10 +452,11 @@ int glverify::shape_of(const gl_circuit_desc& d, size_t num_bytes, Shape& s) {
     GL_REQUIRE(total_arity <= s.lgn, GL_ERR_ARG, "gl_verify: FRI reduces below the final polynomial");
     f.final_len = size_t(1) << (s.lgn - total_arity);
     s.nlp = d.num_lookup_polys;                                         // lookup polynomials per challenge, behind Z and the partial products
-    const size_t ncs = (size_t)d.num_constants + R;
-    // hiding: the leaves of the wires, Z / partial-products and quotient trees end in SALT_SIZE = 4 salt elements (mod.rs:431-456)
-    const size_t salt = d.zero_knowledge ? 4 : 0;
-    const size_t leaf_lens[4] = {ncs, W + salt, nch * (1 + NPP + s.nlp) + salt, nch * QF + salt};
+    // the circuit's instance (fri_instance.hpp).  hiding: the leaves of its blinded oracles -- the wires, Z / partial-products and quotient
+    // trees -- end in SALT_SIZE = 4 salt elements (mod.rs:431-456)
+    const glfri::PlonkInstance plonk(d);
+    size_t leaf_lens[4];
+    for (uint32_t o = 0; o < 4; o++) leaf_lens[o] = plonk.inst.oracle_num_polys[o] + (d.zero_knowledge && plonk.inst.oracle_blinding[o] ? glfri::SALT_SIZE : 0);
     // the table in wire order (util/serialization/mod.rs:1939-1981; OpeningSet mod.rs:1409-1423: the lookup vectors sit between zs_next
     // and the partial products), the FriProof behind the openings
     size_t at = 0;
@@ -472,10 +464,7 @@ int glverify::shape_of(const gl_circuit_desc& d, size_t num_bytes, Shape& s) {
     s.o_caps = take(3 * 4 * f.ncap);
     s.o_const = take(2 * s.num_constants); s.o_sig = take(2 * R); s.o_wires = take(2 * W); s.o_zs = take(2 * nch); s.o_zsn = take(2 * nch);
     s.o_lk = take(2 * nch * s.nlp); s.o_lkn = take(2 * nch * s.nlp); s.o_pp = take(2 * nch * NPP); s.o_quot = take(2 * nch * QF);
-    uint32_t batch_len[2];
-    std::vector<uint32_t> polys;
-    plonk_polys(ncs, nch * s.nlp, batch_len, polys);
-    glopen::lay_out(f, leaf_lens, batch_len, polys.data(), at);
+    glopen::lay_out(f, leaf_lens, plonk.inst.batch_len, plonk.polys.data(), at);
     s.o_pis = f.t_words;
     s.t_words = sat_add(s.o_pis, d.num_public_inputs);
     return GL_OK;

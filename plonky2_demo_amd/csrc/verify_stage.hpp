@@ -1,6 +1,6 @@
 // The circuit-proof stage in front of the one FRI verifier (openings_stage.hpp; verifier.hip holds the definitions; host code, no HIP
 // calls): what follows from the description alone -- gl_verify's checks of it, the place of the caps, the openings and the public
-// inputs inside the decoded word table, and the FRI instance of fri_openings() (prove.hip) as a glopen::Shape over that table -- and
+// inputs inside the decoded word table, and the circuit's FRI instance (glfri::PlonkInstance) as a glopen::Shape over that table -- and
 // the per-proof host stage: decode, challenges, the vanishing identity at zeta, the proof of work and the reduced openings.  What is
 // left of a proof after that stage is the shared query loop, on the host (gl_verify) or on the device (batch_verify.hip).
 #pragma once

@@ -154,7 +154,7 @@ def divide_by_linear(coeffs, z):
 
 def opened_polys(groups):
     """(the polynomials opened at zeta, those opened at g zeta) of the four oracles constants || sigmas, wires, Z || partial products
-    (|| lookup polynomials), quotient chunks, each [columns][n] coefficients: the order of fri_openings() in prove.hip (FriOpenings,
+    (|| lookup polynomials), quotient chunks, each [columns][n] coefficients: the order of glfri::PlonkInstance in fri_instance.hpp (FriOpenings,
     proof.rs:346-380; circuit_data.rs:564-597), the lookup polynomials last in both batches"""
     cs, wires, zs, quotient = (list(grp) for grp in groups)
     return cs + wires + zs[:20] + quotient + zs[20:], zs[:2] + zs[20:]

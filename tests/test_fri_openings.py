@@ -2,7 +2,7 @@
 fri/oracle.rs:162-219; verify_fri_proof, fri/verifier.rs:62-241) against the Python-integer model of fri_openings_model.py.
 
   A  combine and divide by value (k_fri_combine_points, k_div_points_*) at every size where the kernels take another path
-  B  the Plonk instance through the generic path: byte for byte what gl_fri_combine gives
+  B  the Plonk instance through the generic path: byte for byte what gl_fri_combine gives, and the FRI section of gl_prove's proof
   C  a STARK-shaped instance (rate_bits 1, 84 queries, 16 bits of work) end to end, library verifier and model verifier
   D  the phase form assembled by a caller equals the one-call form
   E  the tamper matrix: one flipped word per case, the check named
@@ -208,7 +208,7 @@ class Recorder:
 
 
 def plonk_instance(p, d, zeta, gzeta):
-    """the four oracles and two batches of fri_openings() (prove.hip), in prover_phase_model.opened_polys order"""
+    """the four oracles and two batches of glfri::PlonkInstance (fri_instance.hpp), in prover_phase_model.opened_polys order"""
     ncs, nzs = d.num_constants + 80, 20 + 2 * d.num_lookup_polys
     names = [[(o, c) for c in range(w)] for o, w in enumerate((ncs, 135, nzs, 16))]
     at_zeta, at_gzeta = pm.opened_polys(names)
@@ -232,24 +232,54 @@ def check_plonk_route(gpu, orc, cd, wires, pis, hasher, rounds):
     assert fri.query(r.x_index) == r.query_blob
 
 
+def _plonk_circuits(p, ctx, orc, which):
+    """(circuit data, wires, public inputs, hasher, reduction rounds): the circuits of the two tests above"""
+    if which == "lookups":
+        oc = orc.circuit_of_kind(8, 50, threads=8)
+        w = oc.witness(np.arange(3, 53, dtype=U64), NO_PIS, filler_seed=9)
+        cd = p.GenericCircuitData(oc.product_desc(), oc.constants_sigmas())
+        assert cd.desc.num_lookup_polys
+        return cd, w.wires(), w.public_inputs(), "poseidon", cd.desc.num_fri_rounds
+    import ext_gate_circuits as egc
+    lg_n, hasher, rounds = which
+    c = egc.Chained(seed=3, min_degree_bits=lg_n, hasher=1 if hasher == "keccak" else 0).circuit
+    return p.GenericCircuitData.from_classes(c.desc, c.constants, c.classes, ctx=ctx), c.wires(), NO_PIS, hasher, rounds
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("lg_n,hasher,rounds", [(6, "poseidon", 1), (6, "keccak", 1), (10, "poseidon", 2)])
 def test_plonk_instance_reproduces_the_plonk_path(gpu, orc, lg_n, hasher, rounds):
-    import ext_gate_circuits as egc
-    p, ctx = gpu
-    c = egc.Chained(seed=3, min_degree_bits=lg_n, hasher=1 if hasher == "keccak" else 0).circuit
-    cd = p.GenericCircuitData.from_classes(c.desc, c.constants, c.classes, ctx=ctx)
-    check_plonk_route(gpu, orc, cd, c.wires(), NO_PIS, hasher, rounds)
+    check_plonk_route(gpu, orc, *_plonk_circuits(gpu[0], gpu[1], orc, (lg_n, hasher, rounds)))
 
 
 @pytest.mark.gpu
 def test_plonk_instance_with_lookups_reproduces_the_plonk_path(gpu, orc):
+    check_plonk_route(gpu, orc, *_plonk_circuits(gpu[0], gpu[1], orc, "lookups"))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", [(6, "poseidon", 1), (6, "keccak", 1), (10, "poseidon", 2), "lookups"], ids=str)
+def test_prove_openings_on_the_plonk_instance_writes_the_fri_section_of_the_circuit_proof(gpu, orc, which):
+    """A circuit proof is one more FRI instance on the prover side (the mirror of the cut-out test below): gl_prove_openings on
+    plonk_instance, over the four batches of the phase API and a Challenger advanced through the Plonk transcript up to the observed
+    openings, writes the bytes that stand in gl_prove's proof between the OpeningSet and the public inputs."""
+    from proof_parser import ParsedProof, hash_bytes, opening_columns
+    from transcript import replay_to_openings
     p, ctx = gpu
-    oc = orc.circuit_of_kind(8, 50, threads=8)
-    w = oc.witness(np.arange(3, 53, dtype=U64), NO_PIS, filler_seed=9)
-    cd = p.GenericCircuitData(oc.product_desc(), oc.constants_sigmas())
-    assert cd.desc.num_lookup_polys
-    check_plonk_route(gpu, orc, cd, w.wires(), w.public_inputs(), "poseidon", cd.desc.num_fri_rounds)
+    cd, wires, pis, hasher, rounds = _plonk_circuits(p, ctx, orc, which)
+    d = cd.desc
+    assert d.num_fri_rounds == rounds
+    r = drive_phase_api(p, ctx, orc, cd, LibraryChallenger(p, hasher), wires, pis)
+    by = cd.prove(wires, pis).to_bytes()
+    pp = ParsedProof(d, by)
+    fri_at = (3 << d.cap_height) * hash_bytes(d) + 16 * sum(k for _, k in opening_columns(d))
+    fri_end = len(by) - 8 * (1 + len(pp.public_inputs))                          # behind the proof-of-work witness
+    ch = LibraryChallenger(p, hasher)
+    zeta = replay_to_openings(d, ch, cd.circuit_digest, r.pi_hash, pp)[-1]
+    assert list(zeta) == list(r.zeta)
+    inst = plonk_instance(p, d, r.zeta, r.gzeta)
+    got = p.PolynomialBatch.prove_openings(inst, r.batches, ch.ch, p.FriParams.of_circuit(d), ctx=ctx)
+    assert len(got) == fri_end - fri_at and got == by[fri_at:fri_end]
 
 
 # ------------------------------------------------------------------------------- B': the verifier side of the same fact (CPU)
