@@ -23,6 +23,14 @@
  *    the suffix _h; handles (gl_merkle, gl_batch, gl_circuit, gl_fri, gl_challenger) remember theirs, and mixing them is GL_ERR_ARG.
  *  - `h_` pointers are host memory owned by the caller; `d_` pointers are device (HIP) memory on the
  *    context's device.  Opaque handles own device memory and are released with their *_free.
+ *  - Footprint of a `d_` argument, stated at every entry point in one of three words: READ-ONLY (no word of it is written),
+ *    OUTPUT (every word of the documented shape is written, whatever it held, and no word outside it), IN PLACE (the words named
+ *    are overwritten, every other word of the buffer keeps its value).  Scratch comes from the context's own pool, never from the caller's
+ *    buffers.  tests/test_footprint.py holds every entry to this with guard bands around the caller's buffers.
+ *  - Alignment: the kernels read and write a caller's device buffer one 64-bit word at a time (one 32-bit field at a time for
+ *    gl_memory_op), so a `d_` pointer needs the alignment of its element type and no more: 8 bytes for uint64_t data -- extension
+ *    pairs, digests, 12-word states and matrix columns included -- and 4 bytes for gl_memory_op.  No entry asks for the 256 bytes
+ *    hipMalloc gives, and a column or row may start at any word of an allocation.
  *  - All functions return GL_OK (0) or a GL_ERR_* code and never unwind; gl_last_error() gives the
  *    text for the calling thread.  The reference panics on shape errors (oracle.rs:114,
  *    merkle_tree.rs:137-143, fft.rs:175-181); here they are GL_ERR_ARG.  A C++ exception inside the
@@ -179,13 +187,17 @@ int gl_copy_d2h(gl_ctx* ctx, void* h_dst, const void* d_src, size_t bytes);   /*
 
 /* ---- field micro-kernels (tests; replace nothing on the path by themselves) ----------------------
  * op: 0 add, 1 sub, 2 mul, 3 neg(a), 4 inverse(a), 5 canonicalise(a), 6 a + b*c, 7 a * 2^(b mod 192)
- * (field/src/goldilocks_field.rs:186-274,138-142).  out may alias a. */
+ * (field/src/goldilocks_field.rs:186-274,138-142); b mod 192 is taken of the 64-bit word as it stands.  d_a, d_b, d_c: READ-ONLY, n
+ * words each (d_b may be null for ops 3..5, d_c for all but 6); d_out: OUTPUT, n words.  d_out may alias d_a (then d_a is IN PLACE, all n
+ * words); any other overlap is undefined. */
 int gl_field_op(gl_ctx* ctx, int op, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_c,
                 uint64_t* d_out, size_t n);
-/* op: 0 add, 1 sub, 2 mul, 3 inverse on interleaved (a0,a1) pairs (extension/quadratic.rs:143-193) */
+/* op: 0 add, 1 sub, 2 mul, 3 inverse on interleaved (a0,a1) pairs (extension/quadratic.rs:143-193).  d_a, d_b: READ-ONLY, 2 n words
+ * (d_b may be null for op 3); d_out: OUTPUT, 2 n words. */
 int gl_ext_op(gl_ctx* ctx, int op, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, size_t n);
 
-/* ---- NTT family: d_data is [batch][2^log_n], transformed in place, natural order in and out ------ */
+/* ---- NTT family: d_data is [batch][2^log_n], transformed in place, natural order in and out ------
+ * d_data: IN PLACE, all batch * 2^log_n words; the passes between, and the twiddle tables, live in the context's scratch. */
 /* fft_with_options(poly, None, root_table) (field/src/fft.rs:56-65): values[i] = P(w^i) */
 int gl_ntt_forward(gl_ctx* ctx, uint64_t* d_data, uint32_t log_n, uint32_t batch);
 /* ifft_with_options (field/src/fft.rs:72-95) */
@@ -196,23 +208,26 @@ int gl_ntt_coset_forward(gl_ctx* ctx, uint64_t* d_data, uint32_t log_n, uint32_t
 int gl_ntt_coset_inverse(gl_ctx* ctx, uint64_t* d_data, uint32_t log_n, uint32_t batch, uint64_t shift);
 /* p.lde(rate_bits).coset_fft_with_options(F::coset_shift(), Some(rate_bits), table)
  * (plonky2/src/fri/oracle.rs:111-118): d_coeffs [batch][2^log_n] -> d_out [batch][2^(log_n+rate_bits)],
- * natural order (index i <-> point 7*w^i). */
+ * natural order (index i <-> point 7*w^i).  d_coeffs: READ-ONLY; d_out: OUTPUT, all batch * 2^(log_n+rate_bits) words; the two may not
+ * overlap. */
 int gl_ntt_coset_lde(gl_ctx* ctx, const uint64_t* d_coeffs, uint32_t log_n, uint32_t rate_bits,
                      uint32_t batch, uint64_t* d_out);
 /* host-buffer convenience (H2D + transform + D2H): direction 0 forward, 1 inverse */
 int gl_fft_host(gl_ctx* ctx, uint64_t* h_data, uint32_t log_n, uint32_t batch, int inverse);
 
 /* ---- Poseidon / hashing --------------------------------------------------------------------------*/
-/* Poseidon::poseidon (plonky2/src/hash/poseidon.rs:598-609) on `count` 12-word states, in place */
+/* Poseidon::poseidon (plonky2/src/hash/poseidon.rs:598-609) on `count` 12-word states.  d_states: IN PLACE, all 12 * count words */
 int gl_poseidon_permute(gl_ctx* ctx, uint64_t* d_states, size_t count);
 /* the same permutation with the MDS layer chosen by `layer` (0: vector ALU, 1: i8 matrix cores), leaving the raw u64
-   representatives (not canonicalised): the two layers return the same words */
+   representatives (not canonicalised): the two layers return the same words.  d_states: IN PLACE, all 12 * count words */
 int gl_poseidon_permute_raw(gl_ctx* ctx, uint64_t* d_states, size_t count, int layer);
 /* Hasher::hash_or_noop (plonky2/src/plonk/config.rs:55-66) of `count` rows of `len` elements,
- * row-major d_rows[count][len] -> d_out[count][4] */
+ * row-major d_rows[count][len] -> d_out[count][4].  d_rows: READ-ONLY; d_out: OUTPUT, all 4 * count words (the words of a short row's
+ * digest beyond `len` are written as zero) */
 int gl_hash_rows(gl_ctx* ctx, const uint64_t* d_rows, size_t count, size_t len, uint64_t* d_out);
 /* the same under `hasher`; KeccakHash<25> (hash/keccak.rs:105-117): a row of <= 3 elements is copied into the 25 bytes, a longer one is
- * Keccak-256 (original padding: domain byte 0x01) over its canonical little-endian words, truncated to 25 bytes */
+ * Keccak-256 (original padding: domain byte 0x01) over its canonical little-endian words, truncated to 25 bytes.  d_rows: READ-ONLY;
+ * d_out: OUTPUT, all 4 * count words */
 int gl_hash_rows_h(gl_ctx* ctx, uint32_t hasher, const uint64_t* d_rows, size_t count, size_t len, uint64_t* d_out);
 /* Hasher::hash_or_noop (plonk/config.rs:55-66) and Hasher::two_to_one (hash/hashing.rs:98-115 PoseidonHash, hash/keccak.rs:119-126
  * KeccakHash<25>) on the host, no GPU needed: h_rows[count][len] -> h_out[count][4]; h_left[count][4], h_right[count][4] -> h_out[count][4] */
@@ -250,11 +265,12 @@ int gl_batch_from_values_blinded(gl_ctx* ctx, const uint64_t* const* h_cols, siz
                                  uint32_t cap_height, const uint8_t seed[32], gl_batch** out);
 int gl_batch_from_coeffs_blinded(gl_ctx* ctx, const uint64_t* const* h_cols, size_t ncols, size_t n, uint32_t rate_bits,
                                  uint32_t cap_height, const uint8_t seed[32], gl_batch** out);
-/* same, from a device-resident column-major matrix d_cols[ncols][n]; is_values selects from_values */
+/* same, from a device-resident column-major matrix d_cols[ncols][n]; is_values selects from_values.  d_cols: READ-ONLY (the batch keeps
+ * a copy of its own and does not need it after the call) */
 int gl_batch_from_device(gl_ctx* ctx, const uint64_t* d_cols, size_t ncols, size_t n, uint32_t rate_bits,
                          uint32_t cap_height, int is_values, gl_batch** out);
 /* The five constructors above for PolynomialBatch<F, C, D> with C::Hasher = `hasher` (fri/oracle.rs:43-125): the same polynomials and
- * LDE values, the Merkle tree under that hasher.  seed as above; gl_batch_from_device_h commits without salt. */
+ * LDE values, the Merkle tree under that hasher.  seed as above; gl_batch_from_device_h commits without salt (d_cols: READ-ONLY). */
 int gl_batch_from_values_h(gl_ctx* ctx, uint32_t hasher, const uint64_t* const* h_cols, size_t ncols, size_t n,
                            uint32_t rate_bits, uint32_t blinding, uint32_t cap_height, gl_batch** out);
 int gl_batch_from_coeffs_h(gl_ctx* ctx, uint32_t hasher, const uint64_t* const* h_cols, size_t ncols, size_t n,
@@ -292,7 +308,8 @@ void gl_batch_free(gl_batch* b) GL_NOEXCEPT;
  * index = natural LDE row).  Everywhere a seed is taken, NULL means 32 fresh bytes from getrandom(2), one per proof.
  * A seed must never be reused for two different witnesses of a circuit: the two proofs' blinding and salts cancel, and hiding is
  * lost.  Fixed seeds are for tests and reproducible runs. */
-/* d_out[i] = element first + i of `stream`, i < count (first + count <= 2^34) */
+/* d_out[i] = element first + i of `stream`, i < count (first + count <= 2^34).  d_out: OUTPUT, exactly `count` words, wherever first and
+ * first + count fall inside a 4-element keystream block */
 int gl_random_elements(gl_ctx* ctx, const uint8_t seed[32], uint32_t stream, uint64_t first, uint64_t count, uint64_t* d_out);
 /* the same on the host (no GPU needed) */
 int gl_random_elements_host(const uint8_t seed[32], uint32_t stream, uint64_t first, uint64_t count, uint64_t* h_out);
@@ -320,7 +337,7 @@ int gl_matmul_witness(const gl_host_circuit* hc, const uint64_t* h_a, const uint
                       uint64_t* h_wires, uint64_t* h_public_inputs);
 void gl_host_circuit_free(gl_host_circuit* hc) GL_NOEXCEPT;
 /* The same witness produced directly in HBM: the m^3 ArithmeticGate operations are filled by the GPU, the sequential
- * public-input hash sponge (PoseidonGate rows) by the calling host thread meanwhile.  d_wires[135][n] is overwritten;
+ * public-input hash sponge (PoseidonGate rows) by the calling host thread meanwhile.  d_wires[135][n]: OUTPUT, all 135 n words;
  * h_public_inputs[3 m^2].  The generator borrows `hc` and belongs to `ctx` (one per context / stream). */
 typedef struct gl_matmul_witgen gl_matmul_witgen;
 int gl_matmul_witgen_create(gl_ctx* ctx, const gl_host_circuit* hc, gl_matmul_witgen** out);
@@ -352,7 +369,8 @@ int gl_circuit_warm_up(gl_ctx* ctx, const gl_circuit* c);
 /* The RandomValueGenerators and CopyGenerators of blind() (circuit_builder.rs:777-818) on the device, for a zero-knowledge circuit with
  * num_gate_rows set: from row num_gate_rows on, `regular` rows of 135 random wires, then `pairs` row pairs whose first row's 80 routed
  * wires are random and copied to the second, every other wire of those rows and the padding rows 0 (full_witness, iop/witness.rs:340-352).
- * seed NULL = OS entropy.  A Rust-built zk circuit's witness arrives blinded by Rust's own generators and goes straight to gl_prove*. */
+ * seed NULL = OS entropy.  A Rust-built zk circuit's witness arrives blinded by Rust's own generators and goes straight to gl_prove*.
+ * d_wires[135][n]: IN PLACE, rows num_gate_rows .. n of all 135 columns (the zeros too); rows below num_gate_rows keep their values. */
 int gl_witness_blind(gl_ctx* ctx, const gl_circuit* c, uint64_t* d_wires, const uint8_t seed[32]);
 int gl_circuit_digest(const gl_circuit* c, uint64_t h_out[4]);                 /* verifier_only.circuit_digest */
 int gl_circuit_constants_sigmas_cap(const gl_circuit* c, uint64_t* h_out);     /* [2^cap_height][4]            */
@@ -369,7 +387,8 @@ typedef struct gl_fri gl_fri;
 
 /* all_wires_permutation_partial_products (plonk/prover.rs:189-200,332-416) followed by the commitment of
  * prover.rs:212-223: d_wires[135][n] witness VALUES on the device -> PolynomialBatch of the 2 Z and 18 partial
- * product polynomials (column order zs, then partial products, as prover.rs:202-210). */
+ * product polynomials (column order zs, then partial products, as prover.rs:202-210).  d_wires: READ-ONLY (here and in
+ * gl_partial_products_lookups). */
 int gl_partial_products(gl_ctx* ctx, const gl_circuit* c, const uint64_t* d_wires, const uint64_t betas[2],
                         const uint64_t gammas[2], gl_batch** out);
 /* compute_quotient_polys + the split into quotient_degree_factor chunks + from_coeffs (plonk/prover.rs:229-271,
@@ -561,7 +580,7 @@ void gl_stark_free(gl_stark* s) GL_NOEXCEPT;
  * [j][c] (get_n_permutation_challenge_sets(challenger, num_challenges, q) in the order drawn) -> PolynomialBatch of the Z polynomials.
  * Instance j of a batch takes challenge_sets[j].challenges[chal], (pair, chal) running over pairs x 0..num_challenges in chunks of q
  * (get_permutation_batches, permutation.rs:228-249).  GL_ERR_ARG for a description without pairs, and -- where the reference panics
- * inverting zero -- GL_ERR_ARG "a permutation denominator is zero" (probability about n / p: draw other challenges). */
+ * inverting zero -- GL_ERR_ARG "a permutation denominator is zero" (probability about n / p: draw other challenges).  d_trace_values: READ-ONLY. */
 int gl_stark_permutation_zs(gl_ctx* ctx, const gl_stark* s, const uint64_t* d_trace_values, const uint64_t* challenges, gl_batch** zs);
 /* compute_quotient_polys up to its coset_ifft (prover.rs:198-311): the values of (sum_i alpha^i C_i) / Z_H at the points 7 w^i of the
  * quotient coset of size n << quotient_degree_bits, natural order, h_out[num_challenges][n << quotient_degree_bits]; the Stark's
@@ -587,7 +606,7 @@ size_t gl_stark_proof_size(const gl_stark* s) GL_NOEXCEPT;
  * as in gl_stark_permutation_zs.  Two calls on the same input give the same bytes (the PoW witness is the smallest). */
 int gl_stark_prove(gl_ctx* ctx, const gl_stark* s, const uint64_t* const* h_trace_cols, const uint64_t* h_public_inputs, uint8_t* h_out,
                    size_t cap_bytes, size_t* num_bytes);
-/* the same with the trace already in HBM, d_cols[num_columns][n] (left untouched) */
+/* the same with the trace already in HBM, d_cols[num_columns][n]: READ-ONLY */
 int gl_stark_prove_device(gl_ctx* ctx, const gl_stark* s, const uint64_t* d_cols, const uint64_t* h_public_inputs, uint8_t* h_out,
                           size_t cap_bytes, size_t* num_bytes);
 /* verify_stark_proof (starky/src/verifier.rs:21-145).  Host code, no GPU; degree_bits comes from params and the proof's path lengths
@@ -726,11 +745,11 @@ void gl_stark_set_free(gl_stark_set* s) GL_NOEXCEPT;
  * (may be non-canonical), ctl_challenges[num_challenges][2] = (beta, gamma) of get_grand_product_challenge_set, may be non-canonical.
  * Z[i] = prod_{i' <= i} factor[i'] -- INCLUSIVE, unlike the permutation Zs -- with factor = combine(columns(row)) =
  * reduce_with_powers(evals, beta) + gamma where filter(row) = 1 (or there is no filter) and 1 where filter(row) = 0; any other filter
- * value is GL_ERR_ARG "non-binary CTL filter" (the reference asserts).  GL_ERR_ARG for a table without CTL Zs. */
+ * value is GL_ERR_ARG "non-binary CTL filter" (the reference asserts).  GL_ERR_ARG for a table without CTL Zs.  d_trace_values: READ-ONLY. */
 int gl_stark_set_ctl_z_values(gl_ctx* ctx, const gl_stark_set* s, uint32_t table, const uint64_t* d_trace_values, const uint64_t* ctl_challenges,
                               uint64_t* h_out);
 /* The committed Z batch of table `table` (evm/src/prover.rs:341-352): its permutation Zs (gl_stark_permutation_zs' values under
- * permutation_challenges[q][num_challenges][2]; null exactly for a table without pairs), then its CTL Zs. */
+ * permutation_challenges[q][num_challenges][2]; null exactly for a table without pairs), then its CTL Zs.  d_trace_values: READ-ONLY. */
 int gl_stark_set_zs(gl_ctx* ctx, const gl_stark_set* s, uint32_t table, const uint64_t* d_trace_values, const uint64_t* permutation_challenges,
                     const uint64_t* ctl_challenges, gl_batch** zs);
 /* gl_stark_quotient_values for table `table` of a set: after the Stark's constraints and the permutation checks,
@@ -759,7 +778,7 @@ size_t gl_stark_set_proof_size(const gl_stark_set* s) GL_NOEXCEPT;
  * to be wrong are GL_ERR_ARG as in the phase entries; traces that are not consistent across tables yield a proof the verifier rejects. */
 int gl_stark_set_prove(gl_ctx* ctx, const gl_stark_set* s, const uint64_t* const* const* h_trace_cols, const uint64_t* const* h_public_inputs,
                        uint8_t* h_out, size_t cap_bytes, size_t* num_bytes);
-/* the same with the traces already in HBM: d_cols[num_tables] -> [num_columns][n] (left untouched) */
+/* the same with the traces already in HBM: d_cols is a HOST array of num_tables device pointers -> [num_columns][n], each READ-ONLY */
 int gl_stark_set_prove_device(gl_ctx* ctx, const gl_stark_set* s, const uint64_t* const* d_cols, const uint64_t* const* h_public_inputs,
                               uint8_t* h_out, size_t cap_bytes, size_t* num_bytes);
 /* verify_proof + verify_stark_proof_with_challenges + verify_cross_table_lookups (evm/src/verifier.rs:29-216, cross_table_lookup.rs:542-569).
@@ -792,8 +811,9 @@ int gl_stark_set_dag_verify(const gl_stark_set_desc* desc, const gl_stark_dag* c
  * MemoryStark once (memory_stark.rs:148). */
 typedef struct gl_stark_lookup { uint32_t col_input, col_table, col_permuted_input, col_permuted_table; } gl_stark_lookup;
 /* permuted_cols for `count` lookups of one device trace d_cols[num_columns][n], in place: for every lookup column col_permuted_input
- * becomes the sorted canonical input column and col_permuted_table exactly the permuted_table of the reference's loop.  Input and
- * table columns are left untouched and may hold non-canonical words; outputs are canonical.  Defined for any input: a value that is not
+ * becomes the sorted canonical input column and col_permuted_table exactly the permuted_table of the reference's loop.  d_cols: IN
+ * PLACE, all n words of the two output columns of every lookup; input and table columns, and columns no lookup names, keep their
+ * values (the inputs may hold non-canonical words: they are canonicalised in the context's scratch); outputs are canonical.  Defined for any input: a value that is not
  * in the table is no error here (the reference does not assert; such a trace fails the constraints).  Two lookups may share an input
  * or a table column -- a shared column is sorted once (a shared table once per call, a shared input once per chunk of 2^23 / n lookups:
  * DESIGN.md section 19) -- but not an output.  Stream-ordered on the context; temporaries come from its pool.  No per-lookup serial pass: sorts, binary searches, two prefix sums and a stable sort by stack level.
@@ -849,7 +869,7 @@ int gl_memory_stark_desc(const gl_stark_desc** out);
  * for n above 2^24. */
 int gl_memory_trace_host(const gl_memory_op* ops, size_t num_ops, uint64_t* cols_out, size_t capacity_rows, size_t* n_rows);
 /* The same on the device, as a handle: the height is known before the caller makes its gl_stark.  _new takes the log from host
- * memory, _new_device from HBM (left untouched; it is not needed after the call returns); both sort it, count the rows fill_gaps
+ * memory, _new_device from HBM (d_ops: READ-ONLY; it is not needed after the call returns); both sort it, count the rows fill_gaps
  * will add per neighbour pair, and wait ONCE for the stream, for n.  The refusals and their codes are gl_memory_trace_host's.  The
  * handle holds a reference to the context. */
 typedef struct gl_memory_trace gl_memory_trace;
@@ -857,7 +877,8 @@ int gl_memory_trace_new(gl_ctx* ctx, const gl_memory_op* h_ops, size_t num_ops, 
 int gl_memory_trace_new_device(gl_ctx* ctx, const gl_memory_op* d_ops, size_t num_ops, gl_memory_trace** out);
 size_t gl_memory_trace_rows(const gl_memory_trace* t) GL_NOEXCEPT;
 /* All 26 columns of the trace, d_cols[26][n], the two permuted columns included (gl_stark_lookup_columns' body on the lookup
- * (22, 23, 24, 25); a trace of one row is written without it).  Stream-ordered on the handle's context, temporaries from its pool, no
+ * (22, 23, 24, 25); a trace of one row is written without it).  d_cols: OUTPUT, all 26 n words, the unused columns 17..21 (zero)
+ * included.  Stream-ordered on the handle's context, temporaries from its pool, no
  * host synchronisation; may be called any number of times.  No per-op serial pass: a prefix sum over the per-pair counts places every
  * op, one thread per output row finds its source by binary search. */
 int gl_memory_trace_fill(gl_memory_trace* t, uint64_t* d_cols);
@@ -875,7 +896,7 @@ int gl_prove(gl_ctx* ctx, const gl_circuit* c, const uint64_t* h_wires, const ui
  * (`MatrixWitness.wire_values: Vec<Vec<F>>`), so that the caller does not have to flatten 135 vectors first */
 int gl_prove_columns(gl_ctx* ctx, const gl_circuit* c, const uint64_t* const* h_wire_columns,
                      const uint64_t* h_public_inputs, size_t num_public_inputs, gl_proof** out);
-/* same with the witness matrix already resident in HBM (d_wires[num_wires][n]) */
+/* same with the witness matrix already resident in HBM (d_wires[num_wires][n]: READ-ONLY, in all four gl_prove_device* entries) */
 int gl_prove_device(gl_ctx* ctx, const gl_circuit* c, const uint64_t* d_wires, const uint64_t* h_public_inputs,
                     size_t num_public_inputs, gl_proof** out);
 /* same, with public_inputs_hash = hash_no_pad(public_inputs) (prover.rs:126-127) supplied by the caller -- the witness
