@@ -384,6 +384,12 @@ __device__ __forceinline__ gl_t glx_add_cc(gl_t a, gl_t b) {                    
     const gl_t s = a + b;
     return glx_add_eps_if(s, ((s < a) | (s >= GL_P)) ? 1u : 0u);
 }
+// a + b for ANY u64 representative a and a canonical b: a u64 representative of the sum, not the canonical one.  The sum wraps at most
+// once (a + b - 2^64 < p - 1, so + EPS cannot wrap again): one correction, 4 instructions, for sums that feed a product
+__device__ __forceinline__ gl_t glx_add_1c(gl_t a, gl_t b) {
+    const gl_t s = a + b;
+    return glx_add_eps_if(s, (s < a) ? 1u : 0u);
+}
 __device__ __forceinline__ gl_t glx_sub_cc(gl_t a, gl_t b) {                                             // 5 instructions
 #ifdef GLX_C_BUTTERFLY
     const gl_t d = a - b;
@@ -570,6 +576,7 @@ __device__ gl_t glx_mac_c(gl_t acc, uint32_t x, uint32_t c);
 __device__ gl_t glx_canon(gl_t x);
 __device__ gl_t glx_add_eps_if(gl_t z, uint32_t bit);
 __device__ gl_t glx_add_cc(gl_t a, gl_t b);
+__device__ gl_t glx_add_1c(gl_t a, gl_t b);
 __device__ gl_t glx_sub_cc(gl_t a, gl_t b);
 __device__ void glx_sub_cc4(const gl_t (&a)[4], const gl_t (&b)[4], gl_t (&r)[4]);
 template <int E>

@@ -52,7 +52,13 @@ __global__ __launch_bounds__(256, WPE) void k_merkle_leaves(const gl_t* __restri
 #pragma unroll
             for (int i = 0; i < 8; i++)
                 if ((uint32_t)i < c) s[i] = base[offsets[e0 + i] + r];
-            psd_permute_layer<PSD_LAYER_HASH>(s);
+            // what the next absorb overwrites decides which words are read.  Only the default instantiation takes the sponge form: under
+            // the other register bounds of the GL_LEAF_WPE knob its three last layers cost registers (scratch at 6 to 8, a wave at 4)
+            // (the split can go, all on the sponge form, once the knob's other bounds are dropped or that form fits them without scratch)
+            if constexpr (WPE == 5) {
+                const uint32_t left = leaf_len - e0 - c;
+                psd_sponge_permute<PSD_LAYER_HASH>(s, e0 == 0, left < 8 ? left : 8);
+            } else psd_permute_layer<PSD_LAYER_HASH>(s);
         }
     }
     if (gid >= n) return;
@@ -71,7 +77,7 @@ __global__ __launch_bounds__(256, 5) void k_merkle_level(const gl_t* __restrict_
     const ulonglong2* in = reinterpret_cast<const ulonglong2*>(child + 8ull * i);
     ulonglong2 a = in[0], b = in[1], c = in[2], d = in[3];
     gl_t s[12] = {a.x, a.y, b.x, b.y, c.x, c.y, d.x, d.y, 0, 0, 0, 0};
-    psd_permute_layer<PSD_LAYER_HASH>(s);
+    psd_permute_layer<PSD_LAYER_HASH, PSD_KEEP_DIGEST, true>(s);     // the digest is all that is read; the capacity enters as zero
     if (gid >= count) return;
     ulonglong2* out = reinterpret_cast<ulonglong2*>(parent + 4ull * i);
     out[0] = make_ulonglong2(gl_canon(s[0]), gl_canon(s[1]));
@@ -156,7 +162,8 @@ __global__ __launch_bounds__(64, 5) void k_hash_rows(const gl_t* rows, size_t co
 #pragma unroll
             for (int i = 0; i < 8; i++)
                 if ((uint32_t)i < c) s[i] = row[e0 + i];
-            psd_permute_layer<PSD_LAYER_HASH>(s);
+            const uint32_t left = len - e0 - c;
+            psd_sponge_permute<PSD_LAYER_HASH>(s, e0 == 0, left < 8 ? left : 8);
         }
     }
     if (gid >= count) return;

@@ -152,7 +152,10 @@ GL_HD gl_t psd_acc_reduce(gl_t al, gl_t ah) {
 // multiply-adds + an 11-term dot product" plus the dense 11 x 11 pre-matrix of the factorised form.  The next round's
 // constants ride along as the addend of the first multiply-add of each accumulator, so the constant layer is free.
 // Same function (pinned by the reference's known-answer vectors and by fast == naive in the oracle).
-template <bool WITH_RC>
+// KEEP: the set of output words a layer has to produce, bit i = word i; the words outside it are left unspecified.  What the sponge reads
+// of a permutation's last layer: the digest; the capacity, where a full absorb overwrites the rate; everything before a short absorb.
+enum : uint32_t { PSD_KEEP_ALL = 0xFFFu, PSD_KEEP_DIGEST = 0x00Fu, PSD_KEEP_CAPACITY = 0xF00u };
+template <bool WITH_RC, uint32_t KEEP = PSD_KEEP_ALL>
 GL_HD void psd_mds_then_constants(gl_t (&s)[12], const gl_t* __restrict__ rc) {
     // the power-of-two entries are made opaque: otherwise the compiler turns x * 16 into a 64-bit shift-add, which needs
     // the 32-bit operand zero-extended into a register pair first (two extra moves per term); a multiply-add does not
@@ -168,6 +171,7 @@ GL_HD void psd_mds_then_constants(gl_t (&s)[12], const gl_t* __restrict__ rc) {
     // three output words at a time: their accumulators are reduced together (glx_acc_reduce3: no wait states)
 #pragma unroll
     for (int r0 = 0; r0 < 12; r0 += 3) {
+        if (!((KEEP >> r0) & 7u)) continue;          // (a group with a kept word is computed whole: the reduction is one asm block)
         gl_t al[3], ah[3];
 #pragma unroll
         for (int k = 0; k < 3; k++) {
@@ -240,6 +244,9 @@ __device__ __forceinline__ PsdMfmaA psd_mfma_a() {
 }
 // M s + the constants of round n (kk = d_POSEIDON_MDS_K + 24 n, n = 30: none) on the matrix cores; bit-identical to
 // psd_mds_then_constants for any u64 representatives
+// KEEP (PSD_KEEP_*): the output words to produce; the others are left unspecified (here: undefined values, see below).  A row block without a kept word runs no MFMA,
+// a word that is not kept no recombination and no reduction (the reductions' asm blocks are opaque: the compiler drops none by itself).
+template <uint32_t KEEP>
 __device__ __forceinline__ void psd_mds_mfma(gl_t (&s)[12], const gl_t* __restrict__ kk, const PsdMfmaA& A) {
     psd_i32x4 bl[3], bh[3];
 #pragma unroll
@@ -249,6 +256,11 @@ __device__ __forceinline__ void psd_mds_mfma(gl_t (&s)[12], const gl_t* __restri
             bl[kb][q] = (int)((uint32_t)s[4 * kb + q] ^ 0x80808080u);
             bh[kb][q] = (int)((uint32_t)(s[4 * kb + q] >> 32) ^ 0x80808080u);
         }
+    // a word that is not kept dies here (an undefined value, no instruction): where the caller's next write to it is conditional -- the
+    // sponge's absorb -- the old word would otherwise stay in its registers through the layer
+#pragma unroll
+    for (int i = 0; i < 12; i++)
+        if (!((KEEP >> i) & 1u)) asm("" : "=v"(s[i]));
     // opaque multipliers: the recombination stays one v_mad_i64_i32 per byte position (a known power of two becomes a
     // sign-extension and a 64-bit shift-add); `one` in a VGPR leaves the one scalar operand to the 64-bit constant k
     int32_t one = 1, m8 = 1 << 8, m16 = 1 << 16, m24 = 1 << 24;
@@ -258,6 +270,7 @@ __device__ __forceinline__ void psd_mds_mfma(gl_t (&s)[12], const gl_t* __restri
     for (int rb = 0; rb < 3; rb++) {
 #pragma unroll
         for (int hf = 0; hf < 2; hf++) {
+            if (!((KEEP >> (4 * rb)) & 0xFu)) continue;
             // one accumulator chain at a time (16 VGPRs): the scheduler would otherwise start all six at once
             __builtin_amdgcn_sched_barrier(0);
             psd_i32x16 d = {};
@@ -267,6 +280,7 @@ __device__ __forceinline__ void psd_mds_mfma(gl_t (&s)[12], const gl_t* __restri
 #pragma unroll
             for (int o = 0; o < 4; o++) {
                 const int i = 4 * rb + o;
+                if (!((KEEP >> i) & 1u)) continue;
                 int64_t x = (int64_t)d[4 * o] * one + (int64_t)kk[2 * i + hf];
                 x += (int64_t)d[4 * o + 1] * m8;
                 x += (int64_t)d[4 * o + 2] * m16;
@@ -274,10 +288,18 @@ __device__ __forceinline__ void psd_mds_mfma(gl_t (&s)[12], const gl_t* __restri
                 acc[hf][i] = (gl_t)x;
             }
         }
-        // reduce the groups of three this row block completes (outputs 0-2 | 3-5 | 6-8, 9-11)
+        // reduce the groups of three this row block completes (outputs 0-2 | 3-5 | 6-8, 9-11): three at once where all are kept,
+        // one by one otherwise
 #pragma unroll
-        for (int r0 = 3 * rb; r0 < 4 * rb + 2; r0 += 3)
-            glx_acc_reduce3(acc[0][r0], acc[1][r0], acc[0][r0 + 1], acc[1][r0 + 1], acc[0][r0 + 2], acc[1][r0 + 2], s[r0], s[r0 + 1], s[r0 + 2]);
+        for (int r0 = 3 * rb; r0 < 4 * rb + 2; r0 += 3) {
+            if (((KEEP >> r0) & 7u) == 7u)
+                glx_acc_reduce3(acc[0][r0], acc[1][r0], acc[0][r0 + 1], acc[1][r0 + 1], acc[0][r0 + 2], acc[1][r0 + 2], s[r0], s[r0 + 1], s[r0 + 2]);
+            else {
+#pragma unroll
+                for (int r = r0; r < r0 + 3; r++)
+                    if ((KEEP >> r) & 1u) s[r] = glx_acc_reduce(acc[0][r], acc[1][r]);
+            }
+        }
     }
     __builtin_amdgcn_sched_barrier(0);
 }
@@ -288,13 +310,20 @@ GL_HD constexpr uint32_t psd_mds_entry(int r, int c) {
     constexpr uint32_t circ[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
     return circ[(c - r + 12) % 12] + ((r == 0 && c == 0) ? 8u : 0u);
 }
-GL_HD void psd_sbox_all(gl_t (&s)[12]) {
+// cap0 (wave-uniform): the layer is that of full round 0 and the capacity words entered the permutation as zero, so the S-boxes of
+// words 9..11 are the tabled sbox(RC[0][9..11]) and their triple is skipped (word 8 rides in the triple of words 6 and 7)
+GL_HD void psd_sbox_all(gl_t (&s)[12], bool cap0 = false) {
 #if defined(__HIP_DEVICE_COMPILE__)
     // x^7 = (x * x^2) * x^4, three words at a time: glx_mul3 interleaves three independent products so that its carry chains
     // need no wait states (12 instructions per product; each call tests its three borrow masks on the scalar unit and leaves
     // the rare subtracting side of the fix-up to a cold block: 16 wave-uniform branches per layer, none taken on ordinary data)
 #pragma unroll
     for (int k = 0; k < 12; k += 3) {
+        if (k == 9 && cap0) {
+#pragma unroll
+            for (int i = 9; i < 12; i++) s[i] = d_POSEIDON_CAP0_SBOX[i - 8];
+            continue;
+        }
         gl_t a2, b2, c2, a4, b4, c4, a3, b3, c3;
         glx_mul3<false>(s[k], s[k], s[k + 1], s[k + 1], s[k + 2], s[k + 2], a2, b2, c2);
         glx_mul3<false>(a2, a2, b2, b2, c2, c2, a4, b4, c4);
@@ -427,31 +456,31 @@ __device__ __forceinline__ void psd_partial_group4(gl_t (&s)[12], const gl_t* __
 #endif
 
 #if defined(__HIP_DEVICE_COMPILE__)
-// the MDS layer of round n - 1 followed by the constants of round n (n = 30: none), on the chosen unit
-template <int LAYER, bool WITH_RC>
+// the MDS layer of round n - 1 followed by the constants of round n (n = 30: none), on the chosen unit; KEEP: the words to produce
+template <int LAYER, bool WITH_RC, uint32_t KEEP = PSD_KEEP_ALL>
 __device__ __forceinline__ void psd_mds_layer(gl_t (&s)[12], int n, const PsdMfmaA& A) {
-    if constexpr (LAYER == PSD_LAYER_MFMA) psd_mds_mfma(s, d_POSEIDON_MDS_K + 24 * (WITH_RC ? n : 8 + POSEIDON_PARTIAL_ROUNDS), A);
-    else psd_mds_then_constants<WITH_RC>(s, WITH_RC ? d_POSEIDON_RC + 12 * n : nullptr);
+    if constexpr (LAYER == PSD_LAYER_MFMA) psd_mds_mfma<KEEP>(s, d_POSEIDON_MDS_K + 24 * (WITH_RC ? n : 8 + POSEIDON_PARTIAL_ROUNDS), A);
+    else psd_mds_then_constants<WITH_RC, KEEP>(s, WITH_RC ? d_POSEIDON_RC + 12 * n : nullptr);
 }
+// The permutation up to and including the S-box layer of its last round: the last MDS layer is the caller's (psd_permute_layer,
+// psd_sponge_permute), which knows the words that are read.  cap0 (wave-uniform): words 8..11 enter as zero (psd_sbox_all).
 // LAYER = PSD_LAYER_MFMA: every lane of the wave must be active (psd_mds_mfma)
 template <int LAYER>
-__device__ __forceinline__ void psd_permute_layer(gl_t (&s)[12]) {
+__device__ __forceinline__ void psd_permute_rounds(gl_t (&s)[12], const PsdMfmaA& A, bool cap0) {
     const gl_t* __restrict__ rc = d_POSEIDON_RC;
-    PsdMfmaA A;
-    if constexpr (LAYER == PSD_LAYER_MFMA) A = psd_mfma_a();
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = gl_add_c(s[i], rc[i]);
 #if PSD_GROUP4
     // three full rounds and the S-box layer of the fourth; its MDS layer and those of the 22 partial rounds are 23 linear maps with
     // 22 one-word S-boxes between them, run as 4 + 4 + 4 + 4 + 4 + 3 (six dense maps): five groups of four, one of three
 #pragma unroll 1
-    for (int r = 0; r < 4; r++) { psd_sbox_all(s); if (r < 3) psd_mds_layer<LAYER, true>(s, r + 1, A); }
+    for (int r = 0; r < 4; r++) { psd_sbox_all(s, cap0 && r == 0); if (r < 3) psd_mds_layer<LAYER, true>(s, r + 1, A); }
 #pragma unroll 1
     for (int g = 0; g < POSEIDON_G4_GROUPS; g++) psd_partial_group4(s, d_POSEIDON_G4_K + 15 * g, g != 0);
     { gl_t a[3]; psd_partial_group_k<false>(s, d_POSEIDON_G4_K + 15 * POSEIDON_G4_GROUPS, nullptr, a); }
 #else
 #pragma unroll 1
-    for (int r = 0; r < 4; r++) { psd_sbox_all(s); psd_mds_layer<LAYER, true>(s, r + 1, A); }
+    for (int r = 0; r < 4; r++) { psd_sbox_all(s, cap0 && r == 0); psd_mds_layer<LAYER, true>(s, r + 1, A); }
 #pragma unroll 1
     for (int g = 0; g < POSEIDON_PARTIAL_GROUPS; g++) { gl_t a[3]; psd_partial_group<false>(s, g, nullptr, a); }
 #pragma unroll 1
@@ -460,14 +489,36 @@ __device__ __forceinline__ void psd_permute_layer(gl_t (&s)[12]) {
 #pragma unroll 1
     for (int r = 4 + POSEIDON_PARTIAL_ROUNDS; r < 7 + POSEIDON_PARTIAL_ROUNDS; r++) { psd_sbox_all(s); psd_mds_layer<LAYER, true>(s, r + 1, A); }
     psd_sbox_all(s);
-    psd_mds_layer<LAYER, false>(s, 0, A);
+}
+// One permutation of which the words in KEEP are read afterwards; CAP0: words 8..11 are zero on entry (two_to_one, a sponge's first block)
+template <int LAYER, uint32_t KEEP = PSD_KEEP_ALL, bool CAP0 = false>
+__device__ __forceinline__ void psd_permute_layer(gl_t (&s)[12]) {
+    PsdMfmaA A;
+    if constexpr (LAYER == PSD_LAYER_MFMA) A = psd_mfma_a();
+    psd_permute_rounds<LAYER>(s, A, CAP0);
+    psd_mds_layer<LAYER, false, KEEP>(s, 0, A);
+}
+// One permutation of an overwrite-mode sponge (hashing.rs:117-131) whose capacity started as zero.  first: the sponge's first block;
+// next: the number of words the next absorb overwrites -- 8: only the capacity is read; 1..7, a short last block: words next..11 are,
+// and the whole layer is run (one copy of the layer for every length would be seven more); 0: the last permutation, the digest is
+// read.  Both are wave-uniform, so the round body is there once and only the last layer has three forms.
+template <int LAYER>
+__device__ __forceinline__ void psd_sponge_permute(gl_t (&s)[12], bool first, uint32_t next) {
+    PsdMfmaA A;
+    if constexpr (LAYER == PSD_LAYER_MFMA) A = psd_mfma_a();
+    psd_permute_rounds<LAYER>(s, A, first);
+    if (next == 8) psd_mds_layer<LAYER, false, PSD_KEEP_CAPACITY>(s, 0, A);
+    else if (next == 0) psd_mds_layer<LAYER, false, PSD_KEEP_DIGEST>(s, 0, A);
+    else psd_mds_layer<LAYER, false>(s, 0, A);
 }
 // any EXEC mask: the VALU layer (the hash kernels call psd_permute_layer<PSD_LAYER_HASH> with the whole wave active)
 GL_HD void psd_permute(gl_t (&s)[12]) { psd_permute_layer<PSD_LAYER_VALU>(s); }
 #else
 #if defined(__HIPCC__)
-template <int LAYER>
+template <int LAYER, uint32_t KEEP = PSD_KEEP_ALL, bool CAP0 = false>
 __device__ void psd_permute_layer(gl_t (&s)[12]);       // host pass of a .hip file: kernels that call it must still parse
+template <int LAYER>
+__device__ void psd_sponge_permute(gl_t (&s)[12], bool first, uint32_t next);
 #endif
 GL_HD void psd_permute(gl_t (&s)[12]) {         // host formulation (GL_HD only so that kernels parse in the host pass)
     for (int r = 0; r < 4; r++) psd_full_round(s, r);

@@ -324,12 +324,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
                 const gl_t wv = w[(size_t)j * N], sg = cs[(size_t)(p.num_constants + j) * N];
                 if (!p.k_is_powers_of_7) { const gl_t k = p.k_is[j]; glx_mul3<true>(bx0, k, bx1, k, 0, 0, bxk0, bxk1, unused); }
                 // numerator factor w + beta k_j x + gamma, denominator factor w + beta sigma_j(x) + gamma; six products per
-                // wire, three at a time (the carry chains of three independent products interleave)
-                const gl_t f0 = glx_add_cc(glx_add_cc(wv, bxk0), gamma0), f1 = glx_add_cc(glx_add_cc(wv, bxk1), gamma1);
+                // wire, three at a time (the carry chains of three independent products interleave).  w + gamma is formed once per
+                // challenge and serves both factors.  The six products feed only products (the running n, d, which the chunk's
+                // closing products make canonical) or an add whose other operand is canonical (beta sigma, glx_add_1c): any u64
+                // representative will do, so they are the 12-instruction form with the rare fix-up in a cold block.
+                const gl_t wg0 = glx_add_cc(wv, gamma0), wg1 = glx_add_cc(wv, gamma1);
+                const gl_t f0 = glx_add_cc(wg0, bxk0), f1 = glx_add_cc(wg1, bxk1);
                 gl_t sb0, sb1;
-                glx_mul3<true>(sg, beta0, sg, beta1, n0, f0, sb0, sb1, n0);
-                const gl_t g0 = glx_add_cc(glx_add_cc(wv, sb0), gamma0), g1 = glx_add_cc(glx_add_cc(wv, sb1), gamma1);
-                glx_mul3<true>(d0, g0, n1, f1, d1, g1, d0, n1, d1);
+                glx_mul3<false>(sg, beta0, sg, beta1, n0, f0, sb0, sb1, n0);
+                const gl_t g0 = glx_add_1c(sb0, wg0), g1 = glx_add_1c(sb1, wg1);
+                glx_mul3<false>(d0, g0, n1, f1, d1, g1, d0, n1, d1);
                 if (p.k_is_powers_of_7) {                             // 7 y = 8 y - y
                     bxk0 = glx_sub_cc(glx_shl_c<3>(bxk0), bxk0); bxk1 = glx_sub_cc(glx_shl_c<3>(bxk1), bxk1);
                 }
@@ -1035,16 +1039,29 @@ __global__ __launch_bounds__(256) void k_fri_fold(const gl_t* ia, const gl_t* ib
 
 // ---- proof of work: smallest w >= base with clz(permute(state with w at pos)[7]) >= bits ----------------------------------
 struct GlPowParams { gl_t state[12]; uint32_t pos, min_leading_zeros; uint64_t base, count; unsigned long long* result; int prio /* k_pow_grind: gl_launch_prio */; };
+// A witness below every candidate of this wave is recorded already: nothing the wave can find lowers the minimum.  Workgroups start in
+// ascending order of candidates, so in a window larger than the chip holds at once the waves that start behind the first witness leave
+// here (a window of 2^12 candidates is 64 waves, all resident before one finishes: measured, the exit spares nothing there).  The answer stays the window's
+// minimum whatever the timing: a wave that reads an old result hashes for nothing, one that reads any recorded witness below its lowest
+// candidate could not have improved on it, and atomicMin orders the rest.  The test is on the first lane's values, the wave's lowest
+// candidate (a wave-uniform scalar test): the wave leaves as a whole or not at all.
+__device__ __forceinline__ bool gl_pow_wave_is_beaten(const unsigned long long* result, uint64_t cand) {
+    const unsigned long long seen = __hip_atomic_load(result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint64_t lowest = (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)cand) | ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(cand >> 32)) << 32);
+    const uint64_t best = (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)seen) | ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(seen >> 32)) << 32);
+    return lowest > best;
+}
 __global__ __launch_bounds__(256, 5) void k_pow_grind(GlPowParams p) {
     gl_raise_prio(p.prio);
     const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t cand = p.base + idx;
+    if (gl_pow_wave_is_beaten(p.result, cand)) return;      // the whole wave leaves, or none of it (MFMA layer)
     gl_t s[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = p.state[i];
 #pragma unroll
     for (int i = 0; i < 8; i++) if ((uint32_t)i == p.pos) s[i] = cand;
-    psd_permute_layer<PSD_LAYER_HASH>(s);            // the whole wave active (MFMA layer); candidates past count are not reported
+    psd_permute_layer<PSD_LAYER_HASH, 1u << 7>(s);   // the whole wave active (MFMA layer); candidates past count are not reported; word 7 is the response
     const gl_t r = gl_canon(s[7]);
     const uint32_t lz = r ? (uint32_t)__clzll((long long)r) : 64u;
     if (idx < p.count && lz >= p.min_leading_zeros) atomicMin(p.result, (unsigned long long)cand);
@@ -1053,6 +1070,7 @@ __global__ __launch_bounds__(256, 5) void k_pow_grind(GlPowParams p) {
 // second hash unless a word was rejected, which kck_onion follows.  p.state is canonical.
 __global__ __launch_bounds__(256) void k_kck_pow_grind(GlPowParams p) {
     const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gl_pow_wave_is_beaten(p.result, p.base + idx)) return;
     if (idx >= p.count) return;
     const uint64_t cand = p.base + idx;
     gl_t s[12], e[8];

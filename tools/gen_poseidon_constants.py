@@ -504,6 +504,8 @@ def emit(path, rc, T, G, F, G4):
         "// diagonal; and per round n (n = 30: no constants) the bias-corrected (k_lo, k_hi) of output word i at 24 n + 2 i",
         arr32("POSEIDON_MDS_I8A", F["A"], 16),
         arr("POSEIDON_MDS_K", F["K"]),
+        "// a state whose capacity words 8..11 enter the permutation as zero: their S-boxes of full round 0, sbox(RC[0][8..11])",
+        arr("POSEIDON_CAP0_SBOX", [sbox(rc[0][i]) for i in range(8, W)]),
         "",
     ]
     inc_path = path[:-2] + ".inc" if path.endswith(".h") else path + ".inc"

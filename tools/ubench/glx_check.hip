@@ -83,6 +83,7 @@ __global__ __launch_bounds__(256) void k_acc3w(const u64* acc, const u64* term, 
 
 template <bool CANON> struct F_mul { __device__ __forceinline__ gl_t operator()(gl_t a, gl_t b) const { return glx_mul<CANON>(a, b); } };
 struct F_add_cc { __device__ __forceinline__ gl_t operator()(gl_t a, gl_t b) const { return glx_add_cc(a, b); } };
+struct F_add_1c { __device__ __forceinline__ gl_t operator()(gl_t a, gl_t b) const { return glx_add_1c(a, b); } };
 struct F_sub_cc { __device__ __forceinline__ gl_t operator()(gl_t a, gl_t b) const { return glx_sub_cc(a, b); } };
 struct F_canon { __device__ __forceinline__ gl_t operator()(gl_t a, gl_t) const { return glx_canon(a); } };
 struct F_add_eps_if { __device__ __forceinline__ gl_t operator()(gl_t a, gl_t b) const { return glx_add_eps_if(a, (u32)b & 1u); } };
@@ -416,6 +417,9 @@ int main() {
     auto radd = [](u64 a, u64 b) { return h_mod((u128)a + b); };
     auto rsub = [](u64 a, u64 b) { return h_mod((u128)a + P - b); };
     check2("glx_add_cc", F_add_cc(), hac, hbc, radd, [](u64 a, u64 b) { const u128 s = (u128)a + b; return s >> 64 ? 0 : (u64)s >= P ? 1 : 2; }, {"carry", ">= p", "none"}, 0x7, true, false);
+    // glx_add_1c: any word plus a canonical one; the exact word (the wrapped sum + EPS where it wrapped), a representative of the sum
+    check2("glx_add_1c", F_add_1c(), ha, hbc, [](u64 a, u64 b) { const u128 s = (u128)a + b; return (u64)s + (s >> 64 ? EPS : 0); },
+           [](u64 a, u64 b) { return ((u128)a + b) >> 64 ? 0 : 1; }, {"carry", "none"}, 0x3, false, true);
     check2("glx_sub_cc", F_sub_cc(), hac, hbc, rsub, [](u64 a, u64 b) { return a < b ? 0 : 1; }, {"borrow", "none"}, 0x3, true, false);
     {
         Tally t("glx_sub_cc4", {"borrow", "none"}, 0x3);
